@@ -116,7 +116,14 @@ def parse(argv=None):
                          "rocprofv3 --pmc passes) and, with a path, write the summary there (profiles/rNN_step_traffic.json)")
     ap.add_argument("--plumbing", action="store_true",
                     help="CPU-only launch check (gloo, tiny model): exercises --gpus N rank spawning without a GPU")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): "
+                         "image.npy (the generated images) and grad_sample.npy (a fixed, seeded sample of the parameter "
+                         "gradients); the same arguments give the same inputs, so two builds compare output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def free_port():
@@ -769,6 +776,43 @@ def plumbing_main(args, rank, world):
                           "steps": args.steps, "warmup": 0, "data": "synthetic", "train_step": train_res}))
 
 
+DUMP_MAX_VALUES = 15_000_000          # float32 values over all dumped files: 60 MB, under the 64 MB bound
+DUMP_IMAGE_MAX_VALUES = 7_000_000     # the images are written whole up to this size (batch 16 at 256^2: 3.1 M)
+
+
+def _seeded_sample(flat, n, seed):
+    """n entries of a 1-D tensor at sorted positions drawn without replacement by a seeded generator (all if n >= len)."""
+    import numpy as np
+    import torch
+
+    if n >= flat.numel():
+        return flat
+    idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), n, replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)]
+
+
+def dump_outputs(out_dir, img, g):
+    """What the last timed step hands its caller, as float32 .npy files: the images (image.npy, or image_sample.npy
+    when they exceed DUMP_IMAGE_MAX_VALUES) and the parameter gradients (30 M values at 256^2, so grad_sample.npy holds
+    what is left of DUMP_MAX_VALUES, taken from their concatenation in named_parameters() order).  Samples are drawn at
+    fixed seeded positions, so the same arguments sample the same entries."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    img = img.float()
+    if img.numel() <= DUMP_IMAGE_MAX_VALUES:
+        np.save(os.path.join(out_dir, "image.npy"), img.cpu().numpy())
+    else:
+        img = _seeded_sample(img.reshape(-1), DUMP_IMAGE_MAX_VALUES, 0)
+        np.save(os.path.join(out_dir, "image_sample.npy"), img.cpu().numpy())
+    params = [p for _, p in g.named_parameters() if p.requires_grad]
+    flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().reshape(-1)
+                      for p in params])
+    grads = _seeded_sample(flat, DUMP_MAX_VALUES - img.numel(), 1)
+    np.save(os.path.join(out_dir, "grad_sample.npy"), grads.cpu().numpy())
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -835,6 +879,7 @@ def main():
             p_.grad = None
         img, _ = net([z])
         img.sum().backward()
+        return img.detach()
 
     def fence():
         if world > 1:
@@ -847,10 +892,14 @@ def main():
     conv_op.PROFILE = [] if rank == 0 else None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last_img = None                  # freed before the next step allocates, like an image nobody holds
+        last_img = step()
     fence()
     elapsed = time.perf_counter() - t0
     prof, conv_op.PROFILE = conv_op.PROFILE, None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_img, g)
+    del last_img
     # ---- secondary, opt-in arithmetic (NOT the headline): the same step with the stride-2 convolutions and the stride-2 /
     # 1x1 weight gradients on the bf16 matrix cores, every fp32 operand split into three bf16 pieces (csrc/conv_wgrad_bf16x3.hip; error table in
     # profiles/r05_split_bf16.md: at or below the exact-fp32 MFMA kernels' under the same 2e-6 * sum|a||b| bar)

@@ -1,5 +1,5 @@
 import torch, sys, time
-sys.path.insert(0, '/root/repo')
+import os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from stylerenderer_amd.op.smallconv import _fwd, _dx, _dw
 for (b,c,res) in ((16,128,256),(16,256,128),(16,512,64)):
     x=torch.randn(b,c,res,res,device='cuda'); ws=torch.randn(b,3,c,device='cuda'); g=torch.randn(b,3,res,res,device='cuda')

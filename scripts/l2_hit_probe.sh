@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box: L2 (TCC) hit rate of the headline step's kernels — one --pmc pass, never combined with trace domains.
 # usage: bash scripts/l2_hit_probe.sh   -> gpurun_out/l2_hit.txt
-root=/root/repo
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/l2hit
 mkdir -p $out
 export TMPDIR=/tmp

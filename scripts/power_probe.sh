@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box: shader clock and socket power sampled while the headline step runs (is the step power-managed?).
 # usage: bash scripts/power_probe.sh [extra bench flags]   -> gpurun_out/power_probe.txt
-cd /root/repo
+cd "$(dirname "$0")/.."
 out=gpurun_out/power_probe.txt
 mkdir -p gpurun_out
 rocm-smi --showpower --showclocks --showmaxpower 2>/dev/null | grep -v "^=\|^$" | head -20 > $out
@@ -14,10 +14,11 @@ python bench.py --steps 300 --warmup 5 --no-train --no-raster --no-inversion --n
 kill $SAMPLER 2>/dev/null
 wait $SAMPLER 2>/dev/null
 wc -l gpurun_out/power_samples.txt >> $out
-python - <<'PY' >> gpurun_out/power_probe.txt
-import re
+python - "$(dirname "$out")/power_samples.txt" <<'PY' >> "$out"
+import re, sys
+samples=sys.argv[1]
 rows=[]
-for l in open('/root/repo/gpurun_out/power_samples.txt'):
+for l in open(samples):
     m=re.search(r'sclk clock level: \d+: \((\d+)Mhz\)', l)
     p=re.search(r'Power \(W\): ([\d.]+)', l)
     if m and p: rows.append((float(l.split()[0][2:]), int(m.group(1)), float(p.group(1))))
@@ -31,6 +32,6 @@ if rows:
     print('idle sclk/power:', [(r[1], r[2]) for r in rows[:3]])
 else:
     print('no parsable samples; first lines:')
-    print(open('/root/repo/gpurun_out/power_samples.txt').read()[:600])
+    print(open(samples).read()[:600])
 PY
 cat $out

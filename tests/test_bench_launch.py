@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -87,3 +89,77 @@ def test_roofline_objects_prefer_counters_of_this_run():
         assert abs(v["issue_floor_ms"] - 4.0e7 / (1024 * 2.4e9 / 4) * 1e3) < 1e-4 and abs(v["frac"] - v["issue_floor_ms"] / 0.1) < 1e-3
     finally:
         bench._LIVE_PMC.clear()
+
+
+def test_steps_and_warmup_are_checked():
+    import importlib
+
+    bench = importlib.import_module("bench")
+    args = bench.parse(["--steps", "7", "--warmup", "0"])
+    assert args.steps == 7 and args.warmup == 0 and args.dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_dump_outputs_bounded_float32_and_repeatable(tmp_path, monkeypatch):
+    """bench.dump_outputs on a small CPU generator: float32 files, the value budget holds, the same gradients give the
+    same sample.  The budget is shrunk so that both the image and the gradients have to be sampled."""
+    import importlib
+
+    import numpy as np
+    import torch
+
+    from stylerenderer_amd import model
+
+    bench = importlib.import_module("bench")
+    torch.manual_seed(0)
+    g = model.Generator(16, 64, 2)
+    img, _ = g([torch.randn(2, 64)])
+    img.sum().backward()
+    n_grad = sum(p.numel() for p in g.parameters() if p.requires_grad)
+
+    bench.dump_outputs(str(tmp_path / "whole"), img.detach(), g)
+    whole = {f.name: np.load(f) for f in (tmp_path / "whole").iterdir()}
+    assert sorted(whole) == ["grad_sample.npy", "image.npy"]
+    assert whole["image.npy"].dtype == np.float32 and np.array_equal(whole["image.npy"], img.detach().numpy())
+    assert whole["grad_sample.npy"].dtype == np.float32 and whole["grad_sample.npy"].size == n_grad
+
+    monkeypatch.setattr(bench, "DUMP_MAX_VALUES", 1000)
+    monkeypatch.setattr(bench, "DUMP_IMAGE_MAX_VALUES", 300)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), img.detach(), g)
+    a = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    b = {f.name: np.load(f) for f in (tmp_path / "b").iterdir()}
+    assert sorted(a) == ["grad_sample.npy", "image_sample.npy"]
+    assert a["image_sample.npy"].size == 300 and a["grad_sample.npy"].size == 700
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert np.isin(a["image_sample.npy"], whole["image.npy"]).all()
+    assert np.isin(a["grad_sample.npy"], whole["grad_sample.npy"]).all()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_timed_path_repeat_run_to_run(tmp_path):
+    """`bench.py --dump-outputs DIR` on the device: two runs with the same arguments write the same float32 arrays
+    (the headline step's images and gradient sample), within the 64 MB bound, and the line reports the steps asked for."""
+    import numpy as np
+
+    short = ["--steps", "2", "--warmup", "1", "--no-train", "--no-raster", "--no-inversion", "--no-cpu-baseline",
+             "--no-pmc", "--no-split-bf16"]
+    dumps = []
+    for name in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + short +
+                           ["--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0
+        files = sorted((tmp_path / name).iterdir())
+        assert [f.name for f in files] == ["grad_sample.npy", "image.npy"]
+        assert sum(f.stat().st_size for f in files) <= 64e6
+        dumps.append({f.name: np.load(f) for f in files})
+    a, b = dumps
+    assert a["image.npy"].shape == (16, 3, 256, 256)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all() and np.abs(a[k]).max() > 0
+        assert np.array_equal(a[k], b[k]), k

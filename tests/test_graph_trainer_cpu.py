@@ -52,6 +52,8 @@ def worker(rank, world, port, outdir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     torch.set_num_threads(2)
+    # CPU ranks also where a GPU is visible: initialize() would bind rank r to cuda:r (absent on a one-GPU machine)
+    torch.cuda.is_available = lambda: False
     sr_dist.initialize(backend="gloo")
     out = {}
     tr = make_trainer()
