@@ -593,6 +593,32 @@ int sr_lpips_layer_fwd(float* d, const float* f0, const float* t, const float* l
                        int64_t t_bstride, float eps, float* scratch, sr_stream_t stream);
 int sr_lpips_layer_bwd(float* gf, const float* gd, const float* f0, const float* t, const float* lin, int64_t b,
                        int64_t c, int64_t hw, int64_t t_bstride, float eps, sr_stream_t stream);
+/* Perceptual path length (reference ppl.py:93-178), the glue around the mapping network, the generator and the LPIPS
+ * trunk.
+ * sr_ppl_endpoints: the latents of npairs pairs at t and t + eps, one wave per pair.  Pair i reads a + i * in_stride and
+ * b + i * in_stride ([d] each; the sampled [2B, d] tensor read as pairs is a = x, b = x + d, in_stride = 2 d) and t[i];
+ * it writes out[(i * n_ends + e) * d ...], e = 0 at t[i] and (n_ends = 2) e = 1 at t[i] + eps, rounded to fp32.
+ *   mode 0 (w, ppl.py:14-19 `lerp(t[:, None], a, b)`): out = (0 + a (1 - t)) + b t, bit-identical to torch's fp32 ops;
+ *   mode 1 (z, ppl.py:102-112 two-input `slerp`): a^ = a / max(|a|, 1e-8) (layers.py:13-24 'L2'), b^ likewise,
+ *     w = acos(a^ . b^) without clamp, out = normalize(sin(w (1 - t)) a^ + sin(w t) b^); a few ulp from libm. */
+int sr_ppl_endpoints(float* out, const float* a, const float* b, int64_t in_stride, const float* t, int64_t npairs,
+                     int64_t d, int mode, int n_ends, float eps, sr_stream_t stream);
+/* sr_ppl_prep: generator images img [n, 3, h, w] -> LPIPS trunk input out [n, 3, oh, ow]: the crop window rows
+ * y0 .. y0 + ch, columns x0 .. x0 + cw (ppl.py:159-161 --crop), resized when (oh, ow) != (ch, cw) exactly as
+ * F.interpolate(mode='bilinear', align_corners=False) without antialias (ppl.py:162-165), then the ScalingLayer
+ * (x - shift[c]) / scale[c] (lpips/networks_basic.py:94-101; shift, scale [3] device arrays). */
+int sr_ppl_prep(float* out, const float* img, const float* shift, const float* scale, int64_t n, int64_t h, int64_t w,
+                int64_t y0, int64_t x0, int64_t ch, int64_t cw, int64_t oh, int64_t ow, sr_stream_t stream);
+/* sr_lpips_pair: the LPIPS distance of every pair of interleaved samples (2i, 2i+1) straight from the raw trunk
+ * features (replaces normalize_tensor on full tensors + PNetLin per-layer terms, lpips/__init__.py:42-44,
+ * networks_basic.py:66-76):
+ *   d[i] = (sum_k mean_hw sum_c lin_k[c] (f0/n0 - f1/n1)^2) / div,   n = sqrt(sum_c f^2) + 1e-10
+ * f[k] [2 npairs, c[k], hw[k]] and lin[k] [c[k]] are device pointers held in HOST arrays of n_layers (<= 8) entries;
+ * div is eps^2 for PPL.  Two launches (all layers, then a fixed-order finish), no atomics: deterministic.
+ * scratch: sr_lpips_pair_scratch_floats(npairs, n_layers, hw) floats. */
+int64_t sr_lpips_pair_scratch_floats(int64_t npairs, int64_t n_layers, const int64_t* hw);
+int sr_lpips_pair(float* d, const float* const* f, const float* const* lin, const int64_t* c, const int64_t* hw,
+                  int64_t n_layers, int64_t npairs, float div, float* scratch, sr_stream_t stream);
 /* Pixel term of the inversion loss (BASELINE config[4]): out[0] = mean((a - b)^2) over n elements (one workgroup, fixed
  * order), and ga = gout[0] * 2 / n * (a - b).  a, b 16-byte aligned for the forward. */
 int sr_mse_fwd(float* out, const float* a, const float* b, int64_t n, sr_stream_t stream);

@@ -66,6 +66,10 @@ SIGNATURES = {
     "sr_lpips_layer_scratch_floats": (_l, [_l, _l]),
     "sr_lpips_layer_fwd": (_i, [_p] * 4 + [_l] * 4 + [_f, _p, _p]),
     "sr_lpips_layer_bwd": (_i, [_p] * 5 + [_l] * 4 + [_f, _p]),
+    "sr_ppl_endpoints": (_i, [_p, _p, _p, _l, _p, _l, _l, _i, _i, _f, _p]),
+    "sr_ppl_prep": (_i, [_p] * 4 + [_l] * 9 + [_p]),
+    "sr_lpips_pair_scratch_floats": (_l, [_l, _l, _p]),
+    "sr_lpips_pair": (_i, [_p] * 5 + [_l, _l, _f, _p, _p]),
     "sr_mse_fwd": (_i, [_p] * 3 + [_l, _p]),
     "sr_mse_bwd": (_i, [_p] * 4 + [_l, _p]),
     "sr_maxpool2_fwd": (_i, [_p] * 2 + [_l] * 3 + [_p]),

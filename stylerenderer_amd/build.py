@@ -36,6 +36,7 @@ SOURCES = [
     ("bank_mm.hip", EXACT),
     ("mesh.hip", EXACT),
     ("lpips.hip", EXACT),
+    ("ppl.hip", EXACT),
     ("conv_mfma.hip", []),
     ("conv_wino.hip", []),
     ("conv_wgrad_wino.hip", []),

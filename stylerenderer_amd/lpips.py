@@ -38,6 +38,7 @@ from . import synth
 from .op import conv as _conv
 from .op import fused_leaky_relu
 from .op import lpips_layer as _lpips_layer
+from .op import ppl as _ppl
 from .op.weight_prep import weight_prep as _weight_prep
 
 VGG_CFG = ((64, 64), (128, 128), (256, 256, 256), (512, 512, 512), (512, 512, 512))
@@ -238,6 +239,29 @@ class PNetLin(nn.Module):
             res = self.per_layer(self.features(in0), feats1)
             return sum(res[1:], res[0]), res
         return self.distance_to(feats1, in0)
+
+    def pair_distance(self, images, eps=1.0, crop=False):
+        """Perceptual path length distances (reference ppl.py:159-167) of interleaved pairs: images [2B, 3, H, W] in
+        [-1, 1], pair i = samples 2i, 2i+1 -> [B] = d(pair) / eps^2.  `crop` takes rows 3c:7c and columns 2c:6c
+        (c = H // 8); a crop of 512 or more is resized to 256^2 (bilinear, align_corners=False), as the reference.
+        Device float32 tensors: one prep launch (crop, resize, ScalingLayer), the trunk ONCE on all 2B images, and the
+        distance from the raw features in one table-driven launch plus a fixed-order finish (op/ppl.py).  Otherwise:
+        `forward(images[1::2], images[::2])`, the reference's PerceptualLoss.forward(pred, target) ->
+        model.forward(target, pred) argument order."""
+        n, _, h, w = images.shape
+        if n % 2:
+            raise ValueError("pair_distance: an even number of interleaved images expected, got %d" % n)
+        y0, x0, ch, cw = _ppl.crop_window(h, w, crop)
+        size = (256, 256) if ch // 256 > 1 else (ch, cw)
+        div = eps * eps
+        if (images.device.type == "cuda" and images.dtype == torch.float32
+                and not (torch.is_grad_enabled() and images.requires_grad)):
+            x = _ppl.prep(images, self.scaling_layer.shift, self.scaling_layer.scale, (y0, x0, ch, cw), size)
+            return _ppl.lpips_pair(self.net(x), self.lins, div)
+        x = images[:, :, y0:y0 + ch, x0:x0 + cw]
+        if size != (ch, cw):
+            x = F.interpolate(x, size=size, mode="bilinear", align_corners=False)
+        return self.forward(x[1::2], x[::2]).view(n // 2) / div
 
     def load_lin_state_dict(self, state):
         """LPIPS weights/v0.1/vgg.pth: keys 'lin0.model.1.weight' ... 'lin4.model.1.weight' [1, C, 1, 1]."""
