@@ -619,6 +619,32 @@ int sr_ppl_prep(float* out, const float* img, const float* shift, const float* s
 int64_t sr_lpips_pair_scratch_floats(int64_t npairs, int64_t n_layers, const int64_t* hw);
 int sr_lpips_pair(float* d, const float* const* f, const float* const* lin, const int64_t* c, const int64_t* hw,
                   int64_t n_layers, int64_t npairs, float div, float* scratch, sr_stream_t stream);
+/* FID Inception-v3 trunk (reference inception.py InceptionV3([3]) on fid_inception_v3) and FID feature statistics,
+ * csrc/inception.hip.  Forward only, float32 NCHW.
+ * sr_incep_conv: BasicConv2d with BatchNorm folded in: out = relu(conv(in, wt) + bias), in [B, C, H, W], wt [K, M] with
+ * K = C * kh * kw in (c, ky, kx) order (the [M, C, kh, kw] weight transposed), bias [M].  kh, kw in {1, 3, 5, 7},
+ * one stride (1 or 2) for both axes, padding ph / pw, OH = (H + 2 ph - kh) / stride + 1 (OW likewise).  GEMM rows
+ * seg_m0[s] .. seg_m0[s + 1] (the last to M; seg_m0[0] = 0, nseg <= 3) go to seg_out[s] [B, seg_ctot[s], OH, OW] at
+ * channel seg_coff[s]: a branch writes into its slice of the block's concatenated output, and the 1x1 heads of a block
+ * run as one GEMM.  seg_out / seg_m0 / seg_coff / seg_ctot are HOST arrays of nseg entries. */
+int sr_incep_conv(const float* in, const float* wt, const float* bias, int64_t B, int64_t C, int64_t H, int64_t W,
+                  int64_t M, int kh, int kw, int stride, int ph, int pw, int nseg, float* const* seg_out,
+                  const int64_t* seg_m0, const int64_t* seg_coff, const int64_t* seg_ctot, sr_stream_t stream);
+/* sr_incep_pool: in [B, C, H, W] -> channels coff .. coff + C of out [B, ctot, OH, OW].  mode 0: max 3x3 stride 2 no
+ * padding (OH = (H - 3) / 2 + 1); mode 1: average 3x3 stride 1 padding 1 over the in-map taps only
+ * (count_include_pad=False); mode 2: max 3x3 stride 1 padding 1. */
+int sr_incep_pool(float* out, const float* in, int64_t B, int64_t C, int64_t H, int64_t W, int mode, int64_t coff,
+                  int64_t ctot, sr_stream_t stream);
+/* sr_incep_gap: out[p] = mean of in[p * hw .. (p + 1) * hw), summed in order (adaptive average pool to 1 x 1). */
+int sr_incep_gap(float* out, const float* in, int64_t planes, int64_t hw, sr_stream_t stream);
+/* FID feature statistics in fp64 over rows of float32 features f [n, d]: first != 0 sets shift[d] = the mean of this
+ * batch; every call adds sum[j] += sum_r (f[r, j] - shift[j]) and, on the upper 64 x 64 tiles of gram [d, d],
+ * gram[i, j] += sum_r (f[r, i] - shift[i]) (f[r, j] - shift[j]), rows in order, no atomics (deterministic).
+ * sr_fstats_finalize: mean[d] = shift + sum / count, cov[d, d] = (gram - sum sum^T / count) / (count - 1). */
+int sr_fstats_update(double* sum, double* gram, double* shift, const float* f, int64_t n, int64_t d, int first,
+                     sr_stream_t stream);
+int sr_fstats_finalize(double* mean, double* cov, const double* sum, const double* gram, const double* shift,
+                       int64_t count, int64_t d, sr_stream_t stream);
 /* Pixel term of the inversion loss (BASELINE config[4]): out[0] = mean((a - b)^2) over n elements (one workgroup, fixed
  * order), and ga = gout[0] * 2 / n * (a - b).  a, b 16-byte aligned for the forward. */
 int sr_mse_fwd(float* out, const float* a, const float* b, int64_t n, sr_stream_t stream);

@@ -70,6 +70,11 @@ SIGNATURES = {
     "sr_ppl_prep": (_i, [_p] * 4 + [_l] * 9 + [_p]),
     "sr_lpips_pair_scratch_floats": (_l, [_l, _l, _p]),
     "sr_lpips_pair": (_i, [_p] * 5 + [_l, _l, _f, _p, _p]),
+    "sr_incep_conv": (_i, [_p] * 3 + [_l] * 5 + [_i] * 6 + [_p] * 5),
+    "sr_incep_pool": (_i, [_p] * 2 + [_l] * 4 + [_i, _l, _l, _p]),
+    "sr_incep_gap": (_i, [_p] * 2 + [_l] * 2 + [_p]),
+    "sr_fstats_update": (_i, [_p] * 4 + [_l, _l, _i, _p]),
+    "sr_fstats_finalize": (_i, [_p] * 5 + [_l, _l, _p]),
     "sr_mse_fwd": (_i, [_p] * 3 + [_l, _p]),
     "sr_mse_bwd": (_i, [_p] * 4 + [_l, _p]),
     "sr_maxpool2_fwd": (_i, [_p] * 2 + [_l] * 3 + [_p]),

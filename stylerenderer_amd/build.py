@@ -45,6 +45,7 @@ SOURCES = [
     ("conv_s2_bf16x3.hip", []),
     ("conv_generic.hip", []),
     ("conv1x1_gemm.hip", []),
+    ("inception.hip", []),
 ]
 
 
