@@ -656,6 +656,35 @@ int sr_mse_bwd(float* ga, const float* gout, const float* a, const float* b, int
 int sr_maxpool2_fwd(float* out, const float* x, int64_t planes, int64_t ih, int64_t iw, sr_stream_t stream);
 int sr_maxpool2_bwd(float* gx, const float* gy, const float* x, int64_t planes, int64_t ih, int64_t iw, sr_stream_t stream);
 
+/* Adaptive discriminator augmentation (reference utils_3d.py:155-359 `augment`, train.py:269-280), csrc/augment.hip.
+ * Float32 NCHW images with 3 channels, any B <= 65535, H, W.  Every entry point is one or two launches, allocation-free
+ * and never reads back to the host: they all run under graph capture.
+ * sr_ada_params: draws [B, SR_ADA_NDRAW] standard normals -> rec [B, SR_ADA_REC], one lane per sample, in fp64:
+ *   draws 0..4  pose: tx, ty, rotation, log-zoom (sigma pose_p[0..3], mean pose_p[4]), flip (u < pose_p[5])
+ *   draws 5..9  colour: brightness, log-contrast (sigma color_p[0..1]), luma flip (u < color_p[2]), hue,
+ *               log-saturation (sigma color_p[3..4])
+ *   draw 10     select (u < p, p = *p_dev when p_dev is not NULL, else p_host)
+ * where u = Phi(draw) for the three uniform slots.  pose_p [6] and color_p [5] are HOST arrays (|.| is taken).
+ *   rec[0..11]  six DOUBLES (rec 8-byte aligned): the output-pixel -> source-pixel affine map, ix = a0 x + a1 y + a2,
+ *               iy = a3 x + a4 y + a5, i.e. the composite's grid (pad=None: the zoom raised until no border shows)
+ *               under grid_sample(align_corners=True); source coordinates are evaluated in fp64
+ *   rec[12..23] the 3 x 4 colour matrix, row-major;  rec[24]  1 if the sample is augmented, else 0;  rec[25..27]  0
+ * sr_ada_apply: out = C[:, :3] bilinear(img, A (x, y)) + with_bias * C[:, 3] for a selected sample (taps outside the
+ *   image contribute 0), out = img otherwise (bit for bit).  out must not alias img.
+ * sr_ada_apply_grad: the adjoint in the image (of the with_bias = 0 map): gin = Bilinear^T (C[:, :3]^T gout) for a
+ *   selected sample, gin = gout otherwise.  A gather in a fixed order, no atomics: reruns are bit-identical.
+ * sr_ada_update: state [4] fp64 = {sum of sign(D(real)), count, p, r_t}; adds stat [2] (this iteration's sign sum and
+ *   count, already summed over ranks) and, once the count exceeds 255, sets r_t = sum / count,
+ *   p = clamp(p + ((sign(r_t - target) * target) / length) * count, 0, 1) and zeroes the sums (train.Trainer.step). */
+#define SR_ADA_NDRAW 11
+#define SR_ADA_REC 28
+int sr_ada_params(float* rec, const float* draws, int64_t B, const float* pose_p, const float* color_p, const double* p_dev,
+                  double p_host, int64_t H, int64_t W, sr_stream_t stream);
+int sr_ada_apply(float* out, const float* img, const float* rec, int64_t B, int64_t H, int64_t W, int with_bias,
+                 sr_stream_t stream);
+int sr_ada_apply_grad(float* gin, const float* gout, const float* rec, int64_t B, int64_t H, int64_t W, sr_stream_t stream);
+int sr_ada_update(double* state, const float* stat, double target, double length, sr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

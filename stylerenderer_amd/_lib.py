@@ -79,6 +79,10 @@ SIGNATURES = {
     "sr_mse_bwd": (_i, [_p] * 4 + [_l, _p]),
     "sr_maxpool2_fwd": (_i, [_p] * 2 + [_l] * 3 + [_p]),
     "sr_maxpool2_bwd": (_i, [_p] * 3 + [_l] * 3 + [_p]),
+    "sr_ada_params": (_i, [_p, _p, _l, _p, _p, _p, _d, _l, _l, _p]),
+    "sr_ada_apply": (_i, [_p] * 3 + [_l] * 3 + [_i, _p]),
+    "sr_ada_apply_grad": (_i, [_p] * 3 + [_l] * 3 + [_p]),
+    "sr_ada_update": (_i, [_p, _p, _d, _d, _p]),
     "sr_upfirdn2d": (_i, [_p, _p, _p, _l] + [_i] * 14 + [_p]),
     "sr_upsample2_add": (_i, [_p] * 4 + [_l] + [_i] * 6 + [_p]),
     "sr_blur_noise_bias_act": (_i, [_p] * 6 + [_f, _f, _l, _l] + [_i] * 6 + [_l, _p]),

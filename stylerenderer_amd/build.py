@@ -37,6 +37,7 @@ SOURCES = [
     ("mesh.hip", EXACT),
     ("lpips.hip", EXACT),
     ("ppl.hip", EXACT),
+    ("augment.hip", EXACT),
     ("conv_mfma.hip", []),
     ("conv_wino.hip", []),
     ("conv_wgrad_wino.hip", []),

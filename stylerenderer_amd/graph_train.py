@@ -9,8 +9,11 @@ One iteration = up to four phases, each `graph(forward -> backward)`; the phase'
 the ranks by RCCL collectives that run OUTSIDE the graphs but DURING the replay (below); then `graph(Adam step)`:
 
     D      fake = G(z, mesh) (no grad) ; D(fake | real interleaved) ; logistic loss         train.py:245-268
+           (--augment: fake and real augmented first; sign(D(real)) summed into a device slot)
+    ADA    every iteration with an adaptive p: the slot (summed over ranks) updates the
+           device state {acc, p, r_t} in one launch (sr_ada_update), between D and G      train.py:269-280
     R1     every d_reg_every: r1/2 * |grad_x D(real)|^2 * d_reg_every                       train.py:281-289
-    G      non-saturating loss through D                                                    train.py:292-333
+    G      non-saturating loss through D (of the augmented fake batch with --augment)     train.py:292-333
     path   every g_reg_every: path-length regulariser on batch // path_batch_shrink         train.py:335-354
     EMA    g_ema <- decay * g_ema + (1 - decay) * g  (two multi-tensor launches, eager)     train.py:358
 
@@ -60,10 +63,17 @@ class GraphedTrainer(Trainer):
         if capture and not on_gpu:
             raise RuntimeError("GraphedTrainer(capture=True) needs a GPU (hipGraph capture); CPU tensors run the same "
                                "phases eagerly with capture=False")
-        if self.args["augment"]:
-            raise RuntimeError("GraphedTrainer: the ADA branch reads statistics on the host; use train.Trainer")
         a = self.args
         dev = self.device
+        # ADA state on the device: {sum of sign(D(real)), count, p, r_t} in fp64, and this iteration's statistic.  The
+        # captured phases read p from it; sr_ada_update advances it between the D and G phases; nothing reads it back
+        # except ada_aug_p (checkpoints, logging)
+        self.ada_adaptive = bool(a["augment"]) and a["augment_p"] <= 0
+        self.s_ada = torch.zeros(4, dtype=torch.float64, device=dev)
+        self.s_ada[2] = self.__dict__.pop("_ada_p_init", 0.0)
+        self.s_ada[3] = self.__dict__.pop("_ada_rt_init", 0.0)
+        self.s_ada_stat = torch.zeros(2, device=dev)
+        self.ada_augment = self.s_ada[:2]
         self.batch = batch
         self.capture = capture
         g, d = self.generator, self.discriminator
@@ -192,6 +202,46 @@ class GraphedTrainer(Trainer):
             self.s_mesh[key][0].copy_(v)
             self.s_mesh[key][1].copy_(nrm)
 
+    # ---- adaptive discriminator augmentation ---------------------------------------------------------------
+    @property
+    def ada_aug_p(self):
+        """The augmentation probability (a host read of the device state)."""
+        return float(self.s_ada[2])
+
+    @ada_aug_p.setter
+    def ada_aug_p(self, value):
+        if "s_ada" not in self.__dict__:
+            self.__dict__["_ada_p_init"] = float(value)           # Trainer.__init__, before the state exists
+        else:
+            with torch.no_grad():
+                self.s_ada[2].fill_(float(value))
+
+    @property
+    def r_t_stat(self):
+        return float(self.s_ada[3])
+
+    @r_t_stat.setter
+    def r_t_stat(self, value):
+        if "s_ada" not in self.__dict__:
+            self.__dict__["_ada_rt_init"] = float(value)
+        else:
+            with torch.no_grad():
+                self.s_ada[3].fill_(float(value))
+
+    def _aug(self, img):
+        from .utils_3d import augment
+
+        return augment(img, self.s_ada[2]) if self.args["augment"] else img
+
+    def _ada_update(self):
+        """After the D phase and its collectives: this iteration's sign statistic, summed over the ranks (one small
+        all-reduce, stream-ordered), advances p on the device.  No host read."""
+        if self.world > 1:
+            torch.distributed.all_reduce(self.s_ada_stat)
+        from .op import augment as ada
+
+        ada.update(self.s_ada, self.s_ada_stat, self.args["ada_target"], self.args["ada_length"])
+
     def _phase_ema(self):
         accumulate(self.g_ema, self.generator, self.accum)
 
@@ -204,10 +254,14 @@ class GraphedTrainer(Trainer):
         with torch.no_grad():
             fake, _, _ = self._generate(g, self._latents(self.batch), self._mesh_tuple("d"),
                                         inject_index=self.s_inject["d"])
-        fake_pred, real_pred = d_fake_real(d, d, fake, self.s_real)      # one interleaved pass when batch % 4 == 0
+            fake, real = self._aug(fake), self._aug(self.s_real)
+        fake_pred, real_pred = d_fake_real(d, d, fake, real)             # one interleaved pass when batch % 4 == 0
         loss = d_logistic_loss(real_pred, fake_pred)
         loss.backward()
         self.reduce_d.finish()
+        if self.ada_adaptive:
+            self.s_ada_stat[0].copy_(torch.sign(real_pred.detach()).sum())
+            self.s_ada_stat[1].fill_(real_pred.shape[0])
         self.s_loss["d"].copy_(loss.detach())
         self.s_loss["real_score"].copy_(real_pred.detach().mean())
         self.s_loss["fake_score"].copy_(fake_pred.detach().mean())
@@ -230,7 +284,7 @@ class GraphedTrainer(Trainer):
         self._sample_mesh("g")             # the path phase reuses this batch's first meshes (train.py:337-338)
         fake, _, _ = self._generate(g, self._latents(self.batch), self._mesh_tuple("g"),
                                     inject_index=self.s_inject["g"])
-        loss = g_nonsaturating_loss(d(fake))
+        loss = g_nonsaturating_loss(d(self._aug(fake)))
         loss.backward()
         self.reduce_g.finish()
         self.s_loss["g"].copy_(loss.detach())
@@ -269,7 +323,7 @@ class GraphedTrainer(Trainer):
         are constants no phase writes, and the EMA copy is only touched by step(): neither needs a snapshot.)"""
         snap = {"tensors": [(t, t.detach().clone()) for t in (
             self.g_optim.flat_p, self.g_optim.m, self.g_optim.v, self.g_optim.step_t, self.d_optim.flat_p,
-            self.d_optim.m, self.d_optim.v, self.d_optim.step_t, self.mean_path_length)],
+            self.d_optim.m, self.d_optim.v, self.d_optim.step_t, self.mean_path_length, self.s_ada, self.s_ada_stat)],
             "np": self.np_rng.get_state(), "torch": torch.get_rng_state()}
         if self.device.type == "cuda":
             snap["cuda"] = torch.cuda.get_rng_state(self.device)
@@ -381,6 +435,8 @@ class GraphedTrainer(Trainer):
         for k in self.s_inject:
             self._draw_inject(k)
         self._run("d")
+        if self.ada_adaptive:
+            self._ada_update()
         self._run("d_opt")
         ran = ["d", "real_score", "fake_score", "g"]
         if i % a["d_reg_every"] == 0:

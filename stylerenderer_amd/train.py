@@ -12,7 +12,8 @@ restates the *step* it describes:
   logging          ONE packed all-reduce instead of 7 `.item()` round trips (distributed.reduce_scalars)
 
 `python -m stylerenderer_amd.train --size 256 --batch 4 --iter 64` runs it on a synthetic in-memory
-dataset (uniform [-1, 1] images, the tensor contract of reference train.py:557-560) and, with
+dataset (uniform [-1, 1] images, the tensor contract of reference train.py:557-560) or, with `--data PATH`, on a
+multi-resolution image store (dataset.MultiResolutionDataset, reference train.py:557-573) and, with
 `--mesh`, on GeneratorWithMap with a formula ellipsoid in place of the licensed 3DMM.
 """
 import argparse
@@ -288,6 +289,32 @@ class SyntheticImages:
         return torch.where(flip[:, None, None, None], x.flip(3), x)
 
 
+class StoreImages:
+    """Batches of a multi-resolution store (LMDB, dataset.DictStore or a directory) through the reference's training
+    transform (random flip, ToTensor, Normalize: reference train.py:557-573): a shuffled DataLoader sharded by rank,
+    cycled for ever, each batch moved to `device`."""
+
+    def __init__(self, path, size, batch, device, seed=1234):
+        from . import dataset
+
+        ds = dataset.MultiResolutionDataset(path, dataset.train_transform(np.random.RandomState(seed + sr_dist.get_rank())),
+                                            size)
+        world, rank = sr_dist.get_world_size(), sr_dist.get_rank()
+        if world > 1:
+            sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=True,
+                                                                      seed=seed)
+        else:
+            sampler = torch.utils.data.RandomSampler(ds, generator=torch.Generator().manual_seed(seed))
+        loader = torch.utils.data.DataLoader(ds, batch_size=batch, sampler=sampler, drop_last=True)
+        if len(loader) == 0:
+            raise ValueError("--data: %d images per rank cannot fill one batch of %d" % (len(sampler), batch))
+        self.device = device
+        self._it = dataset.sample_data(loader)
+
+    def batch(self, b):
+        return next(self._it).to(self.device, non_blocking=True)
+
+
 def synthetic_mesh(batch, device, seed=0, face_sized=True):
     v0, tri = synth.face_sized_mesh() if face_sized else synth.uv_ellipsoid(16, 14)
     v = synth.random_poses(v0, batch, seed=seed)
@@ -369,7 +396,11 @@ def main():
     ap.add_argument("--ckpt", type=str, default=None, help="checkpoint to resume from (reference layout)")
     ap.add_argument("--save", type=str, default=None, help="write a checkpoint here after the last iteration")
     ap.add_argument("--graphs", action="store_true",
-                    help="replay every phase from a hipGraph (graph_train.GraphedTrainer: GPU only, no --augment)")
+                    help="replay every phase from a hipGraph (graph_train.GraphedTrainer: GPU only; --augment runs "
+                         "inside the graphs, its p controller on the device)")
+    ap.add_argument("--data", type=str, default=None,
+                    help="multi-resolution image store (LMDB, or a directory written by dataset.write_store) at --size; "
+                         "default: synthetic images")
     ap.add_argument("--log_every", type=int, default=1, help="print (and read back) the losses every N iterations")
     args = ap.parse_args()
     rank, _, world, device = sr_dist.initialize(seed=args.seed)
@@ -388,7 +419,10 @@ def main():
         from . import checkpoint
 
         checkpoint.load_checkpoint(args.ckpt, tr, map_location=device)
-    data = SyntheticImages(max(64, args.batch * 4), args.size, device)
+    if args.data:
+        data = StoreImages(args.data, args.size, args.batch, device, seed=args.seed)
+    else:
+        data = SyntheticImages(max(64, args.batch * 4), args.size, device)
     t0 = None
     for it in range(args.iter):
         if it == 1:

@@ -261,50 +261,76 @@ def _axis_angle_matrix(axis_angle):
     return eye + s * K + (1 - c) * torch.matmul(K, K)
 
 
-def random_apply_color(p=[.2, .3, 0, .15, .5], img=None):
-    """Random brightness / contrast / luma flip / hue rotation / saturation as one 3x4 colour matrix per sample
-    (p = sigmas of [brightness, log-contrast], luma-flip probability, sigmas of [hue, log-saturation])."""
-    batch = len(img) if img is not None and img.dim() >= 4 else 1
+def _color_sigmas(p):
     p = torch.abs(torch.as_tensor(p, dtype=torch.float32).reshape(-1)[:5])
-    p = torch.cat((p, torch.zeros(5 - len(p))))
-    z = torch.cat([torch.normal(mean=0, std=p[:2].unsqueeze(0).expand(batch, -1)), torch.rand(batch, 1),
-                   torch.normal(mean=0, std=p[3:].unsqueeze(0).expand(batch, -1))], 1)
+    return torch.cat((p, torch.zeros(5 - len(p))))
+
+
+def _color_draws(batch, p):
+    """z [B, 5] = brightness, log-contrast ~ N(0, p[:2]^2); luma-flip uniform; hue, log-saturation ~ N(0, p[3:]^2)."""
+    return torch.cat([torch.normal(mean=0, std=p[:2].unsqueeze(0).expand(batch, -1)), torch.rand(batch, 1),
+                      torch.normal(mean=0, std=p[3:].unsqueeze(0).expand(batch, -1))], 1)
+
+
+def _color_matrix(z, p):
+    """[B, 3, 4] colour matrices of the draws z (dtype of z)."""
+    batch = z.shape[0]
     bright, contrast = z[:, 0], torch.exp(z[:, 1])
     luma = (z[:, 2] < p[2]).to(z.dtype)
     hue, sat = z[:, 3:4], torch.exp(z[:, 4]).view(-1, 1, 1)
-    eye = torch.eye(3).unsqueeze(0)
-    ones = torch.ones(3, 3).unsqueeze(0)
+    eye = torch.eye(3, dtype=z.dtype).unsqueeze(0)
+    ones = torch.ones(3, 3, dtype=z.dtype).unsqueeze(0)
     C = torch.cat([contrast.view(-1, 1, 1) * eye.expand(batch, -1, -1),
                    (contrast * bright).view(-1, 1, 1).expand(-1, 3, 1)], 2)               # [B, 3, 4]
     C = torch.matmul(eye - luma.view(-1, 1, 1) * 2. / 3, C)
     C = torch.matmul(_axis_angle_matrix(hue.expand(-1, 3) / (3 ** 0.5)), C)
-    C = torch.matmul(eye * sat + ones * (1 - sat) / 3., C)
-    if img is None:
-        return C[0]
+    return torch.matmul(eye * sat + ones * (1 - sat) / 3., C)
+
+
+def _color_from_draws(img, z, p):
+    """The apply half of random_apply_color: img [B, C, H, W] (or [C, H, W]) coloured by the draws z [B, 5]."""
+    C = _color_matrix(z, p)
+    batch = z.shape[0]
     shape = img.shape
     x = img.reshape(batch, -1, shape[-1] * shape[-2])
     C = C.to(dtype=img.dtype, device=img.device)
     return (torch.matmul(C[:, :, :3], x) + C[:, :, 3:4]).view(shape)
 
 
-def random_apply_pose2D_img(p=[.1, .1, .05, .15, 0, .5], img=None, pad=None):
-    """Random translation / in-plane rotation / zoom / horizontal flip of a batch of images by bilinear resampling.
-    pad=None: the zoom is raised per sample until the rotated, shifted frame stays inside the source (no border
-    shows), the behaviour `augment` relies on; 'zeros' / 'border' / 'reflection' skip that and pad instead."""
-    if img is None or img.dim() < 4:
-        raise ValueError("random_apply_pose2D_img: a batch of images [B, C, H, W] is required")
-    batch, hi, wi = img.shape[0], int(img.shape[-2]), int(img.shape[-1])
-    ho, wo = hi, wi
+def random_apply_color(p=[.2, .3, 0, .15, .5], img=None):
+    """Random brightness / contrast / luma flip / hue rotation / saturation as one 3x4 colour matrix per sample
+    (p = sigmas of [brightness, log-contrast], luma-flip probability, sigmas of [hue, log-saturation])."""
+    batch = len(img) if img is not None and img.dim() >= 4 else 1
+    p = _color_sigmas(p)
+    z = _color_draws(batch, p)
+    if img is None:
+        return _color_matrix(z, p)[0]
+    return _color_from_draws(img, z, p)
+
+
+def _pose2d_sigmas(p):
     p = torch.abs(torch.as_tensor(p, dtype=torch.float32).reshape(-1)[:6])
-    p = torch.cat((p, torch.zeros(6 - len(p))))
-    z = torch.cat([torch.normal(mean=0, std=p[:3].unsqueeze(0).expand(batch, -1)),
-                   torch.normal(mean=p[4:5].unsqueeze(0).expand(batch, 1), std=p[3:4].unsqueeze(0).expand(batch, -1)),
-                   torch.rand(batch, 1)], 1)
+    return torch.cat((p, torch.zeros(6 - len(p))))
+
+
+def _pose2d_draws(batch, p):
+    """z [B, 5] = tx, ty, rotation ~ N(0, p[:3]^2); log-zoom ~ N(p[4], p[3]^2); flip uniform."""
+    return torch.cat([torch.normal(mean=0, std=p[:3].unsqueeze(0).expand(batch, -1)),
+                      torch.normal(mean=p[4:5].unsqueeze(0).expand(batch, 1), std=p[3:4].unsqueeze(0).expand(batch, -1)),
+                      torch.rand(batch, 1)], 1)
+
+
+def _pose2d_grid(z, p, hi, wi, pad=None):
+    """The sampling grid [B, H, W, 2] (grid_sample, align_corners=True) of the draws z, in z's dtype, and the padding
+    mode.  pad=None: the zoom is raised per sample until the rotated, shifted frame stays inside the source."""
+    batch = z.shape[0]
+    ho, wo = hi, wi
     flip = z[:, 4:5] < p[-1]
     f = torch.exp(z[:, 3:4])
     s, c = torch.sin(z[:, 2:3]), torch.cos(z[:, 2:3])
     tx, ty = z[:, 0:1], z[:, 1:2]
-    yy, xx = torch.meshgrid(torch.linspace(0, ho, ho), torch.linspace(0, wo, wo), indexing="ij")
+    yy, xx = torch.meshgrid(torch.linspace(0, ho, ho, dtype=z.dtype), torch.linspace(0, wo, wo, dtype=z.dtype),
+                            indexing="ij")
     half = max(wo, ho) / 2.
     x = ((xx.reshape(1, -1) - wo / 2.) / half).expand(batch, -1)
     y = ((ho / 2. - yy.reshape(1, -1)) / half).expand(batch, -1)
@@ -324,17 +350,50 @@ def random_apply_pose2D_img(p=[.1, .1, .05, .15, 0, .5], img=None, pad=None):
     x, y = c * x + s * y, -s * x + c * y
     gx = (x * max(wo, ho) / float(wi)).view(-1, ho, wo, 1)
     gy = (-y * max(wo, ho) / float(hi)).view(-1, ho, wo, 1)
-    grid = torch.cat((gx, gy), -1).to(dtype=img.dtype, device=img.device)
+    return torch.cat((gx, gy), -1), mode
+
+
+def _pose2d_from_draws(img, z, p, pad=None):
+    """The apply half of random_apply_pose2D_img: img [B, C, H, W] resampled by the draws z [B, 5]."""
+    grid, mode = _pose2d_grid(z, p, int(img.shape[-2]), int(img.shape[-1]), pad)
+    grid = grid.to(dtype=img.dtype, device=img.device)
     # the reference's grid runs linspace(-1, 1) over pixel CENTRES, i.e. it was written for grid_sample's
     # pre-1.3 default (align_corners=True); with today's default the identity transform would blur the image
     return torch.nn.functional.grid_sample(img, grid, mode="bilinear", padding_mode=mode, align_corners=True)
 
 
+def random_apply_pose2D_img(p=[.1, .1, .05, .15, 0, .5], img=None, pad=None):
+    """Random translation / in-plane rotation / zoom / horizontal flip of a batch of images by bilinear resampling.
+    pad=None: the zoom is raised per sample until the rotated, shifted frame stays inside the source (no border
+    shows), the behaviour `augment` relies on; 'zeros' / 'border' / 'reflection' skip that and pad instead."""
+    if img is None or img.dim() < 4:
+        raise ValueError("random_apply_pose2D_img: a batch of images [B, C, H, W] is required")
+    p = _pose2d_sigmas(p)
+    return _pose2d_from_draws(img, _pose2d_draws(img.shape[0], p), p, pad)
+
+
+def _augment_from_draws(img, z_pose, z_color, pick, augment_ratio, pose_p=(.1, .1, .05, .15, 0, .5),
+                        color_p=(.2, .3, 0, .15, .5)):
+    """The composite `augment` of a 4-D batch given its draws: pose, then colour, then the per-sample choice."""
+    aug = _color_from_draws(_pose2d_from_draws(img, z_pose, _pose2d_sigmas(pose_p), None), z_color,
+                            _color_sigmas(color_p))
+    return torch.where(pick.expand_as(img) < augment_ratio, aug, img)
+
+
 def augment(img, augment_ratio=.5):
-    """Per sample, with probability `augment_ratio`: random 2-D pose then random colour (reference utils_3d.py:350-359)."""
+    """Per sample, with probability `augment_ratio` (a float or a 0-d tensor): random 2-D pose then random colour
+    (reference utils_3d.py:350-359).  Float32 3-channel images on the GPU take the native kernels (op.augment: three
+    launches, nothing read back, capturable); everything else the composite form below."""
     shape = img.shape
     while img.dim() < 4:
         img = img.unsqueeze(0)
-    aug = random_apply_color(img=random_apply_pose2D_img(img=img, pad=None))
-    pick = torch.rand(img.shape[0], 1, 1, 1, dtype=img.dtype, device=img.device)
-    return torch.where(pick.expand_as(img) < augment_ratio, aug, img).view(shape)
+    if img.is_cuda and img.dtype == torch.float32 and img.shape[1] == 3:
+        from .op import augment as native
+
+        return native.augment(img, augment_ratio).view(shape)
+    batch = img.shape[0]
+    pose_p, color_p = _pose2d_sigmas([.1, .1, .05, .15, 0, .5]), _color_sigmas([.2, .3, 0, .15, .5])
+    z_pose = _pose2d_draws(batch, pose_p)
+    z_color = _color_draws(batch, color_p)
+    pick = torch.rand(batch, 1, 1, 1, dtype=img.dtype, device=img.device)
+    return _augment_from_draws(img, z_pose, z_color, pick, augment_ratio).view(shape)
