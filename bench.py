@@ -13,10 +13,15 @@ Inputs are generated on the device (resident in HBM when the timed region starts
 One process per GPU; N > 1 is data parallel (weak scaling: 16 images per GPU) with the gradient
 all-reduce over RCCL overlapped with backward (nccl backend == RCCL on ROCm).
 
-Prints ONE JSON line on rank 0 with the driver's contract fields plus
+Prints ONE JSON line on rank 0 with the driver's contract fields plus what the events recorded inside the
+timed steps give without running anything more:
   roofline      achieved TFLOP/s of the dominant kernel (3x3 stride-1 MFMA convolution, forward and
                 data-gradient launches) measured with events on the launch stream INSIDE the timed
                 steps, against the 157.3 TFLOP/s fp32-MFMA peak of gfx950 (frac = EXECUTED MFMA flops);
+  kernel_breakdown   ms, TFLOP/s and launches per step of each kind of MFMA launch, from the same events;
+  step_executed_mfma_frac   executed matrix-core flops of the WHOLE headline step / wall time / 157.3 TFLOP/s.
+A plain run ends there: it sets up, warms up, times the steps, writes --dump-outputs and prints the line.
+`--full` then runs everything else the benchmark measures, each one after the timed steps, and adds
   cpu_baseline  the CPU oracle (oracle/model_oracle.py, a restatement of the reference's grouped-
                 convolution formulation) timed on this host's cores on a bounded sample;
   train_step    BASELINE config[2]: the full G+D iteration (GeneratorWithMap(256) + Discriminator(256),
@@ -28,10 +33,11 @@ Prints ONE JSON line on rank 0 with the driver's contract fields plus
                 the single-thread C oracle (the reference's CPU rasterizer restated) beside it;
   inversion     BASELINE config[4]: 400-step latent inversion (generator + rasterizer + LPIPS metric), steps/s, with a
                 roofline object (executed MFMA flops, launches and microseconds per launch of the replayed step);
-  step_executed_mfma_frac   executed matrix-core flops of the WHOLE headline step / wall time / 157.3 TFLOP/s.
-`roofline.traffic`, `mfma_pipe_busy` and the rasterizer's traffic / VALU instruction counts are measured IN this run:
-after the timed steps rank 0 spawns three short `rocprofv3 --pmc` passes (counters only, one TCC counter per pass) over
-a child of this script (`collect_live_pmc`; `--no-pmc` skips them and cites the committed profiles/ summary instead).
+  split_bf16_variant   the same step timed again with the opt-in split-bf16 weight gradients.
+With --full, `roofline.traffic`, `mfma_pipe_busy` and the rasterizer's traffic / VALU instruction counts are measured IN
+this run: after the timed steps rank 0 spawns three short `rocprofv3 --pmc` passes (counters only, one TCC counter per
+pass) over a child of this script (`collect_live_pmc`; `--no-pmc` skips them).  A plain run, or --no-pmc, cites the
+committed profiles/ summary instead.
 """
 import argparse
 import json
@@ -94,6 +100,10 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=16, help="images per GPU (generator leg)")
     ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also run everything else the benchmark measures: the split-bf16 "
+                         "variant, the live --pmc passes, the G+D step, rasterizer and inversion legs and the CPU "
+                         "baselines (the --no-* options below skip single ones).  Without it only the headline runs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-raster", action="store_true", help="skip the rasterizer (BASELINE config[3]) leg")
     ap.add_argument("--no-train", action="store_true", help="skip the full G+D step (BASELINE config[2]) leg")
@@ -112,8 +122,9 @@ def parse(argv=None):
                     help="skip the secondary timing of the step with SR_CONV_SPLIT_BF16=1 (opt-in split-bf16 weight gradients)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--step-traffic", nargs="?", const="1", default=None, metavar="JSON",
-                    help="collect the whole-step HBM traffic of the config[2] / config[4] legs live (minutes of "
-                         "rocprofv3 --pmc passes) and, with a path, write the summary there (profiles/rNN_step_traffic.json)")
+                    help="with --full: collect the whole-step HBM traffic of the config[2] / config[4] legs live "
+                         "(minutes of rocprofv3 --pmc passes) and, with a path, write the summary there "
+                         "(profiles/rNN_step_traffic.json)")
     ap.add_argument("--plumbing", action="store_true",
                     help="CPU-only launch check (gloo, tiny model): exercises --gpus N rank spawning without a GPU")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -123,6 +134,12 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        if args.step_traffic:
+            ap.error("--step-traffic needs --full")
+        # a plain run measures the headline alone: every secondary leg is off, as if each --no-* option were given
+        args.no_cpu_baseline = args.no_raster = args.no_train = args.no_inversion = True
+        args.no_pmc = args.no_split_bf16 = True
     return args
 
 
@@ -268,8 +285,8 @@ def collect_live_pmc(timeout_s=150):
     if tool is None:
         return "rocprofv3 not found"
     out = tempfile.mkdtemp(prefix="sr_pmc_", dir="/tmp")
-    child = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--no-train", "--no-inversion",
-             "--no-cpu-baseline", "--no-split-bf16", "--pmc-child"]
+    child = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--full", "--no-train",
+             "--no-inversion", "--no-cpu-baseline", "--no-split-bf16", "--pmc-child"]
     env = dict(os.environ, TMPDIR="/tmp")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
@@ -305,8 +322,8 @@ def graph_step_traffic(probe, probe_args, segments, timeout_s=420):
     dispatches are the replays in question.  `segments` = [(name, dispatches), ...] in execution order: the tail of the
     process's dispatch list is cut into those pieces and every piece's counters are summed over ALL its kernels
     (2 * FETCH_SIZE + WRITE_SIZE KB: the gfx950 correction of pmc_traffic).  Returns ({name: bytes} or None, note).
-    Counter collection costs ~10 ms per dispatch: this is run by `bench.py --step-traffic` (scripts/profile_round.sh),
-    not by the default run, which reads the committed summary profiles/r*_step_traffic.json."""
+    Counter collection costs ~10 ms per dispatch: this is run by `bench.py --full --step-traffic`, not by a --full run
+    without --step-traffic, which reads the committed summary profiles/r*_step_traffic.json."""
     import csv
     import glob
     import shutil
@@ -1026,7 +1043,7 @@ def main():
     inversion_res = None
     if not args.no_inversion and rank == 0 and world == 1:
         inversion_res = leg(inversion_leg, dev, args.inversion_steps, args.size)
-    if rank == 0 and world == 1 and not args.pmc_child:
+    if args.full and rank == 0 and world == 1 and not args.pmc_child:
         # whole-step HBM traffic of the two replayed workloads: collected live with --step-traffic (separate --pmc passes
         # over their probes in scripts/, minutes of counter collection), otherwise read from the committed summary
         CAD = {"d": 1.0, "r1": 1.0 / 16, "g": 1.0, "path": 1.0 / 4, "d_opt": 1.0 + 1.0 / 16, "g_opt": 1.0 + 1.0 / 4, "ema": 1.0}

@@ -25,7 +25,7 @@ def test_gpus_2_self_launches_two_ranks_and_runs_the_train_leg():
     """Two gloo ranks run bench.py's OWN train_leg (GraphedTrainer capture=False, bucketed reducer) — the N > 1 branches
     of the line the driver's SCALE run parses: gradient_collective (bucket layout, issue order) and the all-reduce
     timing against the xGMI ring / direct-mesh bounds."""
-    out = run_bench("--gpus", "2")
+    out = run_bench("--gpus", "2", "--full")
     assert out["n_gpus"] == 2 and out["plumbing"] is True and out["value"] > 0
     tl = out["train_step"]
     assert "error" not in tl and tl["value"] > 0 and tl["losses_finite"] is True and tl["parallelism"] == "dp2"
@@ -43,7 +43,7 @@ def test_gpus_2_self_launches_two_ranks_and_runs_the_train_leg():
 
 
 def test_train_leg_single_rank_has_no_collective_block():
-    out = run_bench()
+    out = run_bench("--full")
     tl = out["train_step"]
     assert tl["gradient_collective"] is None and "allreduce_125MB" not in tl and tl["parallelism"] == "dp1"
 
@@ -51,6 +51,24 @@ def test_train_leg_single_rank_has_no_collective_block():
 def test_single_rank_default():
     out = run_bench("--no-train")
     assert out["n_gpus"] == 1 and out["train_step"] is None
+
+
+def test_plain_run_is_the_headline_alone():
+    """Without --full every secondary leg is off, as if each --no-* option were given; --full runs them and the --no-*
+    options skip single ones.  The plumbing line shows it on the train leg."""
+    import importlib
+
+    bench = importlib.import_module("bench")
+    legs = ("no_cpu_baseline", "no_raster", "no_train", "no_inversion", "no_pmc", "no_split_bf16")
+    plain, full = bench.parse([]), bench.parse(["--full"])
+    assert not plain.full and all(getattr(plain, k) for k in legs)
+    assert full.full and not any(getattr(full, k) for k in legs)
+    assert bench.parse(["--full", "--no-raster"]).no_raster and not bench.parse(["--full", "--no-raster"]).no_train
+    with pytest.raises(SystemExit):
+        bench.parse(["--step-traffic"])
+    assert bench.parse(["--full", "--step-traffic"]).step_traffic == "1"
+    out = run_bench()
+    assert out["n_gpus"] == 1 and out["value"] > 0 and out["train_step"] is None
 
 
 def test_world_size_mismatch_is_refused():
