@@ -198,6 +198,32 @@ int sr_affine3_fwd(float* out, const float* v, const float* m, const float* t, i
 int sr_affine3_bwd(float* gm, float* gt, const float* v, const float* g, int64_t B, int64_t nv, int64_t v_bstride,
                    sr_stream_t stream);
 
+/* Morphable-mesh node of face reconstruction (csrc/morph.hip; reference face_model.py:71-74, utils_3d.py euler_mat "yxz"
+ * and mesh_point_normal).  w = fc.weight [3 nv, d] as stored, bias [3 nv], coeff [B, d], pose [B, 7] = (yaw, pitch, roll,
+ * tx, ty, tz, log-scale), lin [B, 3, 3] = exp(log-scale) R (sr_pose_batch_fwd).
+ * sr_morph_fwd: vs[b] = (bias + w coeff[b]).view(nv, 3) (the unposed shape) and v[b] = vs[b] @ lin[b] + pose[b, 3:6]; one
+ *   pass over w for all B samples (B d <= 8192, else SR_ERANGE).  reg (may be NULL) = lam * sum (coeff / sigma)^2, sigma
+ *   [d] (NULL: 1).  The normals are sr_vertex_normals_f32 of vs, rotated by R (sr_affine3_fwd).
+ * sr_vertex_normals_bwd_f32: gvs[b, i] = gv[b, i] @ lin[b]^T + (adjoint of the vertex normals at vertex i given gn, the
+ *   gradient of the normals ns @ rot[b]); v = the unposed vertices, ns / normc = the outputs of sr_vertex_normals_f32 of
+ *   v (normc = the clamped length).  gv may be NULL (then lin may be), rot may be NULL (identity).  The gradient of the
+ *   composite normalize() below eps too; a gather over the CSR incidence in the forward's fixed order, no atomics.
+ * sr_morph_gcoeff: gcoeff[b, k] = sum_j w[j, k] gvs[b, j] + 2 lam greg[0] coeff[b, k] / sigma[k]^2 (greg: device scalar,
+ *   may be NULL), rows = 3 nv; split-K over slabs of rows into scratch [sr_morph_gcoeff_scratch_floats] and a fixed-order
+ *   second pass.  sr_morph_pose_bwd: gpose[b] from glin, grot [B, 3, 3] (either may be NULL) and gt [B, 3]. */
+int sr_morph_fwd(float* v, float* vs, float* reg, const float* w, const float* bias, const float* coeff, const float* lin,
+                 const float* pose, const float* sigma, float lam, int64_t B, int64_t nv, int64_t d, sr_stream_t stream);
+int sr_vertex_normals_bwd_f32(float* gvs, const float* gv, const float* gn, const float* lin, const float* rot,
+                              const float* v, const float* ns, const float* normc, const int64_t* tri,
+                              const int32_t* adj_off, const int32_t* adj, int64_t B, int64_t nv, int64_t nf, float eps,
+                              sr_stream_t stream);
+int64_t sr_morph_gcoeff_scratch_floats(int64_t rows, int64_t B, int64_t d);
+int sr_morph_gcoeff(float* gcoeff, float* scratch, const float* w, const float* gvs, const float* coeff,
+                    const float* sigma, float lam, const float* greg, int64_t B, int64_t rows, int64_t d,
+                    sr_stream_t stream);
+int sr_morph_pose_bwd(float* gpose, const float* glin, const float* grot, const float* gt, const float* pose, int64_t B,
+                      sr_stream_t stream);
+
 /* Pose parameters of the inversion loop, pose = (yaw, pitch, roll, tx, ty, tz, log-scale): rot [3,3] = Rz(roll) Rx(pitch)
  * Ry(yaw) (utils_3d.euler_mat(angles, "yxz"), row-major), lin = exp(log-scale) * rot; sr_pose_bwd: gradient of the seven
  * numbers from the gradients of the two matrices (either may be NULL; entries 3..5 are written as 0: the translation's

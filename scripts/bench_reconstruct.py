@@ -1,0 +1,152 @@
+"""Face reconstruction on one GPU: the fit-shape inversion (LatentInverter(fit_shape=True), W+ + pose + 3DMM coefficients)
+against the pose-only inversion (BASELINE config[4]) at 256^2 on the face-sized synthetic 3DMM (d = 80 + 64), and the
+device time of the morphable-mesh node's kernels (csrc/morph.hip).
+
+    python scripts/bench_reconstruct.py [--steps 100] [--rounds 3] [--reps 50]
+
+One JSON line per measurement:
+  * inversion: replayed steps/s of both inverters in the same process (hipGraph replays, alternated in --rounds rounds
+    of --steps replays each; the median round counts), launches per step (kernel nodes of the captured graph) and the
+    ratio fit-shape / pose-only;
+  * kernels: device time per call (CUDA events) of sr_morph_fwd, sr_vertex_normals_bwd_f32 and sr_morph_gcoeff (both
+    passes), WARM (back-to-back calls: W = fc.weight, 42.8 MB, stays in the 256 MiB Infinity Cache) and COLD (a 512 MiB
+    write between calls evicts it; only the call itself is between the events), with the HBM bytes each call must move
+    at least and the achieved bytes/s against the 8 TB/s peak.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from stylerenderer_amd import _lib, inversion, lpips, model, synth, train, utils_3d  # noqa: E402
+from stylerenderer_amd.op import morph  # noqa: E402
+
+HBM_BYTES_PER_S = 8.0e12
+DEV = torch.device("cuda:0")
+
+
+def make_inverters(size):
+    g = model.GeneratorWithMap(size, 512, 8)
+    synth.fill_state_dict(g.state_dict(), salt=7)
+    g = g.to(DEV)
+    src = train.SyntheticFaceSource(DEV)
+    fm, tri = src.model, src.tri
+    net = lpips.PNetLin().to(DEV)
+    noise = [torch.from_numpy(synth.det_normal(tuple(n.shape), 300 + i)).to(DEV) for i, n in enumerate(g.make_noise())]
+    with torch.no_grad():
+        c_true = torch.from_numpy(synth.det_normal((1, fm.sigma.numel()), 8)).to(DEV) * fm.sigma
+        pose = torch.tensor([[0.2, -0.1, 0.0, 0.0, 0.0, 0.0, 0.0]], device=DEV)
+        v, n, _ = morph.morph_mesh(fm, c_true, pose, tri)
+        w_true = g.style(torch.from_numpy(synth.det_normal((1, 512), 9)).to(DEV)).unsqueeze(1).repeat(1, g.n_latent, 1)
+        target, _, _ = g([w_true], (v, n, tri), input_is_latent=True, noise=noise)
+        zero = torch.zeros(1, fm.sigma.numel(), device=DEV)
+        v0, n0, _ = morph.morph_mesh(fm, zero, torch.zeros(1, 7, device=DEV), tri)       # the mean face
+    common = dict(lr=0.05, pose_lr=0.01, noise=noise, n_mean_latent=4096, use_graph=True)
+    torch.manual_seed(11)
+    pose_only = inversion.LatentInverter(g, net, target, (v0, n0, tri), **common)
+    torch.manual_seed(11)
+    fit_shape = inversion.LatentInverter(g, net, target, None, face=(fm, tri), fit_shape=True, coeff_lr=0.05,
+                                         shape_reg=1e-3, **common)
+    return {"pose_only": pose_only, "fit_shape": fit_shape}, fm, tri
+
+
+def bench_inversion(size, steps, rounds):
+    invs, _, _ = make_inverters(size)
+    for inv in invs.values():
+        inv.run(8)                                     # warm-up iterations + capture
+        torch.cuda.synchronize()
+    rates = {k: [] for k in invs}
+    for _ in range(rounds):
+        for k, inv in invs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(steps):
+                inv.graph.replay()
+            b.record()
+            torch.cuda.synchronize()
+            rates[k].append(steps * 1000.0 / a.elapsed_time(b))
+    out = {"what": "inversion", "size": size, "steps_per_round": steps, "rounds": rounds}
+    for k, inv in invs.items():
+        out[k + "_steps_per_s"] = round(statistics.median(rates[k]), 2)
+        out[k + "_rounds"] = [round(r, 2) for r in rates[k]]
+        out[k + "_launches_per_step"] = inv.graph.kernel_nodes
+    out["ratio_fit_over_pose"] = round(out["fit_shape_steps_per_s"] / out["pose_only_steps_per_s"], 4)
+    print(json.dumps(out), flush=True)
+
+
+def event_time(fn, reps, flush=None):
+    ts = []
+    fn()
+    torch.cuda.synchronize()
+    for _ in range(reps):
+        if flush is not None:
+            flush.fill_(1.0)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b) * 1e-3)
+    return statistics.median(ts)
+
+
+def bench_kernels(reps):
+    src = train.SyntheticFaceSource(DEV)
+    fm, tri = src.model, src.tri
+    w, bias, sigma = fm.fc.weight.detach().contiguous(), fm.fc.bias.detach().contiguous(), fm.sigma.detach().contiguous()
+    nv, d, b = bias.numel() // 3, w.shape[1], 1
+    c = (torch.from_numpy(synth.det_normal((b, d), 8)).to(DEV) * sigma).contiguous()
+    pose = torch.tensor([[0.2, -0.1, 0.05, 0.01, 0.02, 0.0, 0.1]], device=DEV)
+    off, adj, _ = utils_3d.incidence_lists(tri, nv)
+    L, ptr, st = _lib.lib(), _lib.ptr, _lib.current_stream(DEV)
+    lin, rot = torch.empty(b, 3, 3, device=DEV), torch.empty(b, 3, 3, device=DEV)
+    vs, v, ns, n = (torch.empty(b, nv, 3, device=DEV) for _ in range(4))
+    normc, reg = torch.empty(b, nv, device=DEV), torch.empty((), device=DEV)
+    gv, gn = torch.randn(b, nv, 3, device=DEV), torch.randn(b, nv, 3, device=DEV)
+    gvs, gc, greg = torch.empty(b, nv, 3, device=DEV), torch.empty(b, d, device=DEV), torch.ones((), device=DEV)
+    scratch = torch.empty(int(L.sr_morph_gcoeff_scratch_floats(3 * nv, b, d)), device=DEV)
+    _lib.check(L.sr_pose_batch_fwd(ptr(lin), ptr(rot), ptr(pose), b, st))
+    calls = {
+        "sr_morph_fwd": (lambda: L.sr_morph_fwd(ptr(v), ptr(vs), ptr(reg), ptr(w), ptr(bias), ptr(c), ptr(lin), ptr(pose),
+                                                ptr(sigma), 1e-3, b, nv, d, st),
+                         # W + bias + vs + v
+                         4 * (w.numel() + bias.numel() + 2 * 3 * nv * b)),
+        "sr_vertex_normals_bwd_f32": (lambda: L.sr_vertex_normals_bwd_f32(
+            ptr(gvs), ptr(gv), ptr(gn), ptr(lin), ptr(rot), ptr(vs), ptr(ns), ptr(normc), ptr(tri), ptr(off), ptr(adj),
+            b, nv, tri.size(0), 1e-8, st),
+            # gv, gn, vs, ns, normc, gvs + tri + CSR lists (each read once at best)
+            4 * (5 * 3 * nv * b + nv * b) + 8 * tri.numel() + 4 * (adj.numel() + off.numel())),
+        "sr_morph_gcoeff": (lambda: L.sr_morph_gcoeff(ptr(gc), ptr(scratch), ptr(w), ptr(gvs), ptr(c), ptr(sigma), 1e-3,
+                                                      ptr(greg), b, 3 * nv, d, st),
+                            4 * (w.numel() + 3 * nv * b + 2 * scratch.numel())),
+    }
+    _lib.check(L.sr_vertex_normals_f32(ptr(ns), ptr(normc), ptr(vs), ptr(tri), ptr(off), ptr(adj), b, nv, tri.size(0),
+                                       1e-8, st))
+    flush = torch.empty(128 * 1024 * 1024, device=DEV)              # 512 MiB: twice the Infinity Cache
+    for name, (fn, nbytes) in calls.items():
+        for state, fl in (("warm", None), ("cold", flush)):
+            t = event_time(fn, reps, fl)
+            print(json.dumps({"what": "kernel", "name": name, "cache": state, "nv": nv, "d": d, "B": b,
+                              "us": round(t * 1e6, 2), "hbm_bytes": int(nbytes),
+                              "bytes_per_s": round(nbytes / t / 1e12, 3) * 1e12,
+                              "share_of_8TBps": round(nbytes / t / HBM_BYTES_PER_S, 3)}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=50)
+    args = ap.parse_args()
+    os.environ.setdefault("SR_STRICT_NATIVE", "1")
+    bench_kernels(args.reps)
+    bench_inversion(args.size, args.steps, args.rounds)
+
+
+if __name__ == "__main__":
+    main()

@@ -119,6 +119,11 @@ SIGNATURES = {
     "sr_pose_batch_fwd": (_i, [_p, _p, _p, _l, _p]),
     "sr_affine3_fwd": (_i, [_p, _p, _p, _p, _l, _l, _l, _p]),
     "sr_affine3_bwd": (_i, [_p, _p, _p, _p, _l, _l, _l, _p]),
+    "sr_morph_fwd": (_i, [_p] * 9 + [_f, _l, _l, _l, _p]),
+    "sr_vertex_normals_bwd_f32": (_i, [_p] * 11 + [_l, _l, _l, _f, _p]),
+    "sr_morph_gcoeff_scratch_floats": (_l, [_l, _l, _l]),
+    "sr_morph_gcoeff": (_i, [_p] * 6 + [_f, _p, _l, _l, _l, _p]),
+    "sr_morph_pose_bwd": (_i, [_p] * 5 + [_l, _p]),
     "sr_signal_bump": (_i, [_p, _p]),
     "sr_signal_wait": (_i, [_p, ctypes.c_uint32, _p]),
     "sr_signal_set": (_i, [_p, _p, _p]),

@@ -35,6 +35,7 @@ SOURCES = [
     ("style_linear.hip", EXACT),
     ("bank_mm.hip", EXACT),
     ("mesh.hip", EXACT),
+    ("morph.hip", []),
     ("lpips.hip", EXACT),
     ("ppl.hip", EXACT),
     ("augment.hip", EXACT),

@@ -11,6 +11,7 @@
 //     fn(f) = (b - a) x (c - a)       out = vn / max(sqrt((x^2 + y^2) + z^2), eps)      (layers.py:19-22)
 // Compiled with -ffp-contract=off like the other bit-comparable kernels.
 #include "common.h"
+#include "pose.h"
 
 namespace {
 
@@ -157,23 +158,6 @@ __global__ __launch_bounds__(1024) void k_affine3_bwd(float* __restrict__ gm, fl
 // order of utils_3d.euler_mat: later axes multiply from the left) and lin = exp(log-scale) * rot, and the gradient of the
 // seven numbers given the gradients of the two matrices.  As tensor algebra this is ~60 launches of one-element kernels
 // per step (sin / cos / cat / view / three 3x3 products and their backward); here one lane each way.
-__device__ __forceinline__ void mat3_mul(const float* a, const float* b, float* o) {      // o = a @ b, row-major
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) o[3 * i + j] = (a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j]) + a[3 * i + 2] * b[6 + j];
-}
-__device__ __forceinline__ void axis_mats(const float* pose, float* ry, float* rx, float* rz, float* dry, float* drx,
-                                          float* drz) {
-    const float c0 = cosf(pose[0]), s0 = sinf(pose[0]), c1 = cosf(pose[1]), s1 = sinf(pose[1]);
-    const float c2 = cosf(pose[2]), s2 = sinf(pose[2]);
-    const float y[9] = {c0, 0.f, s0, 0.f, 1.f, 0.f, -s0, 0.f, c0}, dy[9] = {-s0, 0.f, c0, 0.f, 0.f, 0.f, -c0, 0.f, -s0};
-    const float x[9] = {1.f, 0.f, 0.f, 0.f, c1, -s1, 0.f, s1, c1}, dx[9] = {0.f, 0.f, 0.f, 0.f, -s1, -c1, 0.f, c1, -s1};
-    const float z[9] = {c2, -s2, 0.f, s2, c2, 0.f, 0.f, 0.f, 1.f}, dz[9] = {-s2, -c2, 0.f, c2, -s2, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 9; ++i) { ry[i] = y[i]; rx[i] = x[i]; rz[i] = z[i]; dry[i] = dy[i]; drx[i] = dx[i]; drz[i] = dz[i]; }
-}
-
 __global__ void k_pose_fwd(float* __restrict__ lin, float* __restrict__ rot, const float* __restrict__ pose, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;          // one pose per thread
     if (b >= B) return;

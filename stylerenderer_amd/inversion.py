@@ -6,9 +6,12 @@ The reference has no fitting script; its pieces are the generato
 
     variables   w [1, n_latent, style_dim]  (W+ latent, initialised at the mean latent)
                 pose [7] = yaw, pitch, roll (rad), tx, ty, tz, log-scale of the 3DMM mesh
+                coeff [1, d] = 3DMM shape + expression coefficients (fit_shape=True only; from 0, the mean face)
     forward     vertices = v0 @ (exp(s) * R(yaw, pitch, roll)) + t ; normals = n0 @ R
                 image = GeneratorWithMap([w], (vertices, normals, tri), input_is_latent=True, noise=fixed)
+                with fit_shape=True: vertices, normals = op.morph.morph_mesh(face model, coeff, pose, tri)
     loss        LPIPS-shaped distance(image, target) + pixel_weight * mean((image - target)^2)
+                (+ shape_reg * face_model.regulation(coeff), reference face_model.py:73-74, with fit_shape=True)
     update      Adam, `steps` iterations (default 400)
 
 The pose gradient reaches the vertices only through the rasterizer's backward (deterministic gather, so two
@@ -43,7 +46,8 @@ class _FlatAdamSet:
 
 class LatentInverter:
     def __init__(self, generator, perceptual, target, mesh, lr=0.05, pose_lr=0.01, pixel_weight=1.0, noise=None,
-                 n_mean_latent=4096, use_graph=None, optimise_pose=True):
+                 n_mean_latent=4096, use_graph=None, optimise_pose=True, *, face=None, fit_shape=False, coeff_lr=0.01,
+                 shape_reg=0.0):
         self.g = generator.eval()
         self.perceptual = perceptual.eval()
         for p in list(self.g.parameters()) + list(self.perceptual.parameters()):
@@ -54,7 +58,17 @@ class LatentInverter:
         freeze_prepared_weights(self.g)
         self.device = target.device
         self.target = target.detach()
-        self.v0, self.n0, self.tri = (t.detach() for t in mesh)
+        self.fit_shape = bool(fit_shape)
+        self.shape_reg = float(shape_reg)
+        if self.fit_shape:
+            if face is None:
+                raise ValueError("LatentInverter: fit_shape=True needs face=(LinearMorphableModel, tri)")
+            self.face_model, self.tri = face[0], face[1].detach()
+            self.face_model.requires_grad_(False)
+            # the fitted mesh comes from the morphable-mesh node; `mesh` is not used
+            self.v0 = self.n0 = None
+        else:
+            self.v0, self.n0, self.tri = (t.detach() for t in mesh)
         self.pixel_weight = float(pixel_weight)
         self.with_map = hasattr(self.g, "norm_to_style")
         with torch.no_grad():
@@ -62,11 +76,16 @@ class LatentInverter:
             self.target_feats = [f.detach() for f in self.perceptual.features(self.target)]
         self.w = mean_w.unsqueeze(1).repeat(1, self.g.n_latent, 1).clone().requires_grad_(True)
         self.pose = torch.zeros(7, device=self.device, requires_grad=optimise_pose)
+        # 3DMM coefficients [1, d], from the mean face
+        self.coeff = (torch.zeros(1, self.face_model.sigma.numel(), device=self.device, requires_grad=True)
+                      if self.fit_shape else None)
         self.noise = noise if noise is not None else [n.detach() for n in self.g.make_noise()]
         on_gpu = self.device.type == "cuda"
         groups = [{"params": [self.w], "lr": lr}]
         if optimise_pose:
             groups.append({"params": [self.pose], "lr": pose_lr})
+        if self.fit_shape:
+            groups.append({"params": [self.coeff], "lr": coeff_lr})
         if on_gpu:
             # one sr_adam_flat launch per variable (optim.FlatAdam, the training loop's optimiser) instead of the ~30
             # multi-tensor passes of torch's capturable foreach Adam: at batch 1 every launch is ~5 us of an 8 ms step
@@ -87,16 +106,37 @@ class LatentInverter:
         self.image = None
 
     # ---- model ----------------------------------------------------------------------------------------
+    def _shape_mesh(self):
+        """(v, n, tri, reg) of the fitted coefficients and pose (op.morph: one node, no library GEMM on the device)."""
+        from .op.morph import morph_mesh
+
+        v, n, reg = morph_mesh(self.face_model, self.coeff, self.pose.view(1, 7), self.tri, self.shape_reg)
+        return v, n, self.tri, reg
+
     def posed_mesh(self):
+        if self.fit_shape:
+            return self._shape_mesh()[:3]
         lin, rot = utils_3d.pose_matrices(self.pose)                                    # [1, 3, 3] each
         # [nv, 3] x [3, 3]: one streaming kernel each (utils_3d.affine3), not a 3-wide library GEMM
         v = utils_3d.affine3(self.v0, lin, self.pose[3:6].view(1, 3))
         n = utils_3d.affine3(self.n0, rot)
         return v.contiguous(), n.contiguous(), self.tri
 
+    def fitted_mesh(self):
+        """(v, n, tri) of the current fit, posed and detached."""
+        with torch.no_grad():
+            v, n, tri = self.posed_mesh()
+        return v.detach(), n.detach(), tri
+
     def render(self):
+        self._reg = None
         if self.with_map:
-            img, _, _ = self.g([self.w], self.posed_mesh(), input_is_latent=True, noise=self.noise)
+            if self.fit_shape:
+                v, n, tri, self._reg = self._shape_mesh()
+                mesh = (v, n, tri)
+            else:
+                mesh = self.posed_mesh()
+            img, _, _ = self.g([self.w], mesh, input_is_latent=True, noise=self.noise)
         else:
             img, _ = self.g([self.w], input_is_latent=True, noise=self.noise)
         return img
@@ -105,11 +145,16 @@ class LatentInverter:
         from .op.lpips_layer import mse
 
         d = self.perceptual.distance_to(self.target_feats, img).mean()
-        return d + self.pixel_weight * mse(img, self.target)
+        value = d + self.pixel_weight * mse(img, self.target)
+        if self.fit_shape and self.shape_reg != 0.0 and getattr(self, "_reg", None) is not None:
+            value = value + self._reg                    # shape_reg * regulation(coeff), from the node's forward
+        return value
 
     def _iteration(self):
         self.w.grad = None
         self.pose.grad = None
+        if self.coeff is not None:
+            self.coeff.grad = None
         img = self.render()
         value = self.loss(img)
         value.backward()

@@ -1,0 +1,148 @@
+"""Face reconstruction by inverting the generative renderer (the paper's use of the model; the reference ships no script
+for it):
+
+    python -m stylerenderer_amd.reconstruct [--size 256] [--steps 400] [--lr] [--pose_lr] [--coeff_lr] [--shape_reg]
+        [--bfm BFM.mat] [--lpips-trunk VGG16.pth] [--gpu 0] [--seed S] [--out DIR] CHECKPOINT IMAGE [IMAGE ...]
+
+For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with inversion.LatentInverter(fit_shape=True)
+— the W+ latent, a rigid pose and the 3DMM shape / expression coefficients are fitted together (op.morph on the device)
+— and DIR receives
+
+    <stem>.obj            the posed mesh with vertex normals
+    <stem>_canonical.obj  the fitted shape without the pose
+    <stem>_render.png     the generator's image of the fit
+    <stem>_normal.png     the rasterised normal map of the posed mesh
+    <stem>.npz            w, coeff, pose and the loss history
+
+Images are PNG / JPG (PIL) or .npy in [-1, 1] (HWC or CHW), resized on the host.  The 3DMM is the Basel Face Model with
+--bfm (face_model.load_bfm), else the synthetic model `train --mesh` trains with (train.SyntheticFaceSource).  Without
+--lpips-trunk the perceptual trunk is the deterministic synthetic fill and the result is not a meaningful
+reconstruction (stderr says so).
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import checkpoint, generate, inversion, lpips, utils_3d
+
+
+def load_image(path, size):
+    """[1, 3, size, size] float32 in [-1, 1] on the host."""
+    if path.lower().endswith(".npy"):
+        a = np.load(path).astype(np.float32)
+        if a.ndim == 4:
+            a = a[0]
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.shape[0] in (1, 3) and a.shape[-1] not in (1, 3):       # CHW
+            a = a.transpose(1, 2, 0)
+        x = torch.from_numpy(np.ascontiguousarray(a)).permute(2, 0, 1)[None]
+    else:
+        from PIL import Image
+
+        im = Image.open(path).convert("RGB")
+        x = torch.from_numpy(np.asarray(im, np.float32) / 127.5 - 1.0).permute(2, 0, 1)[None]
+    if x.shape[1] == 1:
+        x = x.expand(-1, 3, -1, -1)
+    x = x[:, :3]
+    if tuple(x.shape[-2:]) != (size, size):
+        x = torch.nn.functional.interpolate(x, size=(size, size), mode="bilinear", align_corners=False, antialias=True)
+    return x.clamp(-1, 1).contiguous()
+
+
+def face_model(bfm, device, seed=0):
+    """(LinearMorphableModel, tri) on `device`: the Basel model of --bfm, else train.SyntheticFaceSource's."""
+    if bfm:
+        from .face_model import load_bfm
+
+        model, tri = load_bfm(bfm)
+        return model.to(device), tri.to(device)
+    from .train import SyntheticFaceSource
+
+    src = SyntheticFaceSource(device, seed=seed)
+    return src.model, src.tri
+
+
+def reconstruct(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr=0.01, shape_reg=0.0,
+                n_mean_latent=4096):
+    """Fits one image; returns the inverter (w, pose, coeff, image, fitted_mesh()) and the loss history (host)."""
+    inv = inversion.LatentInverter(g, percept, target, None, lr=lr, pose_lr=pose_lr, n_mean_latent=n_mean_latent,
+                                   face=face, fit_shape=True, coeff_lr=coeff_lr, shape_reg=shape_reg)
+    hist = inv.run(steps)
+    return inv, hist.cpu().numpy()
+
+
+def write_outputs(inv, hist, out_dir, stem):
+    from .op.morph import morph_mesh
+    from .op.rasterize import rasterize
+
+    v, n, tri = inv.fitted_mesh()
+    with torch.no_grad():
+        zero = torch.zeros_like(inv.pose).view(1, 7)
+        vc, nc, _ = morph_mesh(inv.face_model, inv.coeff.detach(), zero, tri)
+        size = int(inv.target.shape[-1])
+        normal_map = rasterize(v.contiguous(), n.contiguous(), tri, size, size, channel_major=True)
+    tri_h = tri.cpu().numpy()
+    utils_3d.save_obj(os.path.join(out_dir, stem + ".obj"), v[0].cpu().numpy(), tri_h, vn=n[0].cpu().numpy())
+    utils_3d.save_obj(os.path.join(out_dir, stem + "_canonical.obj"), vc[0].cpu().numpy(), tri_h,
+                      vn=nc[0].cpu().numpy())
+    generate.save_image(inv.image.cpu(), os.path.join(out_dir, stem + "_render.png"))
+    generate.save_image(normal_map.cpu(), os.path.join(out_dir, stem + "_normal.png"))
+    np.savez(os.path.join(out_dir, stem + ".npz"), w=inv.w.detach().cpu().numpy(),
+             coeff=inv.coeff.detach().cpu().numpy(), pose=inv.pose.detach().cpu().numpy(), loss=hist)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Face reconstruction: fit W+, pose and 3DMM coefficients to images")
+    ap.add_argument("--size", type=int, default=256, help="output image size of the generator [%(default)d]")
+    ap.add_argument("--steps", type=int, default=400, help="Adam iterations per image [%(default)d]")
+    ap.add_argument("--lr", type=float, default=0.05, help="learning rate of the W+ latent [%(default)g]")
+    ap.add_argument("--pose_lr", type=float, default=0.01, help="learning rate of the pose [%(default)g]")
+    ap.add_argument("--coeff_lr", type=float, default=0.01, help="learning rate of the 3DMM coefficients [%(default)g]")
+    ap.add_argument("--shape_reg", type=float, default=1e-3,
+                    help="weight of the coefficient prior sum (coeff / sigma)^2 [%(default)g]")
+    ap.add_argument("--bfm", default=None, metavar="BFM.mat", help="Basel Face Model (.mat); default: synthetic 3DMM")
+    ap.add_argument("--lpips-trunk", default=None, metavar="PATH",
+                    help="torchvision vgg16 (or vgg16().features) state dict for the LPIPS trunk")
+    ap.add_argument("--n_mean_latent", type=int, default=4096, help="latents averaged for the starting W+ [%(default)d]")
+    ap.add_argument("--gpu", type=int, default=0, help="use gpu id")
+    ap.add_argument("--seed", type=int, default=0, help="random seed (mean latent, noise)")
+    ap.add_argument("--out", default="reconstruct", metavar="DIR", help="output directory [%(default)s]")
+    ap.add_argument("ckpt", metavar="CHECKPOINT", help="checkpoint holding g_ema of a GeneratorWithMap")
+    ap.add_argument("images", metavar="IMAGE", nargs="+", help="PNG / JPG, or .npy in [-1, 1] (HWC or CHW)")
+    args = ap.parse_args(argv)
+    torch.manual_seed(args.seed)
+    if torch.cuda.is_available() and 0 <= args.gpu < torch.cuda.device_count():
+        device = torch.device("cuda:%d" % args.gpu)
+        torch.cuda.set_device(device)
+        torch.cuda.manual_seed(args.seed)
+    else:
+        device = torch.device("cpu")
+    g = checkpoint.load_generator(args.ckpt, args.size, 512, 8, device=device, with_map=True)
+    percept = lpips.PNetLin()
+    if args.lpips_trunk:
+        percept.net.load_trunk_state_dict(torch.load(args.lpips_trunk, map_location="cpu", weights_only=False))
+    else:
+        sys.stderr.write("warning: no --lpips-trunk given: the LPIPS VGG16 trunk is the deterministic synthetic fill, "
+                         "so this is not a meaningful reconstruction\n")
+    percept = percept.to(device)
+    face = face_model(args.bfm, device, seed=args.seed)
+    os.makedirs(args.out, exist_ok=True)
+    results = []
+    for path in args.images:
+        stem = os.path.splitext(os.path.basename(path))[0]
+        target = load_image(path, args.size).to(device)
+        inv, hist = reconstruct(g, percept, face, target, args.steps, args.lr, args.pose_lr, args.coeff_lr,
+                                args.shape_reg, args.n_mean_latent)
+        write_outputs(inv, hist, args.out, stem)
+        print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f" % (
+            path, float(hist[0]), float(hist[-1]), len(hist), float(inv.coeff.detach().norm())), flush=True)
+        results.append((stem, hist))
+    return results
+
+
+if __name__ == "__main__":
+    main()

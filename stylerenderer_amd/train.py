@@ -372,6 +372,22 @@ class SyntheticFaceSource:
         return vert, self._u.mesh_point_normal(vert, self.tri), self.tri
 
 
+class BfmFaceSource(SyntheticFaceSource):
+    """SyntheticFaceSource's per-iteration sampling (same `sample()` contract, usable with --graphs) over the Basel Face
+    Model of a `.mat` file in face_model.load_bfm's contract, so that `reconstruct --bfm` fits the 3DMM the network was
+    trained with."""
+
+    def __init__(self, device, path):
+        from . import face_model, utils_3d
+
+        model, tri = face_model.load_bfm(path)
+        self.model = model.to(device)
+        self.tri = tri.to(device)
+        self.device = device
+        self._u = utils_3d
+        self.pose_sigma = torch.tensor([.5, .1, .05, .1, .1, .1, .15], dtype=torch.float32, device=device)
+
+
 def main():
     ap = argparse.ArgumentParser(description="StyleRenderer training step on synthetic data")
     ap.add_argument("--iter", type=int, default=16)
@@ -389,6 +405,9 @@ def main():
     ap.add_argument("--channel_multiplier", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--mesh", action="store_true", help="GeneratorWithMap + rasterised normal maps")
+    ap.add_argument("--bfm", type=str, default=None, metavar="PATH",
+                    help="with --mesh: sample meshes from this Basel Face Model (.mat, face_model.load_bfm) instead of "
+                         "the synthetic 3DMM")
     ap.add_argument("--augment", action="store_true", help="adaptive discriminator augmentation")
     ap.add_argument("--augment_p", type=float, default=0)
     ap.add_argument("--ada_target", type=float, default=0.6)
@@ -407,7 +426,12 @@ def main():
     targs = (args.size, args.latent, args.n_mlp, args.channel_multiplier, args.lr, args.r1, args.path_regularize,
              args.path_batch_shrink, args.d_reg_every, args.g_reg_every, args.mixing, args.mesh, device, args.seed,
              args.augment, args.augment_p, args.ada_target, args.ada_length)
-    faces = SyntheticFaceSource(device, seed=args.seed) if args.mesh else None
+    if args.bfm and not args.mesh:
+        ap.error("--bfm needs --mesh")
+    if args.mesh:
+        faces = BfmFaceSource(device, args.bfm) if args.bfm else SyntheticFaceSource(device, seed=args.seed)
+    else:
+        faces = None
     if args.graphs:
         from . import graph_train
 

@@ -6,6 +6,7 @@ meaning as reference utils_3d.py / layers.py:
     euler_mat(angle, _type='yxz')                          utils_3d.py:43-80
     random_apply_pose3D(p=[...], v=None)                   utils_3d.py:360-378
     mesh_point_normal(v, tri)                              utils_3d.py:379-404
+    save_obj(file_name, v, tri, vt, trit, vn, trin)        utils_3d.py:405-444
 
 `mesh_point_normal` on device tensors runs ONE gather kernel (csrc/mesh.hip, C ABI
 sr_vertex_normals_f32) over a per-topology incidence list built once and cached, instead of three
@@ -246,6 +247,49 @@ def mesh_point_normal(v, tri):
     if v.device.type == "cuda" and v.dtype == torch.float32:
         return _VertexNormals.apply(v[:, :, :3], tri)
     return _normals_composite(v[:, :, :3], tri)
+
+
+def save_obj(file_name, v, tri=[], vt=[], trit=[], vn=[], trin=[]):
+    """Wavefront OBJ with the reference's output contract: `v` lines (every coordinate given), `vt` (first two) and
+    `vn` (first three) lines with %f, then one `f` record per face with 1-based indices in the richest form the
+    attributes allow — `a/t/n`, `a/t`, `a//n` or `a`.  Texture (normal) indices default to `tri` when vt (vn) has one
+    entry per vertex; a texture (normal) index list whose length differs from `tri` drops that attribute.  Tensors
+    or arrays are accepted.  Returns whether the file exists."""
+    import os
+
+    def rows(a):
+        if isinstance(a, torch.Tensor):
+            a = a.detach().cpu()
+        return [list(r) for r in (a.tolist() if hasattr(a, "tolist") else a)]
+
+    v, tri, vt, trit, vn, trin = (rows(a) for a in (v, tri, vt, trit, vn, trin))
+    if not trit and len(vt) == len(v):
+        trit = tri
+    elif len(trit) != len(tri):
+        vt, trit = [], []
+    if not trin and len(vn) == len(v):
+        trin = tri
+    elif len(trin) != len(tri):
+        vn, trin = [], []
+    out = []
+    out += ["v" + "".join(" %f" % x for x in p) for p in v]
+    out += ["vt" + "".join(" %f" % x for x in p[:2]) for p in vt]
+    out += ["vn" + "".join(" %f" % x for x in p[:3]) for p in vn]
+    for i, face in enumerate(tri):
+        has_t = len(trit) > i and len(trit[i]) >= len(face)
+        has_n = len(trin) > i and len(trin[i]) >= len(face)
+        if has_t and has_n:
+            corners = ["%d/%d/%d" % (face[j] + 1, trit[i][j] + 1, trin[i][j] + 1) for j in range(len(face))]
+        elif has_t:
+            corners = ["%d/%d" % (face[j] + 1, trit[i][j] + 1) for j in range(len(face))]
+        elif has_n:
+            corners = ["%d//%d" % (face[j] + 1, trin[i][j] + 1) for j in range(len(face))]
+        else:
+            corners = ["%d" % (face[j] + 1) for j in range(len(face))]
+        out.append("f " + " ".join(corners) if corners else "f")
+    with open(file_name, "w") as f:
+        f.write("".join(line + "\n" for line in out))
+    return os.path.exists(file_name)
 
 
 # ---- ADA augmentation (reference utils_3d.py:155-188, 189-349 cam=None branch, 350-359) ------------
