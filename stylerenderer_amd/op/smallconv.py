@@ -18,8 +18,15 @@ def supported(x, n_out):
             and (x.size(2) * x.size(3)) % 4 == 0 and x.size(0) * x.size(1) <= 65535 and x.size(1) <= 4096)
 
 
+def _aligned(t):
+    """t contiguous on a 16-byte boundary, as the kernels' float4 rows need: a contiguous view at another storage offset
+    (e.g. x[1:] of a flat buffer) is copied; every other tensor passes through untouched."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _fwd(x, ws, bias=None):
-    x, ws = x.contiguous(), ws.contiguous()
+    x, ws = _aligned(x), ws.contiguous()
     b, c, h, w = x.shape
     n = ws.size(1)
     out = torch.empty((b, n, h, w), dtype=x.dtype, device=x.device)
@@ -33,7 +40,7 @@ def _fwd(x, ws, bias=None):
 
 def _dx(g, ws, addend=None):
     """W^T g (+ addend [B, C, H, W]: the other gradient of the same feature map, added in the same pass)."""
-    g, ws = g.contiguous(), ws.contiguous()
+    g, ws = _aligned(g), ws.contiguous()
     b, n, h, w = g.shape
     c = ws.size(2)
     dx = torch.empty((b, c, h, w), dtype=g.dtype, device=g.device)
@@ -46,7 +53,7 @@ def _dx(g, ws, addend=None):
 
 def _dw(g, x, want_bias=False):
     """dws [B, N, C] (and, with want_bias, gb [N] = sum over samples and pixels of g — summed by the same launch)."""
-    g, x = g.contiguous(), x.contiguous()
+    g, x = _aligned(g), _aligned(x)
     b, n, h, w = g.shape
     c = x.size(1)
     L = _lib.lib()

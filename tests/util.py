@@ -253,3 +253,29 @@ def run_discriminator_case(gold, size, dev, tol_y, tol_g1, tol_g2):
                                     tol_g2, truth=f64("r1_grad_samples_f64"))
     meas["forced"] = forcer.disagreements()
     return meas
+
+
+def launched_kernels(fn):
+    """(fn(), names of the device kernels fn launched, in launch order), from torch.profiler's device activity."""
+    import torch
+    from torch.profiler import ProfilerActivity, profile
+
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        out = fn()
+        torch.cuda.synchronize()
+    events = sorted((e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA),
+                    key=lambda e: e.time_range.start)
+    return out, [e.name for e in events]
+
+
+def kernel_ran(names, base, targs=None):
+    """Whether a kernel `base` is among `names`.  `targs` ("<4, 16>") narrows it to one instantiation where the profiler's
+    names carry template arguments; where they do not, only the base name can be checked."""
+    import re
+
+    pat = re.compile(r"(?<![A-Za-z0-9_])%s(?![A-Za-z0-9_])" % re.escape(base))
+    hits = [n.replace(" ", "") for n in names if pat.search(n)]
+    if targs is None or not any(base + "<" in h for h in hits):
+        return bool(hits)
+    return any(base + targs.replace(" ", "") in h for h in hits)
