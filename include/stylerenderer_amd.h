@@ -675,6 +675,25 @@ int sr_fstats_finalize(double* mean, double* cov, const double* sum, const doubl
  * order), and ga = gout[0] * 2 / n * (a - b).  a, b 16-byte aligned for the forward. */
 int sr_mse_fwd(float* out, const float* a, const float* b, int64_t n, sr_stream_t stream);
 int sr_mse_bwd(float* ga, const float* gout, const float* a, const float* b, int64_t n, sr_stream_t stream);
+/* Per-sample terms of the batched inversion loss (B targets, objective sum_b L_b), csrc/lpips.hip.
+ * sr_mse_rows_fwd: out[b] = mean((a[b] - t[b])^2) over the n elements of row b of [B, n] (B <= 65535); a fixed-order
+ *   two-level reduction (chunk partials into scratch [sr_mse_rows_scratch_floats], then one wave per row), no atomics.
+ *   a, t 4-byte aligned (float4 loads on the aligned body when both are 16-byte aligned, scalar head and tail).
+ * sr_mse_rows_bwd: ga[b, i] = gout[b] * 2 / n * (a[b, i] - t[b, i]).
+ * sr_fit_loss_rows: rows[b] = d0[b] + d1[b] + d2[b] + d3[b] + d4[b] + pixel_weight * mse[b]
+ *   (+ shape_reg * sum_k (coeff[b, k] / sigma[k])^2 when coeff [B, d] is not NULL; sigma NULL: 1), the five LPIPS layer
+ *   distances [B] each; total[0] = sum_b rows[b] in sample order.  One launch.
+ * sr_fit_loss_rows_bwd: gd[b] = gtotal[0] (the gradient of every layer distance) and gmse[b] = pixel_weight * gtotal[0]
+ *   (gmse may be NULL).  The prior's gradient is not formed here: the morph node's scalar reg carries it. */
+int64_t sr_mse_rows_scratch_floats(int64_t B, int64_t n);
+int sr_mse_rows_fwd(float* out, const float* a, const float* t, int64_t B, int64_t n, float* scratch,
+                    sr_stream_t stream);
+int sr_mse_rows_bwd(float* ga, const float* gout, const float* a, const float* t, int64_t B, int64_t n,
+                    sr_stream_t stream);
+int sr_fit_loss_rows(float* rows, float* total, const float* d0, const float* d1, const float* d2, const float* d3,
+                     const float* d4, const float* mse, float pixel_weight, const float* coeff, const float* sigma,
+                     float shape_reg, int64_t B, int64_t d, sr_stream_t stream);
+int sr_fit_loss_rows_bwd(float* gd, float* gmse, const float* gtotal, float pixel_weight, int64_t B, sr_stream_t stream);
 /* 2 x 2 / stride 2 max pooling of the LPIPS trunk (reference lpips/pretrained_networks.py:97-135, torchvision VGG16
  * features 4 / 9 / 16 / 23) over `planes` maps of ih x iw (both even), and its gradient: gx gets gy at the arg-max of
  * every window (first maximum in row-major order, a NaN wins — torch.nn.functional.max_pool2d's rule) and zero elsewhere;

@@ -2,7 +2,7 @@
 against the pose-only inversion (BASELINE config[4]) at 256^2 on the face-sized synthetic 3DMM (d = 80 + 64), and the
 device time of the morphable-mesh node's kernels (csrc/morph.hip).
 
-    python scripts/bench_reconstruct.py [--steps 100] [--rounds 3] [--reps 50]
+    python scripts/bench_reconstruct.py [--steps 100] [--rounds 3] [--reps 50] [--batch 1,4,8,16]
 
 One JSON line per measurement:
   * inversion: replayed steps/s of both inverters in the same process (hipGraph replays, alternated in --rounds rounds
@@ -12,6 +12,10 @@ One JSON line per measurement:
     passes), WARM (back-to-back calls: W = fc.weight, 42.8 MB, stays in the 256 MiB Infinity Cache) and COLD (a 512 MiB
     write between calls evicts it; only the call itself is between the events), with the HBM bytes each call must move
     at least and the achieved bytes/s against the 8 TB/s peak.
+
+With --batch B1,B2,... only the batched fit-shape inverter is measured instead (one line per batch size): B images in one
+captured step, replayed --steps times per round, --rounds rounds, the median round; replayed ms per step, image-steps/s
+(B steps per replay) and kernel nodes per captured step.
 """
 import argparse
 import json
@@ -78,6 +82,36 @@ def bench_inversion(size, steps, rounds):
     print(json.dumps(out), flush=True)
 
 
+def bench_batches(size, batches, steps, rounds):
+    invs, fm, tri = make_inverters(size)
+    base = invs["pose_only"]
+    g, net, noise, target = base.g, base.perceptual, base.noise, base.target
+    del invs, base
+    for b in batches:
+        torch.cuda.empty_cache()
+        torch.manual_seed(11)
+        inv = inversion.LatentInverter(g, net, target.expand(b, -1, -1, -1).contiguous(), None, lr=0.05, pose_lr=0.01,
+                                       noise=noise, n_mean_latent=4096, use_graph=True, face=(fm, tri), fit_shape=True,
+                                       coeff_lr=0.05, shape_reg=1e-3)
+        inv.run(8)                                     # warm-up iterations + capture
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(rounds):
+            a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(steps):
+                inv.graph.replay()
+            e.record()
+            torch.cuda.synchronize()
+            ms.append(a.elapsed_time(e) / steps)
+        t = statistics.median(ms)
+        print(json.dumps({"what": "batched_inversion", "size": size, "batch": b, "steps_per_round": steps,
+                          "rounds": rounds, "ms_per_step": round(t, 4), "steps_per_s": round(1000.0 / t, 2),
+                          "image_steps_per_s": round(b * 1000.0 / t, 2), "rounds_ms": [round(x, 4) for x in ms],
+                          "kernel_nodes_per_step": inv.graph.kernel_nodes}), flush=True)
+        del inv
+
+
 def event_time(fn, reps, flush=None):
     ts = []
     fn()
@@ -142,8 +176,13 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--batch", default=None, metavar="B1,B2,...",
+                    help="measure the batched fit-shape inverter at these batch sizes instead")
     args = ap.parse_args()
     os.environ.setdefault("SR_STRICT_NATIVE", "1")
+    if args.batch:
+        bench_batches(args.size, [int(x) for x in args.batch.split(",")], args.steps, args.rounds)
+        return
     bench_kernels(args.reps)
     bench_inversion(args.size, args.steps, args.rounds)
 

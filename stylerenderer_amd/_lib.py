@@ -77,6 +77,11 @@ SIGNATURES = {
     "sr_fstats_finalize": (_i, [_p] * 5 + [_l, _l, _p]),
     "sr_mse_fwd": (_i, [_p] * 3 + [_l, _p]),
     "sr_mse_bwd": (_i, [_p] * 4 + [_l, _p]),
+    "sr_mse_rows_scratch_floats": (_l, [_l, _l]),
+    "sr_mse_rows_fwd": (_i, [_p] * 3 + [_l, _l, _p, _p]),
+    "sr_mse_rows_bwd": (_i, [_p] * 4 + [_l, _l, _p]),
+    "sr_fit_loss_rows": (_i, [_p] * 8 + [_f, _p, _p, _f, _l, _l, _p]),
+    "sr_fit_loss_rows_bwd": (_i, [_p] * 3 + [_f, _l, _p]),
     "sr_maxpool2_fwd": (_i, [_p] * 2 + [_l] * 3 + [_p]),
     "sr_maxpool2_bwd": (_i, [_p] * 3 + [_l] * 3 + [_p]),
     "sr_ada_params": (_i, [_p, _p, _l, _p, _p, _p, _d, _l, _l, _p]),

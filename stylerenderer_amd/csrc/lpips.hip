@@ -202,6 +202,192 @@ extern "C" int sr_mse_bwd(float* ga, const float* gout, const float* a, const fl
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// Per-sample terms of the batched inversion loss (LatentInverter with B > 1 targets, objective sum_b L_b).
+//   k_mse_rows_partial / k_mse_rows_finish   out[b] = mean((a[b] - t[b])^2) over row b of [B, n], in two levels:
+//       a workgroup per (chunk of MSE_CHUNK elements, row) sums its chunk lane by lane, then by a fixed butterfly and
+//       the waves in order, into part[b, chunk]; one wave per row then sums its chunks in order.  float4 loads on the
+//       16-byte aligned body of a chunk, scalar head and tail (rows start anywhere when n % 4 != 0).
+//   k_mse_rows_bwd   ga[b, i] = gout[b] * 2 / n * (a[b, i] - t[b, i]).
+//   k_fit_loss_rows / _bwd   rows[b] = sum of the five LPIPS layer distances + pw * mse[b] + lam * sum_k (c[b,k] / s_k)^2
+//       and total = sum_b rows[b] in order; the backward hands every input d(total)/d(input).
+// No atomics anywhere: reruns are bit-identical, and row b reads row b only — no sample can reach another's value.
+namespace {
+
+constexpr int MSE_LB = 256;
+constexpr int64_t MSE_CHUNK = 8192;            // a multiple of 4: 8 float4 per lane
+
+__global__ __launch_bounds__(MSE_LB) void k_mse_rows_partial(float* __restrict__ part, const float* __restrict__ a,
+                                                             const float* __restrict__ t, int64_t n, int nchunk,
+                                                             int vec) {
+    __shared__ float wsum[MSE_LB / SR_WAVE];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.y;
+    const int64_t c0 = (int64_t)blockIdx.x * MSE_CHUNK;
+    const int64_t o0 = b * n + c0, o1 = b * n + (c0 + MSE_CHUNK < n ? c0 + MSE_CHUNK : n);   // flat element range
+    // float4 body [v0, v1) on multiples of 4 (16-byte addresses: both bases are aligned when vec), scalar head [o0, v0)
+    // and tail [v1, o1) of fewer than 4 elements each; without vec the head is the whole range
+    int64_t v0 = o1, v1 = o1;
+    if (vec) {
+        const int64_t up = (o0 + 3) & ~(int64_t)3, down = o1 & ~(int64_t)3;
+        v0 = up < o1 ? up : o1;
+        v1 = down > v0 ? down : v0;
+    }
+    float acc = 0.0f;
+    const float4* a4 = reinterpret_cast<const float4*>(a);
+    const float4* t4 = reinterpret_cast<const float4*>(t);
+#pragma unroll 8
+    for (int64_t i = (v0 >> 2) + tid; i < (v1 >> 2); i += MSE_LB) {
+        const float4 x = a4[i], y = t4[i];
+        const float d0 = x.x - y.x, d1 = x.y - y.y, d2 = x.z - y.z, d3 = x.w - y.w;
+        acc += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    }
+    for (int64_t i = o0 + tid; i < v0; i += MSE_LB) {
+        const float d = a[i] - t[i];
+        acc += d * d;
+    }
+    for (int64_t i = v1 + tid; i < o1; i += MSE_LB) {
+        const float d = a[i] - t[i];
+        acc += d * d;
+    }
+    acc = sr_wave_sum(acc);
+    if ((tid & (SR_WAVE - 1)) == 0) wsum[tid / SR_WAVE] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        float s = 0.0f;
+#pragma unroll
+        for (int w = 0; w < MSE_LB / SR_WAVE; ++w) s += wsum[w];
+        part[b * nchunk + blockIdx.x] = s;
+    }
+}
+
+__global__ __launch_bounds__(SR_WAVE) void k_mse_rows_finish(float* __restrict__ out, const float* __restrict__ part,
+                                                             int nchunk, float inv_n) {
+    const int64_t b = blockIdx.x;
+    float acc = 0.0f;
+    for (int c = threadIdx.x; c < nchunk; c += SR_WAVE) acc += part[b * nchunk + c];
+    acc = sr_wave_sum(acc);
+    if (threadIdx.x == 0) out[b] = acc * inv_n;
+}
+
+__global__ __launch_bounds__(256) void k_mse_rows_bwd(float* __restrict__ ga, const float* __restrict__ gout,
+                                                      const float* __restrict__ a, const float* __restrict__ t, int64_t n,
+                                                      float two_inv_n) {
+    const int64_t b = blockIdx.y;
+    const float k = gout[b] * two_inv_n;
+    const int64_t base = b * n;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        ga[base + i] = k * (a[base + i] - t[base + i]);
+}
+
+constexpr int FIT_LB = 256;
+
+__global__ __launch_bounds__(FIT_LB) void k_fit_loss_rows(float* __restrict__ rows, float* __restrict__ total,
+                                                          const float* __restrict__ d0, const float* __restrict__ d1,
+                                                          const float* __restrict__ d2, const float* __restrict__ d3,
+                                                          const float* __restrict__ d4, const float* __restrict__ mse,
+                                                          float pw, const float* __restrict__ coeff,
+                                                          const float* __restrict__ sigma, float lam, int64_t B,
+                                                          int64_t d) {
+    __shared__ float s_rows[FIT_LB];
+    float run = 0.0f;                                  // thread 0's running total, in sample order
+    for (int64_t b0 = 0; b0 < B; b0 += FIT_LB) {
+        const int64_t b = b0 + threadIdx.x;
+        float r = 0.0f;
+        if (b < B) {
+            r = (((d0[b] + d1[b]) + d2[b]) + d3[b]) + d4[b];   // the order of PNetLin.distance_to's additions
+            r += pw * mse[b];
+            if (coeff) {
+                float q = 0.0f;
+                for (int64_t k = 0; k < d; ++k) {
+                    const float x = sigma ? coeff[b * d + k] / sigma[k] : coeff[b * d + k];
+                    q += x * x;
+                }
+                r += lam * q;
+            }
+            rows[b] = r;
+        }
+        s_rows[threadIdx.x] = r;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int m = (int)(B - b0 < FIT_LB ? B - b0 : FIT_LB);
+            for (int i = 0; i < m; ++i) run += s_rows[i];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) total[0] = run;
+}
+
+__global__ __launch_bounds__(FIT_LB) void k_fit_loss_rows_bwd(float* __restrict__ gd, float* __restrict__ gmse,
+                                                              const float* __restrict__ gtotal, float pw, int64_t B) {
+    const float g = gtotal[0];
+    for (int64_t b = threadIdx.x; b < B; b += FIT_LB) {
+        gd[b] = g;
+        if (gmse) gmse[b] = pw * g;
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t sr_mse_rows_scratch_floats(int64_t B, int64_t n) {
+    if (B <= 0 || n <= 0) return 1;
+    return B * sr_ceil_div(n, MSE_CHUNK);
+}
+
+extern "C" int sr_mse_rows_fwd(float* out, const float* a, const float* t, int64_t B, int64_t n, float* scratch,
+                               sr_stream_t stream) {
+    if (B < 0 || n <= 0) return SR_EINVAL;
+    if (B == 0) return SR_OK;
+    if (!out || !a || !t || !scratch) return SR_EINVAL;
+    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(t)) & 3) != 0) return SR_EINVAL;
+    const int64_t nchunk = sr_ceil_div(n, MSE_CHUNK);
+    if (B > 65535 || nchunk > (1 << 30) || B * n > (1LL << 46)) return SR_ERANGE;
+    const int vec = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(t)) & 15) == 0;
+    hipStream_t st = sr_stream(stream);
+    hipLaunchKernelGGL(k_mse_rows_partial, dim3((unsigned)nchunk, (unsigned)B), dim3(MSE_LB), 0, st, scratch, a, t, n,
+                       (int)nchunk, vec);
+    hipLaunchKernelGGL(k_mse_rows_finish, dim3((unsigned)B), dim3(SR_WAVE), 0, st, out, scratch, (int)nchunk,
+                       1.0f / (float)n);
+    return sr_launch_status();
+}
+
+extern "C" int sr_mse_rows_bwd(float* ga, const float* gout, const float* a, const float* t, int64_t B, int64_t n,
+                               sr_stream_t stream) {
+    if (B < 0 || n <= 0) return SR_EINVAL;
+    if (B == 0) return SR_OK;
+    if (!ga || !gout || !a || !t) return SR_EINVAL;
+    if (B > 65535 || B * n > (1LL << 46)) return SR_ERANGE;
+    int64_t gx = sr_ceil_div(n, 256);
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(k_mse_rows_bwd, dim3((unsigned)gx, (unsigned)B), dim3(256), 0, sr_stream(stream), ga, gout, a, t,
+                       n, 2.0f / (float)n);
+    return sr_launch_status();
+}
+
+extern "C" int sr_fit_loss_rows(float* rows, float* total, const float* d0, const float* d1, const float* d2,
+                                const float* d3, const float* d4, const float* mse, float pixel_weight,
+                                const float* coeff, const float* sigma, float shape_reg, int64_t B, int64_t d,
+                                sr_stream_t stream) {
+    if (B < 0 || d < 0) return SR_EINVAL;
+    if (B == 0) return SR_OK;
+    if (!rows || !total || !d0 || !d1 || !d2 || !d3 || !d4 || !mse || (coeff && d == 0)) return SR_EINVAL;
+    if (B > (1LL << 24)) return SR_ERANGE;
+    hipLaunchKernelGGL(k_fit_loss_rows, dim3(1), dim3(FIT_LB), 0, sr_stream(stream), rows, total, d0, d1, d2, d3, d4,
+                       mse, pixel_weight, coeff, sigma, shape_reg, B, d);
+    return sr_launch_status();
+}
+
+extern "C" int sr_fit_loss_rows_bwd(float* gd, float* gmse, const float* gtotal, float pixel_weight, int64_t B,
+                                    sr_stream_t stream) {
+    if (B < 0) return SR_EINVAL;
+    if (B == 0) return SR_OK;
+    if (!gd || !gtotal) return SR_EINVAL;
+    if (B > (1LL << 24)) return SR_ERANGE;
+    hipLaunchKernelGGL(k_fit_loss_rows_bwd, dim3(1), dim3(FIT_LB), 0, sr_stream(stream), gd, gmse, gtotal, pixel_weight,
+                       B);
+    return sr_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // 2 x 2 / stride 2 max pooling of the VGG trunk (torchvision features 4 / 9 / 16 / 23, reference
 // lpips/pretrained_networks.py:97-135) and its gradient, one launch each.  The gradient recomputes the arg-max from the
 // saved input with torch's rule (the first maximum of the window in row-major order wins; a NaN wins) and writes EVERY

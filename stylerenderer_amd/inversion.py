@@ -4,15 +4,23 @@ The reference has no fitting script; its pieces are the generato
 (reference model.py:224-295), the differentiable rasterizer (op/rasterize.py:17-82) and the LPIPS metric
 (lpips/networks_basic.py:27-92).  This module defines the loop BASELINE.json names:
 
-    variables   w [1, n_latent, style_dim]  (W+ latent, initialised at the mean latent)
-                pose [7] = yaw, pitch, roll (rad), tx, ty, tz, log-scale of the 3DMM mesh
-                coeff [1, d] = 3DMM shape + expression coefficients (fit_shape=True only; from 0, the mean face)
+    variables   w [B, n_latent, style_dim]  (W+ latent, initialised at the mean latent)
+                pose [7] = yaw, pitch, roll (rad), tx, ty, tz, log-scale of the 3DMM mesh ([B, 7] when B > 1)
+                coeff [B, d] = 3DMM shape + expression coefficients (fit_shape=True only; from 0, the mean face)
     forward     vertices = v0 @ (exp(s) * R(yaw, pitch, roll)) + t ; normals = n0 @ R
                 image = GeneratorWithMap([w], (vertices, normals, tri), input_is_latent=True, noise=fixed)
                 with fit_shape=True: vertices, normals = op.morph.morph_mesh(face model, coeff, pose, tri)
     loss        LPIPS-shaped distance(image, target) + pixel_weight * mean((image - target)^2)
                 (+ shape_reg * face_model.regulation(coeff), reference face_model.py:73-74, with fit_shape=True)
     update      Adam, `steps` iterations (default 400)
+
+A target [B, 3, H, W] with B > 1 fits B independent images in one iteration (one captured graph): every variable
+carries the batch, the noise is one fixed set broadcast over it, and the objective is sum_b L_b, so each sample's
+gradient is the one it would have alone and the element-wise Adam moves every sample along its own single-image
+trajectory.  Per-sample losses come from op.lpips_layer.mse_rows and fit_loss_rows (one launch each way for the sum of
+the LPIPS layers, the pixel term and the prior); `loss_value` is [B] and `run` returns [steps, B].  B = 1 keeps the
+shapes and launches above.  `reset(target)` re-targets an inverter whose graph is captured: the next `run` computes
+exactly what a fresh inverter on that target would, with no new warm-up or capture.
 
 The pose gradient reaches the vertices only through the rasterizer's backward (deterministic gather, so two
 runs from the same state produce bit-identical trajectories).  On a GPU the whole iteration — forward, backward,
@@ -57,7 +65,9 @@ class LatentInverter:
 
         freeze_prepared_weights(self.g)
         self.device = target.device
-        self.target = target.detach()
+        # (a copy: reset() writes new targets into it under the captured graph)
+        self.target = target.detach().clone()
+        self.batch = int(self.target.shape[0])
         self.fit_shape = bool(fit_shape)
         self.shape_reg = float(shape_reg)
         if self.fit_shape:
@@ -74,10 +84,12 @@ class LatentInverter:
         with torch.no_grad():
             mean_w = self.g.mean_latent(n_mean_latent)                                  # [1, D]
             self.target_feats = [f.detach() for f in self.perceptual.features(self.target)]
-        self.w = mean_w.unsqueeze(1).repeat(1, self.g.n_latent, 1).clone().requires_grad_(True)
-        self.pose = torch.zeros(7, device=self.device, requires_grad=optimise_pose)
-        # 3DMM coefficients [1, d], from the mean face
-        self.coeff = (torch.zeros(1, self.face_model.sigma.numel(), device=self.device, requires_grad=True)
+        self._mean_w = mean_w
+        self.w = mean_w.unsqueeze(1).repeat(self.batch, self.g.n_latent, 1).clone().requires_grad_(True)
+        pose_shape = (7,) if self.batch == 1 else (self.batch, 7)
+        self.pose = torch.zeros(pose_shape, device=self.device, requires_grad=optimise_pose)
+        # 3DMM coefficients [B, d], from the mean face
+        self.coeff = (torch.zeros(self.batch, self.face_model.sigma.numel(), device=self.device, requires_grad=True)
                       if self.fit_shape else None)
         self.noise = noise if noise is not None else [n.detach() for n in self.g.make_noise()]
         on_gpu = self.device.type == "cuda"
@@ -102,7 +114,7 @@ class LatentInverter:
             self.optim = optim.Adam(groups, betas=(0.9, 0.999))
         self.use_graph = on_gpu if use_graph is None else bool(use_graph)
         self.graph = None
-        self.loss_value = torch.zeros((), device=self.device)
+        self.loss_value = torch.zeros(() if self.batch == 1 else (self.batch,), device=self.device)
         self.image = None
 
     # ---- model ----------------------------------------------------------------------------------------
@@ -110,15 +122,16 @@ class LatentInverter:
         """(v, n, tri, reg) of the fitted coefficients and pose (op.morph: one node, no library GEMM on the device)."""
         from .op.morph import morph_mesh
 
-        v, n, reg = morph_mesh(self.face_model, self.coeff, self.pose.view(1, 7), self.tri, self.shape_reg)
+        v, n, reg = morph_mesh(self.face_model, self.coeff, self.pose.view(-1, 7), self.tri, self.shape_reg)
         return v, n, self.tri, reg
 
     def posed_mesh(self):
         if self.fit_shape:
             return self._shape_mesh()[:3]
-        lin, rot = utils_3d.pose_matrices(self.pose)                                    # [1, 3, 3] each
+        lin, rot = utils_3d.pose_matrices(self.pose)                                    # [B, 3, 3] each
         # [nv, 3] x [3, 3]: one streaming kernel each (utils_3d.affine3), not a 3-wide library GEMM
-        v = utils_3d.affine3(self.v0, lin, self.pose[3:6].view(1, 3))
+        t = self.pose[3:6].view(1, 3) if self.batch == 1 else self.pose[:, 3:6]
+        v = utils_3d.affine3(self.v0, lin, t)
         n = utils_3d.affine3(self.n0, rot)
         return v.contiguous(), n.contiguous(), self.tri
 
@@ -142,6 +155,8 @@ class LatentInverter:
         return img
 
     def loss(self, img):
+        if self.batch > 1:
+            return self._loss_rows(img)
         from .op.lpips_layer import mse
 
         d = self.perceptual.distance_to(self.target_feats, img).mean()
@@ -149,6 +164,18 @@ class LatentInverter:
         if self.fit_shape and self.shape_reg != 0.0 and getattr(self, "_reg", None) is not None:
             value = value + self._reg                    # shape_reg * regulation(coeff), from the node's forward
         return value
+
+    def _loss_rows(self, img):
+        """sum_b L_b; the per-sample L_b go to self._rows (one fit_loss_rows node: no per-sample launches)."""
+        from .op.lpips_layer import fit_loss_rows, mse_rows
+
+        layers = self.perceptual.layer_distances(self.target_feats, img)
+        prior = self.fit_shape and self.shape_reg != 0.0 and getattr(self, "_reg", None) is not None
+        self._rows, total = fit_loss_rows(layers, mse_rows(img, self.target), self.pixel_weight,
+                                          coeff=self.coeff if prior else None,
+                                          sigma=self.face_model.sigma if prior else None, shape_reg=self.shape_reg,
+                                          reg=self._reg if prior else None)
+        return total
 
     def _iteration(self):
         self.w.grad = None
@@ -159,7 +186,7 @@ class LatentInverter:
         value = self.loss(img)
         value.backward()
         self.optim.step()
-        self.loss_value.copy_(value.detach())
+        self.loss_value.copy_(value.detach() if self.batch == 1 else self._rows)
         self.image = img.detach()
 
     # ---- driver ---------------------------------------------------------------------------------------
@@ -177,9 +204,35 @@ class LatentInverter:
         self.graph = graphs.capture(self._iteration)      # memset nodes of torch's reductions repaired: graphs.py
         return warmup
 
+    @torch.no_grad()
+    def reset(self, target):
+        """Re-targets the inverter to `target` (the shape of the first): copies it and its LPIPS features into the
+        buffers the captured graph reads, puts w back at the mean latent, pose and coeff at zero, and zeroes the Adam
+        moments and step counts.  `run(steps)` then gives what a fresh inverter on `target` gives (same mean latent,
+        same noise), bit for bit, without a new warm-up or capture."""
+        target = target.detach()
+        if tuple(target.shape) != tuple(self.target.shape):
+            raise ValueError("LatentInverter.reset: target %s, the inverter fits %s"
+                             % (tuple(target.shape), tuple(self.target.shape)))
+        self.target.copy_(target)
+        for buf, f in zip(self.target_feats, self.perceptual.features(self.target)):
+            buf.copy_(f)
+        self.w.copy_(self._mean_w.unsqueeze(1).expand_as(self.w))
+        self.pose.zero_()
+        if self.coeff is not None:
+            self.coeff.zero_()
+        if self._adams is not None:
+            for _, adam in self._adams:
+                for t in (adam.m, adam.v, adam.step_t, adam.flat_g):
+                    t.zero_()
+        else:
+            self.optim.state.clear()                     # torch's Adam initialises its state at the next step
+        self.loss_value.zero_()
+
     def run(self, steps=400):
-        """Runs `steps` Adam iterations; returns the loss history [steps] (device tensor: no host read here)."""
-        history = torch.zeros(steps, device=self.device)
+        """Runs `steps` Adam iterations; returns the loss history [steps] ([steps, B] for B > 1; device tensor: no host
+        read here)."""
+        history = torch.zeros((steps,) if self.batch == 1 else (steps, self.batch), device=self.device)
         done = 0
         if self.use_graph and self.graph is None and steps > 4:
             done = self._warm_and_capture(history)

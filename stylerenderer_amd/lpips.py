@@ -218,16 +218,19 @@ class PNetLin(nn.Module):
         return [spatial_average((((feats0[k] - feats1[k]) ** 2) * lins[k]).sum(1, keepdim=True))
                 for k in range(self.L)]
 
-    def distance_to(self, feats1, in0):
-        """Distance of `in0` to precomputed `features(in1)` (the target of an optimisation is fixed)."""
+    def layer_distances(self, feats1, in0):
+        """The L per-layer terms [B, 1, 1, 1] of `distance_to` (their sum), unsummed."""
         raw = self.net(self.scaling_layer(in0))
         lins = self.lins
         if all(_lpips_layer.supported(raw[k], feats1[k], lins[k]) for k in range(self.L)):
             # device tensors, fixed target and heads: normalisation, squared difference, `lin` and the spatial mean
             # of a layer are one launch forward and one backward (op/lpips_layer.py) instead of ~25
-            res = [_lpips_layer.lpips_layer(raw[k], feats1[k], lins[k]) for k in range(self.L)]
-        else:
-            res = self.per_layer([normalize_tensor(f) for f in raw], feats1)
+            return [_lpips_layer.lpips_layer(raw[k], feats1[k], lins[k]) for k in range(self.L)]
+        return self.per_layer([normalize_tensor(f) for f in raw], feats1)
+
+    def distance_to(self, feats1, in0):
+        """Distance of `in0` to precomputed `features(in1)` (the target of an optimisation is fixed)."""
+        res = self.layer_distances(feats1, in0)
         val = res[0]
         for r in res[1:]:
             val = val + r

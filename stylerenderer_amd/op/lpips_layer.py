@@ -125,3 +125,115 @@ def max_pool2(x):
             and x.shape[3] % 2 == 0 and x.numel() > 0):
         return _MaxPool2.apply(x)
     return torch.nn.functional.max_pool2d(x, 2, 2)
+
+
+# ---- per-sample terms of the batched inversion loss ------------------------------------------------------------------
+class _MSERows(Function):
+    """out[b] = mean((a[b] - t[b])^2) over row b of a [B, ...] -> [B], differentiable once w.r.t. a (sr_mse_rows_fwd:
+    chunk partials and a fixed-order finish; sr_mse_rows_bwd: one launch)."""
+
+    @staticmethod
+    def forward(ctx, a, t):
+        a, t = a.contiguous(), t.contiguous()
+        b = a.shape[0]
+        n = a.numel() // b
+        out = torch.empty(b, dtype=a.dtype, device=a.device)
+        L = _lib.lib()
+        scratch = torch.empty(L.sr_mse_rows_scratch_floats(b, n), dtype=a.dtype, device=a.device)
+        with on_device_of(a):
+            rc = L.sr_mse_rows_fwd(_lib.ptr(out), _lib.ptr(a), _lib.ptr(t), b, n, _lib.ptr(scratch), stream_of(a))
+        _lib.check(rc, "sr_mse_rows_fwd")
+        ctx.save_for_backward(a, t)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a, t = ctx.saved_tensors
+        b = a.shape[0]
+        ga = torch.empty_like(a)
+        with on_device_of(a):
+            rc = _lib.lib().sr_mse_rows_bwd(_lib.ptr(ga), _lib.ptr(g.contiguous()), _lib.ptr(a), _lib.ptr(t), b,
+                                            a.numel() // b, stream_of(a))
+        _lib.check(rc, "sr_mse_rows_bwd")
+        return ga, None
+
+
+def mse_rows(a, t):
+    """((a - t) ** 2) averaged over everything but the first dimension -> [B], t fixed; device float32 tensors take
+    the kernels (`mse` is the batch-wide mean)."""
+    if (a.device.type == "cuda" and a.dtype == torch.float32 and t.dtype == torch.float32 and a.shape == t.shape
+            and a.dim() >= 1 and a.numel() > 0 and not t.requires_grad):
+        return _MSERows.apply(a, t)
+    return ((a - t) ** 2).reshape(a.shape[0], -1).mean(1)
+
+
+class _FitLossRows(Function):
+    """(rows [B], total []) of `fit_loss_rows` in one launch; the backward is one launch that writes the gradient of
+    every layer distance and of the pixel term, and hands `reg` the total's gradient.  `rows` is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, pixel_weight, coeff, sigma, shape_reg, mse, reg, *layers):
+        ctx.set_materialize_grads(False)
+        b = mse.shape[0]
+        rows = torch.empty(b, dtype=mse.dtype, device=mse.device)
+        total = torch.empty((), dtype=mse.dtype, device=mse.device)
+        d = [t.reshape(b).contiguous() for t in layers]
+        m = mse.contiguous()
+        c = coeff.detach().contiguous() if coeff is not None else None
+        s = sigma.detach().contiguous() if sigma is not None else None
+        with on_device_of(m):
+            rc = _lib.lib().sr_fit_loss_rows(_lib.ptr(rows), _lib.ptr(total), *[_lib.ptr(t) for t in d], _lib.ptr(m),
+                                             float(pixel_weight), _lib.ptr(c), _lib.ptr(s), float(shape_reg), b,
+                                             c.shape[1] if c is not None else 0, stream_of(m))
+        _lib.check(rc, "sr_fit_loss_rows")
+        ctx.mark_non_differentiable(rows)
+        ctx.pixel_weight = float(pixel_weight)
+        ctx.layer_shapes = [t.shape for t in layers]
+        ctx.has_reg = reg is not None
+        return rows, total
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_rows, g_total):
+        n_in = 6 + len(ctx.layer_shapes)
+        if g_total is None:
+            return (None,) * n_in
+        b = ctx.layer_shapes[0][0]
+        gd = torch.empty(b, dtype=g_total.dtype, device=g_total.device)
+        gm = torch.empty_like(gd)
+        with on_device_of(gd):
+            rc = _lib.lib().sr_fit_loss_rows_bwd(_lib.ptr(gd), _lib.ptr(gm), _lib.ptr(g_total.contiguous()),
+                                                 ctx.pixel_weight, b, stream_of(gd))
+        _lib.check(rc, "sr_fit_loss_rows_bwd")
+        greg = g_total if ctx.has_reg else None
+        return (None, None, None, None, gm, greg) + tuple(gd.view(s) for s in ctx.layer_shapes)
+
+
+def fit_loss_rows(layers, mse, pixel_weight, coeff=None, sigma=None, shape_reg=0.0, reg=None):
+    """Per-sample losses of a batched fit and their sum:
+
+        rows[b] = sum_k layers[k][b] + pixel_weight * mse[b] (+ shape_reg * sum_j (coeff[b, j] / sigma[j])^2)
+        total   = sum_b rows[b]
+
+    layers: the five LPIPS layer distances ([B] or [B, 1, 1, 1] each), mse [B] (`mse_rows`), coeff [B, d] with the
+    prior.  Returns (rows [B], not differentiable, total []).  On the device the prior's gradient is NOT formed here:
+    `reg`, the scalar shape_reg * regulation(coeff) of op.morph.morph_mesh, receives d(total)/d(reg) and the morph node
+    carries it to the coefficients (reg is required with coeff).  The composite (CPU, float64) differentiates the prior
+    through coeff and does not use reg."""
+    if len(layers) != 5:
+        raise ValueError("fit_loss_rows: five LPIPS layer distances expected, got %d" % len(layers))
+    ts = list(layers) + [mse] + ([coeff] if coeff is not None else [])
+    if all(t.device.type == "cuda" and t.dtype == torch.float32 for t in ts):
+        if coeff is not None and reg is None:
+            raise ValueError("fit_loss_rows: the device node needs the morph node's reg with coeff")
+        return _FitLossRows.apply(float(pixel_weight), coeff, sigma, float(shape_reg), mse, reg, *layers)
+    b = mse.shape[0]
+    rows = layers[0].reshape(b)
+    for t in layers[1:]:
+        rows = rows + t.reshape(b)
+    rows = rows + pixel_weight * mse
+    if coeff is not None:
+        x = coeff / sigma.view(1, -1) if sigma is not None else coeff
+        rows = rows + shape_reg * (x ** 2).sum(1)
+    return rows.detach(), rows.sum()

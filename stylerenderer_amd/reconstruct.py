@@ -2,7 +2,7 @@
 for it):
 
     python -m stylerenderer_amd.reconstruct [--size 256] [--steps 400] [--lr] [--pose_lr] [--coeff_lr] [--shape_reg]
-        [--bfm BFM.mat] [--lpips-trunk VGG16.pth] [--gpu 0] [--seed S] [--out DIR] CHECKPOINT IMAGE [IMAGE ...]
+        [--bfm BFM.mat] [--lpips-trunk VGG16.pth] [--batch N] [--gpu 0] [--seed S] [--out DIR] CHECKPOINT IMAGE [IMAGE ...]
 
 For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with inversion.LatentInverter(fit_shape=True)
 — the W+ latent, a rigid pose and the 3DMM shape / expression coefficients are fitted together (op.morph on the device)
@@ -13,6 +13,11 @@ For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with in
     <stem>_render.png     the generator's image of the fit
     <stem>_normal.png     the rasterised normal map of the posed mesh
     <stem>.npz            w, coeff, pose and the loss history
+
+With --batch N the images are fitted N at a time, each group as one batched LatentInverter (one captured graph; every
+image still follows its own single-image optimisation): the first group builds the inverter, the following ones
+re-target it with `reset`, and a short last group is padded with copies of its last image whose results are dropped.
+The files and their shapes are those of --batch 1, the default, which fits one image per inverter.
 
 Images are PNG / JPG (PIL) or .npy in [-1, 1] (HWC or CHW), resized on the host.  The 3DMM is the Basel Face Model with
 --bfm (face_model.load_bfm), else the synthetic model `train --mesh` trains with (train.SyntheticFaceSource).  Without
@@ -75,24 +80,42 @@ def reconstruct(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr
     return inv, hist.cpu().numpy()
 
 
-def write_outputs(inv, hist, out_dir, stem):
+def reconstruct_batch(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr=0.01, shape_reg=0.0,
+                      n_mean_latent=4096, inv=None):
+    """Fits the B images of target [B, 3, H, W] together; `inv` (an inverter of the same batch from an earlier call) is
+    re-targeted instead of built anew.  Returns the inverter and the loss history [steps, B] (host)."""
+    if inv is None:
+        inv = inversion.LatentInverter(g, percept, target, None, lr=lr, pose_lr=pose_lr, n_mean_latent=n_mean_latent,
+                                       face=face, fit_shape=True, coeff_lr=coeff_lr, shape_reg=shape_reg)
+    else:
+        inv.reset(target)
+    hist = inv.run(steps)
+    return inv, hist.cpu().numpy().reshape(steps, -1)
+
+
+def write_outputs(inv, hist, out_dir, stem, index=0):
+    """The five files of sample `index` of the inverter (hist: its loss history [steps])."""
     from .op.morph import morph_mesh
     from .op.rasterize import rasterize
 
+    k = slice(index, index + 1)
     v, n, tri = inv.fitted_mesh()
+    v, n = v[k], n[k]
+    coeff = inv.coeff.detach()[k]
+    pose = inv.pose.detach().view(-1, 7)[index]
     with torch.no_grad():
-        zero = torch.zeros_like(inv.pose).view(1, 7)
-        vc, nc, _ = morph_mesh(inv.face_model, inv.coeff.detach(), zero, tri)
+        zero = torch.zeros_like(pose).view(1, 7)
+        vc, nc, _ = morph_mesh(inv.face_model, coeff, zero, tri)
         size = int(inv.target.shape[-1])
         normal_map = rasterize(v.contiguous(), n.contiguous(), tri, size, size, channel_major=True)
     tri_h = tri.cpu().numpy()
     utils_3d.save_obj(os.path.join(out_dir, stem + ".obj"), v[0].cpu().numpy(), tri_h, vn=n[0].cpu().numpy())
     utils_3d.save_obj(os.path.join(out_dir, stem + "_canonical.obj"), vc[0].cpu().numpy(), tri_h,
                       vn=nc[0].cpu().numpy())
-    generate.save_image(inv.image.cpu(), os.path.join(out_dir, stem + "_render.png"))
+    generate.save_image(inv.image[k].cpu(), os.path.join(out_dir, stem + "_render.png"))
     generate.save_image(normal_map.cpu(), os.path.join(out_dir, stem + "_normal.png"))
-    np.savez(os.path.join(out_dir, stem + ".npz"), w=inv.w.detach().cpu().numpy(),
-             coeff=inv.coeff.detach().cpu().numpy(), pose=inv.pose.detach().cpu().numpy(), loss=hist)
+    np.savez(os.path.join(out_dir, stem + ".npz"), w=inv.w.detach()[k].cpu().numpy(), coeff=coeff.cpu().numpy(),
+             pose=pose.cpu().numpy(), loss=hist)
 
 
 def main(argv=None):
@@ -108,12 +131,16 @@ def main(argv=None):
     ap.add_argument("--lpips-trunk", default=None, metavar="PATH",
                     help="torchvision vgg16 (or vgg16().features) state dict for the LPIPS trunk")
     ap.add_argument("--n_mean_latent", type=int, default=4096, help="latents averaged for the starting W+ [%(default)d]")
+    ap.add_argument("--batch", type=int, default=1,
+                    help="images fitted together in one batched inverter (one captured graph) [%(default)d]")
     ap.add_argument("--gpu", type=int, default=0, help="use gpu id")
     ap.add_argument("--seed", type=int, default=0, help="random seed (mean latent, noise)")
     ap.add_argument("--out", default="reconstruct", metavar="DIR", help="output directory [%(default)s]")
     ap.add_argument("ckpt", metavar="CHECKPOINT", help="checkpoint holding g_ema of a GeneratorWithMap")
     ap.add_argument("images", metavar="IMAGE", nargs="+", help="PNG / JPG, or .npy in [-1, 1] (HWC or CHW)")
     args = ap.parse_args(argv)
+    if args.batch < 1:
+        ap.error("--batch must be at least 1")
     torch.manual_seed(args.seed)
     if torch.cuda.is_available() and 0 <= args.gpu < torch.cuda.device_count():
         device = torch.device("cuda:%d" % args.gpu)
@@ -132,15 +159,31 @@ def main(argv=None):
     face = face_model(args.bfm, device, seed=args.seed)
     os.makedirs(args.out, exist_ok=True)
     results = []
-    for path in args.images:
-        stem = os.path.splitext(os.path.basename(path))[0]
-        target = load_image(path, args.size).to(device)
-        inv, hist = reconstruct(g, percept, face, target, args.steps, args.lr, args.pose_lr, args.coeff_lr,
-                                args.shape_reg, args.n_mean_latent)
-        write_outputs(inv, hist, args.out, stem)
-        print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f" % (
-            path, float(hist[0]), float(hist[-1]), len(hist), float(inv.coeff.detach().norm())), flush=True)
-        results.append((stem, hist))
+    if args.batch == 1:
+        for path in args.images:
+            stem = os.path.splitext(os.path.basename(path))[0]
+            target = load_image(path, args.size).to(device)
+            inv, hist = reconstruct(g, percept, face, target, args.steps, args.lr, args.pose_lr, args.coeff_lr,
+                                    args.shape_reg, args.n_mean_latent)
+            write_outputs(inv, hist, args.out, stem)
+            print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f" % (
+                path, float(hist[0]), float(hist[-1]), len(hist), float(inv.coeff.detach().norm())), flush=True)
+            results.append((stem, hist))
+        return results
+    inv = None
+    for start in range(0, len(args.images), args.batch):
+        group = args.images[start:start + args.batch]
+        targets = [load_image(path, args.size) for path in group]
+        targets += targets[-1:] * (args.batch - len(group))          # padding: fitted, then discarded
+        inv, hist = reconstruct_batch(g, percept, face, torch.cat(targets, 0).to(device), args.steps, args.lr,
+                                      args.pose_lr, args.coeff_lr, args.shape_reg, args.n_mean_latent, inv=inv)
+        for i, path in enumerate(group):
+            stem = os.path.splitext(os.path.basename(path))[0]
+            h = np.ascontiguousarray(hist[:, i])
+            write_outputs(inv, h, args.out, stem, index=i)
+            print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f" % (
+                path, float(h[0]), float(h[-1]), len(h), float(inv.coeff.detach()[i].norm())), flush=True)
+            results.append((stem, h))
     return results
 
 

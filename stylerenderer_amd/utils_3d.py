@@ -161,12 +161,46 @@ class _PoseMatrices(Function):
         return gp
 
 
+class _PoseBatchMatrices(Function):
+    """(lin, rot) [B, 3, 3] from pose [B, 7] on the device path: sr_pose_batch_fwd forward, sr_morph_pose_bwd (without
+    the translation's gradient, which is affine3's: entries 3..5 are 0) backward, one launch each."""
+
+    @staticmethod
+    def forward(ctx, pose):
+        pc = pose.contiguous()
+        b = pc.shape[0]
+        lin = torch.empty((b, 3, 3), dtype=pc.dtype, device=pc.device)
+        rot = torch.empty_like(lin)
+        with on_device_of(pc):
+            _lib.check(_lib.lib().sr_pose_batch_fwd(_lib.ptr(lin), _lib.ptr(rot), _lib.ptr(pc), b, stream_of(pc)),
+                       "sr_pose_batch_fwd")
+        ctx.save_for_backward(pc)
+        return lin, rot
+
+    @staticmethod
+    def backward(ctx, glin, grot):
+        (pc,) = ctx.saved_tensors
+        gp = torch.empty_like(pc)
+        gl = glin.contiguous() if glin is not None else None
+        gr = grot.contiguous() if grot is not None else None
+        with on_device_of(pc):
+            _lib.check(_lib.lib().sr_morph_pose_bwd(_lib.ptr(gp), _lib.ptr(gl), _lib.ptr(gr), None, _lib.ptr(pc),
+                                                    pc.shape[0], stream_of(pc)), "sr_morph_pose_bwd")
+        return gp
+
+
 def pose_matrices(pose):
     """pose [7] = (yaw, pitch, roll, tx, ty, tz, log-scale) -> (lin, rot), each [1, 3, 3]: rot = euler_mat(pose[:3],
-    "yxz"), lin = exp(pose[6]) * rot.  Device fp32: one launch forward, one backward (first order); otherwise the
-    tensor algebra it stands for."""
-    if pose.device.type == "cuda" and pose.dtype == torch.float32 and pose.numel() == 7:
-        return _PoseMatrices.apply(pose)
+    "yxz"), lin = exp(pose[6]) * rot; pose [B, 7] -> [B, 3, 3] each.  Device fp32: one launch forward, one backward
+    (first order); otherwise the tensor algebra it stands for."""
+    if pose.device.type == "cuda" and pose.dtype == torch.float32:
+        if pose.numel() == 7:
+            return _PoseMatrices.apply(pose)
+        if pose.dim() == 2 and pose.shape[1] == 7:
+            return _PoseBatchMatrices.apply(pose)
+    if pose.dim() == 2:
+        rot = euler_mat(pose[:, :3], "yxz")
+        return torch.exp(pose[:, 6]).view(-1, 1, 1) * rot, rot
     rot = euler_mat(pose[:3].view(1, 3), "yxz")
     return torch.exp(pose[6]) * rot, rot
 
