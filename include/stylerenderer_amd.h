@@ -224,6 +224,35 @@ int sr_morph_gcoeff(float* gcoeff, float* scratch, const float* w, const float* 
 int sr_morph_pose_bwd(float* gpose, const float* glin, const float* grot, const float* gt, const float* pose, int64_t B,
                       sr_stream_t stream);
 
+/* Skinning node of face reconstruction (csrc/skin.hip; reference face_model.py:313-341 LinearBlendSkinningModel, utils_3d.py
+ * rodrigues).  nj joints of which the first nroot are roots, np = nj - nroot, parent [np] (parent before child);
+ * coeff [B, ds + 3 np] = shape, then one axis-angle per moving joint; pose [B, 7] as above or NULL (no global pose);
+ * j0 [nj, 3] = Jreg v_template, js [3 nj, ds] = Jreg S[:ds]; sigma [ds] and pose_inv [np, 3, 3] of the prior (NULL: 1 / I);
+ * st [3 nv, D] = the stacked basis transposed, D = ds + 9 np; vt [3 nv] the template; wts [nv, nj] the skinning weights.
+ * nj <= 32, else SR_ERANGE.
+ * sr_skin_joints_fwd: cx [B, D] = [shape, vec(R_i - I)], chain [B, nj, 15] = (A_i, t_i, J_i) of the kinematic chain,
+ *   G [B, nj, 12] = [A_i lin ; (t_i - J_i A_i) lin + t] with the global pose folded in, reg (may be NULL) = lam *
+ *   regulation(coeff).  One launch for all B.
+ * sr_skin_fwd: vp[b] = (vt + st cx[b]).view(nv, 3) and v[b, k] = vp[b, k] (sum_i wts[k, i] G[b, i, :3]) + sum_i wts[k, i]
+ *   G[b, i, 3]; one pass over st per slice of floor(12288 / (D + 12 nj)) samples (D + 12 nj <= 12288, else SR_ERANGE).
+ * sr_skin_bwd: with g = gv + gvn (gvn may be NULL), gvp[b, k] = g M_k^T and part [B, ceil(nv / 256), nj, 12] = the
+ *   per-workgroup sums of wts[k, i] [vp_k^T g ; g] (sr_skin_bwd_scratch_floats floats), in a fixed order.
+ * sr_skin_joints_bwd: sums part over its nblk workgroups in order, then the adjoints of the pose fold, the chain, the
+ *   joint regressor and rodrigues: gcoeff [B, ds + 3 np] from gcx [B, D] (sr_morph_gcoeff of st and gvp) plus 2 lam
+ *   greg[0] times the prior's gradient (greg: device scalar, may be NULL), and gpose [B, 7] (may be NULL). */
+int sr_skin_joints_fwd(float* cx, float* G, float* chain, float* reg, const float* coeff, const float* pose,
+                       const float* j0, const float* js, const int32_t* parent, const float* sigma, const float* pose_inv,
+                       float lam, int64_t B, int64_t nj, int64_t nroot, int64_t ds, sr_stream_t stream);
+int sr_skin_fwd(float* v, float* vp, const float* st, const float* vt, const float* cx, const float* wts, const float* G,
+                int64_t B, int64_t nv, int64_t D, int64_t nj, sr_stream_t stream);
+int64_t sr_skin_bwd_scratch_floats(int64_t nv, int64_t B, int64_t nj);
+int sr_skin_bwd(float* gvp, float* part, const float* gv, const float* gvn, const float* vp, const float* wts,
+                const float* G, int64_t B, int64_t nv, int64_t nj, sr_stream_t stream);
+int sr_skin_joints_bwd(float* gcoeff, float* gpose, const float* gcx, const float* part, const float* coeff,
+                       const float* pose, const float* chain, const float* js, const int32_t* parent, const float* sigma,
+                       const float* pose_inv, float lam, const float* greg, int64_t B, int64_t nblk, int64_t nj,
+                       int64_t nroot, int64_t ds, sr_stream_t stream);
+
 /* Pose parameters of the inversion loop, pose = (yaw, pitch, roll, tx, ty, tz, log-scale): rot [3,3] = Rz(roll) Rx(pitch)
  * Ry(yaw) (utils_3d.euler_mat(angles, "yxz"), row-major), lin = exp(log-scale) * rot; sr_pose_bwd: gradient of the seven
  * numbers from the gradients of the two matrices (either may be NULL; entries 3..5 are written as 0: the translation's

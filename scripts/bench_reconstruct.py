@@ -2,7 +2,7 @@
 against the pose-only inversion (BASELINE config[4]) at 256^2 on the face-sized synthetic 3DMM (d = 80 + 64), and the
 device time of the morphable-mesh node's kernels (csrc/morph.hip).
 
-    python scripts/bench_reconstruct.py [--steps 100] [--rounds 3] [--reps 50] [--batch 1,4,8,16]
+    python scripts/bench_reconstruct.py [--steps 100] [--rounds 3] [--reps 50] [--batch 1,4,8,16] [--face morph|flame]
 
 One JSON line per measurement:
   * inversion: replayed steps/s of both inverters in the same process (hipGraph replays, alternated in --rounds rounds
@@ -16,6 +16,11 @@ One JSON line per measurement:
 With --batch B1,B2,... only the batched fit-shape inverter is measured instead (one line per batch size): B images in one
 captured step, replayed --steps times per round, --rounds rounds, the median round; replayed ms per step, image-steps/s
 (B steps per replay) and kernel nodes per captured step.
+
+With --face flame the skinned fit (op.skin on train.synthetic_flame_dict: the same mesh, shape_dim 144, five joints in
+FLAME's tree) is measured against the linear fit-shape step in the same process, rounds alternated, the median round:
+steps/s and kernel nodes of both, their ratio, and the warm device time per call of the node's new kernels
+(sr_skin_joints_fwd, sr_skin_fwd, sr_skin_bwd, sr_skin_joints_bwd).
 """
 import argparse
 import json
@@ -170,6 +175,75 @@ def bench_kernels(reps):
                               "share_of_8TBps": round(nbytes / t / HBM_BYTES_PER_S, 3)}), flush=True)
 
 
+def bench_flame(size, steps, rounds, reps):
+    from stylerenderer_amd import face_model
+    from stylerenderer_amd.op import skin
+
+    invs, _, _ = make_inverters(size)
+    base = invs.pop("pose_only")
+    g, net, noise, target = base.g, base.perceptual, base.noise, base.target
+    del base
+    fm, tri = face_model.load_flame(train.synthetic_flame_dict())
+    fm, tri = fm.to(DEV), tri.to(DEV)
+    torch.manual_seed(11)
+    invs["fit_flame"] = inversion.LatentInverter(g, net, target, None, lr=0.05, pose_lr=0.01, noise=noise,
+                                                 n_mean_latent=4096, use_graph=True, face=(fm, tri), fit_shape=True,
+                                                 coeff_lr=0.05, shape_reg=1e-3)
+    for inv in invs.values():
+        inv.run(8)
+        torch.cuda.synchronize()
+    rates = {k: [] for k in invs}
+    for _ in range(rounds):
+        for k, inv in invs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(steps):
+                inv.graph.replay()
+            b.record()
+            torch.cuda.synchronize()
+            rates[k].append(steps * 1000.0 / a.elapsed_time(b))
+    out = {"what": "inversion_flame", "size": size, "steps_per_round": steps, "rounds": rounds}
+    for k, inv in invs.items():
+        out[k + "_steps_per_s"] = round(statistics.median(rates[k]), 2)
+        out[k + "_rounds"] = [round(r, 2) for r in rates[k]]
+        out[k + "_kernel_nodes"] = inv.graph.kernel_nodes
+    out["ratio_flame_over_morph"] = round(out["fit_flame_steps_per_s"] / out["fit_shape_steps_per_s"], 4)
+    out["extra_kernel_nodes"] = out["fit_flame_kernel_nodes"] - out["fit_shape_kernel_nodes"]
+    print(json.dumps(out), flush=True)
+    # the node's new kernels, warm
+    b = 1
+    stt, tmpl, wts, j0, js, parent, sigma, pinv = skin._native_args(fm)
+    nv, nj, ds = tmpl.numel() // 3, j0.shape[0], fm.dim[0]
+    dfull = stt.shape[1]
+    c = torch.from_numpy(synth.det_normal((b, ds + 3 * (nj - 1)), 8)).to(DEV) * 0.2
+    pose = torch.tensor([[0.2, -0.1, 0.05, 0.01, 0.02, 0.0, 0.1]], device=DEV)
+    L, ptr, st = _lib.lib(), _lib.ptr, _lib.current_stream(DEV)
+    cx, tg, chain = torch.empty(b, dfull, device=DEV), torch.empty(b, nj, 12, device=DEV), torch.empty(b, nj, 15, device=DEV)
+    reg, greg = torch.empty((), device=DEV), torch.ones((), device=DEV)
+    v, vp, gvp = (torch.empty(b, nv, 3, device=DEV) for _ in range(3))
+    gv, gvn = torch.randn(b, nv, 3, device=DEV), torch.randn(b, nv, 3, device=DEV)
+    nblk = (nv + 255) // 256
+    part = torch.empty(int(L.sr_skin_bwd_scratch_floats(nv, b, nj)), device=DEV)
+    gcx, gc, gp = torch.randn(b, dfull, device=DEV), torch.empty_like(c), torch.empty_like(pose)
+    calls = {
+        "sr_skin_joints_fwd": lambda: L.sr_skin_joints_fwd(ptr(cx), ptr(tg), ptr(chain), ptr(reg), ptr(c), ptr(pose),
+                                                           ptr(j0), ptr(js), ptr(parent), ptr(sigma), ptr(pinv), 1e-3, b,
+                                                           nj, 1, ds, st),
+        "sr_skin_fwd": lambda: L.sr_skin_fwd(ptr(v), ptr(vp), ptr(stt), ptr(tmpl), ptr(cx), ptr(wts), ptr(tg), b, nv,
+                                             dfull, nj, st),
+        "sr_skin_bwd": lambda: L.sr_skin_bwd(ptr(gvp), ptr(part), ptr(gv), ptr(gvn), ptr(vp), ptr(wts), ptr(tg), b, nv,
+                                             nj, st),
+        "sr_skin_joints_bwd": lambda: L.sr_skin_joints_bwd(ptr(gc), ptr(gp), ptr(gcx), ptr(part), ptr(c), ptr(pose),
+                                                           ptr(chain), ptr(js), ptr(parent), ptr(sigma), ptr(pinv), 1e-3,
+                                                           ptr(greg), b, nblk, nj, 1, ds, st),
+    }
+    for name, fn in calls.items():
+        _lib.check(fn(), name)
+        t = event_time(fn, reps)
+        print(json.dumps({"what": "kernel", "name": name, "cache": "warm", "nv": nv, "D": dfull, "nj": nj, "B": b,
+                          "us": round(t * 1e6, 2)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=256)
@@ -178,8 +252,13 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--batch", default=None, metavar="B1,B2,...",
                     help="measure the batched fit-shape inverter at these batch sizes instead")
+    ap.add_argument("--face", choices=("morph", "flame"), default="morph",
+                    help="flame: the skinned fit against the linear fit-shape step, and the skinning kernels")
     args = ap.parse_args()
     os.environ.setdefault("SR_STRICT_NATIVE", "1")
+    if args.face == "flame":
+        bench_flame(args.size, args.steps, args.rounds, args.reps)
+        return
     if args.batch:
         bench_batches(args.size, [int(x) for x in args.batch.split(",")], args.steps, args.rounds)
         return

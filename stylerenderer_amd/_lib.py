@@ -129,6 +129,11 @@ SIGNATURES = {
     "sr_morph_gcoeff_scratch_floats": (_l, [_l, _l, _l]),
     "sr_morph_gcoeff": (_i, [_p] * 6 + [_f, _p, _l, _l, _l, _p]),
     "sr_morph_pose_bwd": (_i, [_p] * 5 + [_l, _p]),
+    "sr_skin_joints_fwd": (_i, [_p] * 11 + [_f] + [_l] * 4 + [_p]),
+    "sr_skin_fwd": (_i, [_p] * 7 + [_l] * 4 + [_p]),
+    "sr_skin_bwd_scratch_floats": (_l, [_l, _l, _l]),
+    "sr_skin_bwd": (_i, [_p] * 7 + [_l] * 3 + [_p]),
+    "sr_skin_joints_bwd": (_i, [_p] * 11 + [_f, _p] + [_l] * 5 + [_p]),
     "sr_signal_bump": (_i, [_p, _p]),
     "sr_signal_wait": (_i, [_p, ctypes.c_uint32, _p]),
     "sr_signal_set": (_i, [_p, _p, _p]),

@@ -36,6 +36,7 @@ SOURCES = [
     ("bank_mm.hip", EXACT),
     ("mesh.hip", EXACT),
     ("morph.hip", []),
+    ("skin.hip", []),
     ("lpips.hip", EXACT),
     ("ppl.hip", EXACT),
     ("augment.hip", EXACT),

@@ -1,7 +1,11 @@
-"""3D morphable model in front of the rasterizer — same class name, constructor arguments,
-parameter names (`fc.weight`, `fc.bias`, `sigma`) and methods as reference face_model.py:4-74, so
-its checkpoints load unchanged.  Vertices = fc(coefficients).view(B, nv, 3): one [B, d] x [d, 3 nv]
-GEMM (d = shape + expression dims), a library call on the device."""
+"""Face models in front of the rasterizer.
+
+LinearMorphableModel — same class name, constructor arguments, parameter names (`fc.weight`, `fc.bias`, `sigma`) and
+methods as reference face_model.py:4-74, so its checkpoints load unchanged.  Vertices = fc(coefficients).view(B, nv, 3):
+one [B, d] x [d, 3 nv] GEMM (d = shape + expression dims), a library call on the device.
+
+LinearBlendSkinningModel / load_flame — the skinned, articulated model (FLAME: neck, jaw, eyeballs) of reference
+face_model.py:146-341 and 378-408; on the device its forward is the skinning node's kernels (op/skin.py)."""
 import numpy as np
 import torch
 from torch import nn
@@ -98,4 +102,211 @@ def load_bfm(file_name="/data/BaselFaceModel.mat"):
     if tri.shape[0] == 3 and tri.shape[1] != 3:
         tri = tri.T
     model = LinearMorphableModel(len(v), w_shape.shape[1], w_exp.shape[1], v, w_shape, w_exp)
+    return model, torch.from_numpy(np.ascontiguousarray(tri))
+
+
+def _is_diagonal(cov):
+    return bool((cov - torch.diag_embed(torch.diagonal(cov, dim1=-2, dim2=-1))).abs().max() == 0) if cov.numel() else True
+
+
+class LinearBlendSkinningModel(nn.Module):
+    """Linear blend skinning over a shape basis with pose-corrective blendshapes (reference face_model.py:146-341): same
+    constructor arguments, attributes (`dim` = [shape_dim, 3 (nj - 1), 3 nv], `parent`, `fc` = [S, v], `weight` =
+    [W, Jreg], `sigma`, `pose_mean`, `pose_cov`, `pose_inv`), methods and state-dict keys (`sigma`, `pose_mean`,
+    `pose_cov`: the four arrays are outside it, as in the reference, so its checkpoints load).  Unlike the reference's
+    Python lists the arrays are non-persistent buffers, so `.to()` moves them; `learnable=True` makes them require
+    gradients (leaves for as long as the model is not moved).
+
+    Three defects of the reference's constructor are not reproduced:
+    * its re-ordering of a `kintree_table` that is not parent-before-child reads `j`, `w`, `s` before they exist (lines
+      180-188) and cannot run.  Tables in parent-before-child order (FLAME's) are supported, others raise ValueError.
+      The root's parent may be any value outside [0, nj): -1, or 2^32 - 1 in FLAME's uint32 table.
+    * the number of `posedirs` rows copied is taken from `shapedirs` (line 222); here from `posedirs`.
+    * without `weights` it needs scikit-learn for the nearest joint (lines 247-252); here the same weight
+      exp(-d^2 / d_max^2) on the nearest joint comes from a brute-force argmin (nj is tiny)."""
+
+    def __init__(self, vertices_num, pose_nodes=1, shape_dim=0, v_template=None, J_regressor=None, kintree_table=None,
+                 weights=None, posedirs=None, shapedirs=None, sigma_shape=1, sigma_pose=1, mean_pose=0, learnable=False):
+        super().__init__()
+        nv = max(int(vertices_num), 1)
+        ds = max(int(shape_dim), 0)
+        nj = max(int(pose_nodes), 1)
+        if kintree_table is not None:
+            kt = np.asarray(kintree_table).astype(np.int64)
+            if kt.ndim == 1:
+                if len(kt) == nj - 1:
+                    kt = np.concatenate(([-1], kt))
+                kt = np.vstack((kt, np.arange(nj)))
+            elif kt.shape[1] == 2 and kt.shape[0] == nj:
+                kt = kt.T
+            par = kt[0]
+            root = np.logical_or(par < 0, par >= nj)
+            k = int(root.sum())
+            ok = (kt.shape[1] == nj and np.array_equal(kt[1], np.arange(nj)) and k >= 1 and root[:k].all()
+                  and all(par[c] < c for c in range(k, nj)))
+            if not ok:
+                raise ValueError("LinearBlendSkinningModel: kintree_table must list the joints 0..%d in order, roots "
+                                 "first and every parent before its children" % (nj - 1))
+            self.parent = par[k:].copy()
+        else:
+            self.parent = np.zeros(nj - 1, np.int64)
+        npose = len(self.parent)
+        scale = np.sqrt(ds + npose * 9)
+        # random model when no data is given (reference face_model.py:191-196)
+        v = (np.random.rand(nv * 3).astype(np.float32) * 2 - 1) * scale
+        s = (np.random.rand(ds + (nj - 1) * 9, v.shape[0]).astype(np.float32) * 2 - 1) * scale
+        j = (np.random.rand(nj, nv).astype(np.float32) * 2 - 1) * np.sqrt(nj)
+        if v_template is not None:
+            m = np.array(v_template, np.float32)
+            if m.shape[0] == 3:
+                m = m.reshape(3, -1).T
+            elif m.ndim > 1:
+                m = m.reshape(-1, m.shape[-1])
+            else:
+                m = m.reshape(-1, 3)
+            n = min(nv, m.shape[0])
+            v[:3 * n] = m[:n, :3].reshape(-1)
+        if shapedirs is not None:
+            b = _as_basis(shapedirs, s.shape[1], ds)
+            d, n = min(ds, b.shape[0]), min(nv, b.shape[1] // 3)
+            s[:d, :3 * n] = b[:d, :3 * n]
+        if posedirs is not None:
+            b = _as_basis(posedirs, s.shape[1], npose * 9)
+            d, n = min(npose * 9, b.shape[0]), min(nv, b.shape[1] // 3)
+            s[ds:ds + d, :3 * n] = b[:d, :3 * n]
+        if J_regressor is not None:
+            if hasattr(J_regressor, "todense"):
+                jr = np.asarray(J_regressor.astype(np.float32).todense())
+            else:
+                jr = np.array(J_regressor, np.float32)
+            if jr.shape[1] == nj and jr.shape[0] >= nv:
+                jr = jr.T
+            m, n = min(nj, jr.shape[0]), min(nv, jr.shape[1])
+            j[:m, :n] = jr[:m, :n]
+        w = np.zeros((nv, nj), np.float32)
+        if weights is not None:
+            ws = np.array(weights, np.float32)
+            if ws.shape[0] == nj and ws.shape[1] >= nv:
+                ws = ws.T
+            m, n = min(nj, ws.shape[1]), min(nv, ws.shape[0])
+            w[:n, :m] = ws[:n, :m]
+        else:
+            joints = j.dot(v.reshape(-1, 3))
+            d2 = ((v.reshape(-1, 1, 3) - joints.reshape(1, -1, 3)) ** 2).sum(2)
+            idx = d2.argmin(1)
+            dis = np.sqrt(d2[np.arange(nv), idx])
+            w[np.arange(nv), idx] = np.exp(-dis * dis / (dis.max() * dis.max()))
+        w = abs(w)
+        w = w / np.maximum(w.sum(1).reshape(-1, 1), 1e-5)
+
+        def flat(src):
+            return [] if src is None else [float(x) for x in np.reshape(src, -1)]
+
+        def padded(src, count, default, f=lambda x: x):
+            return [f(src[i]) if len(src) > i else (f(src[-1]) if src else default) for i in range(count)]
+
+        sigma_shape, sigma_pose, mean_pose = flat(sigma_shape), flat(sigma_pose), flat(mean_pose)
+        self.dim = [ds, npose * 3, nv * 3]
+        self.register_buffer("_basis", torch.from_numpy(s).float(), persistent=False)
+        self.register_buffer("_template", torch.from_numpy(v).float(), persistent=False)
+        self.register_buffer("_skin_weights", torch.from_numpy(w).float(), persistent=False)
+        self.register_buffer("_joint_regressor", torch.from_numpy(j).float(), persistent=False)
+        self.register_buffer("_parent", torch.from_numpy(np.asarray(self.parent, np.int32)), persistent=False)
+        self.sigma = nn.Parameter(torch.tensor(padded(sigma_shape, ds, 1, abs) + [1.0] * (npose * 3), dtype=torch.float32),
+                                  requires_grad=False)
+        if len(mean_pose) <= npose:
+            mean = np.repeat(np.array(padded(mean_pose, npose, 0), np.float32), 3)
+        else:
+            mean = np.array(padded(mean_pose, npose * 3, 0), np.float32)
+        self.pose_mean = nn.Parameter(torch.from_numpy(mean).float().reshape(-1), requires_grad=False)
+        if len(sigma_pose) <= npose:
+            cov = torch.stack([x * torch.eye(3) for x in padded(sigma_pose, npose, 1)]) if npose else torch.zeros(0, 3, 3)
+        elif len(sigma_pose) <= npose * 3:
+            cov = torch.diag_embed(torch.tensor(padded(sigma_pose, npose * 3, 1), dtype=torch.float32).view(-1, 3))
+        else:
+            full = [sigma_pose[i] if len(sigma_pose) > i else float((i % 9) % 4 == 0) for i in range(npose * 9)]
+            cov = torch.tensor(full, dtype=torch.float32).view(-1, 3, 3)
+        self.pose_cov = nn.Parameter(cov.float(), requires_grad=False)
+        self.register_buffer("pose_inv", torch.inverse(self.pose_cov.detach()) if npose else cov.clone(), persistent=False)
+        self.learnable = bool(learnable)
+        if learnable:
+            for t in self.fc + self.weight:
+                t.requires_grad_(True)
+
+    # the reference's list attributes
+    @property
+    def fc(self):
+        return [self._basis, self._template]
+
+    @property
+    def weight(self):
+        return [self._skin_weights, self._joint_regressor]
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        if self.pose_cov.numel():
+            self.pose_inv = torch.inverse(self.pose_cov.detach())
+
+    def effective_sigma(self):
+        """[sigma_shape, diag(pose_cov)]: regulation(x) == sum (x / effective_sigma)^2 when pose_cov is diagonal."""
+        return torch.cat([self.sigma.detach()[:self.dim[0]], torch.diagonal(self.pose_cov.detach(), dim1=1, dim2=2).reshape(-1)])
+
+    def pose_cov_is_diagonal(self):
+        return _is_diagonal(self.pose_cov.detach())
+
+    def random_input(self, batch_size=1):
+        # randn * sigma like LinearMorphableModel.random_input (no host-side check: usable under graph capture), then the
+        # reference's per-joint x_i @ pose_cov[i] + pose_mean[i] (face_model.py:306-312)
+        x = torch.randn(batch_size, self.sigma.shape[0], device=self.sigma.device, dtype=self.sigma.dtype) * self.sigma
+        ds = self.dim[0]
+        if self.dim[1] == 0:
+            return x
+        th = (x[:, ds:].reshape(batch_size, -1, 1, 3) * self.pose_cov.permute(0, 2, 1).unsqueeze(0)).sum(3)
+        return torch.cat([x[:, :ds], th.reshape(batch_size, -1) + self.pose_mean.view(1, -1)], 1)
+
+    def forward(self, x):
+        from .op import skin
+
+        return skin.skin_vertices(self, x)
+
+    def regulation(self, x):
+        ds = self.dim[0]
+        l_shape = ((x[:, :ds] / self.sigma[np.newaxis, :ds]) ** 2).sum()
+        if self.dim[1] == 0:
+            return l_shape
+        y = (x[:, ds:].reshape(x.shape[0], -1, 3, 1) * self.pose_inv.to(x.dtype).unsqueeze(0)).sum(2)
+        return l_shape + (y ** 2).sum()
+
+
+def load_flame(file_name="/data/flame/generic_model.mat"):
+    """FLAME -> (LinearBlendSkinningModel, tri int64 [nf, 3]) with the reference's contract (face_model.py:378-408):
+    `file_name` is a `.pkl` (pickle, latin1), a `.mat`, or an already loaded dict with the keys `v_template` [nv, 3],
+    `shapedirs` [nv, 3, ds], `posedirs` [nv, 3, 9 (nj - 1)], `J_regressor` [nj, nv] (dense or scipy sparse),
+    `kintree_table` [2, nj], `weights` [nv, nj] and `f` [nf, 3].  The pose prior's sigmas are the reference's neck / jaw /
+    eye values in degrees (pitch, yaw, roll).  The licensed file is not distributed."""
+    if isinstance(file_name, str):
+        if file_name.endswith(".pkl"):
+            import pickle
+
+            with open(file_name, "rb") as f:
+                data = pickle.load(f, encoding="latin1")
+        elif file_name.endswith(".mat"):
+            import scipy.io as sio
+
+            data = sio.loadmat(file_name)
+        else:
+            raise ValueError("load_flame: %r is neither .pkl nor .mat" % (file_name,))
+    else:
+        data = file_name
+    neck, jaw, eye = [10, 30, 5], [10, 1, 1], [10, 10, 1e-5]
+    sigma_pose = [a * np.pi / 180 for a in neck + jaw + eye * 2]
+    v_template = np.asarray(data["v_template"])
+    model = LinearBlendSkinningModel(v_template.shape[0], np.asarray(data["posedirs"]).shape[-1] // 9 + 1,
+                                     np.asarray(data["shapedirs"]).shape[-1], v_template, data["J_regressor"],
+                                     data["kintree_table"], data["weights"], data["posedirs"], data["shapedirs"], 1,
+                                     sigma_pose)
+    f = np.asarray(data["f"])
+    tri = (f - f.min()).astype(np.int64)
+    if tri.shape[0] == 3 and tri.shape[1] != 3:
+        tri = tri.T
     return model, torch.from_numpy(np.ascontiguousarray(tri))

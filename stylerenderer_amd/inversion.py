@@ -9,7 +9,8 @@ The reference has no fitting script; its pieces are the generato
                 coeff [B, d] = 3DMM shape + expression coefficients (fit_shape=True only; from 0, the mean face)
     forward     vertices = v0 @ (exp(s) * R(yaw, pitch, roll)) + t ; normals = n0 @ R
                 image = GeneratorWithMap([w], (vertices, normals, tri), input_is_latent=True, noise=fixed)
-                with fit_shape=True: vertices, normals = op.morph.morph_mesh(face model, coeff, pose, tri)
+                with fit_shape=True: vertices, normals = op.morph.morph_mesh(face model, coeff, pose, tri), or
+                op.skin.skin_mesh for a LinearBlendSkinningModel (coeff = shape, then one axis-angle per joint)
     loss        LPIPS-shaped distance(image, target) + pixel_weight * mean((image - target)^2)
                 (+ shape_reg * face_model.regulation(coeff), reference face_model.py:73-74, with fit_shape=True)
     update      Adam, `steps` iterations (default 400)
@@ -70,11 +71,22 @@ class LatentInverter:
         self.batch = int(self.target.shape[0])
         self.fit_shape = bool(fit_shape)
         self.shape_reg = float(shape_reg)
+        self.skinned = False
         if self.fit_shape:
             if face is None:
                 raise ValueError("LatentInverter: fit_shape=True needs face=(LinearMorphableModel, tri)")
             self.face_model, self.tri = face[0], face[1].detach()
             self.face_model.requires_grad_(False)
+            from .face_model import LinearBlendSkinningModel
+
+            # a skinned model (FLAME): coeff = shape, then one axis-angle per joint, through op.skin instead of op.morph
+            self.skinned = isinstance(self.face_model, LinearBlendSkinningModel)
+            self._prior_sigma = self.face_model.sigma
+            if self.skinned:
+                # fit_loss_rows takes a diagonal prior: exact for a diagonal pose_cov (load_flame's)
+                if self.batch > 1 and self.shape_reg != 0.0 and not self.face_model.pose_cov_is_diagonal():
+                    raise ValueError("LatentInverter: a batched fit with shape_reg != 0 needs a diagonal pose_cov")
+                self._prior_sigma = self.face_model.effective_sigma()
             # the fitted mesh comes from the morphable-mesh node; `mesh` is not used
             self.v0 = self.n0 = None
         else:
@@ -119,10 +131,14 @@ class LatentInverter:
 
     # ---- model ----------------------------------------------------------------------------------------
     def _shape_mesh(self):
-        """(v, n, tri, reg) of the fitted coefficients and pose (op.morph: one node, no library GEMM on the device)."""
-        from .op.morph import morph_mesh
+        """(v, n, tri, reg) of the fitted coefficients and pose (op.morph / op.skin: one node, no library GEMM on the
+        device)."""
+        if self.skinned:
+            from .op.skin import skin_mesh as node
+        else:
+            from .op.morph import morph_mesh as node
 
-        v, n, reg = morph_mesh(self.face_model, self.coeff, self.pose.view(-1, 7), self.tri, self.shape_reg)
+        v, n, reg = node(self.face_model, self.coeff, self.pose.view(-1, 7), self.tri, self.shape_reg)
         return v, n, self.tri, reg
 
     def posed_mesh(self):
@@ -173,7 +189,7 @@ class LatentInverter:
         prior = self.fit_shape and self.shape_reg != 0.0 and getattr(self, "_reg", None) is not None
         self._rows, total = fit_loss_rows(layers, mse_rows(img, self.target), self.pixel_weight,
                                           coeff=self.coeff if prior else None,
-                                          sigma=self.face_model.sigma if prior else None, shape_reg=self.shape_reg,
+                                          sigma=self._prior_sigma if prior else None, shape_reg=self.shape_reg,
                                           reg=self._reg if prior else None)
         return total
 

@@ -2,17 +2,17 @@
 for it):
 
     python -m stylerenderer_amd.reconstruct [--size 256] [--steps 400] [--lr] [--pose_lr] [--coeff_lr] [--shape_reg]
-        [--bfm BFM.mat] [--lpips-trunk VGG16.pth] [--batch N] [--gpu 0] [--seed S] [--out DIR] CHECKPOINT IMAGE [IMAGE ...]
+        [--bfm BFM.mat | --flame FLAME.{pkl,mat}] [--lpips-trunk VGG16.pth] [--batch N] [--gpu 0] [--seed S] [--out DIR] CHECKPOINT IMAGE [IMAGE ...]
 
 For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with inversion.LatentInverter(fit_shape=True)
 — the W+ latent, a rigid pose and the 3DMM shape / expression coefficients are fitted together (op.morph on the device)
 — and DIR receives
 
     <stem>.obj            the posed mesh with vertex normals
-    <stem>_canonical.obj  the fitted shape without the pose
+    <stem>_canonical.obj  the fitted shape without the pose (with --flame: with the fitted articulation)
     <stem>_render.png     the generator's image of the fit
     <stem>_normal.png     the rasterised normal map of the posed mesh
-    <stem>.npz            w, coeff, pose and the loss history
+    <stem>.npz            w, coeff, pose and the loss history (with --flame also joints [nj-1, 3], the axis-angles)
 
 With --batch N the images are fitted N at a time, each group as one batched LatentInverter (one captured graph; every
 image still follows its own single-image optimisation): the first group builds the inverter, the following ones
@@ -20,7 +20,7 @@ re-target it with `reset`, and a short last group is padded with copies of its l
 The files and their shapes are those of --batch 1, the default, which fits one image per inverter.
 
 Images are PNG / JPG (PIL) or .npy in [-1, 1] (HWC or CHW), resized on the host.  The 3DMM is the Basel Face Model with
---bfm (face_model.load_bfm), else the synthetic model `train --mesh` trains with (train.SyntheticFaceSource).  Without
+--bfm (face_model.load_bfm), FLAME with --flame (face_model.load_flame, op.skin), else the synthetic model `train --mesh` trains with (train.SyntheticFaceSource).  Without
 --lpips-trunk the perceptual trunk is the deterministic synthetic fill and the result is not a meaningful
 reconstruction (stderr says so).
 """
@@ -58,8 +58,13 @@ def load_image(path, size):
     return x.clamp(-1, 1).contiguous()
 
 
-def face_model(bfm, device, seed=0):
-    """(LinearMorphableModel, tri) on `device`: the Basel model of --bfm, else train.SyntheticFaceSource's."""
+def face_model(bfm, device, seed=0, flame=None):
+    """(model, tri) on `device`: the Basel model of --bfm, FLAME of --flame, else train.SyntheticFaceSource's."""
+    if flame:
+        from .face_model import load_flame
+
+        model, tri = load_flame(flame)
+        return model.to(device), tri.to(device)
     if bfm:
         from .face_model import load_bfm
 
@@ -95,8 +100,14 @@ def reconstruct_batch(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, co
 
 def write_outputs(inv, hist, out_dir, stem, index=0):
     """The five files of sample `index` of the inverter (hist: its loss history [steps])."""
-    from .op.morph import morph_mesh
+    from .face_model import LinearBlendSkinningModel
     from .op.rasterize import rasterize
+
+    skinned = isinstance(inv.face_model, LinearBlendSkinningModel)
+    if skinned:
+        from .op.skin import skin_mesh as node
+    else:
+        from .op.morph import morph_mesh as node
 
     k = slice(index, index + 1)
     v, n, tri = inv.fitted_mesh()
@@ -105,7 +116,7 @@ def write_outputs(inv, hist, out_dir, stem, index=0):
     pose = inv.pose.detach().view(-1, 7)[index]
     with torch.no_grad():
         zero = torch.zeros_like(pose).view(1, 7)
-        vc, nc, _ = morph_mesh(inv.face_model, coeff, zero, tri)
+        vc, nc, _ = node(inv.face_model, coeff, zero, tri)
         size = int(inv.target.shape[-1])
         normal_map = rasterize(v.contiguous(), n.contiguous(), tri, size, size, channel_major=True)
     tri_h = tri.cpu().numpy()
@@ -114,8 +125,9 @@ def write_outputs(inv, hist, out_dir, stem, index=0):
                       vn=nc[0].cpu().numpy())
     generate.save_image(inv.image[k].cpu(), os.path.join(out_dir, stem + "_render.png"))
     generate.save_image(normal_map.cpu(), os.path.join(out_dir, stem + "_normal.png"))
+    extra = {"joints": coeff[0, inv.face_model.dim[0]:].view(-1, 3).cpu().numpy()} if skinned else {}
     np.savez(os.path.join(out_dir, stem + ".npz"), w=inv.w.detach()[k].cpu().numpy(), coeff=coeff.cpu().numpy(),
-             pose=pose.cpu().numpy(), loss=hist)
+             pose=pose.cpu().numpy(), loss=hist, **extra)
 
 
 def main(argv=None):
@@ -127,7 +139,10 @@ def main(argv=None):
     ap.add_argument("--coeff_lr", type=float, default=0.01, help="learning rate of the 3DMM coefficients [%(default)g]")
     ap.add_argument("--shape_reg", type=float, default=1e-3,
                     help="weight of the coefficient prior sum (coeff / sigma)^2 [%(default)g]")
-    ap.add_argument("--bfm", default=None, metavar="BFM.mat", help="Basel Face Model (.mat); default: synthetic 3DMM")
+    which = ap.add_mutually_exclusive_group()
+    which.add_argument("--bfm", default=None, metavar="BFM.mat", help="Basel Face Model (.mat); default: synthetic 3DMM")
+    which.add_argument("--flame", default=None, metavar="FLAME.{pkl,mat}",
+                       help="FLAME skinned model: shape and the neck / jaw / eye rotations are fitted")
     ap.add_argument("--lpips-trunk", default=None, metavar="PATH",
                     help="torchvision vgg16 (or vgg16().features) state dict for the LPIPS trunk")
     ap.add_argument("--n_mean_latent", type=int, default=4096, help="latents averaged for the starting W+ [%(default)d]")
@@ -156,7 +171,7 @@ def main(argv=None):
         sys.stderr.write("warning: no --lpips-trunk given: the LPIPS VGG16 trunk is the deterministic synthetic fill, "
                          "so this is not a meaningful reconstruction\n")
     percept = percept.to(device)
-    face = face_model(args.bfm, device, seed=args.seed)
+    face = face_model(args.bfm, device, seed=args.seed, flame=args.flame)
     os.makedirs(args.out, exist_ok=True)
     results = []
     if args.batch == 1:

@@ -388,6 +388,53 @@ class BfmFaceSource(SyntheticFaceSource):
         self.pose_sigma = torch.tensor([.5, .1, .05, .1, .1, .1, .15], dtype=torch.float32, device=device)
 
 
+class FlameFaceSource(SyntheticFaceSource):
+    """SyntheticFaceSource's per-iteration sampling (same `sample()` contract, usable with --graphs) over the skinned
+    FLAME model of a `.pkl` / `.mat` file or dict in face_model.load_flame's contract: shape and joint rotations are drawn
+    from the model's prior and skinned by op.skin's native forward (two launches), so that `reconstruct --flame` fits the
+    model the network was trained with."""
+
+    def __init__(self, device, path):
+        from . import face_model, utils_3d
+
+        model, tri = face_model.load_flame(path)
+        self.model = model.to(device)
+        self.tri = tri.to(device)
+        self.device = device
+        self._u = utils_3d
+        self.pose_sigma = torch.tensor([.5, .1, .05, .1, .1, .1, .15], dtype=torch.float32, device=device)
+
+
+def synthetic_flame_dict(shape_dim=144, face_sized=True, mesh=None, shape_amplitude=None, pose_amplitude=0.02, key=951):
+    """A FLAME-shaped dict (face_model.load_flame's keys) on the face-sized mesh, or on `mesh` = (v0, tri) — FLAME itself
+    is licensed and absent: five joints in FLAME's tree (root, neck, then jaw and two eyeballs on the neck), smooth shape
+    and pose-corrective bases (`smooth_basis`), skinning weights and a joint regressor that fall off smoothly with the
+    distance to the joints."""
+    if mesh is not None:
+        v0, tri = mesh
+    else:
+        v0, tri = synth.face_sized_mesh() if face_sized else synth.uv_ellipsoid(16, 14)
+    if shape_amplitude is None:
+        shape_amplitude = 0.05 / np.sqrt(max(shape_dim, 1))
+    nv, nj = v0.shape[0], 5
+    lo, hi = v0.min(0), v0.max(0)
+    mid, ext = (lo + hi) / 2, (hi - lo)
+    # in units of the bounding box: root low behind, neck above it, jaw low in front, the eyes high in front
+    place = np.array([[0, -.45, -.3], [0, -.25, -.2], [0, -.2, .3], [-.2, .2, .4], [.2, .2, .4]], np.float64)
+    joints = mid[None] + place * ext[None]
+    d2 = ((v0[:, None, :].astype(np.float64) - joints[None]) ** 2).sum(2)                     # [nv, nj]
+    weights = np.exp(-d2 / (0.25 * float(ext.max())) ** 2) + 1e-4
+    weights /= weights.sum(1, keepdims=True)
+    reg = np.exp(-d2.T / (0.1 * float(ext.max())) ** 2) + 1e-12
+    reg /= reg.sum(1, keepdims=True)
+    shapedirs = smooth_basis(v0, shape_dim, key, shape_amplitude)
+    posedirs = smooth_basis(v0, 9 * (nj - 1), key + 4, pose_amplitude)
+    return {"v_template": v0.astype(np.float64), "shapedirs": shapedirs.T.reshape(nv, 3, shape_dim).astype(np.float64),
+            "posedirs": posedirs.T.reshape(nv, 3, 9 * (nj - 1)).astype(np.float64), "J_regressor": reg,
+            "kintree_table": np.array([[2 ** 32 - 1, 0, 1, 1, 1], [0, 1, 2, 3, 4]], np.uint32), "weights": weights,
+            "f": (tri + 1).astype(np.uint32)}
+
+
 def main():
     ap = argparse.ArgumentParser(description="StyleRenderer training step on synthetic data")
     ap.add_argument("--iter", type=int, default=16)
@@ -408,6 +455,8 @@ def main():
     ap.add_argument("--bfm", type=str, default=None, metavar="PATH",
                     help="with --mesh: sample meshes from this Basel Face Model (.mat, face_model.load_bfm) instead of "
                          "the synthetic 3DMM")
+    ap.add_argument("--flame", type=str, default=None, metavar="PATH",
+                    help="with --mesh: sample meshes from this FLAME model (.pkl / .mat, face_model.load_flame)")
     ap.add_argument("--augment", action="store_true", help="adaptive discriminator augmentation")
     ap.add_argument("--augment_p", type=float, default=0)
     ap.add_argument("--ada_target", type=float, default=0.6)
@@ -426,9 +475,13 @@ def main():
     targs = (args.size, args.latent, args.n_mlp, args.channel_multiplier, args.lr, args.r1, args.path_regularize,
              args.path_batch_shrink, args.d_reg_every, args.g_reg_every, args.mixing, args.mesh, device, args.seed,
              args.augment, args.augment_p, args.ada_target, args.ada_length)
-    if args.bfm and not args.mesh:
-        ap.error("--bfm needs --mesh")
-    if args.mesh:
+    if (args.bfm or args.flame) and not args.mesh:
+        ap.error("--bfm / --flame need --mesh")
+    if args.bfm and args.flame:
+        ap.error("--bfm and --flame are mutually exclusive")
+    if args.mesh and args.flame:
+        faces = FlameFaceSource(device, args.flame)
+    elif args.mesh:
         faces = BfmFaceSource(device, args.bfm) if args.bfm else SyntheticFaceSource(device, seed=args.seed)
     else:
         faces = None

@@ -475,3 +475,29 @@ def augment(img, augment_ratio=.5):
     z_color = _color_draws(batch, color_p)
     pick = torch.rand(batch, 1, 1, 1, dtype=img.dtype, device=img.device)
     return _augment_from_draws(img, z_pose, z_color, pick, augment_ratio).view(shape)
+
+
+# ---- axis-angle rotations ----------------------------------------------------------------------------
+def rodrigues(rvec, eps=1e-8):
+    """Rotation matrices [N, 3, 3] ([3, 3]) of axis-angle vectors rvec [N, 3] ([3]): R = cos(r) I + cc r r^T + sc [r]_x
+    with r = |rvec|, sc = sin(r) / r, cc = (1 - cos(r)) / r^2 (reference utils_3d.py:81-154).  For r <= eps the series
+    sc = 1 - r^2/6, cc = 1/2 - r^2/24 take over, whose derivatives are the reference's backward coefficients
+    -1/3 + r^2/30 and -1/12 + r^2/180 up to O(r^4).  Plain tensor algebra: differentiable to any order, finite at 0.
+    The device kernels of the skinning node use the same function as a __device__ helper (csrc/rodrigues.h)."""
+    eps = abs(eps)
+    single = rvec.dim() == 1
+    a = rvec.view(1, 3) if single else rvec
+    r2 = (a * a).sum(1)
+    small = torch.sqrt(r2.detach()) <= eps
+    r2s = torch.where(small, torch.ones_like(r2), r2)           # the unused branch stays finite (and its gradient)
+    r = torch.sqrt(r2s)
+    c = torch.where(small, 1 - r2 / 2, torch.cos(r))
+    sc = torch.where(small, 1 - r2 / 6, torch.sin(r) / r)
+    cc = torch.where(small, .5 - r2 / 24, (1 - torch.cos(r)) / r2s)
+    zero = torch.zeros_like(r2)
+    x, y, z = a[:, 0], a[:, 1], a[:, 2]
+    rx = torch.stack((zero, -z, y, z, zero, -x, -y, x, zero), 1).view(-1, 3, 3)
+    rr = a.unsqueeze(2) * a.unsqueeze(1)
+    eye = torch.eye(3, dtype=a.dtype, device=a.device).view(1, 3, 3)
+    out = c.view(-1, 1, 1) * eye + cc.view(-1, 1, 1) * rr + sc.view(-1, 1, 1) * rx
+    return out.view(3, 3) if single else out
