@@ -253,6 +253,29 @@ int sr_skin_joints_bwd(float* gcoeff, float* gpose, const float* gcx, const floa
                        const float* pose_inv, float lam, const float* greg, int64_t B, int64_t nblk, int64_t nj,
                        int64_t nroot, int64_t ds, sr_stream_t stream);
 
+/* Bilinear blendshape node of face reconstruction (csrc/blend.hip; reference face_model.py:128-146 BlendShapeModel).
+ * x [B, ds + de] = identity logits, then expression logits; w = weight [(ds + 1)(de + 1), 3 nv] as stored (the vertex
+ * coordinate contiguous; rows need 4-byte alignment only); beta [ds + 1 + 2 de] of the Dirichlet / Beta prior.
+ * ds + de + 2 <= 8192 and B <= 65535, else SR_ERANGE.
+ * sr_blend_head: xs [B, ds + 1] = softmax(cat(x_s, -sum x_s)), xe [B, de + 1] = cat(1 - sum s, s), s = sigmoid(x_e),
+ *   prior [B] = lam * regulation(x[b]) and z [sr_blend_z_floats] = the products xs (x) xe of every sample in blocks of
+ *   eight samples, [block][k][8], zero where a block has fewer.  One launch for all B.
+ * sr_blend_fwd: vs[b] = (z[b] w).view(nv, 3), v[b] = vs[b] @ lin[b] + pose[b, 3:6] (v NULL: vs alone; then lin and pose
+ *   may be NULL), reg (may be NULL) = sum_b prior[b] in sample order.  One pass over w per eight samples.
+ * sr_blend_gz: gz[b, k] = sum_c w[k, c] gvs[b, c], gz [B, (ds + 1)(de + 1)]; one pass over w per eight samples, fixed-order
+ *   sums, no scratch.
+ * sr_blend_tail: gcoeff [B, ds + de] from gz (NULL: zero) through the softmax / sigmoid Jacobians and the couplings of
+ *   the last identity and the neutral expression, plus lam greg[0] d regulation / dx (greg: device scalar, may be NULL). */
+int64_t sr_blend_z_floats(int64_t B, int64_t ds, int64_t de);
+int sr_blend_head(float* xs, float* xe, float* prior, float* z, const float* x, const float* beta, float lam, int64_t B,
+                  int64_t ds, int64_t de, sr_stream_t stream);
+int sr_blend_fwd(float* v, float* vs, float* reg, const float* w, const float* z, const float* prior, const float* lin,
+                 const float* pose, int64_t B, int64_t nv, int64_t ds, int64_t de, sr_stream_t stream);
+int sr_blend_gz(float* gz, const float* w, const float* gvs, int64_t B, int64_t nv, int64_t ds, int64_t de,
+                sr_stream_t stream);
+int sr_blend_tail(float* gcoeff, const float* gz, const float* xs, const float* xe, const float* beta, float lam,
+                  const float* greg, int64_t B, int64_t ds, int64_t de, sr_stream_t stream);
+
 /* Pose parameters of the inversion loop, pose = (yaw, pitch, roll, tx, ty, tz, log-scale): rot [3,3] = Rz(roll) Rx(pitch)
  * Ry(yaw) (utils_3d.euler_mat(angles, "yxz"), row-major), lin = exp(log-scale) * rot; sr_pose_bwd: gradient of the seven
  * numbers from the gradients of the two matrices (either may be NULL; entries 3..5 are written as 0: the translation's

@@ -2,7 +2,8 @@
 against the pose-only inversion (BASELINE config[4]) at 256^2 on the face-sized synthetic 3DMM (d = 80 + 64), and the
 device time of the morphable-mesh node's kernels (csrc/morph.hip).
 
-    python scripts/bench_reconstruct.py [--steps 100] [--rounds 3] [--reps 50] [--batch 1,4,8,16] [--face morph|flame]
+    python scripts/bench_reconstruct.py [--steps 100] [--rounds 3] [--reps 50] [--batch 1,4,8,16]
+        [--face morph|flame|facewarehouse]
 
 One JSON line per measurement:
   * inversion: replayed steps/s of both inverters in the same process (hipGraph replays, alternated in --rounds rounds
@@ -21,6 +22,12 @@ With --face flame the skinned fit (op.skin on train.synthetic_flame_dict: the sa
 FLAME's tree) is measured against the linear fit-shape step in the same process, rounds alternated, the median round:
 steps/s and kernel nodes of both, their ratio, and the warm device time per call of the node's new kernels
 (sr_skin_joints_fwd, sr_skin_fwd, sr_skin_bwd, sr_skin_joints_bwd).
+
+With --face facewarehouse a synthetic bilinear blendshape model at FaceWarehouse's own dimensions (ds = 149, de = 46,
+nv = 11 510: W = 974 MB, train.synthetic_facewarehouse_dict on a UV ellipsoid of that many vertices) is fitted at the
+batch sizes of --batch (default 1,8): image-steps/s and kernel nodes per captured step; then the two contraction kernels
+alone (sr_blend_fwd, sr_blend_gz) at the same batch sizes: device time, bytes of W / time, and next to it the rate of a
+device-to-device copy of the same number of bytes timed in the same run.
 """
 import argparse
 import json
@@ -244,6 +251,70 @@ def bench_flame(size, steps, rounds, reps):
                           "us": round(t * 1e6, 2)}), flush=True)
 
 
+def bench_facewarehouse(size, batches, steps, rounds, reps):
+    from stylerenderer_amd import face_model
+    from stylerenderer_amd.op import blend
+
+    invs, _, _ = make_inverters(size)
+    base = invs.pop("pose_only")
+    g, net, noise, target = base.g, base.perceptual, base.noise, base.target
+    del base, invs
+    ds, de = 149, 46
+    fm, tri = face_model.load_facewarehouse(train.synthetic_facewarehouse_dict(ds, de, mesh=synth.uv_ellipsoid(138, 84)), 2.0)
+    fm, tri = fm.to(DEV), tri.to(DEV)
+    nv = fm.dim[2] // 3
+    w_bytes = fm.weight.numel() * 4
+    for b in batches:
+        torch.cuda.empty_cache()
+        torch.manual_seed(11)
+        inv = inversion.LatentInverter(g, net, target.expand(b, -1, -1, -1).contiguous(), None, lr=0.05, pose_lr=0.01,
+                                       noise=noise, n_mean_latent=4096, use_graph=True, face=(fm, tri), fit_shape=True,
+                                       coeff_lr=0.05, shape_reg=1e-3)
+        inv.run(8)
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(rounds):
+            a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(steps):
+                inv.graph.replay()
+            e.record()
+            torch.cuda.synchronize()
+            ms.append(a.elapsed_time(e) / steps)
+        t = statistics.median(ms)
+        print(json.dumps({"what": "inversion_facewarehouse", "size": size, "batch": b, "nv": nv, "ds": ds, "de": de,
+                          "w_bytes": w_bytes, "ms_per_step": round(t, 4), "image_steps_per_s": round(b * 1000.0 / t, 2),
+                          "rounds_ms": [round(x, 4) for x in ms], "kernel_nodes_per_step": inv.graph.kernel_nodes}),
+              flush=True)
+        del inv
+    L, ptr, st = _lib.lib(), _lib.ptr, _lib.current_stream(DEV)
+    src = torch.empty(w_bytes // 4, device=DEV)
+    dst = torch.empty_like(src)
+    t_copy = event_time(lambda: dst.copy_(src), reps)
+    del dst, src
+    print(json.dumps({"what": "copy", "bytes": w_bytes, "us": round(t_copy * 1e6, 2),
+                      "bytes_per_s": round(w_bytes / t_copy / 1e12, 3)}), flush=True)
+    for b in batches:
+        c = torch.from_numpy(synth.det_normal((b, ds + de), 8)).to(DEV)
+        pose = torch.zeros(b, 7, device=DEV)
+        lin = torch.eye(3, device=DEV).repeat(b, 1, 1).contiguous()
+        xs, xe, prior, z = blend._head(L, c, fm.beta.detach(), 1e-3, ds, de, st)
+        v, vs, gvs = (torch.randn(b, nv, 3, device=DEV) for _ in range(3))
+        reg = torch.empty((), device=DEV)
+        gz = torch.empty(b, (ds + 1) * (de + 1), device=DEV)
+        calls = {
+            "sr_blend_fwd": lambda: L.sr_blend_fwd(ptr(v), ptr(vs), ptr(reg), ptr(fm.weight), ptr(z), ptr(prior), ptr(lin),
+                                                   ptr(pose), b, nv, ds, de, st),
+            "sr_blend_gz": lambda: L.sr_blend_gz(ptr(gz), ptr(fm.weight), ptr(gvs), b, nv, ds, de, st),
+        }
+        for name, fn in calls.items():
+            _lib.check(fn(), name)
+            t = event_time(fn, reps)
+            print(json.dumps({"what": "kernel", "name": name, "B": b, "nv": nv, "w_bytes": w_bytes, "us": round(t * 1e6, 2),
+                              "w_bytes_per_s": round(w_bytes / t / 1e12, 3),
+                              "over_copy_rate": round(t_copy / t, 3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=256)
@@ -252,10 +323,15 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--batch", default=None, metavar="B1,B2,...",
                     help="measure the batched fit-shape inverter at these batch sizes instead")
-    ap.add_argument("--face", choices=("morph", "flame"), default="morph",
-                    help="flame: the skinned fit against the linear fit-shape step, and the skinning kernels")
+    ap.add_argument("--face", choices=("morph", "flame", "facewarehouse"), default="morph",
+                    help="flame: the skinned fit against the linear fit-shape step, and the skinning kernels; "
+                         "facewarehouse: the blendshape fit at FaceWarehouse's dimensions and its contraction kernels")
     args = ap.parse_args()
     os.environ.setdefault("SR_STRICT_NATIVE", "1")
+    if args.face == "facewarehouse":
+        bench_facewarehouse(args.size, [int(x) for x in (args.batch or "1,8").split(",")], args.steps, args.rounds,
+                            args.reps)
+        return
     if args.face == "flame":
         bench_flame(args.size, args.steps, args.rounds, args.reps)
         return

@@ -134,6 +134,11 @@ SIGNATURES = {
     "sr_skin_bwd_scratch_floats": (_l, [_l, _l, _l]),
     "sr_skin_bwd": (_i, [_p] * 7 + [_l] * 3 + [_p]),
     "sr_skin_joints_bwd": (_i, [_p] * 11 + [_f, _p] + [_l] * 5 + [_p]),
+    "sr_blend_z_floats": (_l, [_l, _l, _l]),
+    "sr_blend_head": (_i, [_p] * 6 + [_f] + [_l] * 3 + [_p]),
+    "sr_blend_fwd": (_i, [_p] * 8 + [_l] * 4 + [_p]),
+    "sr_blend_gz": (_i, [_p] * 3 + [_l] * 4 + [_p]),
+    "sr_blend_tail": (_i, [_p] * 5 + [_f, _p] + [_l] * 3 + [_p]),
     "sr_signal_bump": (_i, [_p, _p]),
     "sr_signal_wait": (_i, [_p, ctypes.c_uint32, _p]),
     "sr_signal_set": (_i, [_p, _p, _p]),

@@ -37,6 +37,7 @@ SOURCES = [
     ("mesh.hip", EXACT),
     ("morph.hip", []),
     ("skin.hip", []),
+    ("blend.hip", []),
     ("lpips.hip", EXACT),
     ("ppl.hip", EXACT),
     ("augment.hip", EXACT),

@@ -5,7 +5,10 @@ methods as reference face_model.py:4-74, so its checkpoints load unchanged.  Ver
 one [B, d] x [d, 3 nv] GEMM (d = shape + expression dims), a library call on the device.
 
 LinearBlendSkinningModel / load_flame — the skinned, articulated model (FLAME: neck, jaw, eyeballs) of reference
-face_model.py:146-341 and 378-408; on the device its forward is the skinning node's kernels (op/skin.py)."""
+face_model.py:146-341 and 378-408; on the device its forward is the skinning node's kernels (op/skin.py).
+
+BlendShapeModel / load_facewarehouse — the bilinear identity x expression model (FaceWarehouse) of reference
+face_model.py:75-146 and 363-377; on the device its forward is the blendshape node's kernels (op/blend.py)."""
 import numpy as np
 import torch
 from torch import nn
@@ -102,6 +105,112 @@ def load_bfm(file_name="/data/BaselFaceModel.mat"):
     if tri.shape[0] == 3 and tri.shape[1] != 3:
         tri = tri.T
     model = LinearMorphableModel(len(v), w_shape.shape[1], w_exp.shape[1], v, w_shape, w_exp)
+    return model, torch.from_numpy(np.ascontiguousarray(tri))
+
+
+class BlendShapeModel(nn.Module):
+    """Bilinear identity x expression blendshape model (FaceWarehouse; reference face_model.py:75-146): same constructor
+    arguments, `dim` = [shape_dim, expression_dim, 3 nv], methods and state-dict keys (`beta` [ds + 1 + 2 de], `weight`
+    [ds + 1, de + 1, 3 nv], in that order), so its checkpoints load.  With x [B, ds + de]:
+
+        xs = softmax(cat(x[:, :ds], -sum x[:, :ds]))        identity weights, on the simplex
+        xe = cat(1 - sum s, s),  s = sigmoid(x[:, ds:])     expression weights in [0, 1], xe[0] the neutral face
+        forward(x)[b] = sum_ij xs[b, i] xe[b, j] weight[i, j].view(nv, 3)
+
+    `regulation` is the reference's negative Dirichlet / Beta log-likelihood in the logits, written with log-sum-exp and
+    softplus (equal to its log(sum(exp)) and log(exp + 1) wherever those are finite).  With concentrations below 1
+    (`load_facewarehouse`'s beta_shape = .01) its identity part is unbounded below: it falls without limit as one logit
+    grows, so a positive weight on it pushes the identity away from the mean.
+
+    One defect of the reference is not reproduced: its `random_input` centres the identity log-ratios log(p_i / p_last) by
+    their sum over ds (line 126), which is not the inverse of forward's softmax (with beta = (2, 3, 5) the weights it
+    yields average (.27, .42, .30), not (.2, .3, .5)); here they are centred over all ds + 1 parts, so that
+    softmax(cat(x, -sum x)) is the Dirichlet draw itself.  It also runs with expression_dim = 0, where the reference's
+    raises."""
+
+    def __init__(self, vertices_num, shape_dim=0, expression_dim=0, bs=None, beta_shape=1, beta_expression=[1, 10],
+                 learnable=False):
+        super().__init__()
+        vertices_num = max(int(vertices_num), 1)
+        shape_dim = max(int(shape_dim), 0)
+        expression_dim = max(int(expression_dim), 0)
+        # random model when no data is given (reference face_model.py:85-86)
+        w = (np.random.rand(shape_dim + 1, expression_dim + 1, vertices_num * 3).astype(np.float32) * 2 - 1) \
+            * np.sqrt(shape_dim + expression_dim)
+        if bs is not None:
+            bs = np.array(bs, np.float32)
+            if bs.ndim >= 3:
+                bs = bs.reshape(bs.shape[0], bs.shape[1], -1)
+                if bs.shape[0] == w.shape[-1]:                      # [3 nv, ., .] -> [., ., 3 nv]
+                    bs = np.transpose(bs, [1, 2, 0])
+                d = [min(bs.shape[0], w.shape[0]), min(bs.shape[1], w.shape[1]), min((bs.shape[2] // 3) * 3, w.shape[2])]
+                w[:d[0], :d[1], :d[2]] = bs[:d[0], :d[1], :d[2]]
+        bsh = [] if beta_shape is None else [float(v) for v in np.reshape(beta_shape, -1)]
+        bex = [] if beta_expression is None else [float(v) for v in np.reshape(beta_expression, -1)]
+        self.dim = [shape_dim, expression_dim, vertices_num * 3]
+        # the reference's padding rule (lines 104-110): a short identity list repeats its last value; an expression list
+        # that does not reach pair i repeats its last pair (a single value or none: 1)
+        beta = [abs(bsh[i]) if len(bsh) > i else (abs(bsh[-1]) if bsh else 1) for i in range(shape_dim + 1)]
+        beta += [abs(bex[2 * i + j]) if len(bex) > 2 * i + 1 else (abs(bex[j - 2]) if len(bex) > 1 else 1)
+                 for i in range(expression_dim) for j in range(2)]
+        self.beta = nn.Parameter(torch.tensor(beta, dtype=torch.float32), requires_grad=False)
+        self.weight = nn.Parameter(torch.from_numpy(w).float(), requires_grad=bool(learnable))
+
+    def random_input(self, batch_size=1):
+        # Dirichlet(beta_s) identity weights and Beta(a_j, b_j) expression weights from unit-scale gamma draws on the
+        # model's device, mapped to centred log-ratios and logits in log space: finite (the gamma sampler never returns
+        # 0) and with no host-side check, so that it runs under graph capture like the other models' samplers.
+        ds, de = self.dim[0], self.dim[1]
+        lg = torch.log(torch._standard_gamma(self.beta.detach().unsqueeze(0).expand(batch_size, -1).contiguous()))
+        ls = lg[:, :ds + 1]
+        xs = ls[:, :ds] - ls.mean(1, keepdim=True)
+        le = lg[:, ds + 1:].reshape(batch_size, de, 2)
+        return torch.cat((xs, le[:, :, 0] - le[:, :, 1]), 1)
+
+    def mixing_weights(self, x):
+        """(xs [B, ds + 1], xe [B, de + 1]): the identity and expression weights of coefficients x."""
+        ds = self.dim[0]
+        xs = torch.softmax(torch.cat((x[:, :ds], -x[:, :ds].sum(1, keepdim=True)), 1), dim=1)
+        s = torch.sigmoid(x[:, ds:])
+        return xs, torch.cat((1 - s.sum(1, keepdim=True), s), 1)
+
+    def forward(self, x):
+        from .op import blend
+
+        return blend.blend_vertices(self, x)
+
+    def regulation(self, x):
+        ds = self.dim[0]
+        beta = self.beta.to(x.dtype)
+        ls = torch.cat((x[:, :ds], -x[:, :ds].sum(1, keepdim=True)), 1)
+        xe = x[:, ds:]
+        bs, be = beta[:ds + 1], beta[ds + 1:].reshape(self.dim[1], 2)
+        return -((ls * bs.unsqueeze(0)).sum() - torch.logsumexp(ls, 1).sum() * (bs.sum() - ds - 1)
+                 + (xe * be[:, 0].unsqueeze(0) - 1).sum()
+                 - (torch.nn.functional.softplus(xe) * (be.sum(1) - 2).unsqueeze(0)).sum())
+
+
+def load_facewarehouse(file_name="/data/FaceWareHouse.mat", beta_shape=.01):
+    """FaceWarehouse -> (BlendShapeModel, tri int64 [nf, 3]) with the reference's contract (face_model.py:363-377):
+    keys `v` [3, nv] (a mean shape: only its per-axis mean is used, to centre), `p` [3 nv, de + 1, ds + 1] (every
+    identity's every expression, vertex coordinate first) and `tri` (any base, [nf, 3] or [3, nf]).  `file_name` is the
+    path of the (licensed, not distributed) `.mat` or an already loaded dict.  `beta_shape` is the Dirichlet concentration
+    of the identity prior; the default is the reference's .01, with which `regulation` is unbounded below (see
+    BlendShapeModel) — give a value >= 1 for a prior that pulls towards the mean identity."""
+    if isinstance(file_name, str):
+        import scipy.io as sio
+
+        data = sio.loadmat(file_name)
+    else:
+        data = file_name
+    v, p = np.asarray(data["v"]), np.asarray(data["p"])
+    v_mean = np.tile(v.mean(1).reshape(-1, 1, 1), (v.shape[1], 1, 1))
+    bs = np.transpose(p - v_mean, [2, 1, 0])
+    t = np.asarray(data["tri"])
+    tri = (t - t.min()).astype(np.int64)
+    if tri.shape[0] == 3 and tri.shape[1] != 3:
+        tri = tri.T
+    model = BlendShapeModel(v.shape[1], bs.shape[0] - 1, bs.shape[1] - 1, bs, beta_shape)
     return model, torch.from_numpy(np.ascontiguousarray(tri))
 
 

@@ -10,7 +10,9 @@ The reference has no fitting script; its pieces are the generato
     forward     vertices = v0 @ (exp(s) * R(yaw, pitch, roll)) + t ; normals = n0 @ R
                 image = GeneratorWithMap([w], (vertices, normals, tri), input_is_latent=True, noise=fixed)
                 with fit_shape=True: vertices, normals = op.morph.morph_mesh(face model, coeff, pose, tri), or
-                op.skin.skin_mesh for a LinearBlendSkinningModel (coeff = shape, then one axis-angle per joint)
+                op.skin.skin_mesh for a LinearBlendSkinningModel (coeff = shape, then one axis-angle per joint),
+                op.blend.blend_mesh for a BlendShapeModel (coeff = identity logits, then expression logits; 0 is the
+                mean identity with every expression at sigmoid(0))
     loss        LPIPS-shaped distance(image, target) + pixel_weight * mean((image - target)^2)
                 (+ shape_reg * face_model.regulation(coeff), reference face_model.py:73-74, with fit_shape=True)
     update      Adam, `steps` iterations (default 400)
@@ -71,17 +73,20 @@ class LatentInverter:
         self.batch = int(self.target.shape[0])
         self.fit_shape = bool(fit_shape)
         self.shape_reg = float(shape_reg)
-        self.skinned = False
+        self.skinned = self.blended = False
         if self.fit_shape:
             if face is None:
                 raise ValueError("LatentInverter: fit_shape=True needs face=(LinearMorphableModel, tri)")
             self.face_model, self.tri = face[0], face[1].detach()
             self.face_model.requires_grad_(False)
-            from .face_model import LinearBlendSkinningModel
+            from .face_model import BlendShapeModel, LinearBlendSkinningModel
 
             # a skinned model (FLAME): coeff = shape, then one axis-angle per joint, through op.skin instead of op.morph
             self.skinned = isinstance(self.face_model, LinearBlendSkinningModel)
-            self._prior_sigma = self.face_model.sigma
+            # a bilinear blendshape model (FaceWarehouse): op.blend; its Dirichlet / Beta prior is not a diagonal
+            # Gaussian, so the per-sample losses take each sample's prior from the node, not from fit_loss_rows' sigma
+            self.blended = isinstance(self.face_model, BlendShapeModel)
+            self._prior_sigma = None if self.blended else self.face_model.sigma
             if self.skinned:
                 # fit_loss_rows takes a diagonal prior: exact for a diagonal pose_cov (load_flame's)
                 if self.batch > 1 and self.shape_reg != 0.0 and not self.face_model.pose_cov_is_diagonal():
@@ -101,8 +106,8 @@ class LatentInverter:
         pose_shape = (7,) if self.batch == 1 else (self.batch, 7)
         self.pose = torch.zeros(pose_shape, device=self.device, requires_grad=optimise_pose)
         # 3DMM coefficients [B, d], from the mean face
-        self.coeff = (torch.zeros(self.batch, self.face_model.sigma.numel(), device=self.device, requires_grad=True)
-                      if self.fit_shape else None)
+        n_coeff = (sum(self.face_model.dim[:2]) if self.blended else self.face_model.sigma.numel()) if self.fit_shape else 0
+        self.coeff = torch.zeros(self.batch, n_coeff, device=self.device, requires_grad=True) if self.fit_shape else None
         self.noise = noise if noise is not None else [n.detach() for n in self.g.make_noise()]
         on_gpu = self.device.type == "cuda"
         groups = [{"params": [self.w], "lr": lr}]
@@ -131,8 +136,15 @@ class LatentInverter:
 
     # ---- model ----------------------------------------------------------------------------------------
     def _shape_mesh(self):
-        """(v, n, tri, reg) of the fitted coefficients and pose (op.morph / op.skin: one node, no library GEMM on the
-        device)."""
+        """(v, n, tri, reg) of the fitted coefficients and pose (op.morph / op.skin / op.blend: one node, no library
+        GEMM on the device)."""
+        self._prior_rows = None
+        if self.blended:
+            from .op.blend import blend_mesh
+
+            v, n, reg, self._prior_rows = blend_mesh(self.face_model, self.coeff, self.pose.view(-1, 7), self.tri,
+                                                     self.shape_reg, per_sample=True)
+            return v, n, self.tri, reg
         if self.skinned:
             from .op.skin import skin_mesh as node
         else:
@@ -187,6 +199,10 @@ class LatentInverter:
 
         layers = self.perceptual.layer_distances(self.target_feats, img)
         prior = self.fit_shape and self.shape_reg != 0.0 and getattr(self, "_reg", None) is not None
+        if prior and self.blended:
+            self._rows, total = fit_loss_rows(layers, mse_rows(img, self.target), self.pixel_weight, reg=self._reg,
+                                              prior_rows=self._prior_rows)
+            return total
         self._rows, total = fit_loss_rows(layers, mse_rows(img, self.target), self.pixel_weight,
                                           coeff=self.coeff if prior else None,
                                           sigma=self._prior_sigma if prior else None, shape_reg=self.shape_reg,

@@ -1,0 +1,226 @@
+"""Blendshape node of face reconstruction: identity and expression coefficients and a rigid pose -> posed vertices,
+normals and the coefficient prior of a BlendShapeModel (FaceWarehouse), in one autograd node (csrc/blend.hip).
+
+With coeff [B, ds + de], pose [B, 7] = (yaw, pitch, roll, tx, ty, tz, log-scale), W = model.weight [ds + 1, de + 1, 3 nv]
+(reference face_model.py:128-146):
+
+    xs  = softmax(cat(coeff[:, :ds], -sum coeff[:, :ds]))          xe = cat(1 - sum s, s), s = sigmoid(coeff[:, ds:])
+    vs  = sum_ij xs[:, i] xe[:, j] W[i, j].view(nv, 3)
+    v   = vs (exp(s) R(yaw, pitch, roll)) + (tx, ty, tz)
+    n   = mesh_point_normal(v, tri)
+    reg = reg_weight * model.regulation(coeff)
+
+Device fp32 with a frozen model: five launches forward (pose matrices; the head kernel: xs, xe, every sample's prior and
+the products z = xs (x) xe for all B; one streaming pass over W for all B with the pose as its epilogue; the vertex-normal
+gather of the unposed shape; its rotation) and six backward (the vertex-normal adjoint gather, one streaming pass over W
+for gz = W gvs, the tail kernel through the softmax / sigmoid Jacobians with the prior's gradient, the two pose sums and
+the pose gradient).  W is used as stored: no transposed copy.  No library GEMM, no atomics: reruns are bit-identical.  First
+order only.  The per-sample priors reg_weight * regulation(coeff[b]) of the last native call are the node's fourth,
+non-differentiable output (`blend_mesh(..., per_sample=True)`): the batched inverter's per-sample losses take them.
+Anything else (CPU tensors, float64, learnable=True) is the composite tensor algebra, which is also what the kernels are
+tested against.
+"""
+import torch
+from torch.autograd import Function
+
+from .. import _lib, utils_3d
+from ._dispatch import on_device_of, stream_of, strict_native
+
+EPS = 1e-8
+
+
+def blend_vertices_composite(x, weight, ds):
+    """vs [B, nv, 3] of the definition above (no pose)."""
+    ns, ne, c = weight.shape
+    xs = torch.softmax(torch.cat((x[:, :ds], -x[:, :ds].sum(1, keepdim=True)), 1), dim=1)
+    s = torch.sigmoid(x[:, ds:])
+    xe = torch.cat((1 - s.sum(1, keepdim=True), s), 1)
+    z = (xs.unsqueeze(2) * xe.unsqueeze(1)).reshape(-1, ns * ne)
+    return torch.matmul(z, weight.reshape(ns * ne, c)).view(-1, c // 3, 3)
+
+
+def blend_composite(model, coeff, pose, tri, reg_weight=0.0):
+    """The defining tensor algebra of the node (coeff [B, ds + de], pose [B, 7])."""
+    vs = blend_vertices_composite(coeff, model.weight.to(coeff.dtype), model.dim[0])
+    lin = torch.exp(pose[:, 6]).view(-1, 1, 1) * utils_3d.euler_mat(pose[:, :3], "yxz")
+    v = torch.matmul(vs, lin) + pose[:, 3:6].view(-1, 1, 3)
+    n = utils_3d.mesh_point_normal(v, tri)
+    return v, n, reg_weight * model.regulation(coeff)
+
+
+def _head(L, c, beta, reg_weight, ds, de, st):
+    b = c.shape[0]
+    dev, f32 = c.device, c.dtype
+    xs = torch.empty((b, ds + 1), dtype=f32, device=dev)
+    xe = torch.empty((b, de + 1), dtype=f32, device=dev)
+    prior = torch.empty((b,), dtype=f32, device=dev)
+    z = torch.empty((int(L.sr_blend_z_floats(b, ds, de)),), dtype=f32, device=dev)
+    ptr = _lib.ptr
+    _lib.check(L.sr_blend_head(ptr(xs), ptr(xe), ptr(prior), ptr(z), ptr(c), ptr(beta), float(reg_weight), b, ds, de, st),
+               "sr_blend_head")
+    return xs, xe, prior, z
+
+
+class _Blend(Function):
+    @staticmethod
+    def forward(ctx, coeff, pose, weight, beta, tri, reg_weight):
+        c, p = coeff.contiguous(), pose.contiguous()
+        w, bt = weight.contiguous(), beta.contiguous()
+        b = c.shape[0]
+        ds, de, nv = w.shape[0] - 1, w.shape[1] - 1, w.shape[2] // 3
+        off, adj, _ = utils_3d.incidence_lists(tri, nv)
+        tric = tri.contiguous()
+        nf = tric.size(0)
+        dev, f32 = c.device, c.dtype
+        lin = torch.empty((b, 3, 3), dtype=f32, device=dev)
+        rot = torch.empty_like(lin)
+        vs = torch.empty((b, nv, 3), dtype=f32, device=dev)
+        v = torch.empty_like(vs)
+        ns = torch.empty_like(vs)
+        n = torch.empty_like(vs)
+        normc = torch.empty((b, nv), dtype=f32, device=dev)
+        reg = torch.empty((), dtype=f32, device=dev)
+        L = _lib.lib()
+        st = stream_of(c)
+        ptr = _lib.ptr
+        with on_device_of(c):
+            _lib.check(L.sr_pose_batch_fwd(ptr(lin), ptr(rot), ptr(p), b, st), "sr_pose_batch_fwd")
+            xs, xe, prior, z = _head(L, c, bt, reg_weight, ds, de, st)
+            _lib.check(L.sr_blend_fwd(ptr(v), ptr(vs), ptr(reg), ptr(w), ptr(z), ptr(prior), ptr(lin), ptr(p), b,
+                                      nv, ds, de, st), "sr_blend_fwd")
+            _lib.check(L.sr_vertex_normals_f32(ptr(ns), ptr(normc), ptr(vs), ptr(tric), ptr(off), ptr(adj), b, nv, nf,
+                                               EPS, st), "sr_vertex_normals_f32")
+            _lib.check(L.sr_affine3_fwd(ptr(n), ptr(ns), ptr(rot), None, b, nv, nv * 3, st), "sr_affine3_fwd")
+        ctx.save_for_backward(p, w, bt, tric, off, adj, lin, rot, vs, ns, normc, xs, xe)
+        ctx.reg_weight = float(reg_weight)
+        ctx.dims = (b, ds, de, nv)
+        ctx.mark_non_differentiable(prior)
+        return v, n, reg, prior
+
+    @staticmethod
+    def backward(ctx, gv, gn, greg, _gprior):
+        p, w, bt, tric, off, adj, lin, rot, vs, ns, normc, xs, xe = ctx.saved_tensors
+        b, ds, de, nv = ctx.dims
+        gv, gn, greg = gv.contiguous(), gn.contiguous(), greg.contiguous()
+        dev, f32 = p.device, p.dtype
+        L = _lib.lib()
+        st = stream_of(p)
+        ptr = _lib.ptr
+        gcoeff = gpose = None
+        with on_device_of(p):
+            if ctx.needs_input_grad[0]:
+                gvs = torch.empty_like(vs)
+                _lib.check(L.sr_vertex_normals_bwd_f32(ptr(gvs), ptr(gv), ptr(gn), ptr(lin), ptr(rot), ptr(vs), ptr(ns),
+                                                       ptr(normc), ptr(tric), ptr(off), ptr(adj), b, nv, tric.size(0),
+                                                       EPS, st), "sr_vertex_normals_bwd_f32")
+                gz = torch.empty((b, (ds + 1) * (de + 1)), dtype=f32, device=dev)
+                _lib.check(L.sr_blend_gz(ptr(gz), ptr(w), ptr(gvs), b, nv, ds, de, st), "sr_blend_gz")
+                gcoeff = torch.empty((b, ds + de), dtype=f32, device=dev)
+                _lib.check(L.sr_blend_tail(ptr(gcoeff), ptr(gz), ptr(xs), ptr(xe), ptr(bt), ctx.reg_weight, ptr(greg), b,
+                                           ds, de, st), "sr_blend_tail")
+            if ctx.needs_input_grad[1]:
+                glin = torch.empty_like(lin)
+                grot = torch.empty_like(rot)
+                gt = torch.empty((b, 3), dtype=f32, device=dev)
+                gpose = torch.empty_like(p)
+                _lib.check(L.sr_affine3_bwd(ptr(glin), ptr(gt), ptr(vs), ptr(gv), b, nv, nv * 3, st), "sr_affine3_bwd")
+                _lib.check(L.sr_affine3_bwd(ptr(grot), None, ptr(ns), ptr(gn), b, nv, nv * 3, st), "sr_affine3_bwd")
+                _lib.check(L.sr_morph_pose_bwd(ptr(gpose), ptr(glin), ptr(grot), ptr(gt), ptr(p), b, st),
+                           "sr_morph_pose_bwd")
+        return gcoeff, gpose, None, None, None, None
+
+
+class _BlendVertices(Function):
+    """The unposed forward alone (two launches) and its coefficient gradient (two)."""
+
+    @staticmethod
+    def forward(ctx, coeff, weight, beta):
+        c, w, bt = coeff.contiguous(), weight.contiguous(), beta.contiguous()
+        b = c.shape[0]
+        ds, de, nv = w.shape[0] - 1, w.shape[1] - 1, w.shape[2] // 3
+        vs = torch.empty((b, nv, 3), dtype=c.dtype, device=c.device)
+        L = _lib.lib()
+        st = stream_of(c)
+        ptr = _lib.ptr
+        with on_device_of(c):
+            xs, xe, _, z = _head(L, c, bt, 0.0, ds, de, st)
+            _lib.check(L.sr_blend_fwd(None, ptr(vs), None, ptr(w), ptr(z), None, None, None, b, nv, ds, de, st),
+                       "sr_blend_fwd")
+        ctx.save_for_backward(w, bt, xs, xe)
+        ctx.dims = (b, ds, de, nv)
+        return vs
+
+    @staticmethod
+    def backward(ctx, gvs):
+        w, bt, xs, xe = ctx.saved_tensors
+        b, ds, de, nv = ctx.dims
+        gvs = gvs.contiguous()
+        L = _lib.lib()
+        st = stream_of(gvs)
+        ptr = _lib.ptr
+        gz = torch.empty((b, (ds + 1) * (de + 1)), dtype=gvs.dtype, device=gvs.device)
+        gcoeff = torch.empty((b, ds + de), dtype=gvs.dtype, device=gvs.device)
+        with on_device_of(gvs):
+            _lib.check(L.sr_blend_gz(ptr(gz), ptr(w), ptr(gvs), b, nv, ds, de, st), "sr_blend_gz")
+            _lib.check(L.sr_blend_tail(ptr(gcoeff), ptr(gz), ptr(xs), ptr(xe), ptr(bt), 0.0, None, b, ds, de, st),
+                       "sr_blend_tail")
+        return gcoeff, None, None
+
+
+def _native_ok(model, *tensors):
+    return (all(t.device.type == "cuda" and t.dtype == torch.float32 for t in tensors + (model.weight, model.beta))
+            and not model.weight.requires_grad)
+
+
+def _composite_allowed(model, *tensors):
+    """Under SR_STRICT_NATIVE=1 a device tensor never falls to the composite (library matmul) silently."""
+    if strict_native() and any(t.device.type == "cuda" for t in tensors + (model.weight,)):
+        raise RuntimeError("SR_STRICT_NATIVE: the blendshape node takes device fp32 tensors and a frozen model on the "
+                           "device; this call (%s, learnable=%s) would run the composite on library GEMMs"
+                           % (", ".join(str(t.dtype) + "@" + t.device.type for t in tensors),
+                              model.weight.requires_grad))
+
+
+def _check(model, coeff):
+    if coeff.dim() != 2 or coeff.shape[1] != model.dim[0] + model.dim[1]:
+        raise ValueError("blend: coefficients %s, the model takes [B, %d + %d]"
+                         % (tuple(coeff.shape), model.dim[0], model.dim[1]))
+
+
+def blend_vertices(model, x):
+    """model.forward: vs [B, nv, 3] (no pose, no normals); the native forward on device fp32 with a frozen model."""
+    _check(model, x)
+    if _native_ok(model, x):
+        return _BlendVertices.apply(x, model.weight.detach(), model.beta.detach())
+    _composite_allowed(model, x)
+    return blend_vertices_composite(x, model.weight.to(x.dtype), model.dim[0])
+
+
+def prior_rows(model, coeff, reg_weight):
+    """[B]: reg_weight * regulation(coeff[b]) of every sample by the defining algebra (regulation is a sum over the batch)."""
+    ds, de = model.dim[0], model.dim[1]
+    beta = model.beta.to(coeff.dtype)
+    ls = torch.cat((coeff[:, :ds], -coeff[:, :ds].sum(1, keepdim=True)), 1)
+    xe = coeff[:, ds:]
+    bs, be = beta[:ds + 1], beta[ds + 1:].reshape(de, 2)
+    return -reg_weight * ((ls * bs).sum(1) - torch.logsumexp(ls, 1) * (bs.sum() - ds - 1) + (xe * be[:, 0] - 1).sum(1)
+                          - (torch.nn.functional.softplus(xe) * (be.sum(1) - 2)).sum(1))
+
+
+def blend_mesh(model, coeff, pose, tri, reg_weight=0.0, per_sample=False):
+    """(v [B, nv, 3], n [B, nv, 3], reg []) of a BlendShapeModel at coefficients coeff [B, ds + de] (or 1-D) and poses
+    pose [B, 7] (or [7]); reg = reg_weight * model.regulation(coeff).  With per_sample=True a fourth, detached output
+    [B] holds reg_weight * regulation(coeff[b]) of every sample (their sum is reg)."""
+    if coeff.dim() == 1:
+        coeff = coeff.view(1, -1)
+    if pose.dim() == 1:
+        pose = pose.view(1, 7)
+    if pose.shape[0] != coeff.shape[0]:
+        raise ValueError("blend_mesh: %d coefficient vectors but %d poses" % (coeff.shape[0], pose.shape[0]))
+    _check(model, coeff)
+    if _native_ok(model, coeff, pose):
+        out = _Blend.apply(coeff, pose, model.weight.detach(), model.beta.detach(), tri, float(reg_weight))
+        return out if per_sample else out[:3]
+    _composite_allowed(model, coeff, pose)
+    out = blend_composite(model, coeff, pose, tri, reg_weight)
+    return out + (prior_rows(model, coeff.detach(), reg_weight),) if per_sample else out

@@ -210,7 +210,7 @@ class _FitLossRows(Function):
         return (None, None, None, None, gm, greg) + tuple(gd.view(s) for s in ctx.layer_shapes)
 
 
-def fit_loss_rows(layers, mse, pixel_weight, coeff=None, sigma=None, shape_reg=0.0, reg=None):
+def fit_loss_rows(layers, mse, pixel_weight, coeff=None, sigma=None, shape_reg=0.0, reg=None, prior_rows=None):
     """Per-sample losses of a batched fit and their sum:
 
         rows[b] = sum_k layers[k][b] + pixel_weight * mse[b] (+ shape_reg * sum_j (coeff[b, j] / sigma[j])^2)
@@ -220,9 +220,18 @@ def fit_loss_rows(layers, mse, pixel_weight, coeff=None, sigma=None, shape_reg=0
     prior.  Returns (rows [B], not differentiable, total []).  On the device the prior's gradient is NOT formed here:
     `reg`, the scalar shape_reg * regulation(coeff) of op.morph.morph_mesh, receives d(total)/d(reg) and the morph node
     carries it to the coefficients (reg is required with coeff).  The composite (CPU, float64) differentiates the prior
-    through coeff and does not use reg."""
+    through coeff and does not use reg.
+
+    A prior that is not a diagonal Gaussian (op.blend's Dirichlet / Beta) comes as `prior_rows` [B], every sample's own
+    prior value (not differentiable), with `reg` their differentiable sum and no coeff: rows[b] += prior_rows[b],
+    total += reg, on every device."""
     if len(layers) != 5:
         raise ValueError("fit_loss_rows: five LPIPS layer distances expected, got %d" % len(layers))
+    if prior_rows is not None:
+        if coeff is not None or reg is None:
+            raise ValueError("fit_loss_rows: prior_rows comes with reg and without coeff")
+        rows, total = fit_loss_rows(layers, mse, pixel_weight)
+        return rows + prior_rows.detach().to(rows.dtype), total + reg
     ts = list(layers) + [mse] + ([coeff] if coeff is not None else [])
     if all(t.device.type == "cuda" and t.dtype == torch.float32 for t in ts):
         if coeff is not None and reg is None:

@@ -2,7 +2,7 @@
 for it):
 
     python -m stylerenderer_amd.reconstruct [--size 256] [--steps 400] [--lr] [--pose_lr] [--coeff_lr] [--shape_reg]
-        [--bfm BFM.mat | --flame FLAME.{pkl,mat}] [--lpips-trunk VGG16.pth] [--batch N] [--gpu 0] [--seed S] [--out DIR] CHECKPOINT IMAGE [IMAGE ...]
+        [--bfm BFM.mat | --flame FLAME.{pkl,mat} | --facewarehouse FW.mat [--beta_shape X]] [--lpips-trunk VGG16.pth] [--batch N] [--gpu 0] [--seed S] [--out DIR] CHECKPOINT IMAGE [IMAGE ...]
 
 For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with inversion.LatentInverter(fit_shape=True)
 — the W+ latent, a rigid pose and the 3DMM shape / expression coefficients are fitted together (op.morph on the device)
@@ -12,7 +12,9 @@ For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with in
     <stem>_canonical.obj  the fitted shape without the pose (with --flame: with the fitted articulation)
     <stem>_render.png     the generator's image of the fit
     <stem>_normal.png     the rasterised normal map of the posed mesh
-    <stem>.npz            w, coeff, pose and the loss history (with --flame also joints [nj-1, 3], the axis-angles)
+    <stem>.npz            w, coeff, pose and the loss history (with --flame also joints [nj-1, 3], the axis-angles; with
+                          --facewarehouse also identity [ds+1] and expression [de+1], the fitted mixing weights, each
+                          summing to 1: expression[0] is the neutral face's share)
 
 With --batch N the images are fitted N at a time, each group as one batched LatentInverter (one captured graph; every
 image still follows its own single-image optimisation): the first group builds the inverter, the following ones
@@ -20,7 +22,8 @@ re-target it with `reset`, and a short last group is padded with copies of its l
 The files and their shapes are those of --batch 1, the default, which fits one image per inverter.
 
 Images are PNG / JPG (PIL) or .npy in [-1, 1] (HWC or CHW), resized on the host.  The 3DMM is the Basel Face Model with
---bfm (face_model.load_bfm), FLAME with --flame (face_model.load_flame, op.skin), else the synthetic model `train --mesh` trains with (train.SyntheticFaceSource).  Without
+--bfm (face_model.load_bfm), FLAME with --flame (face_model.load_flame, op.skin), the FaceWarehouse bilinear blendshape
+model with --facewarehouse (face_model.load_facewarehouse, op.blend), else the synthetic model `train --mesh` trains with (train.SyntheticFaceSource).  Without
 --lpips-trunk the perceptual trunk is the deterministic synthetic fill and the result is not a meaningful
 reconstruction (stderr says so).
 """
@@ -58,8 +61,14 @@ def load_image(path, size):
     return x.clamp(-1, 1).contiguous()
 
 
-def face_model(bfm, device, seed=0, flame=None):
-    """(model, tri) on `device`: the Basel model of --bfm, FLAME of --flame, else train.SyntheticFaceSource's."""
+def face_model(bfm, device, seed=0, flame=None, facewarehouse=None, beta_shape=.01):
+    """(model, tri) on `device`: the Basel model of --bfm, FLAME of --flame, FaceWarehouse of --facewarehouse, else
+    train.SyntheticFaceSource's."""
+    if facewarehouse:
+        from .face_model import load_facewarehouse
+
+        model, tri = load_facewarehouse(facewarehouse, beta_shape)
+        return model.to(device), tri.to(device)
     if flame:
         from .face_model import load_flame
 
@@ -100,11 +109,14 @@ def reconstruct_batch(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, co
 
 def write_outputs(inv, hist, out_dir, stem, index=0):
     """The five files of sample `index` of the inverter (hist: its loss history [steps])."""
-    from .face_model import LinearBlendSkinningModel
+    from .face_model import BlendShapeModel, LinearBlendSkinningModel
     from .op.rasterize import rasterize
 
     skinned = isinstance(inv.face_model, LinearBlendSkinningModel)
-    if skinned:
+    blended = isinstance(inv.face_model, BlendShapeModel)
+    if blended:
+        from .op.blend import blend_mesh as node
+    elif skinned:
         from .op.skin import skin_mesh as node
     else:
         from .op.morph import morph_mesh as node
@@ -126,6 +138,9 @@ def write_outputs(inv, hist, out_dir, stem, index=0):
     generate.save_image(inv.image[k].cpu(), os.path.join(out_dir, stem + "_render.png"))
     generate.save_image(normal_map.cpu(), os.path.join(out_dir, stem + "_normal.png"))
     extra = {"joints": coeff[0, inv.face_model.dim[0]:].view(-1, 3).cpu().numpy()} if skinned else {}
+    if blended:
+        xs, xe = inv.face_model.mixing_weights(coeff)
+        extra = {"identity": xs[0].cpu().numpy(), "expression": xe[0].cpu().numpy()}
     np.savez(os.path.join(out_dir, stem + ".npz"), w=inv.w.detach()[k].cpu().numpy(), coeff=coeff.cpu().numpy(),
              pose=pose.cpu().numpy(), loss=hist, **extra)
 
@@ -138,11 +153,18 @@ def main(argv=None):
     ap.add_argument("--pose_lr", type=float, default=0.01, help="learning rate of the pose [%(default)g]")
     ap.add_argument("--coeff_lr", type=float, default=0.01, help="learning rate of the 3DMM coefficients [%(default)g]")
     ap.add_argument("--shape_reg", type=float, default=1e-3,
-                    help="weight of the coefficient prior sum (coeff / sigma)^2 [%(default)g]")
+                    help="weight of the coefficient prior: sum (coeff / sigma)^2, or the Dirichlet / Beta prior of "
+                         "--facewarehouse, which with a --beta_shape below 1 (the default) is unbounded below and pushes "
+                         "the identity away from the mean: use --beta_shape >= 1 or --shape_reg 0 there [%(default)g]")
     which = ap.add_mutually_exclusive_group()
     which.add_argument("--bfm", default=None, metavar="BFM.mat", help="Basel Face Model (.mat); default: synthetic 3DMM")
     which.add_argument("--flame", default=None, metavar="FLAME.{pkl,mat}",
                        help="FLAME skinned model: shape and the neck / jaw / eye rotations are fitted")
+    which.add_argument("--facewarehouse", default=None, metavar="FW.mat",
+                       help="FaceWarehouse bilinear blendshape model: identity and expression weights are fitted")
+    ap.add_argument("--beta_shape", type=float, default=.01,
+                    help="with --facewarehouse: Dirichlet concentration of the identity prior; the reference's .01 is "
+                         "not a proper prior (see --shape_reg) [%(default)g]")
     ap.add_argument("--lpips-trunk", default=None, metavar="PATH",
                     help="torchvision vgg16 (or vgg16().features) state dict for the LPIPS trunk")
     ap.add_argument("--n_mean_latent", type=int, default=4096, help="latents averaged for the starting W+ [%(default)d]")
@@ -171,7 +193,8 @@ def main(argv=None):
         sys.stderr.write("warning: no --lpips-trunk given: the LPIPS VGG16 trunk is the deterministic synthetic fill, "
                          "so this is not a meaningful reconstruction\n")
     percept = percept.to(device)
-    face = face_model(args.bfm, device, seed=args.seed, flame=args.flame)
+    face = face_model(args.bfm, device, seed=args.seed, flame=args.flame, facewarehouse=args.facewarehouse,
+                      beta_shape=args.beta_shape)
     os.makedirs(args.out, exist_ok=True)
     results = []
     if args.batch == 1:

@@ -405,6 +405,44 @@ class FlameFaceSource(SyntheticFaceSource):
         self.pose_sigma = torch.tensor([.5, .1, .05, .1, .1, .1, .15], dtype=torch.float32, device=device)
 
 
+class FaceWarehouseFaceSource(SyntheticFaceSource):
+    """SyntheticFaceSource's per-iteration sampling (same `sample()` contract, usable with --graphs) over the bilinear
+    blendshape model of a FaceWarehouse `.mat` file or dict in face_model.load_facewarehouse's contract: identity and
+    expression weights are drawn from the model's Dirichlet / Beta prior and blended by op.blend's native forward (two
+    launches), so that `reconstruct --facewarehouse` fits the model the network was trained with."""
+
+    def __init__(self, device, path, beta_shape=.01):
+        from . import face_model, utils_3d
+
+        model, tri = face_model.load_facewarehouse(path, beta_shape)
+        self.model = model.to(device)
+        self.tri = tri.to(device)
+        self.device = device
+        self._u = utils_3d
+        self.pose_sigma = torch.tensor([.5, .1, .05, .1, .1, .1, .15], dtype=torch.float32, device=device)
+
+
+def synthetic_facewarehouse_dict(shape_dim=149, expression_dim=46, face_sized=True, mesh=None, shape_amplitude=0.05,
+                                 expression_amplitude=0.03, key=971):
+    """A FaceWarehouse-shaped dict (face_model.load_facewarehouse's keys) on the face-sized mesh, or on `mesh` = (v0,
+    tri) — FaceWarehouse itself is licensed and absent: identity i's neutral face is the mean plus a smooth displacement
+    (`smooth_basis`), expression j adds a smooth displacement scaled per identity, so the tensor is bilinear but not a
+    sum of an identity and an expression part.  `p` is float32 [3 nv, de + 1, ds + 1]; at the defaults with the
+    face-sized mesh it is FaceWarehouse's own count of identities and expressions."""
+    if mesh is not None:
+        v0, tri = mesh
+    else:
+        v0, tri = synth.face_sized_mesh() if face_sized else synth.uv_ellipsoid(16, 14)
+    ns, ne = shape_dim + 1, expression_dim + 1
+    ident = smooth_basis(v0, ns, key, shape_amplitude)                                         # [ns, 3 nv]
+    expr = smooth_basis(v0, ne, key + 4, expression_amplitude)                                 # [ne, 3 nv]
+    expr[0] = 0.0                                                                              # the neutral face
+    gain = (1.0 + 0.3 * np.sin(0.7 * np.arange(ns, dtype=np.float32)))[:, None, None]          # per identity
+    p = (v0.reshape(-1).astype(np.float32)[None, None] + ident[:, None, :] + gain * expr[None])  # [ns, ne, 3 nv]
+    return {"v": np.ascontiguousarray(v0.T.astype(np.float64)), "p": np.ascontiguousarray(np.transpose(p, [2, 1, 0])),
+            "tri": (tri + 1).astype(np.int32)}
+
+
 def synthetic_flame_dict(shape_dim=144, face_sized=True, mesh=None, shape_amplitude=None, pose_amplitude=0.02, key=951):
     """A FLAME-shaped dict (face_model.load_flame's keys) on the face-sized mesh, or on `mesh` = (v0, tri) — FLAME itself
     is licensed and absent: five joints in FLAME's tree (root, neck, then jaw and two eyeballs on the neck), smooth shape
@@ -457,6 +495,9 @@ def main():
                          "the synthetic 3DMM")
     ap.add_argument("--flame", type=str, default=None, metavar="PATH",
                     help="with --mesh: sample meshes from this FLAME model (.pkl / .mat, face_model.load_flame)")
+    ap.add_argument("--facewarehouse", type=str, default=None, metavar="PATH",
+                    help="with --mesh: sample meshes from this FaceWarehouse bilinear blendshape model (.mat, "
+                         "face_model.load_facewarehouse)")
     ap.add_argument("--augment", action="store_true", help="adaptive discriminator augmentation")
     ap.add_argument("--augment_p", type=float, default=0)
     ap.add_argument("--ada_target", type=float, default=0.6)
@@ -475,11 +516,13 @@ def main():
     targs = (args.size, args.latent, args.n_mlp, args.channel_multiplier, args.lr, args.r1, args.path_regularize,
              args.path_batch_shrink, args.d_reg_every, args.g_reg_every, args.mixing, args.mesh, device, args.seed,
              args.augment, args.augment_p, args.ada_target, args.ada_length)
-    if (args.bfm or args.flame) and not args.mesh:
-        ap.error("--bfm / --flame need --mesh")
-    if args.bfm and args.flame:
-        ap.error("--bfm and --flame are mutually exclusive")
-    if args.mesh and args.flame:
+    if (args.bfm or args.flame or args.facewarehouse) and not args.mesh:
+        ap.error("--bfm / --flame / --facewarehouse need --mesh")
+    if sum(bool(a) for a in (args.bfm, args.flame, args.facewarehouse)) > 1:
+        ap.error("--bfm, --flame and --facewarehouse are mutually exclusive")
+    if args.mesh and args.facewarehouse:
+        faces = FaceWarehouseFaceSource(device, args.facewarehouse)
+    elif args.mesh and args.flame:
         faces = FlameFaceSource(device, args.flame)
     elif args.mesh:
         faces = BfmFaceSource(device, args.bfm) if args.bfm else SyntheticFaceSource(device, seed=args.seed)
