@@ -782,6 +782,27 @@ int sr_ada_apply(float* out, const float* img, const float* rec, int64_t B, int6
 int sr_ada_apply_grad(float* gin, const float* gout, const float* rec, int64_t B, int64_t H, int64_t W, sr_stream_t stream);
 int sr_ada_update(double* state, const float* stat, double target, double length, sr_stream_t stream);
 
+/* Pillow-exact resampling of uint8 images (Pillow's ImagingResample for 8-bit pixels), csrc/resample.hip.
+ * in uint8 [N, H, W, C] contiguous, C in {1, 3, 4}, resized to the virtual image [N, oh, ow, C] of which the window
+ * rows oy0 .. oy0 + ohw, columns ox0 .. ox0 + oww is written: out_form 0: uint8 [N, ohw, oww, C]; 1: float32
+ * [N, C, ohw, oww] = (v / 255 - 0.5) / 0.5.  Two separable passes, horizontal first into `scratch`
+ * (sr_resample_u8_scratch_bytes; 0 when a pass is skipped); each output byte is clip(0, 255, (2^21 + sum_t
+ * pixel[first + t] * k[t]) >> 22) in int32.  A pass whose axis keeps its size is skipped and takes NULL tables.
+ * Per axis the caller supplies Pillow's 22-bit fixed-point tables (stylerenderer_amd/op/resample.py coefficients()):
+ *   coeffs_h_t     DEVICE int32 [ksize_h, ow]: the [ow, ksize_h] table TRANSPOSED;  coeffs_v  DEVICE int32 [oh, ksize_v]
+ *   bounds_h / _v  DEVICE int32 [out, 2] = (first source index, tap count); bounds_*_host the same array on the HOST
+ *                  (validated against the source size and used to size the passes; first and first + count must not
+ *                  decrease along the axis)
+ * mul24 != 0 promises |k| < 2^23 for every coefficient (the 24-bit multiply-add is used).  One or two launches on
+ * `stream`, no allocation, no host synchronisation; N, ohw <= 65535. */
+int64_t sr_resample_u8_scratch_bytes(int64_t N, int64_t H, int64_t W, int64_t C, int64_t oh, int64_t ow,
+                                     const int32_t* bounds_v_host, int64_t oy0, int64_t ox0, int64_t ohw, int64_t oww);
+int sr_resample_u8(void* out, const uint8_t* in, int64_t N, int64_t H, int64_t W, int64_t C, int64_t oh, int64_t ow,
+                   const int32_t* coeffs_h_t, const int32_t* bounds_h, const int32_t* bounds_h_host, int64_t ksize_h,
+                   const int32_t* coeffs_v, const int32_t* bounds_v, const int32_t* bounds_v_host, int64_t ksize_v,
+                   int64_t oy0, int64_t ox0, int64_t ohw, int64_t oww, int out_form, int mul24, uint8_t* scratch,
+                   sr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ SOURCES = [
     ("lpips.hip", EXACT),
     ("ppl.hip", EXACT),
     ("augment.hip", EXACT),
+    ("resample.hip", EXACT),
     ("conv_mfma.hip", []),
     ("conv_wino.hip", []),
     ("conv_wgrad_wino.hip", []),

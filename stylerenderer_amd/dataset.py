@@ -77,8 +77,9 @@ def open_store(path_or_store):
     raise IOError("Cannot open dataset", path_or_store)
 
 
-def encode_image(img_u8, fmt="JPEG"):
-    """uint8 [H, W, 3] -> bytes (JPEG like prepare_data.save_img; 'NPY' = lossless raw payload)."""
+def encode_image(img_u8, fmt="JPEG", quality=None):
+    """uint8 [H, W, 3] -> bytes (JPEG like prepare_data.save_img; 'NPY' = lossless raw payload).  `quality` goes to
+    Pillow when given (prepare_data.save_img uses 100)."""
     if fmt.upper() == "NPY":
         buf = io.BytesIO()
         np.save(buf, np.ascontiguousarray(img_u8))
@@ -86,7 +87,7 @@ def encode_image(img_u8, fmt="JPEG"):
     from PIL import Image
 
     buf = io.BytesIO()
-    Image.fromarray(img_u8).save(buf, format=fmt)
+    Image.fromarray(img_u8).save(buf, format=fmt, **({} if quality is None else {"quality": quality}))
     return buf.getvalue()
 
 
@@ -113,6 +114,66 @@ def write_store(target, images, resolutions, fmt="JPEG"):
             put(make_key(r, i, total), encode_image(per_res[r], fmt))
     put(b"length", str(total).encode("utf-8"))
     return total
+
+
+IMG_EXTS = ('.jpg', '.jpeg', '.png', '.ppm', '.bmp', '.pgm', '.tif', '.tiff', '.webp')
+
+
+def read_image(path):
+    """File -> uint8 [H, W, 3] (RGB), or None when it cannot be read or decoded (prepare_data.read_img)."""
+    from PIL import Image
+
+    try:
+        with Image.open(path) as im:
+            return np.asarray(im.convert("RGB"))
+    except (OSError, ValueError, SyntaxError):
+        return None
+
+
+class ImgDataset(torch.utils.data.Dataset):
+    """reference dataset.py:8-55: the images of a folder, resized on the fly.
+
+    The listing follows the reference: `folder` may be one image file; a name counts as an image when it ends with one
+    of `exts` in any letter case; folders are visited breadth first (only the top one when `recurrent` is false), each
+    in os.listdir order; `imgs` = [(path, 0)] like torchvision's ImageFolder.  An item is the RGB image, brought to
+    resolution x resolution by op.resample.resize_center_crop (Lanczos: what the reference's own call is meant to do,
+    see prepare_data.py in this package) unless it already has that size, then passed through `transform` (default:
+    to_unit_tensor, uint8 HWC -> float32 CHW)."""
+
+    def __init__(self, folder, transform=None, resolution=256, recurrent=True, exts=IMG_EXTS):
+        super().__init__()
+        exts = [exts] if isinstance(exts, str) else list(exts)
+
+        def is_image(name):
+            return any(name[-len(e):].lower() == e.lower() for e in exts)
+
+        files, queue = [], []
+        if os.path.isdir(folder):
+            queue = [folder]
+        elif os.path.exists(folder) and is_image(folder):
+            files = [folder]
+        while queue:
+            here = queue.pop(0)
+            names = os.listdir(here)
+            files += [os.path.join(here, f) for f in names if is_image(f)]
+            if recurrent:
+                queue += [os.path.join(here, f) for f in names if os.path.isdir(os.path.join(here, f))]
+        self.imgs = [(f, 0) for f in files]
+        self.transform = transform if transform is not None else to_unit_tensor
+        self.resolution = resolution
+
+    def __len__(self):
+        return len(self.imgs)
+
+    def __getitem__(self, index):
+        from .op import resample
+
+        img = read_image(self.imgs[index][0])
+        if img is None:
+            raise IOError("Cannot read image", self.imgs[index][0])
+        if img.shape[0] != self.resolution or img.shape[1] != self.resolution:
+            img = resample.resize_center_crop(img, self.resolution, "lanczos")
+        return self.transform(img)
 
 
 class MultiResolutionDataset(torch.utils.data.Dataset):
