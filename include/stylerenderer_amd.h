@@ -803,6 +803,21 @@ int sr_resample_u8(void* out, const uint8_t* in, int64_t N, int64_t H, int64_t W
                    int64_t oy0, int64_t ox0, int64_t ohw, int64_t oww, int out_form, int mul24, uint8_t* scratch,
                    sr_stream_t stream);
 
+/* Pillow-exact bilinear affine warp of uint8 images (Pillow's Image.transform(AFFINE, BILINEAR)), csrc/warp.hip.
+ * in uint8 [N, H, W, C] contiguous, C in {1, 3, 4}; matrix DEVICE float64 [N, 6] (matrix_stride = 6) or [6] shared by
+ * the batch (matrix_stride = 0), in Pillow's pixel-centre convention.  For output pixel (x, y), all in float64, left to
+ * right, no fused multiply-add: xs = x + .5, ys = y + .5, xin = a0 xs + a1 ys + a2, yin = a3 xs + a4 ys + a5,
+ * xf = xin - .5, x0 = floor(xf), dx = xf - x0 (likewise y); x0, y0 are clamped to [-2^30, 2^30]; the taps (x0, x0 + 1) x
+ * (y0, y0 + 1) are mapped into the image by `border`; v1 = p00 + (p01 - p00) dx, v2 = p10 + (p11 - p10) dx,
+ * v = v1 + (v2 - v1) dy, byte = (uint8) v by truncation.
+ * border 0: replicate (clamp); 1: reflect (fedcba|abcdef|fedcba, periodic); 2: constant: `fill` where (xin, yin) is
+ * outside [0, W) x [0, H) (or not a number), clamp elsewhere.
+ * out_form 0: uint8 [N, oh, ow, C]; 1: float32 [N, C, oh, ow] = (v / 255 - 0.5) / 0.5.  One launch on `stream`, no
+ * allocation, no host synchronisation; N <= 65535, oh < 2^20, H, W <= 2^24. */
+int sr_warp_affine_u8(void* out, const uint8_t* in, const double* matrix, int64_t matrix_stride, int64_t N, int64_t H,
+                      int64_t W, int64_t C, int64_t oh, int64_t ow, int border, int fill, int out_form,
+                      sr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

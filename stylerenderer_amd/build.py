@@ -42,6 +42,7 @@ SOURCES = [
     ("ppl.hip", EXACT),
     ("augment.hip", EXACT),
     ("resample.hip", EXACT),
+    ("warp.hip", EXACT),
     ("conv_mfma.hip", []),
     ("conv_wino.hip", []),
     ("conv_wgrad_wino.hip", []),

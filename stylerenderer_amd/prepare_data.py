@@ -2,7 +2,8 @@
 pictures (reference prepare_data.py):
 
     python -m stylerenderer_amd.prepare_data --out STORE [--size 128,256,512,1024] [--resample lanczos]
-        [--n_worker 8] [--quality 100] [--format jpeg|png|npy] [--gpu 0] PATH
+        [--n_worker 8] [--quality 100] [--format jpeg|png|npy] [--gpu 0]
+        [--align LANDMARKS.txt [--bfm BFM.mat | --template FILE] [--align_size S] [--border reflect]] PATH
 
 Every image found by dataset.ImgDataset under PATH (sorted by path) is resized so that its shorter side is the target
 size, centre cropped to size x size (op.resample.resize_center_crop: torchvision's geometry, Pillow's resampler to the
@@ -13,6 +14,14 @@ Work split: a thread pool (at most 16 threads; Pillow releases the GIL while it 
 the parent thread resamples.  --gpu N resamples on that device with the sr_resample_u8 kernels, one upload per image
 (or per run of images of one source shape) for all sizes; --gpu -1 resamples on the host inside the worker threads.
 Only this process opens the GPU: there are no worker processes and nothing forks.  Both paths write identical stores.
+
+--align LANDMARKS.txt first warps every picture onto an S x S canvas (S = --align_size, by default the largest --size;
+without --bfm / --template and without --align_size: the shape of the first picture, whose landmarks are the template)
+on which its landmarks meet the template's, exactly as align_faces does (align.py; template selection as there), and
+resamples that canvas: on the device upload -> op.warp_affine -> resize_pyramid on the canvas tensor with nothing read
+back in between, on the host the same two steps inside the workers.  It stores what prepare_data stores from
+align_faces' lossless output, but decodes every picture once and never writes the aligned intermediates.  Pictures the
+landmark file does not list are skipped and counted; the indices stay compact.
 
 Where the reference's tool does something else than it says, this one does what it says:
   * resize_img tests `elif 'area' or 'box' in resample.lower()`, which is always true: whatever --resample names, the
@@ -32,8 +41,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import dataset
-from .op import resample
+from . import align, dataset
+from .op import resample, warp
 
 MAX_THREADS = 16
 FORMATS = {"jpeg": "JPEG", "png": "PNG", "npy": "NPY"}
@@ -93,8 +102,9 @@ def _pillow_pyramid(img, sizes, name):
 
 
 def prepare(writer, files, sizes=(128, 256, 512, 1024), filter="lanczos", n_worker=8, quality=100, fmt="jpeg",
-            gpu=-1, host_resampler="numpy", log=None):
-    """Writes every size of every readable file of `files` (paths, in the order given) into `writer`.
+            gpu=-1, host_resampler="numpy", log=None, aligner=None):
+    """Writes every size of every readable file of `files` (paths, in the order given) into `writer`; with an
+    align.Aligner every file (all of which it must have landmarks for) is first warped onto its canvas.
     Returns (stored, skipped, seconds) with seconds = {"decode", "resample", "encode", "wall"}: decode / encode are
     summed over the worker threads."""
     sizes = [int(s) for s in sizes]
@@ -122,24 +132,35 @@ def prepare(writer, files, sizes=(128, 256, 512, 1024), filter="lanczos", n_work
 
     def load(path):
         img = timed("decode", dataset.read_image, path)
-        if img is None or device is not None:
-            return img
-        return timed("resample", host_levels, img)
+        if img is None:
+            return None
+        if aligner is None:
+            return img if device is not None else timed("resample", host_levels, img)
+        m = aligner.matrix(path)
+        if device is not None:
+            return img, m
+        return timed("resample", lambda: host_levels(warp.warp_affine(img, m, aligner.canvas, aligner.border)))
 
     def encode(levels):
         return timed("encode", lambda: [dataset.encode_image(np.ascontiguousarray(levels[s]), enc_fmt, q) for s in sizes])
 
     def device_levels(imgs):
-        """[H, W, 3] arrays -> one {size: array} per image; images of one shape share the upload and the launches."""
+        """[H, W, 3] arrays -> one {size: array} per image; images of one shape share the upload and the launches.
+        With an aligner: (array, matrix) pairs, warped to the canvas on the device before the pyramid."""
         import torch
 
         t0 = time.perf_counter()
+        mats = None
+        if aligner is not None:
+            imgs, mats = [im for im, _ in imgs], [m for _, m in imgs]
         out = [None] * len(imgs)
         groups = {}
         for i, im in enumerate(imgs):
             groups.setdefault(im.shape, []).append(i)
         for idx in groups.values():
             x = torch.from_numpy(np.stack([imgs[i] for i in idx])).to(device)
+            if mats is not None:
+                x = warp.warp_affine(x, np.stack([mats[i] for i in idx]), aligner.canvas, aligner.border)
             levels = {s: v.cpu().numpy() for s, v in resample.resize_pyramid(x, sizes, name).items()}
             for j, i in enumerate(idx):
                 out[i] = {s: levels[s][j] for s in sizes}
@@ -183,6 +204,8 @@ def main(argv=None):
     ap.add_argument("--gpu", type=int, default=0, help="device that resamples; -1: the host")
     ap.add_argument("--host_resampler", type=str, default="numpy", choices=["numpy", "pillow"],
                     help="with --gpu -1: the integer restatement of this package, or Pillow itself (the same bytes)")
+    ap.add_argument("--align", type=str, default="", help="landmark .txt file: align every picture before resampling")
+    align.add_arguments(ap, "--align_size")
     ap.add_argument("path", type=str, help="path to the image dataset")
     args = ap.parse_args(argv)
     sizes = []
@@ -196,10 +219,21 @@ def main(argv=None):
     resample._filter(args.resample)
     print("Make dataset of image sizes:" + ",".join("%d" % s for s in sizes))
     files = sorted(f for f, _ in dataset.ImgDataset(args.path).imgs)
+    aligner = None
+    if args.align:
+        # without a template the first picture gives template AND canvas (its own shape), as in align_faces
+        size = args.align_size or (max(sizes) if args.bfm or args.template else 0)
+        aligner = align.aligner_from_args(args.align, args.bfm, args.template, size, args.border, files, dataset.read_image)
+        listed = [f for f in files if aligner.has(f)]
+        print("aligning to %d x %d by %s: %d of %d pictures have landmarks, %d skipped"
+              % (aligner.canvas[0], aligner.canvas[1], args.align, len(listed), len(files), len(files) - len(listed)))
+        files = listed
+    elif args.bfm or args.template or args.align_size:
+        ap.error("--bfm, --template and --align_size go with --align")
     writer = open_writer(args.out)
     try:
         stored, skipped, spent = prepare(writer, files, sizes, args.resample, args.n_worker, args.quality, args.format,
-                                         args.gpu, args.host_resampler)
+                                         args.gpu, args.host_resampler, aligner=aligner)
     finally:
         writer.close()
     wall = spent["wall"]
