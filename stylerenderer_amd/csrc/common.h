@@ -29,6 +29,19 @@ static inline int sr_stream_grid(int64_t work_items, int per_block) {
     return static_cast<int>(g);
 }
 
+static inline bool sr_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// V = 4: one 16-byte load of four floats (p 16-byte aligned); V = 1: one float
+template <int V>
+__device__ __forceinline__ void sr_load_v(float* o, const float* p) {
+    if constexpr (V == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w;
+    } else {
+        o[0] = p[0];
+    }
+}
+
 // wave64 sum via DPP-friendly shuffles
 __device__ __forceinline__ float sr_wave_sum(float x) {
 #pragma unroll

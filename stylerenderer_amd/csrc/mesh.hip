@@ -154,52 +154,27 @@ __global__ __launch_bounds__(1024) void k_affine3_bwd(float* __restrict__ gm, fl
     if (threadIdx.x >= 9 && threadIdx.x < 12 && gt) gt[3 * b + (threadIdx.x - 9)] = s[threadIdx.x][0];
 }
 
-// ---- pose of the latent-inversion loop: (yaw, pitch, roll, tx, ty, tz, log-scale) -> rot = Rz(roll) Rx(pitch) Ry(yaw) ("yxz"
-// order of utils_3d.euler_mat: later axes multiply from the left) and lin = exp(log-scale) * rot, and the gradient of the
-// seven numbers given the gradients of the two matrices.  As tensor algebra this is ~60 launches of one-element kernels
-// per step (sin / cos / cat / view / three 3x3 products and their backward); here one lane each way.
+// ---- pose of the latent-inversion loop (pose.h: the chain and its gradient) -------------------------------------------
+// As tensor algebra this is ~60 launches of one-element kernels per step (sin / cos / cat / view / three 3x3 products and
+// their backward); here one lane each way.
 __global__ void k_pose_fwd(float* __restrict__ lin, float* __restrict__ rot, const float* __restrict__ pose, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;          // one pose per thread
     if (b >= B) return;
-    pose += 7 * b;
-    float ry[9], rx[9], rz[9], d0[9], d1[9], d2[9], t[9], r[9];
-    axis_mats(pose, ry, rx, rz, d0, d1, d2);
-    mat3_mul(rx, ry, t);
-    mat3_mul(rz, t, r);
-    const float sc = expf(pose[6]);
+    float l[9], r[9];
+    pose_fwd(pose + 7 * b, l, r);
 #pragma unroll
     for (int i = 0; i < 9; ++i) {
         if (rot) rot[9 * b + i] = r[i];
-        lin[9 * b + i] = sc * r[i];
+        lin[9 * b + i] = l[i];
     }
 }
 
+// One pose.  morph.hip's k_morph_pose_bwd is the same pose_bwd for a batch, but that file is compiled with floating-point
+// contraction on and this one with it off, so the two round differently in the last bits: each entry point keeps its own.
 __global__ void k_pose_bwd(float* __restrict__ gpose, const float* __restrict__ glin, const float* __restrict__ grot,
                            const float* __restrict__ pose) {
-    float ry[9], rx[9], rz[9], dry[9], drx[9], drz[9], t[9], r[9], u[9], d[9];
-    axis_mats(pose, ry, rx, rz, dry, drx, drz);
-    mat3_mul(rx, ry, t);
-    mat3_mul(rz, t, r);
-    const float sc = expf(pose[6]);
-    float gt[9];                          // dL/dR = grot + sc * glin
-    float gs = 0.f;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        const float gl = glin ? glin[i] : 0.f;
-        gt[i] = (grot ? grot[i] : 0.f) + sc * gl;
-        gs += gl * r[i];
-    }
-    auto dot9 = [&](const float* m) {
-        float a = 0.f;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) a += gt[i] * m[i];
-        return a;
-    };
-    mat3_mul(rx, dry, u); mat3_mul(rz, u, d); gpose[0] = dot9(d);      // d/d yaw:   Rz Rx Ry'
-    mat3_mul(drx, ry, u); mat3_mul(rz, u, d); gpose[1] = dot9(d);      // d/d pitch: Rz Rx' Ry
-    mat3_mul(drz, t, d);                      gpose[2] = dot9(d);      // d/d roll:  Rz' Rx Ry
+    pose_bwd(pose, glin, grot, gpose);
     gpose[3] = gpose[4] = gpose[5] = 0.f;                              // (translation: sr_affine3_bwd's gt)
-    gpose[6] = sc * gs;
 }
 
 }  // namespace

@@ -22,16 +22,6 @@
 
 namespace {
 
-template <int V>
-__device__ __forceinline__ void load_v(float* o, const float* p) {
-    if constexpr (V == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w;
-    } else {
-        o[0] = p[0];
-    }
-}
-
 // One wave per vertex: lanes stride over the 3 d contiguous weights of its three rows (V per load), every sample's dot
 // products accumulate in registers, a fixed butterfly sums the lanes, lane 0 adds the mean, applies the pose and stores.
 template <int V>
@@ -65,7 +55,7 @@ __global__ __launch_bounds__(256) void k_morph_fwd(float* __restrict__ v, float*
             const int e = q * V;
             const int r = e / d, k = e - r * d;                  // d % V == 0: a load never straddles two rows
             float wv[V];
-            load_v<V>(wv, wr + e);
+            sr_load_v<V>(wv, wr + e);
 #pragma unroll
             for (int bb = 0; bb < SR_MORPH_MAXB; ++bb) {
                 if (b0 + bb < B) {
@@ -270,7 +260,7 @@ __global__ __launch_bounds__(256) void k_morph_gcoeff_partial(float* __restrict_
 #pragma unroll 4
                 for (int jj = grp; jj < nr; jj += G) {
                     float wv[V];
-                    load_v<V>(wv, w + (j0 + jj) * d + kq * V);
+                    sr_load_v<V>(wv, w + (j0 + jj) * d + kq * V);
 #pragma unroll
                     for (int bb = 0; bb < SR_MORPH_MAXB; ++bb) {
                         if (bb < nb) {
@@ -327,44 +317,19 @@ __global__ __launch_bounds__(256) void k_morph_gcoeff_reduce(float* __restrict__
     }
 }
 
-// Pose gradient of a batch: dL/dR = grot + exp(s) glin (as k_pose_bwd in mesh.hip), the translation's gradient gt, one
-// lane per sample.
+// Pose gradient of a batch (pose.h's pose_bwd; as k_pose_bwd in mesh.hip up to that file's rounding: it is compiled without
+// floating-point contraction), with the translation's gradient gt (NULL: zero), one lane per sample.
 __global__ void k_morph_pose_bwd(float* __restrict__ gpose, const float* __restrict__ glin,
                                  const float* __restrict__ grot, const float* __restrict__ gt,
                                  const float* __restrict__ pose, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const float* p = pose + 7 * b;
-    float ry[9], rx[9], rz[9], dry[9], drx[9], drz[9], t[9], r[9], u[9], dm[9];
-    axis_mats(p, ry, rx, rz, dry, drx, drz);
-    mat3_mul(rx, ry, t);
-    mat3_mul(rz, t, r);
-    const float sc = expf(p[6]);
-    float gm[9];
-    float gs = 0.f;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        const float gl = glin ? glin[9 * b + i] : 0.f;
-        gm[i] = (grot ? grot[9 * b + i] : 0.f) + sc * gl;
-        gs += gl * r[i];
-    }
-    auto dot9 = [&](const float* m) {
-        float a = 0.f;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) a += gm[i] * m[i];
-        return a;
-    };
     float* o = gpose + 7 * b;
-    mat3_mul(rx, dry, u); mat3_mul(rz, u, dm); o[0] = dot9(dm);
-    mat3_mul(drx, ry, u); mat3_mul(rz, u, dm); o[1] = dot9(dm);
-    mat3_mul(drz, t, dm);                      o[2] = dot9(dm);
+    pose_bwd(pose + 7 * b, glin ? glin + 9 * b : nullptr, grot ? grot + 9 * b : nullptr, o);
     o[3] = gt ? gt[3 * b] : 0.f;
     o[4] = gt ? gt[3 * b + 1] : 0.f;
     o[5] = gt ? gt[3 * b + 2] : 0.f;
-    o[6] = sc * gs;
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int slab_rows(int64_t d) {
     // ~64 KB of W per workgroup (112 rows at d = 144: ~670 workgroups for the face-sized model), whole thread groups
@@ -387,7 +352,7 @@ extern "C" int sr_morph_fwd(float* v, float* vs, float* reg, const float* w, con
     if (B * d > SR_MORPH_MAX_BD || nv >= (1LL << 30) || d >= (1LL << 20)) return SR_ERANGE;
     const int64_t blocks = sr_ceil_div(nv, 4);
     if (blocks > 0x7fffffff) return SR_ERANGE;
-    const bool vec = d % 4 == 0 && aligned16(w);
+    const bool vec = d % 4 == 0 && sr_aligned16(w);
     const size_t lds = (size_t)(B * d > 0 ? B * d : 1) * sizeof(float);
     if (vec)
         hipLaunchKernelGGL(k_morph_fwd<4>, dim3((unsigned)blocks), dim3(256), lds, sr_stream(stream), v, vs, reg, w,
@@ -430,7 +395,7 @@ extern "C" int sr_morph_gcoeff(float* gcoeff, float* scratch, const float* w, co
     const int64_t S = rows > 0 ? sr_ceil_div(rows, R) : 0;
     if (S > 0x7fffffff) return SR_ERANGE;
     if (S > 0) {
-        const bool vec = d % 4 == 0 && aligned16(w);
+        const bool vec = d % 4 == 0 && sr_aligned16(w);
         if (vec)
             hipLaunchKernelGGL(k_morph_gcoeff_partial<4>, dim3((unsigned)S), dim3(256), 0, sr_stream(stream), scratch,
                                w, gvs, (int)B, rows, (int)d, R);

@@ -31,16 +31,6 @@
 
 namespace {
 
-template <int V>
-__device__ __forceinline__ void load_v(float* o, const float* p) {
-    if constexpr (V == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        o[0] = q.x; o[1] = q.y; o[2] = q.z; o[3] = q.w;
-    } else {
-        o[0] = p[0];
-    }
-}
-
 __device__ __forceinline__ void pose_lin(const float* pose, float* lin, float* t) {
     if (!pose) {
 #pragma unroll
@@ -48,13 +38,8 @@ __device__ __forceinline__ void pose_lin(const float* pose, float* lin, float* t
         t[0] = t[1] = t[2] = 0.f;
         return;
     }
-    float ry[9], rx[9], rz[9], dry[9], drx[9], drz[9], u[9], r[9];
-    axis_mats(pose, ry, rx, rz, dry, drx, drz);
-    mat3_mul(rx, ry, u);
-    mat3_mul(rz, u, r);
-    const float sc = expf(pose[6]);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) lin[i] = sc * r[i];
+    float rot[9];
+    pose_fwd(pose, lin, rot);
     t[0] = pose[3]; t[1] = pose[4]; t[2] = pose[5];
 }
 
@@ -188,7 +173,7 @@ __global__ __launch_bounds__(256) void k_skin_fwd(float* __restrict__ v, float* 
             const int e = q * V;
             const int r = e / D, k = e - r * D;                  // D % V == 0: a load never straddles two rows
             float wv[V];
-            load_v<V>(wv, wr + e);
+            sr_load_v<V>(wv, wr + e);
 #pragma unroll
             for (int bb = 0; bb < SR_SKIN_MAXB; ++bb) {
                 if (b0 + bb < B) {
@@ -388,28 +373,10 @@ __global__ __launch_bounds__(64) void k_skin_joints_bwd(float* __restrict__ gcoe
 #pragma unroll
             for (int n = 0; n < 3; ++n) sgJ[3 * i + n] += sg[12 * i + 9 + n];
         if (gpose) {
-            // as k_morph_pose_bwd (morph.hip): dL/dR = exp(s) glin, the scale through <glin, R>
-            const float* ps = pose + 7 * b;
-            float ry[9], rx[9], rz[9], dry[9], drx[9], drz[9], t[9], rr[9], u[9], dm[9], gm[9];
-            axis_mats(ps, ry, rx, rz, dry, drx, drz);
-            mat3_mul(rx, ry, t);
-            mat3_mul(rz, t, rr);
-            const float sc = expf(ps[6]);
-            float gs = 0.f;
-#pragma unroll
-            for (int e = 0; e < 9; ++e) { gm[e] = sc * glin[e]; gs += glin[e] * rr[e]; }
-            auto dot9 = [&](const float* m) {
-                float a = 0.f;
-#pragma unroll
-                for (int e = 0; e < 9; ++e) a += gm[e] * m[e];
-                return a;
-            };
+            // dL/dR = exp(s) glin: pose_bwd forms it as 0 + exp(s) glin, so a -0 there is now +0 (no value changes)
             float* o = gpose + 7 * b;
-            mat3_mul(rx, dry, u); mat3_mul(rz, u, dm); o[0] = dot9(dm);
-            mat3_mul(drx, ry, u); mat3_mul(rz, u, dm); o[1] = dot9(dm);
-            mat3_mul(drz, t, dm);                      o[2] = dot9(dm);
+            pose_bwd(pose + 7 * b, glin, nullptr, o);
             o[3] = gtg[0]; o[4] = gtg[1]; o[5] = gtg[2];
-            o[6] = sc * gs;
         }
     }
     __syncthreads();
@@ -440,8 +407,6 @@ __global__ __launch_bounds__(64) void k_skin_joints_bwd(float* __restrict__ gcoe
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 bool joints_ok(int64_t nj, int64_t nroot) { return nj >= 1 && nj <= SR_SKIN_MAXJ && nroot >= 1 && nroot <= nj; }
 
 }  // namespace
@@ -468,7 +433,7 @@ extern "C" int sr_skin_fwd(float* v, float* vp, const float* st, const float* vt
     if (!v || !vp || !vt || !wts || !G || (D > 0 && (!st || !cx))) return SR_EINVAL;
     if (D + 12 * nj > SR_SKIN_MAX_LDS || nv >= (1LL << 30) || D >= (1LL << 20)) return SR_ERANGE;
     const int64_t blocks = sr_ceil_div(nv, 4);
-    const bool vec = D % 4 == 0 && aligned16(st);
+    const bool vec = D % 4 == 0 && sr_aligned16(st);
     // the coefficients and transforms of a launch's samples sit in LDS: larger batches go in slices of `chunk` samples
     // (every array is sample-major, so a slice is a pointer offset), each slice one more pass over st
     const int64_t chunk = SR_SKIN_MAX_LDS / (D + 12 * nj);

@@ -8,7 +8,17 @@ LinearBlendSkinningModel / load_flame — the skinned, articulated model (FLAME:
 face_model.py:146-341 and 378-408; on the device its forward is the skinning node's kernels (op/skin.py).
 
 BlendShapeModel / load_facewarehouse — the bilinear identity x expression model (FaceWarehouse) of reference
-face_model.py:75-146 and 363-377; on the device its forward is the blendshape node's kernels (op/blend.py)."""
+face_model.py:75-146 and 363-377; on the device its forward is the blendshape node's kernels (op/blend.py).
+
+What the fitting loop (inversion.LatentInverter, reconstruct) asks of a model, the same for all three:
+    kind                           "linear" | "skinned" | "blended"
+    n_coeff                        length of a coefficient vector
+    mesh(coeff, pose, tri, reg_weight=0.0)
+                                   (v, n, reg, prior_rows) of the model's node (op.morph / op.skin / op.blend); prior_rows
+                                   [B] is every sample's share of reg, or None where the prior is a diagonal Gaussian
+                                   (lpips_layer.fit_loss_rows then evaluates it from prior_sigma itself)
+    prior_sigma(batch, shape_reg)  that Gaussian's sigma [n_coeff] for a fit of `batch` images, or None
+    fit_extras(coeff)              the model's own entries of a fit's .npz, from coeff [1, n_coeff]"""
 import numpy as np
 import torch
 from torch import nn
@@ -24,6 +34,8 @@ def _as_basis(w, rows, dim):
 
 
 class LinearMorphableModel(nn.Module):
+    kind = "linear"
+
     def __init__(self, vertices_num, shape_dim=0, expression_dim=0, vertices_mean=None, w_shape_numpy=None,
                  w_expression_numpy=None, sigma_shape=1, sigma_expression=.01, learnable=False):
         super().__init__()
@@ -80,6 +92,21 @@ class LinearMorphableModel(nn.Module):
     def regulation(self, x):
         return ((x / self.sigma[np.newaxis, :]) ** 2).sum()
 
+    @property
+    def n_coeff(self):
+        return self.sigma.numel()
+
+    def mesh(self, coeff, pose, tri, reg_weight=0.0):
+        from .op.morph import morph_mesh
+
+        return morph_mesh(self, coeff, pose, tri, reg_weight) + (None,)
+
+    def prior_sigma(self, batch, shape_reg):
+        return self.sigma
+
+    def fit_extras(self, coeff):
+        return {}
+
 
 def load_bfm(file_name="/data/BaselFaceModel.mat"):
     """Basel Face Model -> (LinearMorphableModel, tri int64 [nf, 3]) with the reference's `.mat` contract
@@ -127,6 +154,7 @@ class BlendShapeModel(nn.Module):
     yields average (.27, .42, .30), not (.2, .3, .5)); here they are centred over all ds + 1 parts, so that
     softmax(cat(x, -sum x)) is the Dirichlet draw itself.  It also runs with expression_dim = 0, where the reference's
     raises."""
+    kind = "blended"
 
     def __init__(self, vertices_num, shape_dim=0, expression_dim=0, bs=None, beta_shape=1, beta_expression=[1, 10],
                  learnable=False):
@@ -169,10 +197,9 @@ class BlendShapeModel(nn.Module):
 
     def mixing_weights(self, x):
         """(xs [B, ds + 1], xe [B, de + 1]): the identity and expression weights of coefficients x."""
-        ds = self.dim[0]
-        xs = torch.softmax(torch.cat((x[:, :ds], -x[:, :ds].sum(1, keepdim=True)), 1), dim=1)
-        s = torch.sigmoid(x[:, ds:])
-        return xs, torch.cat((1 - s.sum(1, keepdim=True), s), 1)
+        from .op import blend
+
+        return blend.mixing_weights(x, self.dim[0])
 
     def forward(self, x):
         from .op import blend
@@ -188,6 +215,22 @@ class BlendShapeModel(nn.Module):
         return -((ls * bs.unsqueeze(0)).sum() - torch.logsumexp(ls, 1).sum() * (bs.sum() - ds - 1)
                  + (xe * be[:, 0].unsqueeze(0) - 1).sum()
                  - (torch.nn.functional.softplus(xe) * (be.sum(1) - 2).unsqueeze(0)).sum())
+
+    @property
+    def n_coeff(self):
+        return self.dim[0] + self.dim[1]
+
+    def mesh(self, coeff, pose, tri, reg_weight=0.0):
+        from .op.blend import blend_mesh
+
+        return blend_mesh(self, coeff, pose, tri, reg_weight, per_sample=True)
+
+    def prior_sigma(self, batch, shape_reg):
+        return None                                  # a Dirichlet / Beta prior: the node's prior_rows
+
+    def fit_extras(self, coeff):
+        xs, xe = self.mixing_weights(coeff)
+        return {"identity": xs[0].cpu().numpy(), "expression": xe[0].cpu().numpy()}
 
 
 def load_facewarehouse(file_name="/data/FaceWareHouse.mat", beta_shape=.01):
@@ -233,6 +276,7 @@ class LinearBlendSkinningModel(nn.Module):
     * the number of `posedirs` rows copied is taken from `shapedirs` (line 222); here from `posedirs`.
     * without `weights` it needs scikit-learn for the nearest joint (lines 247-252); here the same weight
       exp(-d^2 / d_max^2) on the nearest joint comes from a brute-force argmin (nj is tiny)."""
+    kind = "skinned"
 
     def __init__(self, vertices_num, pose_nodes=1, shape_dim=0, v_template=None, J_regressor=None, kintree_table=None,
                  weights=None, posedirs=None, shapedirs=None, sigma_shape=1, sigma_pose=1, mean_pose=0, learnable=False):
@@ -385,6 +429,24 @@ class LinearBlendSkinningModel(nn.Module):
             return l_shape
         y = (x[:, ds:].reshape(x.shape[0], -1, 3, 1) * self.pose_inv.to(x.dtype).unsqueeze(0)).sum(2)
         return l_shape + (y ** 2).sum()
+
+    @property
+    def n_coeff(self):
+        return self.sigma.numel()
+
+    def mesh(self, coeff, pose, tri, reg_weight=0.0):
+        from .op.skin import skin_mesh
+
+        return skin_mesh(self, coeff, pose, tri, reg_weight) + (None,)
+
+    def prior_sigma(self, batch, shape_reg):
+        # fit_loss_rows takes a diagonal prior: exact for a diagonal pose_cov (load_flame's)
+        if batch > 1 and shape_reg != 0.0 and not self.pose_cov_is_diagonal():
+            raise ValueError("LatentInverter: a batched fit with shape_reg != 0 needs a diagonal pose_cov")
+        return self.effective_sigma()
+
+    def fit_extras(self, coeff):
+        return {"joints": coeff[0, self.dim[0]:].view(-1, 3).cpu().numpy()}
 
 
 def load_flame(file_name="/data/flame/generic_model.mat"):

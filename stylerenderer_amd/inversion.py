@@ -73,25 +73,14 @@ class LatentInverter:
         self.batch = int(self.target.shape[0])
         self.fit_shape = bool(fit_shape)
         self.shape_reg = float(shape_reg)
-        self.skinned = self.blended = False
         if self.fit_shape:
             if face is None:
                 raise ValueError("LatentInverter: fit_shape=True needs face=(LinearMorphableModel, tri)")
             self.face_model, self.tri = face[0], face[1].detach()
             self.face_model.requires_grad_(False)
-            from .face_model import BlendShapeModel, LinearBlendSkinningModel
-
-            # a skinned model (FLAME): coeff = shape, then one axis-angle per joint, through op.skin instead of op.morph
-            self.skinned = isinstance(self.face_model, LinearBlendSkinningModel)
-            # a bilinear blendshape model (FaceWarehouse): op.blend; its Dirichlet / Beta prior is not a diagonal
-            # Gaussian, so the per-sample losses take each sample's prior from the node, not from fit_loss_rows' sigma
-            self.blended = isinstance(self.face_model, BlendShapeModel)
-            self._prior_sigma = None if self.blended else self.face_model.sigma
-            if self.skinned:
-                # fit_loss_rows takes a diagonal prior: exact for a diagonal pose_cov (load_flame's)
-                if self.batch > 1 and self.shape_reg != 0.0 and not self.face_model.pose_cov_is_diagonal():
-                    raise ValueError("LatentInverter: a batched fit with shape_reg != 0 needs a diagonal pose_cov")
-                self._prior_sigma = self.face_model.effective_sigma()
+            # the sigma of a diagonal Gaussian prior for fit_loss_rows, or None (the blendshape model's Dirichlet / Beta
+            # prior): the per-sample losses then take each sample's prior from the node
+            self._prior_sigma = self.face_model.prior_sigma(self.batch, self.shape_reg)
             # the fitted mesh comes from the morphable-mesh node; `mesh` is not used
             self.v0 = self.n0 = None
         else:
@@ -106,8 +95,8 @@ class LatentInverter:
         pose_shape = (7,) if self.batch == 1 else (self.batch, 7)
         self.pose = torch.zeros(pose_shape, device=self.device, requires_grad=optimise_pose)
         # 3DMM coefficients [B, d], from the mean face
-        n_coeff = (sum(self.face_model.dim[:2]) if self.blended else self.face_model.sigma.numel()) if self.fit_shape else 0
-        self.coeff = torch.zeros(self.batch, n_coeff, device=self.device, requires_grad=True) if self.fit_shape else None
+        self.coeff = (torch.zeros(self.batch, self.face_model.n_coeff, device=self.device, requires_grad=True)
+                      if self.fit_shape else None)
         self.noise = noise if noise is not None else [n.detach() for n in self.g.make_noise()]
         on_gpu = self.device.type == "cuda"
         groups = [{"params": [self.w], "lr": lr}]
@@ -135,22 +124,13 @@ class LatentInverter:
         self.image = None
 
     # ---- model ----------------------------------------------------------------------------------------
+    skinned = property(lambda self: self.fit_shape and self.face_model.kind == "skinned")       # FLAME: op.skin
+    blended = property(lambda self: self.fit_shape and self.face_model.kind == "blended")       # FaceWarehouse: op.blend
+
     def _shape_mesh(self):
-        """(v, n, tri, reg) of the fitted coefficients and pose (op.morph / op.skin / op.blend: one node, no library
-        GEMM on the device)."""
-        self._prior_rows = None
-        if self.blended:
-            from .op.blend import blend_mesh
-
-            v, n, reg, self._prior_rows = blend_mesh(self.face_model, self.coeff, self.pose.view(-1, 7), self.tri,
-                                                     self.shape_reg, per_sample=True)
-            return v, n, self.tri, reg
-        if self.skinned:
-            from .op.skin import skin_mesh as node
-        else:
-            from .op.morph import morph_mesh as node
-
-        v, n, reg = node(self.face_model, self.coeff, self.pose.view(-1, 7), self.tri, self.shape_reg)
+        """(v, n, tri, reg) of the fitted coefficients and pose (the model's node — op.morph / op.skin / op.blend: no
+        library GEMM on the device)."""
+        v, n, reg, self._prior_rows = self.face_model.mesh(self.coeff, self.pose.view(-1, 7), self.tri, self.shape_reg)
         return v, n, self.tri, reg
 
     def posed_mesh(self):
@@ -199,7 +179,7 @@ class LatentInverter:
 
         layers = self.perceptual.layer_distances(self.target_feats, img)
         prior = self.fit_shape and self.shape_reg != 0.0 and getattr(self, "_reg", None) is not None
-        if prior and self.blended:
+        if prior and self._prior_rows is not None:
             self._rows, total = fit_loss_rows(layers, mse_rows(img, self.target), self.pixel_weight, reg=self._reg,
                                               prior_rows=self._prior_rows)
             return total

@@ -23,18 +23,22 @@ tested against.
 import torch
 from torch.autograd import Function
 
-from .. import _lib, utils_3d
-from ._dispatch import on_device_of, stream_of, strict_native
+from .. import _lib
+from . import _mesh_node
+from ._dispatch import on_device_of, stream_of
 
-EPS = 1e-8
+
+def mixing_weights(x, ds):
+    """(xs [B, ds + 1], xe [B, de + 1]): the identity and expression weights of coefficients x [B, ds + de]."""
+    xs = torch.softmax(torch.cat((x[:, :ds], -x[:, :ds].sum(1, keepdim=True)), 1), dim=1)
+    s = torch.sigmoid(x[:, ds:])
+    return xs, torch.cat((1 - s.sum(1, keepdim=True), s), 1)
 
 
 def blend_vertices_composite(x, weight, ds):
     """vs [B, nv, 3] of the definition above (no pose)."""
     ns, ne, c = weight.shape
-    xs = torch.softmax(torch.cat((x[:, :ds], -x[:, :ds].sum(1, keepdim=True)), 1), dim=1)
-    s = torch.sigmoid(x[:, ds:])
-    xe = torch.cat((1 - s.sum(1, keepdim=True), s), 1)
+    xs, xe = mixing_weights(x, ds)
     z = (xs.unsqueeze(2) * xe.unsqueeze(1)).reshape(-1, ns * ne)
     return torch.matmul(z, weight.reshape(ns * ne, c)).view(-1, c // 3, 3)
 
@@ -42,9 +46,7 @@ def blend_vertices_composite(x, weight, ds):
 def blend_composite(model, coeff, pose, tri, reg_weight=0.0):
     """The defining tensor algebra of the node (coeff [B, ds + de], pose [B, 7])."""
     vs = blend_vertices_composite(coeff, model.weight.to(coeff.dtype), model.dim[0])
-    lin = torch.exp(pose[:, 6]).view(-1, 1, 1) * utils_3d.euler_mat(pose[:, :3], "yxz")
-    v = torch.matmul(vs, lin) + pose[:, 3:6].view(-1, 1, 3)
-    n = utils_3d.mesh_point_normal(v, tri)
+    v, n = _mesh_node.pose_composite(vs, pose, tri)
     return v, n, reg_weight * model.regulation(coeff)
 
 
@@ -68,30 +70,16 @@ class _Blend(Function):
         w, bt = weight.contiguous(), beta.contiguous()
         b = c.shape[0]
         ds, de, nv = w.shape[0] - 1, w.shape[1] - 1, w.shape[2] // 3
-        off, adj, _ = utils_3d.incidence_lists(tri, nv)
-        tric = tri.contiguous()
-        nf = tric.size(0)
-        dev, f32 = c.device, c.dtype
-        lin = torch.empty((b, 3, 3), dtype=f32, device=dev)
-        rot = torch.empty_like(lin)
-        vs = torch.empty((b, nv, 3), dtype=f32, device=dev)
-        v = torch.empty_like(vs)
-        ns = torch.empty_like(vs)
-        n = torch.empty_like(vs)
-        normc = torch.empty((b, nv), dtype=f32, device=dev)
-        reg = torch.empty((), dtype=f32, device=dev)
-        L = _lib.lib()
-        st = stream_of(c)
         ptr = _lib.ptr
-        with on_device_of(c):
-            _lib.check(L.sr_pose_batch_fwd(ptr(lin), ptr(rot), ptr(p), b, st), "sr_pose_batch_fwd")
+
+        def model_fwd(L, st, v, vs, reg, lin):
             xs, xe, prior, z = _head(L, c, bt, reg_weight, ds, de, st)
             _lib.check(L.sr_blend_fwd(ptr(v), ptr(vs), ptr(reg), ptr(w), ptr(z), ptr(prior), ptr(lin), ptr(p), b,
                                       nv, ds, de, st), "sr_blend_fwd")
-            _lib.check(L.sr_vertex_normals_f32(ptr(ns), ptr(normc), ptr(vs), ptr(tric), ptr(off), ptr(adj), b, nv, nf,
-                                               EPS, st), "sr_vertex_normals_f32")
-            _lib.check(L.sr_affine3_fwd(ptr(n), ptr(ns), ptr(rot), None, b, nv, nv * 3, st), "sr_affine3_fwd")
-        ctx.save_for_backward(p, w, bt, tric, off, adj, lin, rot, vs, ns, normc, xs, xe)
+            return xs, xe, prior
+
+        v, n, reg, mesh, (xs, xe, prior) = _mesh_node.forward(c, p, tri, nv, model_fwd)
+        ctx.save_for_backward(w, bt, xs, xe, *mesh)
         ctx.reg_weight = float(reg_weight)
         ctx.dims = (b, ds, de, nv)
         ctx.mark_non_differentiable(prior)
@@ -99,35 +87,20 @@ class _Blend(Function):
 
     @staticmethod
     def backward(ctx, gv, gn, greg, _gprior):
-        p, w, bt, tric, off, adj, lin, rot, vs, ns, normc, xs, xe = ctx.saved_tensors
+        w, bt, xs, xe, *mesh = ctx.saved_tensors
         b, ds, de, nv = ctx.dims
-        gv, gn, greg = gv.contiguous(), gn.contiguous(), greg.contiguous()
-        dev, f32 = p.device, p.dtype
-        L = _lib.lib()
-        st = stream_of(p)
+        greg = greg.contiguous()
         ptr = _lib.ptr
-        gcoeff = gpose = None
-        with on_device_of(p):
-            if ctx.needs_input_grad[0]:
-                gvs = torch.empty_like(vs)
-                _lib.check(L.sr_vertex_normals_bwd_f32(ptr(gvs), ptr(gv), ptr(gn), ptr(lin), ptr(rot), ptr(vs), ptr(ns),
-                                                       ptr(normc), ptr(tric), ptr(off), ptr(adj), b, nv, tric.size(0),
-                                                       EPS, st), "sr_vertex_normals_bwd_f32")
-                gz = torch.empty((b, (ds + 1) * (de + 1)), dtype=f32, device=dev)
-                _lib.check(L.sr_blend_gz(ptr(gz), ptr(w), ptr(gvs), b, nv, ds, de, st), "sr_blend_gz")
-                gcoeff = torch.empty((b, ds + de), dtype=f32, device=dev)
-                _lib.check(L.sr_blend_tail(ptr(gcoeff), ptr(gz), ptr(xs), ptr(xe), ptr(bt), ctx.reg_weight, ptr(greg), b,
-                                           ds, de, st), "sr_blend_tail")
-            if ctx.needs_input_grad[1]:
-                glin = torch.empty_like(lin)
-                grot = torch.empty_like(rot)
-                gt = torch.empty((b, 3), dtype=f32, device=dev)
-                gpose = torch.empty_like(p)
-                _lib.check(L.sr_affine3_bwd(ptr(glin), ptr(gt), ptr(vs), ptr(gv), b, nv, nv * 3, st), "sr_affine3_bwd")
-                _lib.check(L.sr_affine3_bwd(ptr(grot), None, ptr(ns), ptr(gn), b, nv, nv * 3, st), "sr_affine3_bwd")
-                _lib.check(L.sr_morph_pose_bwd(ptr(gpose), ptr(glin), ptr(grot), ptr(gt), ptr(p), b, st),
-                           "sr_morph_pose_bwd")
-        return gcoeff, gpose, None, None, None, None
+
+        def model_bwd(L, st, gvs):
+            gz = torch.empty((b, (ds + 1) * (de + 1)), dtype=gvs.dtype, device=gvs.device)
+            _lib.check(L.sr_blend_gz(ptr(gz), ptr(w), ptr(gvs), b, nv, ds, de, st), "sr_blend_gz")
+            gcoeff = torch.empty((b, ds + de), dtype=gvs.dtype, device=gvs.device)
+            _lib.check(L.sr_blend_tail(ptr(gcoeff), ptr(gz), ptr(xs), ptr(xe), ptr(bt), ctx.reg_weight, ptr(greg), b,
+                                       ds, de, st), "sr_blend_tail")
+            return gcoeff
+
+        return _mesh_node.backward(ctx.needs_input_grad, mesh, gv, gn, model_bwd) + (None,) * 4
 
 
 class _BlendVertices(Function):
@@ -167,20 +140,6 @@ class _BlendVertices(Function):
         return gcoeff, None, None
 
 
-def _native_ok(model, *tensors):
-    return (all(t.device.type == "cuda" and t.dtype == torch.float32 for t in tensors + (model.weight, model.beta))
-            and not model.weight.requires_grad)
-
-
-def _composite_allowed(model, *tensors):
-    """Under SR_STRICT_NATIVE=1 a device tensor never falls to the composite (library matmul) silently."""
-    if strict_native() and any(t.device.type == "cuda" for t in tensors + (model.weight,)):
-        raise RuntimeError("SR_STRICT_NATIVE: the blendshape node takes device fp32 tensors and a frozen model on the "
-                           "device; this call (%s, learnable=%s) would run the composite on library GEMMs"
-                           % (", ".join(str(t.dtype) + "@" + t.device.type for t in tensors),
-                              model.weight.requires_grad))
-
-
 def _check(model, coeff):
     if coeff.dim() != 2 or coeff.shape[1] != model.dim[0] + model.dim[1]:
         raise ValueError("blend: coefficients %s, the model takes [B, %d + %d]"
@@ -190,9 +149,9 @@ def _check(model, coeff):
 def blend_vertices(model, x):
     """model.forward: vs [B, nv, 3] (no pose, no normals); the native forward on device fp32 with a frozen model."""
     _check(model, x)
-    if _native_ok(model, x):
+    if _mesh_node.native_ok((x, model.beta), (model.weight,)):
         return _BlendVertices.apply(x, model.weight.detach(), model.beta.detach())
-    _composite_allowed(model, x)
+    _mesh_node.refuse_composite("blendshape", (x,), (model.weight,))
     return blend_vertices_composite(x, model.weight.to(x.dtype), model.dim[0])
 
 
@@ -211,16 +170,11 @@ def blend_mesh(model, coeff, pose, tri, reg_weight=0.0, per_sample=False):
     """(v [B, nv, 3], n [B, nv, 3], reg []) of a BlendShapeModel at coefficients coeff [B, ds + de] (or 1-D) and poses
     pose [B, 7] (or [7]); reg = reg_weight * model.regulation(coeff).  With per_sample=True a fourth, detached output
     [B] holds reg_weight * regulation(coeff[b]) of every sample (their sum is reg)."""
-    if coeff.dim() == 1:
-        coeff = coeff.view(1, -1)
-    if pose.dim() == 1:
-        pose = pose.view(1, 7)
-    if pose.shape[0] != coeff.shape[0]:
-        raise ValueError("blend_mesh: %d coefficient vectors but %d poses" % (coeff.shape[0], pose.shape[0]))
+    coeff, pose = _mesh_node.as_batch(coeff, pose, "blend_mesh")
     _check(model, coeff)
-    if _native_ok(model, coeff, pose):
+    if _mesh_node.native_ok((coeff, pose, model.beta), (model.weight,)):
         out = _Blend.apply(coeff, pose, model.weight.detach(), model.beta.detach(), tri, float(reg_weight))
         return out if per_sample else out[:3]
-    _composite_allowed(model, coeff, pose)
+    _mesh_node.refuse_composite("blendshape", (coeff, pose), (model.weight,))
     out = blend_composite(model, coeff, pose, tri, reg_weight)
     return out + (prior_rows(model, coeff.detach(), reg_weight),) if per_sample else out

@@ -19,9 +19,9 @@ import torch
 from torch.autograd import Function
 
 from .. import _lib, utils_3d
+from . import _mesh_node
 from ._dispatch import on_device_of, stream_of
-
-EPS = 1e-8
+from ._mesh_node import EPS
 
 
 def _sigma(model, like):
@@ -30,11 +30,8 @@ def _sigma(model, like):
 
 def morph_composite(coeff, pose, weight, bias, sigma, tri, reg_weight=0.0):
     """The defining tensor algebra (coeff [B, d], pose [B, 7])."""
-    b = coeff.shape[0]
-    vs = torch.nn.functional.linear(coeff, weight, bias).view(b, -1, 3)
-    lin = torch.exp(pose[:, 6]).view(-1, 1, 1) * utils_3d.euler_mat(pose[:, :3], "yxz")
-    v = torch.matmul(vs, lin) + pose[:, 3:6].view(-1, 1, 3)
-    n = utils_3d.mesh_point_normal(v, tri)
+    vs = torch.nn.functional.linear(coeff, weight, bias).view(coeff.shape[0], -1, 3)
+    v, n = _mesh_node.pose_composite(vs, pose, tri)
     reg = reg_weight * ((coeff / sigma.view(1, -1)) ** 2).sum()
     return v, n, reg
 
@@ -46,84 +43,44 @@ class _Morph(Function):
         w, bs, sg = weight.contiguous(), bias.contiguous(), sigma.contiguous()
         b, d = c.shape
         nv = bs.numel() // 3
-        off, adj, _ = utils_3d.incidence_lists(tri, nv)
-        tric = tri.contiguous()
-        nf = tric.size(0)
-        dev, f32 = c.device, c.dtype
-        lin = torch.empty((b, 3, 3), dtype=f32, device=dev)
-        rot = torch.empty_like(lin)
-        vs = torch.empty((b, nv, 3), dtype=f32, device=dev)
-        v = torch.empty_like(vs)
-        ns = torch.empty_like(vs)
-        n = torch.empty_like(vs)
-        normc = torch.empty((b, nv), dtype=f32, device=dev)
-        reg = torch.empty((), dtype=f32, device=dev)
-        L = _lib.lib()
-        st = stream_of(c)
         ptr = _lib.ptr
-        with on_device_of(c):
-            _lib.check(L.sr_pose_batch_fwd(ptr(lin), ptr(rot), ptr(p), b, st), "sr_pose_batch_fwd")
+
+        def model_fwd(L, st, v, vs, reg, lin):
             _lib.check(L.sr_morph_fwd(ptr(v), ptr(vs), ptr(reg), ptr(w), ptr(bs), ptr(c), ptr(lin), ptr(p), ptr(sg),
                                       float(reg_weight), b, nv, d, st), "sr_morph_fwd")
-            _lib.check(L.sr_vertex_normals_f32(ptr(ns), ptr(normc), ptr(vs), ptr(tric), ptr(off), ptr(adj), b, nv, nf,
-                                               EPS, st), "sr_vertex_normals_f32")
-            _lib.check(L.sr_affine3_fwd(ptr(n), ptr(ns), ptr(rot), None, b, nv, nv * 3, st), "sr_affine3_fwd")
-        ctx.save_for_backward(c, p, w, sg, tric, off, adj, lin, rot, vs, ns, normc)
-        ctx.reg_weight = float(reg_weight)
+
+        v, n, reg, mesh, _ = _mesh_node.forward(c, p, tri, nv, model_fwd)
+        ctx.save_for_backward(c, w, sg, *mesh)
+        ctx.reg_weight, ctx.rows = float(reg_weight), 3 * nv
         return v, n, reg
 
     @staticmethod
     def backward(ctx, gv, gn, greg):
-        c, p, w, sg, tric, off, adj, lin, rot, vs, ns, normc = ctx.saved_tensors
-        b, d = c.shape
-        nv = vs.shape[1]
-        gv, gn, greg = gv.contiguous(), gn.contiguous(), greg.contiguous()
-        L = _lib.lib()
-        st = stream_of(c)
+        c, w, sg, *mesh = ctx.saved_tensors
+        (b, d), rows = c.shape, ctx.rows
+        greg = greg.contiguous()
         ptr = _lib.ptr
-        gcoeff = gpose = None
-        with on_device_of(c):
-            if ctx.needs_input_grad[0]:
-                gvs = torch.empty_like(vs)
-                _lib.check(L.sr_vertex_normals_bwd_f32(ptr(gvs), ptr(gv), ptr(gn), ptr(lin), ptr(rot), ptr(vs), ptr(ns),
-                                                       ptr(normc), ptr(tric), ptr(off), ptr(adj), b, nv, tric.size(0),
-                                                       EPS, st), "sr_vertex_normals_bwd_f32")
-                scratch = torch.empty(max(1, int(L.sr_morph_gcoeff_scratch_floats(3 * nv, b, d))), dtype=c.dtype,
-                                      device=c.device)
-                gcoeff = torch.empty_like(c)
-                _lib.check(L.sr_morph_gcoeff(ptr(gcoeff), ptr(scratch), ptr(w), ptr(gvs), ptr(c), ptr(sg),
-                                             ctx.reg_weight, ptr(greg), b, 3 * nv, d, st), "sr_morph_gcoeff")
-            if ctx.needs_input_grad[1]:
-                glin = torch.empty_like(lin)
-                grot = torch.empty_like(rot)
-                gt = torch.empty((b, 3), dtype=c.dtype, device=c.device)
-                gpose = torch.empty_like(p)
-                _lib.check(L.sr_affine3_bwd(ptr(glin), ptr(gt), ptr(vs), ptr(gv), b, nv, nv * 3, st), "sr_affine3_bwd")
-                _lib.check(L.sr_affine3_bwd(ptr(grot), None, ptr(ns), ptr(gn), b, nv, nv * 3, st), "sr_affine3_bwd")
-                _lib.check(L.sr_morph_pose_bwd(ptr(gpose), ptr(glin), ptr(grot), ptr(gt), ptr(p), b, st),
-                           "sr_morph_pose_bwd")
-        return gcoeff, gpose, None, None, None, None, None
 
+        def model_bwd(L, st, gvs):
+            scratch = torch.empty(max(1, int(L.sr_morph_gcoeff_scratch_floats(rows, b, d))), dtype=c.dtype,
+                                  device=c.device)
+            gcoeff = torch.empty_like(c)
+            _lib.check(L.sr_morph_gcoeff(ptr(gcoeff), ptr(scratch), ptr(w), ptr(gvs), ptr(c), ptr(sg), ctx.reg_weight,
+                                         ptr(greg), b, rows, d, st), "sr_morph_gcoeff")
+            return gcoeff
 
-def _native_ok(coeff, pose, weight, bias):
-    ts = (coeff, pose, weight, bias)
-    return (all(t.device.type == "cuda" and t.dtype == torch.float32 for t in ts)
-            and not weight.requires_grad and not bias.requires_grad)
+        return _mesh_node.backward(ctx.needs_input_grad, mesh, gv, gn, model_bwd) + (None,) * 5
 
 
 def morph_mesh(model, coeff, pose, tri, reg_weight=0.0):
     """(v [B, nv, 3], n [B, nv, 3], reg []) of a LinearMorphableModel at coefficients coeff [B, d] (or [d]) and poses
     pose [B, 7] (or [7]); reg = reg_weight * model.regulation(coeff)."""
-    if coeff.dim() == 1:
-        coeff = coeff.view(1, -1)
-    if pose.dim() == 1:
-        pose = pose.view(1, 7)
-    if pose.shape[0] != coeff.shape[0]:
-        raise ValueError("morph_mesh: %d coefficient vectors but %d poses" % (coeff.shape[0], pose.shape[0]))
+    coeff, pose = _mesh_node.as_batch(coeff, pose, "morph_mesh")
     weight, bias = model.fc.weight, model.fc.bias
     sigma = _sigma(model, coeff)
-    if _native_ok(coeff, pose, weight, bias):
+    if _mesh_node.native_ok((coeff, pose), (weight, bias)):
         return _Morph.apply(coeff, pose, weight.detach(), bias.detach(), sigma, tri, float(reg_weight))
+    # (no strict-native guard here, unlike skin_mesh and blend_mesh: see _mesh_node.refuse_composite)
     return morph_composite(coeff, pose, weight, bias, sigma, tri, reg_weight)
 
 

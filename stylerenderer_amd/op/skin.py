@@ -24,9 +24,9 @@ import torch
 from torch.autograd import Function
 
 from .. import _lib, utils_3d
-from ._dispatch import DerivedCache, on_device_of, stream_of, strict_native
-
-EPS = 1e-8
+from . import _mesh_node
+from ._dispatch import DerivedCache, on_device_of, stream_of
+from ._mesh_node import EPS
 _PREP_CACHE = DerivedCache(4)
 
 
@@ -60,9 +60,7 @@ def skin_composite(model, coeff, pose, tri, reg_weight=0.0):
     basis, template = (t.to(dt) for t in model.fc)
     weights, regressor = (t.to(dt) for t in model.weight)
     vs = lbs_composite(coeff, basis, template, weights, regressor, model.parent, model.dim[0])
-    lin = torch.exp(pose[:, 6]).view(-1, 1, 1) * utils_3d.euler_mat(pose[:, :3], "yxz")
-    v = torch.matmul(vs, lin) + pose[:, 3:6].view(-1, 1, 3)
-    n = utils_3d.mesh_point_normal(v, tri)
+    v, n = _mesh_node.pose_composite(vs, pose, tri)
     return v, n, reg_weight * model.regulation(coeff)
 
 
@@ -182,20 +180,6 @@ class _Skin(Function):
         return (gcoeff, gpose) + (None,) * 10
 
 
-def _native_ok(model, *tensors):
-    return (all(t.device.type == "cuda" and t.dtype == torch.float32 for t in tensors + tuple(model.fc + model.weight))
-            and not any(t.requires_grad for t in model.fc + model.weight))
-
-
-def _composite_allowed(model, *tensors):
-    """Under SR_STRICT_NATIVE=1 a device tensor never falls to the composite (library matmul) silently."""
-    if strict_native() and any(t.device.type == "cuda" for t in tensors + tuple(model.fc + model.weight)):
-        raise RuntimeError("SR_STRICT_NATIVE: the skinning node takes device fp32 tensors and a frozen model on the "
-                           "device; this call (%s, learnable=%s) would run the composite on library GEMMs"
-                           % (", ".join(str(t.dtype) + "@" + t.device.type for t in tensors),
-                              any(t.requires_grad for t in model.fc + model.weight)))
-
-
 def _check(model, coeff):
     if coeff.shape[1] != model.dim[0] + model.dim[1]:
         raise ValueError("skin: %d coefficients, the model takes %d + %d" % (coeff.shape[1], model.dim[0], model.dim[1]))
@@ -205,9 +189,9 @@ def skin_vertices(model, x):
     """model.forward: v_skin [B, nv, 3] (no global pose, no normals); the native forward on device fp32 with a frozen
     model."""
     _check(model, x)
-    if _native_ok(model, x):
+    if _mesh_node.native_ok((x,), model.fc + model.weight):
         return _Skin.apply(x, None, *_native_args(model), None, 0.0)[0]
-    _composite_allowed(model, x)
+    _mesh_node.refuse_composite("skinning", (x,), model.fc + model.weight)
     dt = x.dtype
     return lbs_composite(x, model.fc[0].to(dt), model.fc[1].to(dt), model.weight[0].to(dt), model.weight[1].to(dt),
                          model.parent, model.dim[0])
@@ -222,14 +206,9 @@ def _native_args(model):
 def skin_mesh(model, coeff, pose, tri, reg_weight=0.0):
     """(v [B, nv, 3], n [B, nv, 3], reg []) of a LinearBlendSkinningModel at coefficients coeff [B, ds + 3 (nj-1)] (or
     1-D) and poses pose [B, 7] (or [7]); reg = reg_weight * model.regulation(coeff)."""
-    if coeff.dim() == 1:
-        coeff = coeff.view(1, -1)
-    if pose.dim() == 1:
-        pose = pose.view(1, 7)
-    if pose.shape[0] != coeff.shape[0]:
-        raise ValueError("skin_mesh: %d coefficient vectors but %d poses" % (coeff.shape[0], pose.shape[0]))
+    coeff, pose = _mesh_node.as_batch(coeff, pose, "skin_mesh")
     _check(model, coeff)
-    if _native_ok(model, coeff, pose):
+    if _mesh_node.native_ok((coeff, pose), model.fc + model.weight):
         return _Skin.apply(coeff, pose, *_native_args(model), tri, float(reg_weight))
-    _composite_allowed(model, coeff, pose)
+    _mesh_node.refuse_composite("skinning", (coeff, pose), model.fc + model.weight)
     return skin_composite(model, coeff, pose, tri, reg_weight)

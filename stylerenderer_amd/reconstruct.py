@@ -64,20 +64,13 @@ def load_image(path, size):
 def face_model(bfm, device, seed=0, flame=None, facewarehouse=None, beta_shape=.01):
     """(model, tri) on `device`: the Basel model of --bfm, FLAME of --flame, FaceWarehouse of --facewarehouse, else
     train.SyntheticFaceSource's."""
-    if facewarehouse:
-        from .face_model import load_facewarehouse
+    if facewarehouse or flame or bfm:
+        from .face_model import load_bfm, load_facewarehouse, load_flame
 
-        model, tri = load_facewarehouse(facewarehouse, beta_shape)
-        return model.to(device), tri.to(device)
-    if flame:
-        from .face_model import load_flame
-
-        model, tri = load_flame(flame)
-        return model.to(device), tri.to(device)
-    if bfm:
-        from .face_model import load_bfm
-
-        model, tri = load_bfm(bfm)
+        if facewarehouse:
+            model, tri = load_facewarehouse(facewarehouse, beta_shape)
+        else:
+            model, tri = load_flame(flame) if flame else load_bfm(bfm)
         return model.to(device), tri.to(device)
     from .train import SyntheticFaceSource
 
@@ -109,17 +102,7 @@ def reconstruct_batch(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, co
 
 def write_outputs(inv, hist, out_dir, stem, index=0):
     """The five files of sample `index` of the inverter (hist: its loss history [steps])."""
-    from .face_model import BlendShapeModel, LinearBlendSkinningModel
     from .op.rasterize import rasterize
-
-    skinned = isinstance(inv.face_model, LinearBlendSkinningModel)
-    blended = isinstance(inv.face_model, BlendShapeModel)
-    if blended:
-        from .op.blend import blend_mesh as node
-    elif skinned:
-        from .op.skin import skin_mesh as node
-    else:
-        from .op.morph import morph_mesh as node
 
     k = slice(index, index + 1)
     v, n, tri = inv.fitted_mesh()
@@ -128,7 +111,7 @@ def write_outputs(inv, hist, out_dir, stem, index=0):
     pose = inv.pose.detach().view(-1, 7)[index]
     with torch.no_grad():
         zero = torch.zeros_like(pose).view(1, 7)
-        vc, nc, _ = node(inv.face_model, coeff, zero, tri)
+        vc, nc = inv.face_model.mesh(coeff, zero, tri)[:2]
         size = int(inv.target.shape[-1])
         normal_map = rasterize(v.contiguous(), n.contiguous(), tri, size, size, channel_major=True)
     tri_h = tri.cpu().numpy()
@@ -137,12 +120,8 @@ def write_outputs(inv, hist, out_dir, stem, index=0):
                       vn=nc[0].cpu().numpy())
     generate.save_image(inv.image[k].cpu(), os.path.join(out_dir, stem + "_render.png"))
     generate.save_image(normal_map.cpu(), os.path.join(out_dir, stem + "_normal.png"))
-    extra = {"joints": coeff[0, inv.face_model.dim[0]:].view(-1, 3).cpu().numpy()} if skinned else {}
-    if blended:
-        xs, xe = inv.face_model.mixing_weights(coeff)
-        extra = {"identity": xs[0].cpu().numpy(), "expression": xe[0].cpu().numpy()}
     np.savez(os.path.join(out_dir, stem + ".npz"), w=inv.w.detach()[k].cpu().numpy(), coeff=coeff.cpu().numpy(),
-             pose=pose.cpu().numpy(), loss=hist, **extra)
+             pose=pose.cpu().numpy(), loss=hist, **inv.face_model.fit_extras(coeff))
 
 
 def main(argv=None):

@@ -75,20 +75,27 @@ def random_apply_pose3D(p=[.5, .1, .05, .1, .1, .1, .15], v=None):
     # randn * p because torch.normal checks `std >= 0` on the host — a device read hipGraph capture refuses
     z = torch.randn(batch, 7, dtype=p.dtype, device=p.device) * p
     if v is not None and v.device.type == "cuda" and v.dtype == torch.float32 and z.device == v.device:
-        # device path: the B scaled rotations in one launch (sr_pose_batch_fwd) and the vertices in one streaming pass
+        # device path: the B scaled rotations in one launch (_pose_batch) and the vertices in one streaming pass
         # (sr_affine3_fwd) instead of ~30 element-wise launches and a 3-wide batched GEMM — this runs twice per training
         # iteration, inside the captured D and G phases
         zc = z.contiguous()
-        lin = torch.empty((batch, 3, 3), dtype=zc.dtype, device=zc.device)
-        with on_device_of(zc):
-            _lib.check(_lib.lib().sr_pose_batch_fwd(_lib.ptr(lin), None, _lib.ptr(zc), batch, stream_of(zc)),
-                       "sr_pose_batch_fwd")
+        lin, _ = _pose_batch(zc, with_rot=False)
         return affine3(v[..., :3].reshape(batch, -1, 3), lin, zc[:, 3:6])
     T = torch.cat((torch.exp(z[:, -1]).view(-1, 1, 1) * euler_mat(z[:, :3], "yxz"), z[:, 3:6].view(-1, 3, 1)), -1)
     if v is None:
         return T[0]
     T = T.to(v.device)
     return torch.matmul(v[..., :3].reshape(batch, -1, 3), T[:, :3, :3]) + T[:, :3, 3:].view(-1, 1, 3)
+
+
+def _pose_batch(pc, with_rot=True):
+    """(lin, rot or None), each [B, 3, 3], of contiguous device poses pc [B, 7]: one launch."""
+    lin = torch.empty((pc.shape[0], 3, 3), dtype=pc.dtype, device=pc.device)
+    rot = torch.empty_like(lin) if with_rot else None
+    with on_device_of(pc):
+        _lib.check(_lib.lib().sr_pose_batch_fwd(_lib.ptr(lin), _lib.ptr(rot), _lib.ptr(pc), pc.shape[0], stream_of(pc)),
+                   "sr_pose_batch_fwd")
+    return lin, rot
 
 
 class _Affine3(Function):
@@ -168,14 +175,8 @@ class _PoseBatchMatrices(Function):
     @staticmethod
     def forward(ctx, pose):
         pc = pose.contiguous()
-        b = pc.shape[0]
-        lin = torch.empty((b, 3, 3), dtype=pc.dtype, device=pc.device)
-        rot = torch.empty_like(lin)
-        with on_device_of(pc):
-            _lib.check(_lib.lib().sr_pose_batch_fwd(_lib.ptr(lin), _lib.ptr(rot), _lib.ptr(pc), b, stream_of(pc)),
-                       "sr_pose_batch_fwd")
         ctx.save_for_backward(pc)
-        return lin, rot
+        return _pose_batch(pc)
 
     @staticmethod
     def backward(ctx, glin, grot):

@@ -70,6 +70,33 @@ def test_batched_pose_node_against_the_composite():
     assert torch.equal(lin, lin2) and torch.equal(rot, rot2) and torch.equal(gp, gp2)
 
 
+def test_one_pose_has_one_gradient_whether_given_as_7_or_1x7():
+    """A pose given as [7] or as [1, 7] takes the single-pose entry point (sr_pose_bwd: pose_matrices sends seven numbers
+    there whatever their shape), so the two gradients are the same bits.  A batch [2, 7] of that pose takes the batched
+    kernel (sr_morph_pose_bwd): the same pose_bwd of csrc/pose.h, but built with floating-point contraction on where
+    sr_pose_bwd's file has it off, so against it only the float64 bound of the test above is guaranteed, not the bits."""
+    p7 = torch.from_numpy(0.3 * synth.det_normal((7,), 86)).to(DEV).requires_grad_(True)
+    glin = torch.from_numpy(synth.det_normal((1, 3, 3), 87)).to(DEV)
+    grot = torch.from_numpy(synth.det_normal((1, 3, 3), 88)).to(DEV)
+
+    def grad(pose):
+        lin, rot = utils_3d.pose_matrices(pose)
+        return torch.autograd.grad((lin * glin).sum() + (rot * grot).sum(), pose)[0]
+
+    g7 = grad(p7)
+    g17 = grad(p7.detach().view(1, 7).clone().requires_grad_(True))
+    g27 = grad(p7.detach().view(1, 7).repeat(2, 1).requires_grad_(True))
+    gw = grad(p7.detach().double().requires_grad_(True))                   # float64: the composite tensor algebra
+    assert g7.shape == (7,) and g17.shape == (1, 7) and g27.shape == (2, 7)
+    print("gradient [7]", g7.tolist(), "[1, 7]", g17.tolist(), "[2, 7]", g27.tolist(), "float64", gw.tolist())
+    assert torch.equal(g7[[0, 1, 2, 6]], g17[0, [0, 1, 2, 6]]) and float(g7[[0, 1, 2, 6]].abs().min()) > 0
+    assert torch.equal(g7, grad(p7))
+    assert torch.equal(g27[0], g27[1])
+    for g in (g7, g17[0], g27[0]):
+        assert float(g[3:6].abs().max()) == 0.0
+        assert float((g.double() - gw).abs().max()) <= 1e-5 * float(gw.abs().max())
+
+
 def test_fit_loss_rows_against_float64():
     b, d = 6, 144
     layers = [torch.from_numpy(synth.det_uniform((b, 1, 1, 1), 60 + k)).to(DEV).requires_grad_(True) for k in range(5)]
