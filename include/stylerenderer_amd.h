@@ -818,6 +818,28 @@ int sr_warp_affine_u8(void* out, const uint8_t* in, const double* matrix, int64_
                       int64_t W, int64_t C, int64_t oh, int64_t ow, int border, int fill, int out_form,
                       sr_stream_t stream);
 
+/* Landmark reprojection term of face reconstruction (stylerenderer_amd/op/landmark.py holds the definition),
+ * csrc/landmark.hip.  Landmark l of an embedding idx int32 [L, 3], bary float32 [L, 3] is P_l = sum_k bary[l, k]
+ * v[b, idx[l, k], :] of the posed vertices v [B, nv, 3]; its pixel is p_l = ((1 + P_l.x) W / 2 - 1/2,
+ * (1 - P_l.y) H / 2 - 1/2), the rasterizer's index coordinates.  With targets target [B, L, 2] in those coordinates,
+ * weights conf [B, L] >= 0 (0: missing) and rho = smooth-L1 with `beta` per coordinate:
+ *   rows[b] = weight * (2 / max(W, H)) * sum_l conf[b, l] (rho(e_l.x) + rho(e_l.y)) / max(sum_l conf[b, l], 1e-12)
+ * sr_landmark_loss_fwd: one launch, one workgroup per sample; writes rows [B], p [B, L, 2] and g [B, L, 2] =
+ *   d rows[b] / d p_l.  The sum over l has a fixed order (lane-strided, then an LDS tree): reruns are bit-identical.
+ *   Every idx must lie in [0, nv): the caller validates (op/landmark.py does when it builds the CSR list).
+ * sr_landmark_loss_bwd: one launch over all B nv vertices; writes (accumulate = 0) or adds to (accumulate != 0) the dense
+ *   gv [B, nv, 3] = g_rows[b] * d rows[b] / d v, z = 0, zero on vertices no landmark uses.  csr_off int32 [nv + 1] and
+ *   csr_l int32 / csr_w float32 [entries] list for every vertex the landmarks l and weights bary[l, k] that use it, in
+ *   ascending 3 l + k; a lane sums its vertex's entries in that order.  g_rows is read at g_rows[b * g_rows_stride]
+ *   (stride 0: one value for every sample).  No memset, no scatter, no atomics.
+ * No allocation and no host read: both run under graph capture on `stream`.  B <= 65535 for the backward. */
+int sr_landmark_loss_fwd(float* rows, float* p, float* g, const float* v, const int32_t* idx, const float* bary,
+                         const float* target, const float* conf, int64_t B, int64_t L, int64_t nv, int64_t H, int64_t W,
+                         float beta, float weight, sr_stream_t stream);
+int sr_landmark_loss_bwd(float* gv, const float* g, const float* g_rows, int64_t g_rows_stride, const int32_t* csr_off,
+                         const int32_t* csr_l, const float* csr_w, int64_t B, int64_t L, int64_t nv, int64_t H, int64_t W,
+                         int accumulate, sr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,8 @@ SIGNATURES = {
     "sr_resample_u8": (_i, [_p, _p] + [_l] * 6 + [_p, _p, ctypes.POINTER(ctypes.c_int32), _l] * 2 + [_l] * 4
                        + [_i, _i, _p, _p]),
     "sr_warp_affine_u8": (_i, [_p, _p, _p] + [_l] * 7 + [_i, _i, _i, _p]),
+    "sr_landmark_loss_fwd": (_i, [_p] * 8 + [_l] * 5 + [_f, _f, _p]),
+    "sr_landmark_loss_bwd": (_i, [_p, _p, _p, _l, _p, _p, _p] + [_l] * 5 + [_i, _p]),
     "sr_signal_bump": (_i, [_p, _p]),
     "sr_signal_wait": (_i, [_p, ctypes.c_uint32, _p]),
     "sr_signal_set": (_i, [_p, _p, _p]),

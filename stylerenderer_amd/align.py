@@ -5,6 +5,8 @@ host or on the device according to the picture it is given.
     LandmarksReader(file).detect(path)            the landmarks [L, 2] a text file lists for a picture, or None
     solve_affine(src, dst)                        least-squares 2-D similarity src -> dst, 2x3
     solve_ortho(src3d, dst2d)                     scaled orthographic fit, 3x4
+    pose_from_landmarks(pts, lmk, size_hw)        that fit as the fitting loop's pose [7] (inversion.LatentInverter)
+    scale_landmarks(lmk, src_hw, dst_hw)          pixel indices of a picture -> of its resized copy
     euler_mat_inv(R, type)                        Euler angles of a rotation matrix
     alignment_matrix(template, lmk, canvas_hw)    3x3 T: canvas index coordinates -> picture index coordinates
     template_from_bfm(mat_or_dict, n)             the 3-D template: the model's landmark vertices on its mean shape
@@ -80,14 +82,20 @@ def solve_affine(src, dst, eps=1e-9):
     return np.array([[a, -b, tx], [b, a, ty]], np.float64)
 
 
-def solve_ortho(src, dst, eps=1e-9):
+def solve_ortho(src, dst, eps=1e-9, weights=None):
     """Scaled orthographic fit dst ~ w (R src)[:2] + t of src [n, 3] to dst [n, 2]: the least-squares 3x2 linear map of
     the centred points, its nearest scaled rotation (SVD, completed to det +1), and the translation that maps mean to
-    mean.  Returns the reference's 3x4 layout: [:3, :3] = w R, [:2, 3] = t, [2, 3] = 1 / max(w, eps)."""
+    mean.  Returns the reference's 3x4 layout: [:3, :3] = w R, [:2, 3] = t, [2, 3] = 1 / max(w, eps).  `weights` [n]
+    >= 0 (not in the reference) makes the means and the least squares weighted; a point of weight 0 does not count."""
     src = np.asarray(src, np.float64)
     dst = np.asarray(dst, np.float64)
-    src_mean, dst_mean = src.mean(0), dst.mean(0)
-    M = _pinv_apply(src - src_mean, dst - dst_mean, eps)            # [3, 2]: dst_ ~ src_ M
+    if weights is None:
+        src_mean, dst_mean = src.mean(0), dst.mean(0)
+        M = _pinv_apply(src - src_mean, dst - dst_mean, eps)        # [3, 2]: dst_ ~ src_ M
+    else:
+        wt = np.asarray(weights, np.float64).reshape(-1, 1)
+        src_mean, dst_mean = (wt * src).sum(0) / wt.sum(), (wt * dst).sum(0) / wt.sum()
+        M = _pinv_apply(np.sqrt(wt) * (src - src_mean), np.sqrt(wt) * (dst - dst_mean), eps)
     u, _, vt = np.linalg.svd(M)
     v3 = np.eye(3)
     v3[:2, :2] = vt
@@ -125,6 +133,38 @@ def euler_mat_inv(R, type="yxz", eps=1e-9):
     elif 1 + D <= eps:
         r[2] = np.arctan2(sign * R[j, k], R[j, j]) + r[0]
     return r
+
+
+def pose_from_landmarks(model_pts, lmk, size_hw, weights=None):
+    """pose [7] = (yaw, pitch, roll, tx, ty, 0, log-scale), float64, of inversion.LatentInverter's convention
+    v = v0 @ (e^s R_yxz) + t, under which the model's landmark points model_pts [L, 3] (on its mean shape) project onto
+    the landmarks lmk [L, 2], given in pixel index coordinates of an (H, W) = size_hw picture.  The rasterizer's
+    projection x = (1 + v.x) W / 2 - 1/2, y = (1 - v.y) H / 2 - 1/2 (y flipped) is undone first, then solve_ortho's
+    closed form gives the scaled rotation and the translation and euler_mat_inv the angles; no iteration.  weights [L]
+    >= 0: the weighted fit (0: the landmark is missing)."""
+    h, w = _hw(size_hw)
+    pts = np.asarray(model_pts, np.float64)
+    lmk = np.asarray(lmk, np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3 or lmk.shape != (len(pts), 2):
+        raise ValueError("align: model points %s and landmarks %s do not pair up" % (pts.shape, lmk.shape))
+    if weights is not None:
+        weights = np.asarray(weights, np.float64).reshape(-1)
+        if weights.shape != (len(pts),) or (weights < 0).any() or not weights.sum() > 0:
+            raise ValueError("align: weights must be [L], not negative and not all zero")
+    ndc = np.stack(((lmk[:, 0] + 0.5) * 2 / w - 1, 1 - (lmk[:, 1] + 0.5) * 2 / h), 1)
+    T = solve_ortho(pts, ndc, weights=weights)
+    scale = 1.0 / T[2, 3]
+    # ndc ~ pts @ M[:, :2] + t with M = T[:3, :3].T = e^s R
+    angles = euler_mat_inv(T[:3, :3].T / scale, "yxz")
+    return np.array([angles[0], angles[1], angles[2], T[0, 3], T[1, 3], 0.0, np.log(scale)], np.float64)
+
+
+def scale_landmarks(lmk, src_hw, dst_hw):
+    """Pixel index coordinates [..., 2] of a picture of (H, W) = src_hw -> of the same picture resized to dst_hw:
+    x' = (x + 1/2) W' / W - 1/2 (pixel centres, as the resize of reconstruct.load_image places them)."""
+    (h0, w0), (h1, w1) = _hw(src_hw), _hw(dst_hw)
+    lmk = np.asarray(lmk, np.float64)
+    return np.stack(((lmk[..., 0] + 0.5) * w1 / w0 - 0.5, (lmk[..., 1] + 0.5) * h1 / h0 - 0.5), -1)
 
 
 def _hw(canvas):

@@ -35,6 +35,7 @@ SOURCES = [
     ("style_linear.hip", EXACT),
     ("bank_mm.hip", EXACT),
     ("mesh.hip", EXACT),
+    ("landmark.hip", EXACT),
     ("morph.hip", []),
     ("skin.hip", []),
     ("blend.hip", []),

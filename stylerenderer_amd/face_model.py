@@ -18,7 +18,9 @@ What the fitting loop (inversion.LatentInverter, reconstruct) asks of a model, t
                                    [B] is every sample's share of reg, or None where the prior is a diagonal Gaussian
                                    (lpips_layer.fit_loss_rows then evaluates it from prior_sigma itself)
     prior_sigma(batch, shape_reg)  that Gaussian's sigma [n_coeff] for a fit of `batch` images, or None
-    fit_extras(coeff)              the model's own entries of a fit's .npz, from coeff [1, n_coeff]"""
+    fit_extras(coeff)              the model's own entries of a fit's .npz, from coeff [1, n_coeff]
+    landmarks                      (idx int32 [L, 3], bary float32 [L, 3]) of `landmark_embedding`, or None: the model's own
+                                   landmarks (load_bfm: the file's `landmarks68`), for the landmark term of the fit"""
 import numpy as np
 import torch
 from torch import nn
@@ -33,8 +35,68 @@ def _as_basis(w, rows, dim):
     return w
 
 
+def _load_array(path):
+    """The array(s) of a landmark file: .npy, .txt (numbers), or .npz with `idx` or with `faces` and `bary`."""
+    path = str(path)
+    if path.lower().endswith(".npz"):
+        with np.load(path, allow_pickle=False) as z:
+            if "faces" in z.files and "bary" in z.files:
+                return z["faces"], z["bary"]
+            if "idx" in z.files:
+                return z["idx"]
+            raise ValueError("landmark_embedding: %s holds neither `idx` nor `faces` and `bary`" % path)
+    if path.lower().endswith(".npy"):
+        return np.load(path, allow_pickle=False)
+    return np.loadtxt(path)
+
+
+def landmark_embedding(source, tri=None):
+    """(idx int32 [L, 3], bary float32 [L, 3]): every landmark as a barycentric combination of three vertices, the form
+    op.landmark takes.  `source` is
+      * an integer array [L] of vertex indices: idx = (i, i, i), bary = (1, 0, 0);
+      * a pair (faces [L], bary [L, 3]): triangle indices into `tri` [nf, 3] and weights on their corners (FLAME's static
+        embedding);
+      * the path of a .npy / .txt holding vertex indices (a .txt with four columns: face, three weights), or of a .npz
+        with `idx`, or with `faces` and `bary`.
+    Negative indices, faces outside `tri` and non-finite weights are refused; the upper bound of a vertex index is the
+    mesh's, checked where the embedding meets one (op.landmark.vertex_lists)."""
+    import os
+
+    if isinstance(source, (str, os.PathLike)):
+        source = _load_array(source)
+        if isinstance(source, np.ndarray) and source.ndim == 2 and source.shape[1] == 4:
+            source = (source[:, 0], source[:, 1:])
+    if isinstance(source, (tuple, list)) and len(source) == 2 and np.ndim(source[1]) == 2:
+        faces, bary = (x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x) for x in source)
+        if tri is None:
+            raise ValueError("landmark_embedding: (faces, bary) needs the mesh's tri")
+        t = tri.detach().cpu().numpy() if isinstance(tri, torch.Tensor) else np.asarray(tri)
+        faces = faces.reshape(-1)
+        if not np.all(np.round(faces) == faces):
+            raise ValueError("landmark_embedding: face indices must be whole numbers")
+        faces = faces.astype(np.int64)
+        bary = np.asarray(bary, np.float32)
+        if bary.shape != (len(faces), 3) or not np.isfinite(bary).all():
+            raise ValueError("landmark_embedding: bary must be finite [L, 3] for %d faces, got %s"
+                             % (len(faces), bary.shape))
+        if len(faces) and (faces.min() < 0 or faces.max() >= len(t)):
+            raise ValueError("landmark_embedding: face index out of range [0, %d)" % len(t))
+        idx = t[faces].astype(np.int64)
+    else:
+        idx = source.detach().cpu().numpy() if isinstance(source, torch.Tensor) else np.asarray(source)
+        idx = idx.reshape(-1)
+        if not np.all(np.round(idx) == idx):
+            raise ValueError("landmark_embedding: vertex indices must be whole numbers")
+        idx = np.repeat(idx.astype(np.int64).reshape(-1, 1), 3, 1)
+        bary = np.tile(np.array([[1.0, 0.0, 0.0]], np.float32), (len(idx), 1))
+    if idx.size and (idx.min() < 0 or idx.max() >= 2 ** 31):
+        raise ValueError("landmark_embedding: vertex index out of range")
+    return torch.from_numpy(idx.astype(np.int32)), torch.from_numpy(np.ascontiguousarray(bary, np.float32))
+
+
 class LinearMorphableModel(nn.Module):
     kind = "linear"
+    landmarks = None
 
     def __init__(self, vertices_num, shape_dim=0, expression_dim=0, vertices_mean=None, w_shape_numpy=None,
                  w_expression_numpy=None, sigma_shape=1, sigma_expression=.01, learnable=False):
@@ -132,6 +194,10 @@ def load_bfm(file_name="/data/BaselFaceModel.mat"):
     if tri.shape[0] == 3 and tri.shape[1] != 3:
         tri = tri.T
     model = LinearMorphableModel(len(v), w_shape.shape[1], w_exp.shape[1], v, w_shape, w_exp)
+    if "landmarks68" in data.keys():
+        # based like `tri` (align.template_from_bfm)
+        base = np.asarray(data["tri"][0, 0]).astype(np.int64).min()
+        model.landmarks = landmark_embedding(np.asarray(data["landmarks68"]).reshape(-1).astype(np.int64) - base, tri)
     return model, torch.from_numpy(np.ascontiguousarray(tri))
 
 
@@ -155,6 +221,7 @@ class BlendShapeModel(nn.Module):
     softmax(cat(x, -sum x)) is the Dirichlet draw itself.  It also runs with expression_dim = 0, where the reference's
     raises."""
     kind = "blended"
+    landmarks = None
 
     def __init__(self, vertices_num, shape_dim=0, expression_dim=0, bs=None, beta_shape=1, beta_expression=[1, 10],
                  learnable=False):
@@ -277,6 +344,7 @@ class LinearBlendSkinningModel(nn.Module):
     * without `weights` it needs scikit-learn for the nearest joint (lines 247-252); here the same weight
       exp(-d^2 / d_max^2) on the nearest joint comes from a brute-force argmin (nj is tiny)."""
     kind = "skinned"
+    landmarks = None
 
     def __init__(self, vertices_num, pose_nodes=1, shape_dim=0, v_template=None, J_regressor=None, kintree_table=None,
                  weights=None, posedirs=None, shapedirs=None, sigma_shape=1, sigma_pose=1, mean_pose=0, learnable=False):

@@ -15,6 +15,9 @@ The reference has no fitting script; its pieces are the generato
                 mean identity with every expression at sigmoid(0))
     loss        LPIPS-shaped distance(image, target) + pixel_weight * mean((image - target)^2)
                 (+ shape_reg * face_model.regulation(coeff), reference face_model.py:73-74, with fit_shape=True)
+                (+ landmark_weight * op.landmark.landmark_loss(vertices, embedding, landmarks, landmark_conf), with
+                 landmarks=: the fit's landmarks against the picture's; the pose then starts at
+                 align.pose_from_landmarks of the mean shape instead of 0)
     update      Adam, `steps` iterations (default 400)
 
 A target [B, 3, H, W] with B > 1 fits B independent images in one iteration (one captured graph): every variable
@@ -58,7 +61,8 @@ class _FlatAdamSet:
 class LatentInverter:
     def __init__(self, generator, perceptual, target, mesh, lr=0.05, pose_lr=0.01, pixel_weight=1.0, noise=None,
                  n_mean_latent=4096, use_graph=None, optimise_pose=True, *, face=None, fit_shape=False, coeff_lr=0.01,
-                 shape_reg=0.0):
+                 shape_reg=0.0, landmarks=None, landmark_conf=None, landmark_weight=1.0, landmark_beta=1.0,
+                 landmark_embedding=None):
         self.g = generator.eval()
         self.perceptual = perceptual.eval()
         for p in list(self.g.parameters()) + list(self.perceptual.parameters()):
@@ -94,6 +98,13 @@ class LatentInverter:
         self.w = mean_w.unsqueeze(1).repeat(self.batch, self.g.n_latent, 1).clone().requires_grad_(True)
         pose_shape = (7,) if self.batch == 1 else (self.batch, 7)
         self.pose = torch.zeros(pose_shape, device=self.device, requires_grad=optimise_pose)
+        # the landmark term: not part of the iteration at all without landmarks
+        self.with_landmarks = landmarks is not None
+        self.landmarks_fit = None
+        if self.with_landmarks:
+            self._init_landmarks(landmarks, landmark_conf, landmark_weight, landmark_beta, landmark_embedding)
+        elif landmark_conf is not None:
+            raise ValueError("LatentInverter: landmark_conf without landmarks")
         # 3DMM coefficients [B, d], from the mean face
         self.coeff = (torch.zeros(self.batch, self.face_model.n_coeff, device=self.device, requires_grad=True)
                       if self.fit_shape else None)
@@ -127,6 +138,77 @@ class LatentInverter:
     skinned = property(lambda self: self.fit_shape and self.face_model.kind == "skinned")       # FLAME: op.skin
     blended = property(lambda self: self.fit_shape and self.face_model.kind == "blended")       # FaceWarehouse: op.blend
 
+    # ---- landmarks -----------------------------------------------------------------------------------
+    def _init_landmarks(self, landmarks, conf, weight, beta, embedding):
+        if not self.fit_shape:
+            raise ValueError("LatentInverter: landmarks need fit_shape=True and face=(model, tri): the landmarks of the "
+                             "fit are read off the model's mesh")
+        emb = embedding if embedding is not None else getattr(self.face_model, "landmarks", None)
+        if emb is None:
+            raise ValueError("LatentInverter: landmarks need a landmark embedding and the face model has none "
+                             "(model.landmarks is None): pass landmark_embedding=face_model.landmark_embedding(...)")
+        self._lmk_idx, self._lmk_bary = (t.detach().to(self.device).contiguous() for t in emb)
+        self.landmark_weight, self.landmark_beta = float(weight), float(beta)
+        n_l = int(self._lmk_idx.shape[0])
+        # the buffers the iteration (and its captured graph) reads; reset() rewrites them
+        self._lmk_target = torch.zeros(self.batch, n_l, 2, device=self.device)
+        self._lmk_conf = torch.zeros(self.batch, n_l, device=self.device)
+        self._pose_start = torch.zeros_like(self.pose)
+        # the model's landmark points on its mean shape (host, float64): what the closed-form pose start is fitted to
+        with torch.no_grad():
+            v_mean = self.face_model.mesh(torch.zeros(1, self.face_model.n_coeff, device=self.device),
+                                          torch.zeros(1, 7, device=self.device), self.tri)[0]
+            from .op.landmark import landmark_points
+
+            self._lmk_points = landmark_points(v_mean.double().cpu(), self._lmk_idx.cpu(),
+                                               self._lmk_bary.double().cpu())[0].numpy()
+        self._set_landmarks(landmarks, conf)
+        with torch.no_grad():
+            self.pose.copy_(self._pose_start)
+
+    @torch.no_grad()
+    def _set_landmarks(self, landmarks, conf):
+        """Target landmarks [B, L, 2] (or [L, 2]) and confidences [B, L] (None: 1; landmarks None: all missing) into the
+        buffers, and every sample's closed-form starting pose into _pose_start (0 for a sample without landmarks)."""
+        import numpy as np
+
+        from .align import pose_from_landmarks
+
+        n_l = int(self._lmk_idx.shape[0])
+        as_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)     # noqa: E731
+        if landmarks is None:
+            lm, c = np.zeros((self.batch, n_l, 2)), np.zeros((self.batch, n_l))
+        else:
+            lm = as_np(landmarks).astype(np.float64)
+            lm = lm[None] if lm.ndim == 2 else lm
+            c = np.ones(lm.shape[:2]) if conf is None else as_np(conf).astype(np.float64).reshape(lm.shape[0], -1)
+        if lm.shape != (self.batch, n_l, 2) or c.shape != (self.batch, n_l):
+            raise ValueError("LatentInverter: %d images and %d landmarks need landmarks [B, L, 2] and landmark_conf "
+                             "[B, L], got %s and %s" % (self.batch, n_l, lm.shape, c.shape))
+        if (c < 0).any() or not np.isfinite(c).all():
+            raise ValueError("LatentInverter: landmark_conf must be finite and not negative")
+        lm = np.where(c[:, :, None] > 0, lm, 0.0)                       # a missing landmark may hold anything
+        if not np.isfinite(lm).all():
+            raise ValueError("LatentInverter: a landmark with a positive confidence is not finite")
+        size = tuple(int(x) for x in self.target.shape[-2:])
+        start = np.zeros((self.batch, 7))
+        for b in range(self.batch):
+            if c[b].sum() > 0:
+                start[b] = pose_from_landmarks(self._lmk_points, lm[b], size, c[b])
+        self._lmk_target.copy_(torch.from_numpy(lm).float())
+        self._lmk_conf.copy_(torch.from_numpy(c).float())
+        self._pose_start.copy_(torch.from_numpy(start).float().view(self._pose_start.shape))
+
+    def _landmark_term(self, v):
+        """landmark_weight * rows [B] of the posed vertices (one launch each way on the device); keeps the fitted
+        landmarks [B, L, 2] (pixel index coordinates of the target) as landmarks_fit: those of this forward pass, that is
+        of the mesh before the iteration's update (reconstruct projects fitted_mesh() for what it writes)."""
+        from .op.landmark import landmark_loss
+
+        self._lmk_rows, p = landmark_loss(v, self._lmk_idx, self._lmk_bary, self._lmk_target, self._lmk_conf,
+                                          tuple(self.target.shape[-2:]), self.landmark_beta, self.landmark_weight)
+        self.landmarks_fit = p.detach()
+
     def _shape_mesh(self):
         """(v, n, tri, reg) of the fitted coefficients and pose (the model's node — op.morph / op.skin / op.blend: no
         library GEMM on the device)."""
@@ -155,10 +237,14 @@ class LatentInverter:
             if self.fit_shape:
                 v, n, tri, self._reg = self._shape_mesh()
                 mesh = (v, n, tri)
+                if self.with_landmarks:
+                    self._landmark_term(v)
             else:
                 mesh = self.posed_mesh()
             img, _, _ = self.g([self.w], mesh, input_is_latent=True, noise=self.noise)
         else:
+            if self.with_landmarks:
+                self._landmark_term(self._shape_mesh()[0])
             img, _ = self.g([self.w], input_is_latent=True, noise=self.noise)
         return img
 
@@ -171,6 +257,8 @@ class LatentInverter:
         value = d + self.pixel_weight * mse(img, self.target)
         if self.fit_shape and self.shape_reg != 0.0 and getattr(self, "_reg", None) is not None:
             value = value + self._reg                    # shape_reg * regulation(coeff), from the node's forward
+        if self.with_landmarks:
+            value = value + self._lmk_rows.view(())
         return value
 
     def _loss_rows(self, img):
@@ -182,11 +270,14 @@ class LatentInverter:
         if prior and self._prior_rows is not None:
             self._rows, total = fit_loss_rows(layers, mse_rows(img, self.target), self.pixel_weight, reg=self._reg,
                                               prior_rows=self._prior_rows)
-            return total
-        self._rows, total = fit_loss_rows(layers, mse_rows(img, self.target), self.pixel_weight,
-                                          coeff=self.coeff if prior else None,
-                                          sigma=self._prior_sigma if prior else None, shape_reg=self.shape_reg,
-                                          reg=self._reg if prior else None)
+        else:
+            self._rows, total = fit_loss_rows(layers, mse_rows(img, self.target), self.pixel_weight,
+                                              coeff=self.coeff if prior else None,
+                                              sigma=self._prior_sigma if prior else None, shape_reg=self.shape_reg,
+                                              reg=self._reg if prior else None)
+        if self.with_landmarks:
+            self._rows = self._rows + self._lmk_rows.detach()
+            total = total + self._lmk_rows.sum()
         return total
 
     def _iteration(self):
@@ -217,12 +308,17 @@ class LatentInverter:
         return warmup
 
     @torch.no_grad()
-    def reset(self, target):
+    def reset(self, target, landmarks=None, landmark_conf=None):
         """Re-targets the inverter to `target` (the shape of the first): copies it and its LPIPS features into the
         buffers the captured graph reads, puts w back at the mean latent, pose and coeff at zero, and zeroes the Adam
-        moments and step counts.  `run(steps)` then gives what a fresh inverter on `target` gives (same mean latent,
-        same noise), bit for bit, without a new warm-up or capture."""
+        moments and step counts.  An inverter built with landmarks also takes the new picture's `landmarks` and
+        `landmark_conf` into its buffers and puts the pose at their closed-form start (landmarks None: every landmark
+        missing, pose 0).  `run(steps)` then gives what a fresh inverter on `target` (and these landmarks) gives (same
+        mean latent, same noise), bit for bit, without a new warm-up or capture."""
         target = target.detach()
+        if not self.with_landmarks and (landmarks is not None or landmark_conf is not None):
+            raise ValueError("LatentInverter.reset: this inverter was built without landmarks; the landmark term is "
+                             "part of the captured iteration or it is not")
         if tuple(target.shape) != tuple(self.target.shape):
             raise ValueError("LatentInverter.reset: target %s, the inverter fits %s"
                              % (tuple(target.shape), tuple(self.target.shape)))
@@ -230,7 +326,11 @@ class LatentInverter:
         for buf, f in zip(self.target_feats, self.perceptual.features(self.target)):
             buf.copy_(f)
         self.w.copy_(self._mean_w.unsqueeze(1).expand_as(self.w))
-        self.pose.zero_()
+        if self.with_landmarks:
+            self._set_landmarks(landmarks, landmark_conf)
+            self.pose.copy_(self._pose_start)
+        else:
+            self.pose.zero_()
         if self.coeff is not None:
             self.coeff.zero_()
         if self._adams is not None:

@@ -2,7 +2,8 @@
 for it):
 
     python -m stylerenderer_amd.reconstruct [--size 256] [--steps 400] [--lr] [--pose_lr] [--coeff_lr] [--shape_reg]
-        [--bfm BFM.mat | --flame FLAME.{pkl,mat} | --facewarehouse FW.mat [--beta_shape X]] [--lpips-trunk VGG16.pth] [--batch N] [--gpu 0] [--seed S] [--out DIR] CHECKPOINT IMAGE [IMAGE ...]
+        [--bfm BFM.mat | --flame FLAME.{pkl,mat} | --facewarehouse FW.mat [--beta_shape X]] [--lpips-trunk VGG16.pth] [--batch N] [--gpu 0] [--seed S] [--out DIR]
+        [--lmk LANDMARKS.txt [--lmk_index FILE] [--lmk_weight 1.0] [--lmk_beta 1.0] [--lmk_contour 1.0]] CHECKPOINT IMAGE [IMAGE ...]
 
 For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with inversion.LatentInverter(fit_shape=True)
 — the W+ latent, a rigid pose and the 3DMM shape / expression coefficients are fitted together (op.morph on the device)
@@ -21,6 +22,16 @@ image still follows its own single-image optimisation): the first group builds t
 re-target it with `reset`, and a short last group is padded with copies of its last image whose results are dropped.
 The files and their shapes are those of --batch 1, the default, which fits one image per inverter.
 
+With --lmk the fit is guided by 2-D landmarks (a text file in align.LandmarksReader's format, pixel indices of each input
+picture): the pose starts at the closed-form scaled-orthographic fit of the model's landmarks to the picture's
+(align.pose_from_landmarks) and --lmk_weight times the reprojection term of op.landmark joins the loss.  The model's
+landmarks are its own (a Basel file's `landmarks68`) or those of --lmk_index (face_model.landmark_embedding: vertex indices,
+or faces and barycentric weights).  --lmk_contour weighs landmarks 0-16 of a 68-point set, the jaw line, which detectors
+slide along the silhouette.  A picture the file does not list is fitted without the term's pull (every confidence 0) and
+counted in the last line of the output.  <stem>.npz then also holds `landmarks` [L, 2] (the fit's, in pixel indices of the
+input picture), `landmarks_target` (the file's; NaN when not listed) and `lmk_error` (their mean distance in those
+pixels over the weighted landmarks).  --lmk_weight's default is a starting value, not tuned on a trained checkpoint.
+
 Images are PNG / JPG (PIL) or .npy in [-1, 1] (HWC or CHW), resized on the host.  The 3DMM is the Basel Face Model with
 --bfm (face_model.load_bfm), FLAME with --flame (face_model.load_flame, op.skin), the FaceWarehouse bilinear blendshape
 model with --facewarehouse (face_model.load_facewarehouse, op.blend), else the synthetic model `train --mesh` trains with (train.SyntheticFaceSource).  Without
@@ -37,8 +48,8 @@ import torch
 from . import checkpoint, generate, inversion, lpips, utils_3d
 
 
-def load_image(path, size):
-    """[1, 3, size, size] float32 in [-1, 1] on the host."""
+def load_image(path, size, with_shape=False):
+    """[1, 3, size, size] float32 in [-1, 1] on the host (with_shape: and the (H, W) of the file's picture)."""
     if path.lower().endswith(".npy"):
         a = np.load(path).astype(np.float32)
         if a.ndim == 4:
@@ -56,9 +67,11 @@ def load_image(path, size):
     if x.shape[1] == 1:
         x = x.expand(-1, 3, -1, -1)
     x = x[:, :3]
-    if tuple(x.shape[-2:]) != (size, size):
+    shape = (int(x.shape[-2]), int(x.shape[-1]))
+    if shape != (size, size):
         x = torch.nn.functional.interpolate(x, size=(size, size), mode="bilinear", align_corners=False, antialias=True)
-    return x.clamp(-1, 1).contiguous()
+    x = x.clamp(-1, 1).contiguous()
+    return (x, shape) if with_shape else x
 
 
 def face_model(bfm, device, seed=0, flame=None, facewarehouse=None, beta_shape=.01):
@@ -78,30 +91,108 @@ def face_model(bfm, device, seed=0, flame=None, facewarehouse=None, beta_shape=.
     return src.model, src.tri
 
 
+class LandmarkGuide:
+    """The landmark options of one run: the reader of --lmk, the embedding and the weights; `lookup` gives what the
+    inverter takes for a picture."""
+
+    def __init__(self, lmk_file, face, index_file=None, weight=1.0, beta=1.0, contour=1.0):
+        from . import align
+        from .face_model import landmark_embedding
+
+        if not os.path.isfile(lmk_file):
+            raise SystemExit("reconstruct: landmark file %s not found" % lmk_file)
+        self.reader = align.LandmarksReader(lmk_file)
+        self.file = lmk_file
+        model, tri = face
+        if index_file:
+            self.embedding = landmark_embedding(index_file, tri)
+        else:
+            self.embedding = getattr(model, "landmarks", None)
+        if self.embedding is None:
+            raise SystemExit("reconstruct: --lmk needs the face model's landmarks and this model names none: pass "
+                             "--lmk_index FILE (vertex indices, or faces and barycentric weights)")
+        self.count = int(self.embedding[0].shape[0])
+        self.weight, self.beta, self.contour = float(weight), float(beta), float(contour)
+        if self.contour < 0:
+            raise SystemExit("reconstruct: --lmk_contour must not be negative")
+        self.missing = 0
+        self.seen = 0
+
+    def lookup(self, path, shape, size):
+        """(landmarks [L, 2] in pixel indices of the size x size target, conf [L], the file's landmarks in the picture's
+        own pixels or None) of the picture at `path`, whose (H, W) is `shape`."""
+        from . import align
+
+        self.seen += 1
+        lmk = self.reader.detect(path)
+        if lmk is None:
+            self.missing += 1
+            return np.zeros((self.count, 2)), np.zeros(self.count), None
+        if lmk.shape[0] != self.count:
+            raise SystemExit("reconstruct: %s lists %d landmarks for %s, the model's embedding has %d"
+                             % (self.file, lmk.shape[0], path, self.count))
+        conf = np.ones(self.count)
+        if self.count == 68:
+            conf[:17] = self.contour
+        return align.scale_landmarks(lmk, shape, (size, size)), conf, lmk
+
+    def inverter_args(self, landmarks, conf):
+        return dict(landmarks=np.stack(landmarks), landmark_conf=np.stack(conf), landmark_weight=self.weight,
+                    landmark_beta=self.beta, landmark_embedding=self.embedding)
+
+    def summary(self):
+        return "landmarks: %d of %d images are not listed in %s and were fitted without them" % (
+            self.missing, self.seen, self.file)
+
+
+def landmark_outputs(inv, index, conf, listed, shape):
+    """The landmark entries of sample `index`'s .npz: the fit's landmarks and the file's in pixel indices of the input
+    picture (H, W) = shape, and their mean distance over the landmarks with a positive weight."""
+    from . import align
+
+    from .op.landmark import landmark_points, project
+
+    size = tuple(int(x) for x in inv.target.shape[-2:])
+    # of the mesh that is written (the saved pose and coeff): inv.landmarks_fit is the last forward's, one Adam step behind
+    with torch.no_grad():
+        v = inv.fitted_mesh()[0][index:index + 1]
+        p = project(landmark_points(v, inv._lmk_idx, inv._lmk_bary), size)[0]
+    fit = align.scale_landmarks(p.cpu().numpy().astype(np.float64), size, shape)
+    if listed is None:
+        return {"landmarks": fit, "landmarks_target": np.full_like(fit, np.nan), "lmk_error": np.float64(np.nan)}
+    on = conf > 0
+    err = np.sqrt(((fit - listed) ** 2).sum(1))[on].mean() if on.any() else np.nan
+    return {"landmarks": fit, "landmarks_target": np.asarray(listed, np.float64), "lmk_error": np.float64(err)}
+
+
 def reconstruct(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr=0.01, shape_reg=0.0,
-                n_mean_latent=4096):
-    """Fits one image; returns the inverter (w, pose, coeff, image, fitted_mesh()) and the loss history (host)."""
+                n_mean_latent=4096, **landmark_args):
+    """Fits one image; returns the inverter (w, pose, coeff, image, fitted_mesh()) and the loss history (host).
+    landmark_args: LatentInverter's landmark keywords."""
     inv = inversion.LatentInverter(g, percept, target, None, lr=lr, pose_lr=pose_lr, n_mean_latent=n_mean_latent,
-                                   face=face, fit_shape=True, coeff_lr=coeff_lr, shape_reg=shape_reg)
+                                   face=face, fit_shape=True, coeff_lr=coeff_lr, shape_reg=shape_reg, **landmark_args)
     hist = inv.run(steps)
     return inv, hist.cpu().numpy()
 
 
 def reconstruct_batch(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr=0.01, shape_reg=0.0,
-                      n_mean_latent=4096, inv=None):
+                      n_mean_latent=4096, inv=None, **landmark_args):
     """Fits the B images of target [B, 3, H, W] together; `inv` (an inverter of the same batch from an earlier call) is
-    re-targeted instead of built anew.  Returns the inverter and the loss history [steps, B] (host)."""
+    re-targeted instead of built anew.  Returns the inverter and the loss history [steps, B] (host).  landmark_args:
+    LatentInverter's landmark keywords."""
     if inv is None:
         inv = inversion.LatentInverter(g, percept, target, None, lr=lr, pose_lr=pose_lr, n_mean_latent=n_mean_latent,
-                                       face=face, fit_shape=True, coeff_lr=coeff_lr, shape_reg=shape_reg)
+                                       face=face, fit_shape=True, coeff_lr=coeff_lr, shape_reg=shape_reg, **landmark_args)
+    elif landmark_args:
+        inv.reset(target, landmark_args["landmarks"], landmark_args["landmark_conf"])
     else:
         inv.reset(target)
     hist = inv.run(steps)
     return inv, hist.cpu().numpy().reshape(steps, -1)
 
 
-def write_outputs(inv, hist, out_dir, stem, index=0):
-    """The five files of sample `index` of the inverter (hist: its loss history [steps])."""
+def write_outputs(inv, hist, out_dir, stem, index=0, extras=None):
+    """The five files of sample `index` of the inverter (hist: its loss history [steps]; extras: further .npz entries)."""
     from .op.rasterize import rasterize
 
     k = slice(index, index + 1)
@@ -121,7 +212,7 @@ def write_outputs(inv, hist, out_dir, stem, index=0):
     generate.save_image(inv.image[k].cpu(), os.path.join(out_dir, stem + "_render.png"))
     generate.save_image(normal_map.cpu(), os.path.join(out_dir, stem + "_normal.png"))
     np.savez(os.path.join(out_dir, stem + ".npz"), w=inv.w.detach()[k].cpu().numpy(), coeff=coeff.cpu().numpy(),
-             pose=pose.cpu().numpy(), loss=hist, **inv.face_model.fit_extras(coeff))
+             pose=pose.cpu().numpy(), loss=hist, **inv.face_model.fit_extras(coeff), **(extras or {}))
 
 
 def main(argv=None):
@@ -149,6 +240,16 @@ def main(argv=None):
     ap.add_argument("--n_mean_latent", type=int, default=4096, help="latents averaged for the starting W+ [%(default)d]")
     ap.add_argument("--batch", type=int, default=1,
                     help="images fitted together in one batched inverter (one captured graph) [%(default)d]")
+    ap.add_argument("--lmk", default=None, metavar="LANDMARKS.txt",
+                    help="landmark file (one picture per line: its name and x y pairs in its pixels): guides the fit")
+    ap.add_argument("--lmk_index", default=None, metavar="FILE",
+                    help="the model's landmarks: .npy / .txt of vertex indices, or .npz with faces and bary; default: the "
+                         "face model's own (a Basel file's landmarks68)")
+    ap.add_argument("--lmk_weight", type=float, default=1.0,
+                    help="weight of the landmark term; a starting value, not tuned on a trained checkpoint [%(default)g]")
+    ap.add_argument("--lmk_beta", type=float, default=1.0, help="smooth-L1 threshold of the term in pixels [%(default)g]")
+    ap.add_argument("--lmk_contour", type=float, default=1.0,
+                    help="weight of landmarks 0-16 (the jaw line) of a 68-point set [%(default)g]")
     ap.add_argument("--gpu", type=int, default=0, help="use gpu id")
     ap.add_argument("--seed", type=int, default=0, help="random seed (mean latent, noise)")
     ap.add_argument("--out", default="reconstruct", metavar="DIR", help="output directory [%(default)s]")
@@ -157,6 +258,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error("--batch must be at least 1")
+    if args.lmk_index and not args.lmk:
+        ap.error("--lmk_index needs --lmk")
     torch.manual_seed(args.seed)
     if torch.cuda.is_available() and 0 <= args.gpu < torch.cuda.device_count():
         device = torch.device("cuda:%d" % args.gpu)
@@ -174,33 +277,60 @@ def main(argv=None):
     percept = percept.to(device)
     face = face_model(args.bfm, device, seed=args.seed, flame=args.flame, facewarehouse=args.facewarehouse,
                       beta_shape=args.beta_shape)
+    guide = (LandmarkGuide(args.lmk, face, args.lmk_index, args.lmk_weight, args.lmk_beta, args.lmk_contour)
+             if args.lmk else None)
     os.makedirs(args.out, exist_ok=True)
     results = []
+
+    def load(path):
+        """(target on the host, what the landmark file says about the picture: LandmarkGuide.lookup's triple, or None)."""
+        if guide is None:
+            return load_image(path, args.size), None
+        x, shape = load_image(path, args.size, with_shape=True)
+        return x, guide.lookup(path, shape, args.size) + (shape,)
+
+    def tail(extras):
+        if extras is None:
+            return ""
+        return ", landmarks %s" % ("not listed" if np.isnan(extras["lmk_error"]) else "%.3f px" % float(extras["lmk_error"]))
+
     if args.batch == 1:
         for path in args.images:
             stem = os.path.splitext(os.path.basename(path))[0]
-            target = load_image(path, args.size).to(device)
-            inv, hist = reconstruct(g, percept, face, target, args.steps, args.lr, args.pose_lr, args.coeff_lr,
-                                    args.shape_reg, args.n_mean_latent)
-            write_outputs(inv, hist, args.out, stem)
-            print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f" % (
-                path, float(hist[0]), float(hist[-1]), len(hist), float(inv.coeff.detach().norm())), flush=True)
+            target, look = load(path)
+            lmk_args = guide.inverter_args([look[0]], [look[1]]) if guide else {}
+            inv, hist = reconstruct(g, percept, face, target.to(device), args.steps, args.lr, args.pose_lr, args.coeff_lr,
+                                    args.shape_reg, args.n_mean_latent, **lmk_args)
+            extras = landmark_outputs(inv, 0, look[1], look[2], look[3]) if guide else None
+            write_outputs(inv, hist, args.out, stem, extras=extras)
+            print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f%s" % (
+                path, float(hist[0]), float(hist[-1]), len(hist), float(inv.coeff.detach().norm()), tail(extras)),
+                flush=True)
             results.append((stem, hist))
+        if guide:
+            print(guide.summary(), flush=True)
         return results
     inv = None
     for start in range(0, len(args.images), args.batch):
         group = args.images[start:start + args.batch]
-        targets = [load_image(path, args.size) for path in group]
+        loaded = [load(path) for path in group]
+        targets = [x for x, _ in loaded]
         targets += targets[-1:] * (args.batch - len(group))          # padding: fitted, then discarded
+        looks = [look for _, look in loaded]
+        looks += looks[-1:] * (args.batch - len(group))
+        lmk_args = guide.inverter_args([k[0] for k in looks], [k[1] for k in looks]) if guide else {}
         inv, hist = reconstruct_batch(g, percept, face, torch.cat(targets, 0).to(device), args.steps, args.lr,
-                                      args.pose_lr, args.coeff_lr, args.shape_reg, args.n_mean_latent, inv=inv)
+                                      args.pose_lr, args.coeff_lr, args.shape_reg, args.n_mean_latent, inv=inv, **lmk_args)
         for i, path in enumerate(group):
             stem = os.path.splitext(os.path.basename(path))[0]
             h = np.ascontiguousarray(hist[:, i])
-            write_outputs(inv, h, args.out, stem, index=i)
-            print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f" % (
-                path, float(h[0]), float(h[-1]), len(h), float(inv.coeff.detach()[i].norm())), flush=True)
+            extras = landmark_outputs(inv, i, looks[i][1], looks[i][2], looks[i][3]) if guide else None
+            write_outputs(inv, h, args.out, stem, index=i, extras=extras)
+            print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f%s" % (
+                path, float(h[0]), float(h[-1]), len(h), float(inv.coeff.detach()[i].norm()), tail(extras)), flush=True)
             results.append((stem, h))
+    if guide:
+        print(guide.summary(), flush=True)
     return results
 
 
