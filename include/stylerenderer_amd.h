@@ -840,6 +840,36 @@ int sr_landmark_loss_bwd(float* gv, const float* g, const float* g_rows, int64_t
                          const int32_t* csr_l, const float* csr_w, int64_t B, int64_t L, int64_t nv, int64_t H, int64_t W,
                          int accumulate, sr_stream_t stream);
 
+/* Pose-aware landmarks: contour lines that slide along the silhouette and a visibility gate (definition:
+ * stylerenderer_amd/op/landmark.py, landmark_dynamic_composite), csrc/landmark.hip.  Contour line c (C of them) replaces
+ * landmark line_lmk[c] by one of its candidate vertices cand[cand_off[c] .. cand_off[c + 1]) (at least one; candidate 0
+ * is the static vertex): with a = (v[b, i_up] - v[b, i_down]).xy and u = (a.y, -a.x) / |a| ((1, 0) when |a| < 1e-6),
+ *   sel[b, c] = cand[first arg max_j side[c] * dot(v[b, cand_j].xy, u)]        (higher score, then lower position)
+ * and P_l = v[b, sel[b, c]] for that landmark; lmk_line int32 [L] holds every landmark's line or -1.  Every other
+ * landmark's confidence is multiplied by gate[b, l] = smoothstep(clamp((m - vis_lo) / (vis_hi - vis_lo), 0, 1)),
+ * m = N.z / max(|N|, 1e-12) of N = sum_k bary[l, k] normals[b, idx[l, k], :] (vis_hi == vis_lo: 1 where m > vis_lo, else
+ * 0); the gate is 1 for contour landmarks and everywhere when use_vis == 0 (normals may then be NULL).  rows, p, g as in
+ * sr_landmark_loss_fwd with conf * gate in place of conf.
+ * sr_landmark_dyn_fwd: one launch, one workgroup of 256 per sample (a wave per line, lanes over its candidates, wave
+ *   arg-max by cross-lane shuffles; then the static forward's fixed-order sums); writes rows [B], p, g [B, L, 2],
+ *   sel int32 [B, C], gate [B, L].  C <= 8192.  Every index (idx, cand, i_up, i_down < nv; lmk_line < C) is the caller's
+ *   to validate (op/landmark.py does when it builds the lists).
+ * sr_landmark_dyn_bwd: sr_landmark_loss_bwd with a second list: csr_* is built from the embedding with the contour
+ *   landmarks' weights dropped; line_off int32 [nv + 1], line_c / line_l int32 [entries] list for every vertex the
+ *   (line, landmark) pairs in which it is a candidate (first occurrence per line, ascending line); an entry adds
+ *   g[b, l] iff sel[b, c] is this vertex.  A lane adds its static entries first, then its line entries, in list order.
+ * No atomics, no memset, no allocation, no host read: both run under graph capture on `stream`; reruns are
+ * bit-identical.  B <= 65535 for the backward. */
+int sr_landmark_dyn_fwd(float* rows, float* p, float* g, int32_t* sel, float* gate, const float* v, const float* normals,
+                        const int32_t* idx, const float* bary, const float* target, const float* conf,
+                        const int32_t* lmk_line, const int32_t* side, const int32_t* cand_off, const int32_t* cand,
+                        int64_t B, int64_t L, int64_t C, int64_t nv, int64_t i_up, int64_t i_down, int use_vis,
+                        float vis_lo, float vis_hi, int64_t H, int64_t W, float beta, float weight, sr_stream_t stream);
+int sr_landmark_dyn_bwd(float* gv, const float* g, const float* g_rows, int64_t g_rows_stride, const int32_t* sel,
+                        const int32_t* csr_off, const int32_t* csr_l, const float* csr_w, const int32_t* line_off,
+                        const int32_t* line_c, const int32_t* line_l, int64_t B, int64_t L, int64_t C, int64_t nv,
+                        int64_t H, int64_t W, int accumulate, sr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,13 @@
 """Landmark-guided face reconstruction on one GPU: the fit-shape inversion (LatentInverter(fit_shape=True)) at 256^2 on the
 face-sized synthetic 3DMM, with and without the landmark term (op.landmark), at the batch sizes of --batch.
 
-    python scripts/bench_landmark_fit.py [--batch 1,8] [--steps 100] [--rounds 5] [--root DIR]
+    python scripts/bench_landmark_fit.py [--batch 1,8] [--steps 100] [--rounds 5] [--dynamic] [--root DIR]
 
 One JSON line per batch size: replayed image-steps/s (B steps per replay of the captured graph) of the inverter without
 landmarks and of the one with 68 landmarks in the same process, the rounds alternated and the median round counted, the
-kernel nodes and all nodes of each captured step, and the cost of the term (ratio of the rates, extra nodes).
+kernel nodes and all nodes of each captured step, and the cost of the term (ratio of the rates, extra nodes).  With
+--dynamic a third inverter runs the pose-aware term (contour lines on landmarks 0-16, 21 candidates each, and the
+visibility gate 0,0.2) in the same alternation: its rate and nodes against the static term's.
 
 --root DIR imports the package from another checkout (built there): a checkout from before the landmark term reports the
 rate without landmarks only.  To compare two commits, run the script once per checkout in turn, twice each, in one
@@ -23,7 +25,7 @@ import torch
 DEV = torch.device("cuda:0")
 
 
-def build(pkg, size, batch, with_landmarks):
+def build(pkg, size, batch, with_landmarks, dynamic=False):
     inversion, lpips, model, synth, train = pkg["inversion"], pkg["lpips"], pkg["model"], pkg["synth"], pkg["train"]
     morph = pkg["morph"]
     g = model.GeneratorWithMap(size, 512, 8)
@@ -48,6 +50,11 @@ def build(pkg, size, batch, with_landmarks):
         idx, bary = face_model.landmark_embedding(np.linspace(0, nv - 1, 68).round().astype(np.int64))
         lmk = landmark.project(landmark.landmark_points(v.double().cpu(), idx, bary.double()), size)[0].numpy()
         kw = dict(landmarks=np.repeat(lmk[None], batch, 0), landmark_embedding=(idx, bary))
+        if dynamic:
+            main = face_model.landmark_vertices((idx, bary))
+            cand = np.concatenate([(main[l] + np.arange(21)) % nv for l in range(17)])
+            kw.update(landmark_lines=(np.arange(17), np.where(np.arange(17) < 8, 1, -1), 21 * np.arange(18), cand),
+                      landmark_axis=(int(main[27]), int(main[8])), landmark_vis=(0.0, 0.2))
     torch.manual_seed(11)
     return inversion.LatentInverter(g, net, target.expand(batch, -1, -1, -1).contiguous(), None, lr=0.05, pose_lr=0.01,
                                     noise=noise, n_mean_latent=4096, use_graph=True, face=(fm, tri), fit_shape=True,
@@ -60,6 +67,8 @@ def main():
     ap.add_argument("--batch", default="1,8", metavar="B1,B2,...")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--dynamic", action="store_true",
+                    help="also measure the pose-aware term (contour lines and the visibility gate)")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                     help="the checkout whose package is measured [this one]")
     args = ap.parse_args()
@@ -77,6 +86,8 @@ def main():
         invs = {"plain": build(pkg, args.size, b, False)}
         if has_term:
             invs["landmarks"] = build(pkg, args.size, b, True)
+        if has_term and args.dynamic:
+            invs["dynamic"] = build(pkg, args.size, b, True, dynamic=True)
         for inv in invs.values():
             inv.run(8)                                     # warm-up iterations + capture
             torch.cuda.synchronize()
@@ -101,6 +112,9 @@ def main():
         if has_term:
             out["landmarks_over_plain"] = round(out["landmarks_image_steps_per_s"] / out["plain_image_steps_per_s"], 4)
             out["extra_kernel_nodes"] = out["landmarks_kernel_nodes"] - out["plain_kernel_nodes"]
+        if "dynamic" in invs:
+            out["dynamic_over_landmarks"] = round(out["dynamic_image_steps_per_s"] / out["landmarks_image_steps_per_s"], 4)
+            out["dynamic_extra_kernel_nodes"] = out["dynamic_kernel_nodes"] - out["landmarks_kernel_nodes"]
         print(json.dumps(out), flush=True)
         del invs
 

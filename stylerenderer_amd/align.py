@@ -159,6 +159,32 @@ def pose_from_landmarks(model_pts, lmk, size_hw, weights=None):
     return np.array([angles[0], angles[1], angles[2], T[0, 3], T[1, 3], 0.0, np.log(scale)], np.float64)
 
 
+def pose_from_landmarks_contour(v_mean, embedding, lines, axis, lmk, size_hw, weights=None):
+    """pose_from_landmarks for landmarks whose jaw line follows the silhouette: two passes, no iteration to convergence.
+    Pass 1 is pose_from_landmarks on the embedding's static points of the mean shape v_mean [nv, 3].  The mean shape is
+    then posed with that result, every contour line of `lines` selects its vertex by op.landmark's rule (the candidate
+    furthest out across the face, `axis` = (i_up, i_down)), and pass 2 solves again with the selected vertices in place of
+    the static jaw points.  Returns (pose [7] float64, sel int64 [C] the selected vertices).  Host float64."""
+    import torch
+
+    from .op.landmark import check_lines, contour_select, landmark_points
+    from .utils_3d import euler_mat
+
+    v = torch.from_numpy(np.asarray(v_mean, np.float64).reshape(1, -1, 3))
+    idx, bary = (torch.as_tensor(t) for t in embedding)
+    pts = landmark_points(v, idx, bary.double())[0].numpy()
+    first = pose_from_landmarks(pts, lmk, size_hw, weights)
+    tables = check_lines(lines, len(pts), v.shape[1])
+    if len(tables[0]) == 0:
+        return first, np.zeros(0, np.int64)
+    p = torch.from_numpy(first)
+    posed = v @ (torch.exp(p[6]) * euler_mat(p[:3], "yxz")) + p[3:6]
+    sel = contour_select(posed, tables, (int(axis[0]), int(axis[1])))[1][0].numpy()
+    pts2 = pts.copy()
+    pts2[tables[0]] = v[0].numpy()[sel]
+    return pose_from_landmarks(pts2, lmk, size_hw, weights), sel
+
+
 def scale_landmarks(lmk, src_hw, dst_hw):
     """Pixel index coordinates [..., 2] of a picture of (H, W) = src_hw -> of the same picture resized to dst_hw:
     x' = (x + 1/2) W' / W - 1/2 (pixel centres, as the resize of reconstruct.load_image places them)."""

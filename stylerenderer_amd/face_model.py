@@ -20,10 +20,14 @@ What the fitting loop (inversion.LatentInverter, reconstruct) asks of a model, t
     prior_sigma(batch, shape_reg)  that Gaussian's sigma [n_coeff] for a fit of `batch` images, or None
     fit_extras(coeff)              the model's own entries of a fit's .npz, from coeff [1, n_coeff]
     landmarks                      (idx int32 [L, 3], bary float32 [L, 3]) of `landmark_embedding`, or None: the model's own
-                                   landmarks (load_bfm: the file's `landmarks68`), for the landmark term of the fit"""
+                                   landmarks (load_bfm: the file's `landmarks68`), for the landmark term of the fit
+`contour_lines` builds, from any model's mean shape, the candidate lines along which the jaw landmarks of that term slide
+with the pose (op.landmark); `load_contour_lines` reads hand-made ones."""
 import numpy as np
 import torch
 from torch import nn
+
+from .op._dispatch import host_array
 
 
 def _as_basis(w, rows, dim):
@@ -92,6 +96,93 @@ def landmark_embedding(source, tri=None):
     if idx.size and (idx.min() < 0 or idx.max() >= 2 ** 31):
         raise ValueError("landmark_embedding: vertex index out of range")
     return torch.from_numpy(idx.astype(np.int32)), torch.from_numpy(np.ascontiguousarray(bary, np.float32))
+
+
+def contour_lines(v_mean, embedding, contour=range(17), max_candidates=64, inner=0.5, normals=None, tri=None):
+    """Contour lines of a model's mean shape for op.landmark's pose-aware term: (line_lmk int32 [C], side int32 [C],
+    cand_off int32 [C + 1], cand int32 [E]) on the host.  v_mean [nv, 3] (or [1, nv, 3]) is the mean shape, centred in x
+    and seen from +z; `embedding` = (idx, bary) of `landmark_embedding`; `contour` names the landmarks of the jaw line in
+    their order along it (0-16 of a 68-point set).  For contour landmark l at mean position P: side = sign of P.x; a
+    landmark with |P.x| below 2 % of the face's half width (max |x|; the chin) gets no line.  Its candidates are the
+    vertices
+      * whose y lies within half the spacing to the neighbouring contour landmarks (an end of the jaw line mirrors its one
+        neighbour),
+      * whose side x lies between inner side P.x and side P.x,
+      * whose mean-shape normal has z > 0 (`normals` [nv, 3], or computed from `tri`; without either this test is left
+        out),
+    ordered by descending side x after the static vertex (the vertex of the landmark's largest weight, always
+    candidate 0) and cut at max_candidates."""
+    v = host_array(v_mean).astype(np.float64).reshape(-1, 3)
+    idx, bary = (host_array(t) for t in embedding)
+    idx, bary = idx.astype(np.int64), bary.astype(np.float64)
+    nv = len(v)
+    if idx.size and (idx.min() < 0 or idx.max() >= nv):
+        raise ValueError("contour_lines: landmark vertex index out of range [0, %d)" % nv)
+    contour = [int(l) for l in contour]
+    if len(set(contour)) != len(contour):
+        raise ValueError("contour_lines: a landmark is named twice in `contour`")
+    if contour and (min(contour) < 0 or max(contour) >= len(idx)):
+        raise ValueError("contour_lines: `contour` names a landmark outside [0, %d)" % len(idx))
+    if int(max_candidates) < 1 or not 0.0 <= float(inner) <= 1.0:
+        raise ValueError("contour_lines: max_candidates >= 1 and 0 <= inner <= 1")
+    if normals is None and tri is not None:
+        from .utils_3d import mesh_point_normal
+
+        normals = mesh_point_normal(torch.from_numpy(v)[None], torch.as_tensor(host_array(tri)).long())[0]
+    facing = np.ones(nv, bool) if normals is None else host_array(normals).reshape(-1, 3)[:, 2] > 0
+    pts = (bary[:, :, None] * v[idx]).sum(1)                                           # [L, 3]
+    half_width = np.abs(v[:, 0]).max()
+    line_lmk, sides, cand, off = [], [], [], [0]
+    for k, l in enumerate(contour):
+        px, py = pts[l, 0], pts[l, 1]
+        if abs(px) < 0.02 * half_width:
+            continue
+        side = 1.0 if px > 0 else -1.0
+        near = [pts[contour[j], 1] for j in (k - 1, k + 1) if 0 <= j < len(contour)]
+        half = [0.5 * abs(y - py) for y in near]
+        if len(near) == 2 and (near[0] - py) * (near[1] - py) < 0:
+            lo, hi = py - half[0 if near[0] < py else 1], py + half[0 if near[0] > py else 1]
+        else:                                   # an end of the line, or a turning point of it: the wider half both ways
+            lo, hi = py - max(half, default=0.0), py + max(half, default=0.0)
+        sx = side * v[:, 0]
+        ok = facing & (v[:, 1] >= lo) & (v[:, 1] <= hi) & (sx >= inner * side * px) & (sx <= side * px)
+        static = int(idx[l, int(np.argmax(bary[l]))])
+        ok[static] = False
+        rest = np.nonzero(ok)[0]
+        rest = rest[np.argsort(-sx[rest], kind="stable")][:int(max_candidates) - 1]
+        line_lmk.append(l)
+        sides.append(int(side))
+        cand.extend([static] + rest.tolist())
+        off.append(len(cand))
+    as_t = lambda a: torch.from_numpy(np.asarray(a, np.int32).reshape(-1))                       # noqa: E731
+    return as_t(line_lmk), as_t(sides), as_t(off), as_t(cand)
+
+
+def save_contour_lines(path, lines):
+    """Writes lines = (line_lmk, side, cand_off, cand) to an .npz under those four names."""
+    a = [host_array(x).astype(np.int32).reshape(-1) for x in lines]
+    np.savez(str(path), line_lmk=a[0], side=a[1], cand_off=a[2], cand=a[3])
+
+
+def load_contour_lines(path, n_landmarks=None, nv=None):
+    """Reads hand-made contour lines from an .npz with `line_lmk` [C], `side` [C], `cand_off` [C + 1] and `cand` [E]
+    (candidate 0 of a line: its landmark's static vertex); checked like op.landmark does (a landmark in two lines, an
+    empty line, a side other than -1 / +1, and, where n_landmarks / nv are given, indices out of range)."""
+    from .op.landmark import check_lines
+
+    with np.load(str(path), allow_pickle=False) as z:
+        missing = [k for k in ("line_lmk", "side", "cand_off", "cand") if k not in z.files]
+        if missing:
+            raise ValueError("load_contour_lines: %s lacks %s" % (path, ", ".join(missing)))
+        raw = tuple(z[k] for k in ("line_lmk", "side", "cand_off", "cand"))
+    n_l = int(n_landmarks) if n_landmarks is not None else (int(np.max(raw[0])) + 1 if np.size(raw[0]) else 0)
+    return tuple(torch.from_numpy(a.astype(np.int32)) for a in check_lines(raw, n_l, nv))
+
+
+def landmark_vertices(embedding):
+    """The main vertex [L] (int64, host) of every landmark of an embedding: the one of its largest weight."""
+    idx, bary = (host_array(t) for t in embedding)
+    return idx.astype(np.int64)[np.arange(len(idx)), np.argmax(bary, 1)]
 
 
 class LinearMorphableModel(nn.Module):

@@ -17,7 +17,9 @@ The reference has no fitting script; its pieces are the generato
                 (+ shape_reg * face_model.regulation(coeff), reference face_model.py:73-74, with fit_shape=True)
                 (+ landmark_weight * op.landmark.landmark_loss(vertices, embedding, landmarks, landmark_conf), with
                  landmarks=: the fit's landmarks against the picture's; the pose then starts at
-                 align.pose_from_landmarks of the mean shape instead of 0)
+                 align.pose_from_landmarks of the mean shape instead of 0; with landmark_lines= (and landmark_axis=) the
+                 jaw landmarks slide along the posed mesh's silhouette, with landmark_vis= landmarks turned away from the
+                 camera are faded out: op.landmark's pose-aware term, the pose start in two closed-form passes)
     update      Adam, `steps` iterations (default 400)
 
 A target [B, 3, H, W] with B > 1 fits B independent images in one iteration (one captured graph): every variable
@@ -62,7 +64,7 @@ class LatentInverter:
     def __init__(self, generator, perceptual, target, mesh, lr=0.05, pose_lr=0.01, pixel_weight=1.0, noise=None,
                  n_mean_latent=4096, use_graph=None, optimise_pose=True, *, face=None, fit_shape=False, coeff_lr=0.01,
                  shape_reg=0.0, landmarks=None, landmark_conf=None, landmark_weight=1.0, landmark_beta=1.0,
-                 landmark_embedding=None):
+                 landmark_embedding=None, landmark_lines=None, landmark_axis=None, landmark_vis=None):
         self.g = generator.eval()
         self.perceptual = perceptual.eval()
         for p in list(self.g.parameters()) + list(self.perceptual.parameters()):
@@ -101,8 +103,12 @@ class LatentInverter:
         # the landmark term: not part of the iteration at all without landmarks
         self.with_landmarks = landmarks is not None
         self.landmarks_fit = None
+        # of the pose-aware term (landmark_lines / landmark_vis): the vertices the contour lines selected [B, C] and the
+        # gate on every landmark's confidence [B, L] in the last forward
+        self.contour_fit = self.landmark_visibility = None
         if self.with_landmarks:
-            self._init_landmarks(landmarks, landmark_conf, landmark_weight, landmark_beta, landmark_embedding)
+            self._init_landmarks(landmarks, landmark_conf, landmark_weight, landmark_beta, landmark_embedding,
+                                 landmark_lines, landmark_axis, landmark_vis)
         elif landmark_conf is not None:
             raise ValueError("LatentInverter: landmark_conf without landmarks")
         # 3DMM coefficients [B, d], from the mean face
@@ -139,7 +145,7 @@ class LatentInverter:
     blended = property(lambda self: self.fit_shape and self.face_model.kind == "blended")       # FaceWarehouse: op.blend
 
     # ---- landmarks -----------------------------------------------------------------------------------
-    def _init_landmarks(self, landmarks, conf, weight, beta, embedding):
+    def _init_landmarks(self, landmarks, conf, weight, beta, embedding, lines=None, axis=None, vis=None):
         if not self.fit_shape:
             raise ValueError("LatentInverter: landmarks need fit_shape=True and face=(model, tri): the landmarks of the "
                              "fit are read off the model's mesh")
@@ -150,6 +156,19 @@ class LatentInverter:
         self._lmk_idx, self._lmk_bary = (t.detach().to(self.device).contiguous() for t in emb)
         self.landmark_weight, self.landmark_beta = float(weight), float(beta)
         n_l = int(self._lmk_idx.shape[0])
+        # the pose-aware term (op.landmark.landmark_loss_ex): contour lines that slide along the silhouette (on the host:
+        # the kernels' lists are built from them once), the two anchor vertices of the face's up direction, the gate
+        self._lmk_dynamic = lines is not None or vis is not None
+        if lines is not None and axis is None:
+            raise ValueError("LatentInverter: landmark_lines need landmark_axis=(i_up, i_down), the vertices that span "
+                             "the face's up direction")
+        if vis is not None and not float(vis[0]) <= float(vis[1]):
+            raise ValueError("LatentInverter: landmark_vis = (lo, hi) needs lo <= hi")
+        self._lmk_lines = None if lines is None else tuple(
+            (t.detach().cpu() if isinstance(t, torch.Tensor) else torch.as_tensor(t)).to(torch.int32).reshape(-1)
+            for t in lines)
+        self._lmk_axis = None if lines is None else (int(axis[0]), int(axis[1]))
+        self._lmk_vis = None if vis is None else (float(vis[0]), float(vis[1]))
         # the buffers the iteration (and its captured graph) reads; reset() rewrites them
         self._lmk_target = torch.zeros(self.batch, n_l, 2, device=self.device)
         self._lmk_conf = torch.zeros(self.batch, n_l, device=self.device)
@@ -162,6 +181,7 @@ class LatentInverter:
 
             self._lmk_points = landmark_points(v_mean.double().cpu(), self._lmk_idx.cpu(),
                                                self._lmk_bary.double().cpu())[0].numpy()
+            self._lmk_mean = v_mean[0].double().cpu().numpy() if self._lmk_lines is not None else None
         self._set_landmarks(landmarks, conf)
         with torch.no_grad():
             self.pose.copy_(self._pose_start)
@@ -172,16 +192,16 @@ class LatentInverter:
         buffers, and every sample's closed-form starting pose into _pose_start (0 for a sample without landmarks)."""
         import numpy as np
 
-        from .align import pose_from_landmarks
+        from .align import pose_from_landmarks, pose_from_landmarks_contour
+        from .op._dispatch import host_array
 
         n_l = int(self._lmk_idx.shape[0])
-        as_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)     # noqa: E731
         if landmarks is None:
             lm, c = np.zeros((self.batch, n_l, 2)), np.zeros((self.batch, n_l))
         else:
-            lm = as_np(landmarks).astype(np.float64)
+            lm = host_array(landmarks).astype(np.float64)
             lm = lm[None] if lm.ndim == 2 else lm
-            c = np.ones(lm.shape[:2]) if conf is None else as_np(conf).astype(np.float64).reshape(lm.shape[0], -1)
+            c = np.ones(lm.shape[:2]) if conf is None else host_array(conf).astype(np.float64).reshape(lm.shape[0], -1)
         if lm.shape != (self.batch, n_l, 2) or c.shape != (self.batch, n_l):
             raise ValueError("LatentInverter: %d images and %d landmarks need landmarks [B, L, 2] and landmark_conf "
                              "[B, L], got %s and %s" % (self.batch, n_l, lm.shape, c.shape))
@@ -193,18 +213,31 @@ class LatentInverter:
         size = tuple(int(x) for x in self.target.shape[-2:])
         start = np.zeros((self.batch, 7))
         for b in range(self.batch):
-            if c[b].sum() > 0:
+            if c[b].sum() > 0 and self._lmk_lines is not None:
+                # the jaw landmarks follow the silhouette: a second closed-form pass on the vertices the lines select
+                start[b] = pose_from_landmarks_contour(self._lmk_mean, (self._lmk_idx.cpu(), self._lmk_bary.cpu()),
+                                                       self._lmk_lines, self._lmk_axis, lm[b], size, c[b])[0]
+            elif c[b].sum() > 0:
                 start[b] = pose_from_landmarks(self._lmk_points, lm[b], size, c[b])
         self._lmk_target.copy_(torch.from_numpy(lm).float())
         self._lmk_conf.copy_(torch.from_numpy(c).float())
         self._pose_start.copy_(torch.from_numpy(start).float().view(self._pose_start.shape))
 
-    def _landmark_term(self, v):
+    def _landmark_term(self, v, n=None):
         """landmark_weight * rows [B] of the posed vertices (one launch each way on the device); keeps the fitted
         landmarks [B, L, 2] (pixel index coordinates of the target) as landmarks_fit: those of this forward pass, that is
-        of the mesh before the iteration's update (reconstruct projects fitted_mesh() for what it writes)."""
-        from .op.landmark import landmark_loss
+        of the mesh before the iteration's update (reconstruct projects fitted_mesh() for what it writes).  With
+        landmark_lines / landmark_vis the pose-aware term runs (the same two launches; n: the posed normals, read
+        detached) and contour_fit / landmark_visibility keep its selection and gate."""
+        from .op.landmark import landmark_loss, landmark_loss_ex
 
+        if self._lmk_dynamic:
+            self._lmk_rows, p, sel, gate = landmark_loss_ex(
+                v, self._lmk_idx, self._lmk_bary, self._lmk_target, self._lmk_conf, tuple(self.target.shape[-2:]),
+                self.landmark_beta, self.landmark_weight, normals=n.detach() if self._lmk_vis is not None else None,
+                lines=self._lmk_lines, axis=self._lmk_axis, vis=self._lmk_vis)
+            self.landmarks_fit, self.contour_fit, self.landmark_visibility = p.detach(), sel.detach(), gate.detach()
+            return
         self._lmk_rows, p = landmark_loss(v, self._lmk_idx, self._lmk_bary, self._lmk_target, self._lmk_conf,
                                           tuple(self.target.shape[-2:]), self.landmark_beta, self.landmark_weight)
         self.landmarks_fit = p.detach()
@@ -238,13 +271,13 @@ class LatentInverter:
                 v, n, tri, self._reg = self._shape_mesh()
                 mesh = (v, n, tri)
                 if self.with_landmarks:
-                    self._landmark_term(v)
+                    self._landmark_term(v, n)
             else:
                 mesh = self.posed_mesh()
             img, _, _ = self.g([self.w], mesh, input_is_latent=True, noise=self.noise)
         else:
             if self.with_landmarks:
-                self._landmark_term(self._shape_mesh()[0])
+                self._landmark_term(*self._shape_mesh()[:2])
             img, _ = self.g([self.w], input_is_latent=True, noise=self.noise)
         return img
 
@@ -314,7 +347,9 @@ class LatentInverter:
         moments and step counts.  An inverter built with landmarks also takes the new picture's `landmarks` and
         `landmark_conf` into its buffers and puts the pose at their closed-form start (landmarks None: every landmark
         missing, pose 0).  `run(steps)` then gives what a fresh inverter on `target` (and these landmarks) gives (same
-        mean latent, same noise), bit for bit, without a new warm-up or capture."""
+        mean latent, same noise), bit for bit, without a new warm-up or capture.  landmarks_fit, contour_fit and
+        landmark_visibility are outputs of the (possibly captured) iteration: they keep the previous picture's values
+        until the next step writes them."""
         target = target.detach()
         if not self.with_landmarks and (landmarks is not None or landmark_conf is not None):
             raise ValueError("LatentInverter.reset: this inverter was built without landmarks; the landmark term is "

@@ -2,6 +2,7 @@
 import collections
 import contextlib
 
+import numpy as np
 import torch
 
 from .. import _lib
@@ -9,6 +10,11 @@ from .. import _lib
 
 def is_device_tensor(t):
     return t.device.type == "cuda"
+
+
+def host_array(x):
+    """A tensor (of any device, detached) or anything array-like as a numpy array on the host."""
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
 
 def require_f32(t, name):

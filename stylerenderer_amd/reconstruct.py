@@ -3,7 +3,8 @@ for it):
 
     python -m stylerenderer_amd.reconstruct [--size 256] [--steps 400] [--lr] [--pose_lr] [--coeff_lr] [--shape_reg]
         [--bfm BFM.mat | --flame FLAME.{pkl,mat} | --facewarehouse FW.mat [--beta_shape X]] [--lpips-trunk VGG16.pth] [--batch N] [--gpu 0] [--seed S] [--out DIR]
-        [--lmk LANDMARKS.txt [--lmk_index FILE] [--lmk_weight 1.0] [--lmk_beta 1.0] [--lmk_contour 1.0]] CHECKPOINT IMAGE [IMAGE ...]
+        [--lmk LANDMARKS.txt [--lmk_index FILE] [--lmk_weight 1.0] [--lmk_beta 1.0] [--lmk_contour 1.0]
+         [--lmk_dynamic | --lmk_lines FILE] [--lmk_axis I,J] [--lmk_vis LO,HI]] CHECKPOINT IMAGE [IMAGE ...]
 
 For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with inversion.LatentInverter(fit_shape=True)
 — the W+ latent, a rigid pose and the 3DMM shape / expression coefficients are fitted together (op.morph on the device)
@@ -31,6 +32,15 @@ slide along the silhouette.  A picture the file does not list is fitted without 
 counted in the last line of the output.  <stem>.npz then also holds `landmarks` [L, 2] (the fit's, in pixel indices of the
 input picture), `landmarks_target` (the file's; NaN when not listed) and `lmk_error` (their mean distance in those
 pixels over the weighted landmarks).  --lmk_weight's default is a starting value, not tuned on a trained checkpoint.
+
+A detector puts the jaw landmarks on the visible silhouette and guesses landmarks that are turned out of sight.  With
+--lmk_dynamic (contour lines built from the model's mean shape, face_model.contour_lines) or --lmk_lines FILE (hand-made
+ones, an .npz of face_model.load_contour_lines) every jaw landmark slides along its line of candidate vertices to the one
+furthest out in the picture; --lmk_axis I,J names the two landmarks (27 and 8 of a 68-point set: nose bridge and chin)
+whose vertices span the face's up direction.  --lmk_vis LO,HI fades a landmark out as its normal turns away from the camera
+(normal z from HI down to LO; 0,0.2 is a starting value, untuned like --lmk_weight).  The pose start then takes two
+closed-form passes, and <stem>.npz also holds `contour_vertices` [C] (the vertex every line selected) and `lmk_visibility`
+[L] (the gate; 1 without --lmk_vis).  Without these options nothing changes.
 
 Images are PNG / JPG (PIL) or .npy in [-1, 1] (HWC or CHW), resized on the host.  The 3DMM is the Basel Face Model with
 --bfm (face_model.load_bfm), FLAME with --flame (face_model.load_flame, op.skin), the FaceWarehouse bilinear blendshape
@@ -95,7 +105,8 @@ class LandmarkGuide:
     """The landmark options of one run: the reader of --lmk, the embedding and the weights; `lookup` gives what the
     inverter takes for a picture."""
 
-    def __init__(self, lmk_file, face, index_file=None, weight=1.0, beta=1.0, contour=1.0):
+    def __init__(self, lmk_file, face, index_file=None, weight=1.0, beta=1.0, contour=1.0, dynamic=False, lines_file=None,
+                 axis=None, vis=None):
         from . import align
         from .face_model import landmark_embedding
 
@@ -117,6 +128,52 @@ class LandmarkGuide:
             raise SystemExit("reconstruct: --lmk_contour must not be negative")
         self.missing = 0
         self.seen = 0
+        self.dynamic = self._dynamic_args(face, dynamic, lines_file, axis, vis)
+
+    def _dynamic_args(self, face, dynamic, lines_file, axis, vis):
+        """LatentInverter's landmark_lines / landmark_axis / landmark_vis of --lmk_dynamic, --lmk_lines, --lmk_axis and
+        --lmk_vis; {} without them."""
+        from .face_model import contour_lines, landmark_vertices, load_contour_lines
+
+        out = {}
+        if vis is not None:
+            try:
+                lo, hi = (float(x) for x in vis.split(","))
+            except ValueError:
+                raise SystemExit("reconstruct: --lmk_vis takes LO,HI")
+            if not lo <= hi:
+                raise SystemExit("reconstruct: --lmk_vis needs LO <= HI")
+            out["landmark_vis"] = (lo, hi)
+        if not (dynamic or lines_file):
+            if axis is not None:
+                raise SystemExit("reconstruct: --lmk_axis needs --lmk_dynamic or --lmk_lines")
+            return out
+        model, tri = face
+        if axis is None and self.count != 68:
+            raise SystemExit("reconstruct: --lmk_axis I,J is required with %d landmarks (its default, 27,8, is of a "
+                             "68-point set)" % self.count)
+        try:
+            i, j = (27, 8) if axis is None else (int(x) for x in axis.split(","))
+        except ValueError:
+            raise SystemExit("reconstruct: --lmk_axis takes two landmark numbers I,J")
+        if not (0 <= i < self.count and 0 <= j < self.count and i != j):
+            raise SystemExit("reconstruct: --lmk_axis names two different landmarks in [0, %d)" % self.count)
+        main = landmark_vertices(self.embedding)
+        out["landmark_axis"] = (int(main[i]), int(main[j]))
+        with torch.no_grad():
+            dev = tri.device
+            v, n = model.mesh(torch.zeros(1, model.n_coeff, device=dev), torch.zeros(1, 7, device=dev), tri)[:2]
+        try:
+            if lines_file:
+                out["landmark_lines"] = load_contour_lines(lines_file, self.count, int(v.shape[1]))
+            else:
+                if self.count != 68:
+                    raise SystemExit("reconstruct: --lmk_dynamic takes landmarks 0-16 of a 68-point set for the jaw line; "
+                                     "with %d landmarks pass --lmk_lines FILE" % self.count)
+                out["landmark_lines"] = contour_lines(v[0].cpu(), self.embedding, normals=n[0].cpu())
+        except (ValueError, OSError) as e:
+            raise SystemExit("reconstruct: %s" % e)
+        return out
 
     def lookup(self, path, shape, size):
         """(landmarks [L, 2] in pixel indices of the size x size target, conf [L], the file's landmarks in the picture's
@@ -138,7 +195,7 @@ class LandmarkGuide:
 
     def inverter_args(self, landmarks, conf):
         return dict(landmarks=np.stack(landmarks), landmark_conf=np.stack(conf), landmark_weight=self.weight,
-                    landmark_beta=self.beta, landmark_embedding=self.embedding)
+                    landmark_beta=self.beta, landmark_embedding=self.embedding, **self.dynamic)
 
     def summary(self):
         return "landmarks: %d of %d images are not listed in %s and were fitted without them" % (
@@ -158,11 +215,25 @@ def landmark_outputs(inv, index, conf, listed, shape):
         v = inv.fitted_mesh()[0][index:index + 1]
         p = project(landmark_points(v, inv._lmk_idx, inv._lmk_bary), size)[0]
     fit = align.scale_landmarks(p.cpu().numpy().astype(np.float64), size, shape)
+    more = {}
+    if getattr(inv, "_lmk_dynamic", False):
+        # the pose-aware term: the jaw landmarks are those the contour lines select on the written mesh
+        from .op.landmark import landmark_dynamic_composite
+
+        with torch.no_grad():
+            n = inv.fitted_mesh()[1][index:index + 1]
+            zero = torch.zeros(1, p.shape[0], device=v.device)
+            _, pd, sel, gate = landmark_dynamic_composite(v, inv._lmk_idx, inv._lmk_bary, torch.zeros_like(p)[None], zero,
+                                                          size, normals=n, lines=inv._lmk_lines, axis=inv._lmk_axis,
+                                                          vis=inv._lmk_vis)
+        fit = align.scale_landmarks(pd[0].cpu().numpy().astype(np.float64), size, shape)
+        more = {"contour_vertices": sel[0].cpu().numpy().astype(np.int64),
+                "lmk_visibility": gate[0].cpu().numpy().astype(np.float64)}
     if listed is None:
-        return {"landmarks": fit, "landmarks_target": np.full_like(fit, np.nan), "lmk_error": np.float64(np.nan)}
+        return dict(more, landmarks=fit, landmarks_target=np.full_like(fit, np.nan), lmk_error=np.float64(np.nan))
     on = conf > 0
     err = np.sqrt(((fit - listed) ** 2).sum(1))[on].mean() if on.any() else np.nan
-    return {"landmarks": fit, "landmarks_target": np.asarray(listed, np.float64), "lmk_error": np.float64(err)}
+    return dict(more, landmarks=fit, landmarks_target=np.asarray(listed, np.float64), lmk_error=np.float64(err))
 
 
 def reconstruct(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr=0.01, shape_reg=0.0,
@@ -250,6 +321,18 @@ def main(argv=None):
     ap.add_argument("--lmk_beta", type=float, default=1.0, help="smooth-L1 threshold of the term in pixels [%(default)g]")
     ap.add_argument("--lmk_contour", type=float, default=1.0,
                     help="weight of landmarks 0-16 (the jaw line) of a 68-point set [%(default)g]")
+    how = ap.add_mutually_exclusive_group()
+    how.add_argument("--lmk_dynamic", action="store_true",
+                     help="the jaw landmarks (0-16 of a 68-point set) slide along the posed mesh's silhouette: contour "
+                          "lines built from the model's mean shape")
+    how.add_argument("--lmk_lines", default=None, metavar="FILE",
+                     help="hand-made contour lines: .npz with line_lmk, side, cand_off and cand")
+    ap.add_argument("--lmk_axis", default=None, metavar="I,J",
+                    help="with contour lines: the two landmarks whose vertices span the face's up direction [27,8 of a "
+                         "68-point set; required for other landmark counts]")
+    ap.add_argument("--lmk_vis", default=None, metavar="LO,HI",
+                    help="fade a landmark out as the z of its normal falls from HI to LO (turned away from the camera); off "
+                         "unless given; 0,0.2 is a starting value, untuned like --lmk_weight")
     ap.add_argument("--gpu", type=int, default=0, help="use gpu id")
     ap.add_argument("--seed", type=int, default=0, help="random seed (mean latent, noise)")
     ap.add_argument("--out", default="reconstruct", metavar="DIR", help="output directory [%(default)s]")
@@ -260,6 +343,8 @@ def main(argv=None):
         ap.error("--batch must be at least 1")
     if args.lmk_index and not args.lmk:
         ap.error("--lmk_index needs --lmk")
+    if (args.lmk_dynamic or args.lmk_lines or args.lmk_axis or args.lmk_vis) and not args.lmk:
+        ap.error("--lmk_dynamic, --lmk_lines, --lmk_axis and --lmk_vis need --lmk")
     torch.manual_seed(args.seed)
     if torch.cuda.is_available() and 0 <= args.gpu < torch.cuda.device_count():
         device = torch.device("cuda:%d" % args.gpu)
@@ -277,8 +362,8 @@ def main(argv=None):
     percept = percept.to(device)
     face = face_model(args.bfm, device, seed=args.seed, flame=args.flame, facewarehouse=args.facewarehouse,
                       beta_shape=args.beta_shape)
-    guide = (LandmarkGuide(args.lmk, face, args.lmk_index, args.lmk_weight, args.lmk_beta, args.lmk_contour)
-             if args.lmk else None)
+    guide = (LandmarkGuide(args.lmk, face, args.lmk_index, args.lmk_weight, args.lmk_beta, args.lmk_contour,
+                           args.lmk_dynamic, args.lmk_lines, args.lmk_axis, args.lmk_vis) if args.lmk else None)
     os.makedirs(args.out, exist_ok=True)
     results = []
 

@@ -1,0 +1,561 @@
+"""CPU: pose-aware landmarks — the composite definition of the sliding jaw contour and the visibility gate
+(op.landmark.landmark_dynamic_composite), face_model.contour_lines and its .npz, the two-pass pose start, the inverter with
+lines and `reconstruct --lmk_dynamic --lmk_vis`."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from stylerenderer_amd import align, face_model, synth, utils_3d
+from stylerenderer_amd.op import landmark
+from test_landmark_cpu import _inverter, composite_case, tiny_landmarks, tiny_problem
+from test_reconstruct_cpu import _env
+
+HW = (48, 64)
+
+
+# ---- a small case for the definition -----------------------------------------------------------------------------------
+def small_case(b=3, nv=12, dtype=torch.float64):
+    """composite_case's kind of input with normals and three contour lines: one of a single candidate, one in which a
+    vertex occurs twice, and one that shares a candidate with another line and with a static landmark."""
+    v = torch.from_numpy(0.8 * synth.det_uniform((b, nv, 3), 71)).to(dtype)
+    n = torch.from_numpy(synth.det_normal((b, nv, 3), 72)).to(dtype)
+    idx = torch.tensor([[0, 0, 0], [3, 3, 3], [3, 3, 3], [1, 2, 4], [5, 7, 8], [8, 8, 8], [9, 10, 11]], dtype=torch.int32)
+    bary = torch.tensor([[1, 0, 0], [1, 0, 0], [1, 0, 0], [0.5, 0.25, 0.25], [0.2, 0.3, 0.5], [1, 0, 0],
+                         [0.25, 0.5, 0.25]], dtype=torch.float32)
+    lines = (np.array([0, 5, 6]), np.array([1, -1, 1]), np.array([0, 1, 5, 9]),
+             np.array([0, 8, 6, 8, 3, 10, 6, 2, 11]))
+    axis = (4, 1)
+    target = torch.from_numpy(np.array(HW[::-1]) * (0.5 + 0.4 * synth.det_uniform((b, 7, 2), 73))).to(dtype)
+    conf = torch.from_numpy(np.abs(synth.det_uniform((b, 7), 74)) + 0.1).to(dtype)
+    conf[-1] = 0.0
+    return v, n, idx, bary, lines, axis, target, conf
+
+
+def score_gaps(v, lines, axis):
+    """For every sample and line, best minus second-best score among candidates at other coordinates (inf for a line of
+    one candidate), by a plain loop in float64."""
+    lm, side, off, cand = (np.asarray(a) for a in lines)
+    out = np.full((v.shape[0], len(lm)), np.inf)
+    for b in range(v.shape[0]):
+        vb = v[b].double().numpy()
+        a = vb[axis[0], :2] - vb[axis[1], :2]
+        na = np.hypot(a[0], a[1])
+        u = np.array([a[1], -a[0]]) / na if na >= 1e-6 else np.array([1.0, 0.0])
+        for c in range(len(lm)):
+            ids = cand[off[c]:off[c + 1]]
+            s = side[c] * (vb[ids, :2] @ u)
+            j = int(np.argmax(s))
+            others = [s[k] for k in range(len(ids)) if not np.array_equal(vb[ids[k], :2], vb[ids[j], :2])]
+            if others:
+                out[b, c] = s[j] - max(others)
+    return out
+
+
+def test_composite_is_the_written_definition():
+    v, n, idx, bary, lines, axis, target, conf = small_case()
+    lo, hi = -0.3, 0.4
+    rows, p, sel, gate = landmark.landmark_dynamic_composite(v, idx, bary, target, conf, HW, beta=0.5, weight=3.0,
+                                                             normals=n, lines=lines, axis=axis, vis=(lo, hi))
+    assert sel.dtype == torch.int32 and sel.shape == (3, 3) and gate.shape == (3, 7) and p.shape == (3, 7, 2)
+    lm, side, off, cand = lines
+    h, w = HW
+    seen_gate = set()
+    for b in range(v.shape[0]):
+        vb, nb = v[b].numpy(), n[b].numpy()
+        a = vb[axis[0], :2] - vb[axis[1], :2]
+        u = np.array([a[1], -a[0]]) / np.hypot(a[0], a[1])
+        chosen = {}
+        for c in range(3):
+            best, arg = -np.inf, None
+            for j in range(off[c], off[c + 1]):
+                s = side[c] * float(vb[cand[j], :2] @ u)
+                if s > best:                                             # strictly: the lowest position wins a tie
+                    best, arg = s, cand[j]
+            assert int(sel[b, c]) == arg
+            chosen[int(lm[c])] = arg
+        num = den = 0.0
+        for l in range(7):
+            if l in chosen:
+                P, g = vb[chosen[l]], 1.0
+            else:
+                P = sum(float(bary[l, k]) * vb[int(idx[l, k])] for k in range(3))
+                N = sum(float(bary[l, k]) * nb[int(idx[l, k])] for k in range(3))
+                m = N[2] / max(np.linalg.norm(N), 1e-12)
+                t = min(max((m - lo) / (hi - lo), 0.0), 1.0)
+                g = t * t * (3 - 2 * t)
+                seen_gate.add(0 if g == 0 else 2 if g == 1 else 1)
+            assert abs(float(gate[b, l]) - g) <= 1e-12
+            px, py = (1 + P[0]) * w / 2 - 0.5, (1 - P[1]) * h / 2 - 0.5
+            assert abs(px - float(p[b, l, 0])) <= 1e-12 and abs(py - float(p[b, l, 1])) <= 1e-12
+            cl = float(conf[b, l]) * g
+            for e in (px - float(target[b, l, 0]), py - float(target[b, l, 1])):
+                num += cl * (0.5 * e * e / 0.5 if abs(e) < 0.5 else abs(e) - 0.25)
+            den += cl
+        want = 3.0 * 2.0 / max(w, h) * num / max(den, landmark.TINY)
+        assert abs(float(rows[b]) - want) <= 1e-12 * max(1.0, abs(want))
+    assert seen_gate == {0, 1, 2}                                        # closed, partly open and open gates all occur
+    # the degenerate axis: u = (1, 0)
+    _, _, sel0, _ = landmark.landmark_dynamic_composite(v, idx, bary, target, conf, HW, lines=lines, axis=(4, 4))
+    for b in range(3):
+        for c in range(3):
+            ids = cand[off[c]:off[c + 1]]
+            assert int(sel0[b, c]) == ids[int(np.argmax(side[c] * v[b, ids, 0].numpy()))]
+    # hi == lo: a step at m > lo
+    _, _, _, step = landmark.landmark_dynamic_composite(v, idx, bary, target, conf, HW, normals=n, vis=(0.1, 0.1))
+    N = landmark.landmark_points(n, idx, bary)
+    assert torch.equal(step, (N[..., 2] / N.norm(dim=-1) > 0.1).double()) and 0 < float(step.mean()) < 1
+
+
+def test_composite_passes_gradcheck_and_gradgradcheck():
+    v, n, idx, bary, lines, axis, target, conf = small_case()
+    assert score_gaps(v, lines, axis).min() >= 1e-3
+    v.requires_grad_(True)
+    n.requires_grad_(True)
+    f = lambda x: landmark.landmark_dynamic_composite(x, idx, bary, target, conf, HW, 1.0, 1.0, n, lines, axis,      # noqa: E731
+                                                      (-0.3, 0.4))[0]
+    assert torch.autograd.gradcheck(f, (v,), eps=1e-6, atol=1e-8)
+    assert torch.autograd.gradgradcheck(f, (v,), eps=1e-6, atol=1e-8)
+    # sel and gate are constants: nothing reaches the normals, and landmark_loss on host float64 is this composite
+    rows, p = landmark.landmark_loss(v, idx, bary, target, conf, HW, normals=n, lines=lines, axis=axis, vis=(-0.3, 0.4))
+    want = landmark.landmark_dynamic_composite(v, idx, bary, target, conf, HW, 1.0, 1.0, n, lines, axis, (-0.3, 0.4))
+    assert torch.equal(rows, want[0]) and torch.equal(p, want[1])
+    gv, gn = torch.autograd.grad(rows.sum(), (v, n), allow_unused=True)
+    assert gn is None and float(gv.abs().max()) > 0
+    ex = landmark.landmark_loss_ex(v, idx, bary, target, conf, HW, normals=n, lines=lines, axis=axis, vis=(-0.3, 0.4))
+    assert len(ex) == 4 and torch.equal(ex[2], want[2]) and torch.equal(ex[3], want[3])
+    # the gradient of a contour landmark lands on the selected vertex alone: vertex 0 is line 0's only candidate
+    # (landmark 0); vertex 9 is landmark 6's static corner and no candidate of its line
+    assert float(gv[0, 0].abs().max()) > 0 and float(gv[0, 9].abs().max()) == 0.0
+
+
+def test_without_lines_and_gate_it_is_the_static_composite_exactly():
+    v, idx, bary, target, conf, hw = composite_case()
+    empty = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(1, np.int64), np.zeros(0, np.int64))
+    want = landmark.landmark_composite(v, idx, bary, target, conf, hw, 0.5, 3.0)
+    for lines, axis in ((None, None), (empty, (0, 1))):
+        rows, p, sel, gate = landmark.landmark_dynamic_composite(v, idx, bary, target, conf, hw, 0.5, 3.0, lines=lines,
+                                                                 axis=axis)
+        assert torch.equal(rows, want[0]) and torch.equal(p, want[1])
+        assert sel.shape == (v.shape[0], 0) and bool((gate == 1).all())
+    # all four None: landmark_loss's present path
+    got = landmark.landmark_loss(v, idx, bary, target, conf, hw, 0.5, 3.0)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+
+
+def test_refusals():
+    v, n, idx, bary, lines, axis, target, conf = small_case()
+    call = lambda **kw: landmark.landmark_loss(v, idx, bary, target, conf, HW, **kw)            # noqa: E731
+    lm, side, off, cand = lines
+    with pytest.raises(ValueError, match="normals"):
+        call(vis=(0.0, 0.2))
+    with pytest.raises(ValueError, match="axis"):
+        call(lines=lines)
+    with pytest.raises(ValueError, match="more than one"):
+        call(lines=(np.array([0, 5, 0]), side, off, cand), axis=axis)
+    with pytest.raises(ValueError, match="empty"):
+        call(lines=(lm, side, np.array([0, 1, 1, 9]), cand), axis=axis)
+    with pytest.raises(ValueError, match="lo <= hi"):
+        call(normals=n, vis=(0.3, 0.2))
+    with pytest.raises(ValueError, match="candidate"):
+        call(lines=(lm, side, off, np.where(cand == 11, 12, cand)), axis=axis)
+    with pytest.raises(ValueError, match="axis"):
+        call(lines=lines, axis=(0, 12))
+    with pytest.raises(ValueError, match="landmark"):
+        call(lines=(np.array([0, 5, 7]), side, off, cand), axis=axis)
+    with pytest.raises(ValueError, match="side"):
+        call(lines=(lm, np.array([1, 0, 1]), off, cand), axis=axis)
+    # the kernels' lists check the same things (host tensors: built without a device)
+    with pytest.raises(ValueError, match="candidate"):
+        landmark.dynamic_lists(idx, bary, (lm, side, off, np.where(cand == 11, 12, cand)), axis, 12)
+    with pytest.raises(ValueError, match="axis"):
+        landmark.dynamic_lists(idx, bary, lines, (12, 0), 12)
+    t = landmark.dynamic_lists(idx, bary, lines, axis, 12)
+    assert t["lmk_line"].tolist() == [0, -1, -1, -1, -1, 1, 2] and t["n_lines"] == 3
+    # static list without the contour landmarks 0, 5, 6: vertices 0, 9, 10, 11 carry nothing, vertex 8 only landmark 4
+    assert t["off"].tolist() == [0, 0, 1, 2, 4, 5, 6, 6, 7, 8, 8, 8, 8] and t["l"].tolist() == [3, 3, 1, 2, 3, 4, 4, 4]
+    # vertex -> (line, landmark): vertex 8 once for line 1 although it is listed twice; vertex 6 in lines 1 and 2
+    pairs = {(i, int(c), int(l)) for i in range(12)
+             for c, l in zip(t["line_c"][t["line_off"][i]:t["line_off"][i + 1]], t["line_l"][t["line_off"][i]:t["line_off"][i + 1]])}
+    assert pairs == {(0, 0, 0), (8, 1, 5), (6, 1, 5), (3, 1, 5), (10, 2, 6), (6, 2, 6), (2, 2, 6), (11, 2, 6)}
+    assert t["line_c"][t["line_off"][6]:t["line_off"][7]].tolist() == [1, 2]                     # ascending line
+    assert landmark.dynamic_lists(idx, bary, lines, axis, 12) is t                               # cached
+
+
+# ---- a half-ellipsoid head --------------------------------------------------------------------------------------------
+RADII = (0.6, 0.8, 0.55)
+N_LAT, N_LON = 31, 31
+
+
+def head():
+    """A half ellipsoid facing +z on a 29 x 31 UV grid (its rim, z = 0, is the jaw line and the ears), outward normals,
+    and 37 landmarks: 0-16 down the rim at +x, over the chin and up the rim at -x; 17-36 inside the face.  Returns
+    (v [nv, 3], normals [nv, 3], (idx, bary), axis) in float64 / host tensors."""
+    lat = np.pi * np.arange(1, N_LAT - 1) / (N_LAT - 1)
+    lon = np.pi * np.arange(N_LON) / (N_LON - 1)
+    st, ct = np.sin(lat)[:, None], np.cos(lat)[:, None]
+    v = np.stack([RADII[0] * st * np.cos(lon)[None], RADII[1] * ct * np.ones_like(lon)[None],
+                  RADII[2] * st * np.sin(lon)[None]], -1).reshape(-1, 3)
+    v[np.abs(v) < 1e-15] = 0.0
+    nrm = v / np.array(RADII) ** 2
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    vid = lambda i, j: i * N_LON + j                                                             # noqa: E731
+    rows_right = [12, 14, 16, 18, 20, 22, 24, 26]                       # going down, towards the chin
+    verts = [vid(i, 0) for i in rows_right] + [vid(28, 15)] + [vid(i, N_LON - 1) for i in rows_right[::-1]]
+    inner = [vid(i, j) for i in (6, 11, 16, 21) for j in (5, 10, 15, 20, 25)]
+    emb = face_model.landmark_embedding(np.array(verts + inner))
+    return v, nrm, emb, (vid(2, 15), vid(28, 15))
+
+
+def posed(v, pose):
+    p = torch.as_tensor(pose, dtype=torch.float64)
+    return (torch.as_tensor(v) @ (torch.exp(p[6]) * utils_3d.euler_mat(p[:3], "yxz")) + p[3:6]).view(1, -1, 3)
+
+
+def head_lines():
+    v, nrm, emb, axis = head()
+    return face_model.contour_lines(v, emb, normals=nrm)
+
+
+def positions(sel, lines):
+    lm, side, off, cand = (np.asarray(t) for t in lines)
+    return [list(cand[off[c]:off[c + 1]]).index(int(sel[c])) for c in range(len(lm))]
+
+
+def test_contour_lines_of_the_head():
+    v, nrm, emb, axis = head()
+    lm, side, off, cand = (t.numpy() for t in face_model.contour_lines(v, emb, normals=nrm))
+    assert lm.tolist() == [0, 1, 2, 3, 4, 5, 6, 7, 9, 10, 11, 12, 13, 14, 15, 16]        # the chin, 8, gets no line
+    assert side.tolist() == [1] * 8 + [-1] * 8
+    main = face_model.landmark_vertices(emb)
+    pts = v[main]
+    for c, l in enumerate(lm):
+        ids = cand[off[c]:off[c + 1]]
+        assert ids[0] == main[l] and len(set(ids)) == len(ids) and 1 < len(ids) <= 64
+        sx = side[c] * v[ids, 0]
+        assert np.all(np.diff(sx) <= 0)                                  # descending side x, the static vertex first
+        assert np.all(sx >= 0.5 * side[c] * pts[l, 0] - 1e-12) and np.all(nrm[ids[1:], 2] > 0)
+        k = list(range(17)).index(l)
+        near = [abs(v[main[j], 1] - pts[l, 1]) for j in (k - 1, k + 1) if 0 <= j < 17]
+        assert np.all(np.abs(v[ids, 1] - pts[l, 1]) <= 0.5 * max(near) + 1e-12)
+    # the cap keeps the head of the list; inner = 1 leaves the static vertex (and whatever shares its x)
+    capped = face_model.contour_lines(v, emb, normals=nrm, max_candidates=3)
+    for c in range(len(lm)):
+        assert capped[3][capped[2][c]:capped[2][c + 1]].tolist() == cand[off[c]:off[c] + 3].tolist()
+    tight = face_model.contour_lines(v, emb, normals=nrm, inner=1.0)
+    assert tight[0].tolist() == lm.tolist() and all(int(tight[3][tight[2][c]]) == main[l] for c, l in enumerate(lm))
+    # a barycentric landmark: its static vertex is the one of its largest weight
+    idx, bary = (t.clone() for t in emb)
+    idx[3] = torch.tensor([main[3] + 1, main[3], main[3] + N_LON], dtype=torch.int32)
+    bary[3] = torch.tensor([0.25, 0.5, 0.25])
+    alt = face_model.contour_lines(v, (idx, bary), normals=nrm)
+    assert int(alt[0][3]) == 3 and int(alt[3][alt[2][3]]) == main[3]
+    # normals from the triangles give the same lines; a vertex turned away is no candidate
+    tri = np.array([(i * N_LON + j, i * N_LON + j + 1, (i + 1) * N_LON + j) for i in range(N_LAT - 3)
+                    for j in range(N_LON - 1)] + [((i + 1) * N_LON + j, i * N_LON + j + 1, (i + 1) * N_LON + j + 1)
+                                                  for i in range(N_LAT - 3) for j in range(N_LON - 1)])
+    tn = utils_3d.mesh_point_normal(torch.from_numpy(v)[None], torch.from_numpy(tri))[0].numpy()
+    assert float((tn * nrm).sum(1).min()) > 0.9                          # cross(b - a, c - a) of this winding: outward
+    away = nrm.copy()
+    away[cand[off[0] + 1]] *= -1
+    assert cand[off[0] + 1] not in face_model.contour_lines(v, emb, normals=away)[3][off[0]:off[1]].tolist()
+    with pytest.raises(ValueError):
+        face_model.contour_lines(v[:800], emb)                           # a landmark's vertex is not in the mesh
+    with pytest.raises(ValueError):
+        face_model.contour_lines(v, emb, contour=[0, 1, 1])
+
+
+def test_normals_of_the_synthetic_model_point_outward():
+    """What the gate and contour_lines' normal test rely on (Normal orientation): on the synthetic model,
+    wound as the rasterizer keeps it, mesh_point_normal points out of the surface, so z > 0 is the half that faces the camera."""
+    v, tri = synth.face_sized_mesh()
+    n = utils_3d.mesh_point_normal(torch.from_numpy(v).double()[None], torch.from_numpy(tri))[0].numpy()
+    outward = v.astype(np.float64) / np.array([0.8, 0.95, 0.6]) ** 2     # the ellipsoid's analytic normal direction
+    assert float((n * outward).sum(1).min()) > 0
+    off_rim = np.abs(v[:, 2]) > 1e-6
+    assert bool(off_rim.sum() > 0.9 * len(v)) and np.array_equal(n[off_rim, 2] > 0, v[off_rim, 2] > 0)
+
+
+def test_contour_lines_npz_round_trips_and_refuses_bad_files(tmp_path):
+    v, nrm, emb, axis = head()
+    lines = face_model.contour_lines(v, emb, normals=nrm)
+    path = str(tmp_path / "lines.npz")
+    face_model.save_contour_lines(path, lines)
+    back = face_model.load_contour_lines(path, 37, len(v))
+    assert all(a.dtype == torch.int32 and torch.equal(a, b) for a, b in zip(back, lines))
+    lm, side, off, cand = (t.numpy() for t in lines)
+
+    def refused(match, n_l=37, nv=len(v), **change):
+        np.savez(path, **dict(dict(line_lmk=lm, side=side, cand_off=off, cand=cand), **change))
+        with pytest.raises(ValueError, match=match):
+            face_model.load_contour_lines(path, n_l, nv)
+
+    refused("candidate", nv=int(cand.max()))                            # index out of range
+    refused("landmark", n_l=16)
+    refused("more than one", line_lmk=np.where(lm == 1, 0, lm))          # duplicate landmark
+    refused("empty", cand_off=np.concatenate(([0, 0], off[2:])))         # empty line
+    np.savez(path, line_lmk=lm, side=side, cand=cand)
+    with pytest.raises(ValueError, match="cand_off"):
+        face_model.load_contour_lines(path)
+
+
+YAWS = (0.0, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8)
+
+
+@pytest.mark.parametrize("sign", [1, -1])
+def test_turning_the_head_slides_the_far_side_and_a_roll_changes_nothing(sign):
+    v, nrm, emb, axis = head()
+    lines = head_lines()
+    side = lines[1].numpy()
+    idx, bary = emb
+    target, conf = torch.zeros(1, 37, 2, dtype=torch.float64), torch.ones(1, 37, dtype=torch.float64)
+    before = None
+    for yaw in YAWS:
+        vp = posed(v, (sign * yaw, 0, 0, 0, 0, 0, 0))
+        sel = landmark.landmark_dynamic_composite(vp, idx, bary.double(), target, conf, HW, lines=lines, axis=axis)[2][0]
+        pos = np.array(positions(sel, lines))
+        if yaw == 0.0:
+            assert not pos.any()
+        else:
+            # the far side: the lines whose rim vertex (candidate 0) has turned behind the face
+            far = np.array([float(vp[0, int(lines[3][lines[2][c]]), 2]) < 0 for c in range(len(side))])
+            assert far.sum() == 8 and len(set(side[far])) == 1
+            assert not pos[~far].any()                                    # the near side keeps candidate 0
+            assert np.all(pos[far] >= before[far])                        # the far side never slides back
+            if yaw == 0.8:
+                assert np.all(pos[far] > 0)
+            # an in-plane roll of the whole head (about the picture's centre, with a shift): the same vertices
+            for roll in (0.4, -1.1):
+                c_, s_ = np.cos(roll), np.sin(roll)
+                rz = torch.tensor([[c_, s_, 0], [-s_, c_, 0], [0, 0, 1]], dtype=torch.float64)
+                rolled = vp @ rz + torch.tensor([0.05, -0.1, 0.0], dtype=torch.float64)
+                sel_r = landmark.landmark_dynamic_composite(rolled, idx, bary.double(), target, conf, HW, lines=lines,
+                                                            axis=axis)[2][0]
+                assert torch.equal(sel_r, sel)
+        before = pos
+
+
+def test_the_gate():
+    v, idx, bary, target, conf, hw = composite_case()
+    conf = conf.clone()
+    conf[-1] = conf[0].flip(0)                                           # (no zero-confidence row here)
+    nv, lo, hi = v.shape[1], 0.0, 0.2
+    unit = lambda m: [np.sqrt(1 - m * m), 0.0, m]                         # noqa: E731
+    # landmark 0 (vertex 0) is turned away, m = -0.3 < lo; landmark 5 (vertex 8) lies between; all others face the camera
+    n = torch.tensor([unit(0.9)] * nv, dtype=torch.float64).repeat(v.shape[0], 1, 1)
+    n[:, 0] = torch.tensor(unit(-0.3), dtype=torch.float64)
+    n[:, 8] = torch.tensor(unit(0.1), dtype=torch.float64)
+    n[:, 5], n[:, 7] = n[:, 8], n[:, 8]                                  # (landmark 4 = vertices 5, 7, 8: the same normal)
+    v.requires_grad_(True)
+    rows, p, _, gate = landmark.landmark_dynamic_composite(v, idx, bary, target, conf, hw, normals=n, vis=(lo, hi))
+    assert gate[0].tolist() == [0.0, 1.0, 1.0, 1.0, 0.5, 0.5]
+    (g,) = torch.autograd.grad(rows.sum(), v)
+    assert float(g[:, 0].abs().max()) == 0.0 and float(g[:, 3].abs().max()) > 0        # hidden: no pull at all
+    # the same as the static term on confidences multiplied by the gate: normalised by sum c', hidden ones do not count
+    want, _ = landmark.landmark_composite(v, idx, bary, target, conf * gate, hw)
+    assert torch.equal(rows, want)
+    moved = target.clone()
+    moved[:, 0] += 7.0                                                   # the hidden landmark's target does not matter
+    assert torch.equal(landmark.landmark_dynamic_composite(v, idx, bary, moved, conf, hw, normals=n, vis=(lo, hi))[0], rows)
+    # every landmark above hi: exactly the term without the gate
+    up = torch.tensor([unit(0.3)] * nv, dtype=torch.float64).repeat(v.shape[0], 1, 1)
+    open_rows, _, _, open_gate = landmark.landmark_dynamic_composite(v, idx, bary, target, conf, hw, normals=up, vis=(lo, hi))
+    plain, _ = landmark.landmark_composite(v, idx, bary, target, conf, hw)
+    assert bool((open_gate == 1).all()) and torch.equal(open_rows, plain)
+    (g_open,), (g_plain,) = torch.autograd.grad(open_rows.sum(), v), torch.autograd.grad(plain.sum(), v)
+    assert torch.equal(g_open, g_plain)
+    # every gate closed: rows 0, gradient 0
+    shut, _, _, shut_gate = landmark.landmark_dynamic_composite(v, idx, bary, target, conf, hw, normals=-up, vis=(lo, hi))
+    (g_shut,) = torch.autograd.grad(shut.sum(), v)
+    assert bool((shut_gate == 0).all()) and bool((shut == 0).all()) and bool((g_shut == 0).all())
+    # contour landmarks are not gated
+    lines = (np.array([0]), np.array([1]), np.array([0, 2]), np.array([0, 6]))
+    _, _, _, gl = landmark.landmark_dynamic_composite(v, idx, bary, target, conf, hw, normals=n, lines=lines, axis=(1, 2),
+                                                      vis=(lo, hi))
+    assert gl[0].tolist() == [1.0, 1.0, 1.0, 1.0, 0.5, 0.5]
+
+
+# ---- the pose bias the feature removes ---------------------------------------------------------------------------------
+def fit_pose(v, emb, target, start, lines, axis, steps=400, lr=0.01):
+    idx, bary = emb[0], emb[1].double()
+    pose = torch.tensor(start, dtype=torch.float64, requires_grad=True)
+    opt = torch.optim.Adam([pose], lr=lr)
+    conf = torch.ones(1, idx.shape[0], dtype=torch.float64)
+    v0 = torch.from_numpy(v)
+    for _ in range(steps):
+        opt.zero_grad()
+        vp = (v0 @ (torch.exp(pose[6]) * utils_3d.euler_mat(pose[:3], "yxz")) + pose[3:6]).view(1, -1, 3)
+        if lines is None:
+            rows = landmark.landmark_composite(vp, idx, bary, target, conf, 256)[0]
+        else:
+            rows = landmark.landmark_dynamic_composite(vp, idx, bary, target, conf, 256, lines=lines, axis=axis)[0]
+        rows.sum().backward()
+        opt.step()
+    return pose.detach().numpy()
+
+
+def test_silhouette_landmarks_bias_the_static_fit_and_not_the_dynamic_one():
+    """The head at yaw 0.6 seen by a detector that follows the silhouette (the composite's own p with lines on).  In this
+    float64 run: yaw error of the one-pass start 0.123 rad and of the two-pass start 0.004436 rad; after 400 Adam steps on
+    the pose alone 0.1239 rad with the static term and 3.405e-12 rad with the lines, a ratio far beyond 10."""
+    v, nrm, emb, axis = head()
+    lines = head_lines()
+    true = np.array([0.6, -0.1, 0.05, 0.03, -0.02, 0.0, -0.1])
+    conf = torch.ones(1, 37, dtype=torch.float64)
+    with torch.no_grad():
+        _, target, sel, _ = landmark.landmark_dynamic_composite(posed(v, true), emb[0], emb[1].double(),
+                                                                torch.zeros(1, 37, 2, dtype=torch.float64), conf, 256,
+                                                                lines=lines, axis=axis)
+    assert sum(p > 0 for p in positions(sel[0], lines)) >= 6             # the far side has left its rim
+    pts = v[face_model.landmark_vertices(emb)]
+    one = align.pose_from_landmarks(pts, target[0].numpy(), 256)
+    two, sel2 = align.pose_from_landmarks_contour(v, emb, lines, axis, target[0].numpy(), 256)
+    assert two.shape == (7,) and sel2.shape == (16,) and two[5] == 0.0
+    err_one, err_two = abs(one[0] - true[0]), abs(two[0] - true[0])
+    static = fit_pose(v, emb, target, one, None, None)
+    dynamic = fit_pose(v, emb, target, two, lines, axis)
+    err_static, err_dynamic = abs(static[0] - true[0]), abs(dynamic[0] - true[0])
+    print("yaw error: one-pass start %.4g, two-pass start %.4g, static fit %.4g, dynamic fit %.4g rad"
+          % (err_one, err_two, err_static, err_dynamic))
+    assert err_two < err_one
+    assert err_static > 0.02 and err_dynamic < err_static / 2
+    # pose_from_landmarks itself is as before, and without lines the two-pass start is the one-pass start
+    none = align.pose_from_landmarks_contour(v, emb, None, None, target[0].numpy(), 256)
+    assert np.array_equal(none[0], one) and none[1].shape == (0,)
+
+
+# ---- the inverter -----------------------------------------------------------------------------------------------------
+def tiny_lines(face, emb):
+    """Hand-made lines on the tiny face: landmarks 0 and 9 slide over a few vertices each; the anchors are the main
+    vertices of landmarks 2 and 7."""
+    main = face_model.landmark_vertices(emb)
+    nv = face[0].fc.bias.numel() // 3
+    a = [int(main[0])] + [i for i in (5, 17, 30, 44) if i != main[0]]
+    b = [int(main[9])] + [i for i in (nv - 6, nv - 19, 30, nv - 41) if i != main[9]]
+    lines = (np.array([0, 9]), np.array([1, -1]), np.array([0, len(a), len(a) + len(b)]), np.array(a + b))
+    return lines, (int(main[2]), int(main[7]))
+
+
+def _state(inv, hist):
+    return [hist] + [t.detach().clone() for t in (inv.w, inv.pose, inv.coeff, inv.landmarks_fit)]
+
+
+def test_inverter_without_the_new_arguments_is_bit_identical_and_empty_lines_change_nothing():
+    problem = tiny_problem()
+    emb, lmk = tiny_landmarks(problem[2])
+    empty = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(1, np.int64), np.zeros(0, np.int64))
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        runs = []
+        for extra in ({}, {"landmark_lines": None, "landmark_axis": None, "landmark_vis": None},
+                      {"landmark_lines": empty, "landmark_axis": (0, 1)}):
+            inv = _inverter(problem, landmarks=lmk, landmark_embedding=emb, landmark_weight=2.0, **extra)
+            runs.append(_state(inv, inv.run(5)))
+            if "landmark_axis" in extra and extra["landmark_axis"]:
+                assert inv.contour_fit.shape == (1, 0) and bool((inv.landmark_visibility == 1).all())
+            else:
+                assert inv.contour_fit is None and inv.landmark_visibility is None and not inv._lmk_dynamic
+        # and without landmarks the new keywords are not looked at, like the old ones
+        plain = [_inverter(problem, **kw) for kw in ({}, {"landmark_lines": empty, "landmark_vis": (0.0, 0.2)})]
+        hist = [inv.run(4) for inv in plain]
+    finally:
+        torch.set_num_threads(threads)
+    for other in runs[1:]:
+        for a, b in zip(runs[0], other):
+            assert torch.equal(a, b)
+    assert torch.equal(hist[0], hist[1]) and torch.equal(plain[0].w, plain[1].w) and not plain[1].with_landmarks
+
+
+def test_inverter_with_lines_and_gate_batched_reset_equals_fresh():
+    g, mesh, face, noise, target = tiny_problem()
+    emb, lmk_a = tiny_landmarks(face)
+    _, lmk_b = tiny_landmarks(face, pose=(-0.3, 0.2, 0.0, -0.05, 0.04, 0.0, -0.1))
+    lines, axis = tiny_lines(face, emb)
+    dyn = dict(landmark_embedding=emb, landmark_lines=lines, landmark_axis=axis, landmark_vis=(0.0, 0.2))
+    targets = torch.cat([target, target.flip(3)], 0).contiguous()
+    first = dict(landmarks=np.stack([lmk_a, lmk_b]), landmark_conf=np.ones((2, 10)))
+    second = dict(landmarks=np.stack([lmk_b, lmk_a]), landmark_conf=np.stack([np.ones(10), np.zeros(10)]))
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        inv = _inverter((g, mesh, face, noise, targets), **dyn, **first)
+        assert inv.run(3).shape == (3, 2)
+        assert inv.contour_fit.shape == (2, 2) and inv.contour_fit.dtype == torch.int32
+        assert inv.landmark_visibility.shape == (2, 10) and not inv.landmark_visibility.requires_grad
+        cand = set(lines[3].tolist())
+        assert all(int(i) in cand for i in inv.contour_fit.reshape(-1))
+        assert bool((inv.landmark_visibility[:, [0, 9]] == 1).all())       # contour landmarks are not gated
+        inv.reset(targets.flip(0).contiguous(), **second)
+        assert float(inv.pose.detach()[1].abs().max()) == 0.0 and float(inv.pose.detach()[0].abs().max()) > 0
+        got = _state(inv, inv.run(3)) + [inv.contour_fit.clone(), inv.landmark_visibility.clone()]
+        fresh = _inverter((g, mesh, face, noise, targets.flip(0).contiguous()), **dyn, **second)
+        want = _state(fresh, fresh.run(3)) + [fresh.contour_fit.clone(), fresh.landmark_visibility.clone()]
+        static = _inverter((g, mesh, face, noise, targets.flip(0).contiguous()), landmark_embedding=emb, **second)
+        other = _state(static, static.run(3))
+    finally:
+        torch.set_num_threads(threads)
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+    assert not torch.equal(got[0][:, 0], other[0][:, 0])                   # the term is another one with lines and gate
+    with pytest.raises(ValueError, match="landmark_axis"):
+        _inverter((g, mesh, face, noise, targets), landmark_embedding=emb, landmark_lines=lines, **first)
+    with pytest.raises(ValueError, match="lo <= hi"):
+        _inverter((g, mesh, face, noise, targets), landmark_embedding=emb, landmark_vis=(0.3, 0.1), **first)
+
+
+# ---- command line ------------------------------------------------------------------------------------------------------
+def test_reconstruct_cli_with_dynamic_landmarks(tmp_path):
+    from PIL import Image
+
+    from stylerenderer_amd import model
+
+    g = model.GeneratorWithMap(16, 512, 8)
+    synth.fill_state_dict(g.state_dict(), salt=5)
+    ckpt = str(tmp_path / "g.pt")
+    torch.save({"g_ema": g.state_dict()}, ckpt)
+    img = str(tmp_path / "face_a.png")
+    Image.fromarray((127.5 * (synth.det_uniform((24, 32, 3), 9) + 1)).clip(0, 255).astype(np.uint8)).save(img)
+    # 68 landmarks on the synthetic model's ellipsoid (130 rings of 192 vertices; ring r, column k is 1 + 192 r + k; z > 0
+    # for columns 1-95): 0-16 round the silhouette at z = 0 from +x over the bottom to -x, 27 high and 8 low on the middle
+    # column, the others spread over the front
+    v0, _ = synth.face_sized_mesh()
+    vid = lambda r, k: 1 + 192 * r + k                                                            # noqa: E731
+    jaw = [vid(r, 0) for r in range(60, 124, 8)] + [vid(128, 48)] + [vid(r, 96) for r in range(116, 52, -8)]
+    rest = [vid(20 + 2 * (k % 40), 8 + (k * 7) % 80) for k in range(51)]
+    verts = np.array(jaw + rest)
+    verts[27], verts[8] = vid(10, 48), vid(128, 48)
+    assert len(verts) == 68 and np.all(v0[verts[17:], 2] > 0) and abs(v0[verts[8], 0]) < 1e-3
+    index = str(tmp_path / "index.txt")
+    np.savetxt(index, verts, fmt="%d")
+    pose = torch.tensor([0.3, -0.1, 0.05, 0.05, -0.04, 0.0, -0.1], dtype=torch.float64)
+    vp = torch.from_numpy(v0[verts].astype(np.float64)) @ (torch.exp(pose[6]) * utils_3d.euler_mat(pose[:3], "yxz")) + pose[3:6]
+    lmk = align.scale_landmarks(landmark.project(vp, (16, 16)).numpy(), (16, 16), (24, 32))
+    lmk_file = str(tmp_path / "lmk.txt")
+    with open(lmk_file, "w") as f:
+        f.write("face_a.png " + " ".join("%.6f" % x for x in lmk.reshape(-1)) + "\n")
+    base = [sys.executable, "-m", "stylerenderer_amd.reconstruct", "--size", "16", "--steps", "3", "--n_mean_latent", "64",
+            "--lmk", lmk_file, "--lmk_index", index]
+    out = str(tmp_path / "dyn")
+    res = subprocess.run(base + ["--lmk_dynamic", "--lmk_vis", "0,0.2", "--out", out, ckpt, img], env=_env(),
+                         cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
+    assert res.returncode == 0, res.stderr[-3000:]
+    r = np.load(os.path.join(out, "face_a.npz"))
+    assert r["contour_vertices"].shape == (16,) and r["lmk_visibility"].shape == (68,)
+    assert np.all((r["lmk_visibility"] >= 0) & (r["lmk_visibility"] <= 1)) and np.all(r["lmk_visibility"][:8] == 1)
+    assert r["landmarks"].shape == (68, 2) and np.isfinite(r["lmk_error"]) and np.isfinite(r["loss"]).all()
+    out2 = str(tmp_path / "static")
+    res = subprocess.run(base + ["--out", out2, ckpt, img], env=_env(), cwd=str(tmp_path), capture_output=True, text=True,
+                         timeout=900)
+    assert res.returncode == 0, res.stderr[-3000:]
+    assert sorted(np.load(os.path.join(out2, "face_a.npz")).files) == sorted(
+        ["w", "coeff", "pose", "loss", "landmarks", "landmarks_target", "lmk_error"])
+    assert sorted(r.files) == sorted(["w", "coeff", "pose", "loss", "landmarks", "landmarks_target", "lmk_error",
+                                      "contour_vertices", "lmk_visibility"])
+    # options that cannot work say why
+    res = subprocess.run(base[:-4] + ["--lmk_vis", "0,0.2", "--out", out2, ckpt, img], env=_env(), cwd=str(tmp_path),
+                         capture_output=True, text=True, timeout=900)
+    assert res.returncode != 0 and "--lmk" in res.stderr
