@@ -870,6 +870,31 @@ int sr_landmark_dyn_bwd(float* gv, const float* g, const float* g_rows, int64_t 
                         const int32_t* line_c, const int32_t* line_l, int64_t B, int64_t L, int64_t C, int64_t nv,
                         int64_t H, int64_t W, int accumulate, sr_stream_t stream);
 
+/* Region-weighted image loss of face reconstruction (definition: stylerenderer_amd/op/region.py), csrc/region.hip.
+ * sr_region_fill: out uint8 [B, 1, H, W] = 1 where pixel (x, y) lies in one of the sample's T closed integer triangles,
+ *   else 0.  points int32 [B, P, 2] (x, y; |coordinate| <= 2^20, the caller's to check), tris int32 [T, 3]
+ *   (tri_bstride 0: shared) or [B, T, 3] (tri_bstride 3 T) of indices into the sample's points; a triangle with an index
+ *   outside [0, P) covers nothing.  In the triangle: inside its bounding box and the three edge functions
+ *   cross(b - a, p - a), cross(c - b, p - b), cross(a - c, p - c) (int64) all >= 0 or all <= 0: either winding, a
+ *   degenerate triangle is its segment or point.  T = 0 gives zeros.  B <= 65535, H, W <= 2^20.
+ * sr_region_grow: out uint8 [N, H, W] (not in place) = in dilated (r > 0: 1 iff a pixel of the picture within Chebyshev
+ *   distance r is set) or eroded (r < 0: 1 iff every pixel of the picture within |r| is set; the border does not
+ *   erode) by a square window; 1 <= |r| <= 32.
+ * sr_region_blend_fwd: m_eff [B, 1, H, W] = mask, times (n.x^2 + n.y^2 + n.z^2 > thresh ? 1 : 0) when normal_map != NULL
+ *   (logical [B, 3, H, W], element (b, c, y, x) at normal_map[b nsb + c nsc + y nsh + x nsw]); y [B, C, H, W] = target +
+ *   m_eff * (img - target), each operation rounded on its own.  One launch; float4 path when H W % 4 == 0 and y, m_eff,
+ *   img, target, mask are 16-byte aligned, one pixel per lane otherwise.
+ * sr_region_blend_bwd: g_img [B, C, H, W] = m_eff * g_y.  One launch, same two paths.
+ * No atomics, no memset, no allocation, no host read: all four run under graph capture on `stream`. */
+int sr_region_fill(uint8_t* out, const int32_t* points, const int32_t* tris, int64_t tri_bstride, int64_t B, int64_t P,
+                   int64_t T, int64_t H, int64_t W, sr_stream_t stream);
+int sr_region_grow(uint8_t* out, const uint8_t* in, int64_t N, int64_t H, int64_t W, int r, sr_stream_t stream);
+int sr_region_blend_fwd(float* y, float* m_eff, const float* img, const float* target, const float* mask,
+                        const float* normal_map, int64_t nsb, int64_t nsc, int64_t nsh, int64_t nsw, float thresh,
+                        int64_t B, int64_t C, int64_t H, int64_t W, sr_stream_t stream);
+int sr_region_blend_bwd(float* g_img, const float* g_y, const float* m_eff, int64_t B, int64_t C, int64_t H, int64_t W,
+                        sr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

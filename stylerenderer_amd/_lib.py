@@ -147,6 +147,10 @@ SIGNATURES = {
     "sr_landmark_loss_bwd": (_i, [_p, _p, _p, _l, _p, _p, _p] + [_l] * 5 + [_i, _p]),
     "sr_landmark_dyn_fwd": (_i, [_p] * 15 + [_l] * 6 + [_i, _f, _f, _l, _l, _f, _f, _p]),
     "sr_landmark_dyn_bwd": (_i, [_p, _p, _p, _l] + [_p] * 7 + [_l] * 6 + [_i, _p]),
+    "sr_region_fill": (_i, [_p, _p, _p] + [_l] * 6 + [_p]),
+    "sr_region_grow": (_i, [_p, _p, _l, _l, _l, _i, _p]),
+    "sr_region_blend_fwd": (_i, [_p] * 6 + [_l] * 4 + [_f] + [_l] * 4 + [_p]),
+    "sr_region_blend_bwd": (_i, [_p] * 3 + [_l] * 4 + [_p]),
     "sr_signal_bump": (_i, [_p, _p]),
     "sr_signal_wait": (_i, [_p, ctypes.c_uint32, _p]),
     "sr_signal_set": (_i, [_p, _p, _p]),

@@ -36,6 +36,7 @@ SOURCES = [
     ("bank_mm.hip", EXACT),
     ("mesh.hip", EXACT),
     ("landmark.hip", EXACT),
+    ("region.hip", EXACT),
     ("morph.hip", []),
     ("skin.hip", []),
     ("blend.hip", []),

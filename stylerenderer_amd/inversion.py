@@ -20,6 +20,11 @@ The reference has no fitting script; its pieces are the generato
                  align.pose_from_landmarks of the mean shape instead of 0; with landmark_lines= (and landmark_axis=) the
                  jaw landmarks slide along the posed mesh's silhouette, with landmark_vis= landmarks turned away from the
                  camera are faded out: op.landmark's pose-aware term, the pose start in two closed-form passes)
+                with mask= ([B, 1, H, W] in [0, 1]) and / or mask_mesh=True the image terms run on
+                y = target + m_eff (image - target) instead of image (op.region.region_blend; m_eff = mask, times the
+                mesh's coverage (n . n of the rendered normal map > 1e-3) with mask_mesh): outside the region the loss
+                sees the target itself.  The pixel term is then mean((m_eff (image - target))^2) over ALL pixels, not
+                renormalised by the region's area.  An all-zero region gives loss 0 and gradient 0.
     update      Adam, `steps` iterations (default 400)
 
 A target [B, 3, H, W] with B > 1 fits B independent images in one iteration (one captured graph): every variable
@@ -64,7 +69,8 @@ class LatentInverter:
     def __init__(self, generator, perceptual, target, mesh, lr=0.05, pose_lr=0.01, pixel_weight=1.0, noise=None,
                  n_mean_latent=4096, use_graph=None, optimise_pose=True, *, face=None, fit_shape=False, coeff_lr=0.01,
                  shape_reg=0.0, landmarks=None, landmark_conf=None, landmark_weight=1.0, landmark_beta=1.0,
-                 landmark_embedding=None, landmark_lines=None, landmark_axis=None, landmark_vis=None):
+                 landmark_embedding=None, landmark_lines=None, landmark_axis=None, landmark_vis=None, mask=None,
+                 mask_mesh=False):
         self.g = generator.eval()
         self.perceptual = perceptual.eval()
         for p in list(self.g.parameters()) + list(self.perceptual.parameters()):
@@ -111,6 +117,20 @@ class LatentInverter:
                                  landmark_lines, landmark_axis, landmark_vis)
         elif landmark_conf is not None:
             raise ValueError("LatentInverter: landmark_conf without landmarks")
+        # the region of the image loss (op.region): not part of the iteration at all without mask / mask_mesh
+        self.mask_mesh = bool(mask_mesh)
+        self.with_mask = mask is not None or self.mask_mesh
+        self.mask_fit = None                             # m_eff [B, 1, H, W] of the last forward
+        self._normal_map = None
+        if self.mask_mesh and not self.with_map:
+            raise ValueError("LatentInverter: mask_mesh=True needs a GeneratorWithMap: the mesh's coverage is read off "
+                             "the normal map it renders")
+        if self.with_mask:
+            # the buffer the iteration (and its captured graph) reads; reset() rewrites it
+            self._mask = torch.ones((self.batch, 1) + tuple(self.target.shape[-2:]), device=self.device)
+            self._set_mask(mask)
+            with torch.no_grad():
+                self.target_feats = self._features_of_target()
         # 3DMM coefficients [B, d], from the mean face
         self.coeff = (torch.zeros(self.batch, self.face_model.n_coeff, device=self.device, requires_grad=True)
                       if self.fit_shape else None)
@@ -223,6 +243,31 @@ class LatentInverter:
         self._lmk_conf.copy_(torch.from_numpy(c).float())
         self._pose_start.copy_(torch.from_numpy(start).float().view(self._pose_start.shape))
 
+    # ---- region ---------------------------------------------------------------------------------------
+    def _features_of_target(self):
+        """The target's LPIPS features.  With a region a render that equals the target inside it must have distance
+        exactly 0, so they are normalised the way the loss normalises the render's (lpips.PNetLin.target_features);
+        without one they are `features`, as ever."""
+        f = self.perceptual.target_features if self.with_mask else self.perceptual.features
+        return [x.detach() for x in f(self.target)]
+
+    @torch.no_grad()
+    def _set_mask(self, mask):
+        """mask [B, 1, H, W] ([1, H, W] / [H, W] at B = 1; None: all ones), finite and in [0, 1], into the buffer."""
+        if mask is None:
+            self._mask.fill_(1.0)
+            return
+        m = mask.detach() if isinstance(mask, torch.Tensor) else torch.as_tensor(mask)
+        if self.batch == 1 and tuple(m.shape) in (tuple(self._mask.shape[1:]), tuple(self._mask.shape[2:])):
+            m = m.reshape(self._mask.shape)
+        if tuple(m.shape) != tuple(self._mask.shape):
+            raise ValueError("LatentInverter: mask %s, the inverter fits %s (a mask is [B, 1, H, W], or [1, H, W] / "
+                             "[H, W] for one image)" % (tuple(m.shape), tuple(self._mask.shape)))
+        m = m.to(torch.float32)
+        if not bool(torch.isfinite(m).all()) or float(m.min()) < 0.0 or float(m.max()) > 1.0:
+            raise ValueError("LatentInverter: a mask is finite and in [0, 1]")
+        self._mask.copy_(m)
+
     def _landmark_term(self, v, n=None):
         """landmark_weight * rows [B] of the posed vertices (one launch each way on the device); keeps the fitted
         landmarks [B, L, 2] (pixel index coordinates of the target) as landmarks_fit: those of this forward pass, that is
@@ -274,7 +319,16 @@ class LatentInverter:
                     self._landmark_term(v, n)
             else:
                 mesh = self.posed_mesh()
-            img, _, _ = self.g([self.w], mesh, input_is_latent=True, noise=self.noise)
+            if self.mask_mesh:
+                # the normal map at the image's resolution gates the region per step (the same nodes: the generator
+                # rasterises it either way)
+                img, _, maps = self.g([self.w], mesh, input_is_latent=True, noise=self.noise, return_normals=True)
+                self._normal_map = maps[-1].detach()
+                if tuple(self._normal_map.shape[-2:]) != tuple(img.shape[-2:]):
+                    raise RuntimeError("LatentInverter: mask_mesh needs the generator's last normal map at the image's "
+                                       "resolution, got %s for %s" % (tuple(self._normal_map.shape), tuple(img.shape)))
+            else:
+                img, _, _ = self.g([self.w], mesh, input_is_latent=True, noise=self.noise)
         else:
             if self.with_landmarks:
                 self._landmark_term(*self._shape_mesh()[:2])
@@ -282,6 +336,13 @@ class LatentInverter:
         return img
 
     def loss(self, img):
+        if self.with_mask:
+            # the loss below runs on y = target + m_eff (img - target): outside the region it sees the target itself
+            # (target composites to itself, so target_feats stay valid)
+            from .op.region import region_blend
+
+            img, m_eff = region_blend(img, self.target, self._mask, self._normal_map)
+            self.mask_fit = m_eff.detach()
         if self.batch > 1:
             return self._loss_rows(img)
         from .op.lpips_layer import mse
@@ -341,7 +402,7 @@ class LatentInverter:
         return warmup
 
     @torch.no_grad()
-    def reset(self, target, landmarks=None, landmark_conf=None):
+    def reset(self, target, landmarks=None, landmark_conf=None, mask=None):
         """Re-targets the inverter to `target` (the shape of the first): copies it and its LPIPS features into the
         buffers the captured graph reads, puts w back at the mean latent, pose and coeff at zero, and zeroes the Adam
         moments and step counts.  An inverter built with landmarks also takes the new picture's `landmarks` and
@@ -349,16 +410,22 @@ class LatentInverter:
         missing, pose 0).  `run(steps)` then gives what a fresh inverter on `target` (and these landmarks) gives (same
         mean latent, same noise), bit for bit, without a new warm-up or capture.  landmarks_fit, contour_fit and
         landmark_visibility are outputs of the (possibly captured) iteration: they keep the previous picture's values
-        until the next step writes them."""
+        until the next step writes them.  An inverter built with a region (mask= or mask_mesh=) takes the new picture's
+        `mask` into its buffer (None: all ones); mask_fit is an output of the iteration like landmarks_fit."""
         target = target.detach()
+        if not self.with_mask and mask is not None:
+            raise ValueError("LatentInverter.reset: this inverter was built without a mask; the region blend is part of "
+                             "the captured iteration or it is not")
         if not self.with_landmarks and (landmarks is not None or landmark_conf is not None):
             raise ValueError("LatentInverter.reset: this inverter was built without landmarks; the landmark term is "
                              "part of the captured iteration or it is not")
         if tuple(target.shape) != tuple(self.target.shape):
             raise ValueError("LatentInverter.reset: target %s, the inverter fits %s"
                              % (tuple(target.shape), tuple(self.target.shape)))
+        if self.with_mask:
+            self._set_mask(mask)
         self.target.copy_(target)
-        for buf, f in zip(self.target_feats, self.perceptual.features(self.target)):
+        for buf, f in zip(self.target_feats, self._features_of_target()):
             buf.copy_(f)
         self.w.copy_(self._mean_w.unsqueeze(1).expand_as(self.w))
         if self.with_landmarks:

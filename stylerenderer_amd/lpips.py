@@ -212,6 +212,16 @@ class PNetLin(nn.Module):
     def features(self, x):
         return [normalize_tensor(f) for f in self.net(self.scaling_layer(x))]
 
+    def target_features(self, x):
+        """`features(x)` of a fixed target such that `distance_to(target_features(x), x)` is exactly 0: where the fused
+        layer kernel serves (device fp32) the normalisation takes the kernel's own summation order
+        (op.lpips_layer.normalize_in_kernel_order; `features` differs from it in the last bit in places), elsewhere it
+        is `features`."""
+        raw = self.net(self.scaling_layer(x))
+        if all(_lpips_layer.supported(raw[k], raw[k].detach(), self.lins[k]) for k in range(self.L)):
+            return [_lpips_layer.normalize_in_kernel_order(f) for f in raw]
+        return [normalize_tensor(f) for f in raw]
+
     def per_layer(self, feats0, feats1):
         """[spatial_average(lin_k((f0_k - f1_k)^2))] (networks_basic.py:66-76, spatial=False)."""
         lins = self.lins

@@ -22,6 +22,31 @@ def supported(f0, t, lin):
             and not t.requires_grad and not lin.requires_grad)
 
 
+SLICES = 16                      # csrc/lpips.hip SL: channel c is summed in slice c % 16, at step c // 16
+
+
+def normalize_in_kernel_order(f, eps=EPS):
+    """f / (sqrt(sum_c f^2) + eps) of f [B, C, H, W] with the channel sum taken in k_lpips_fwd's order: 16 interleaved
+    slices, each from 0 in ascending channel order, then the slices from 0 in order.  Each step is one rounded float
+    operation here as there (the file is compiled without contraction), so this is the normalisation the layer kernel
+    applies to its f0: lpips_layer(f, normalize_in_kernel_order(f), lin) is exactly 0 with a zero gradient, which
+    torch's own sum over the channels (another order, a last-bit difference in places) does not give.  Once per target,
+    not per step: plain element-wise launches."""
+    b, c, h, w = f.shape
+    sq = f * f
+    pad = (-c) % SLICES
+    if pad:                                           # (x + 0 = x: short slices are summed as the kernel sums them)
+        sq = torch.cat((sq, sq.new_zeros(b, pad, h, w)), 1)
+    sq = sq.view(b, -1, SLICES, h, w)
+    ss = torch.zeros_like(sq[:, 0])
+    for k in range(sq.shape[1]):
+        ss = ss + sq[:, k]
+    tot = torch.zeros_like(ss[:, 0])
+    for i in range(SLICES):
+        tot = tot + ss[:, i]
+    return f / (torch.sqrt(tot) + eps).unsqueeze(1)
+
+
 class _LpipsLayer(Function):
     @staticmethod
     def forward(ctx, f0, t, lin):

@@ -4,7 +4,8 @@ for it):
     python -m stylerenderer_amd.reconstruct [--size 256] [--steps 400] [--lr] [--pose_lr] [--coeff_lr] [--shape_reg]
         [--bfm BFM.mat | --flame FLAME.{pkl,mat} | --facewarehouse FW.mat [--beta_shape X]] [--lpips-trunk VGG16.pth] [--batch N] [--gpu 0] [--seed S] [--out DIR]
         [--lmk LANDMARKS.txt [--lmk_index FILE] [--lmk_weight 1.0] [--lmk_beta 1.0] [--lmk_contour 1.0]
-         [--lmk_dynamic | --lmk_lines FILE] [--lmk_axis I,J] [--lmk_vis LO,HI]] CHECKPOINT IMAGE [IMAGE ...]
+         [--lmk_dynamic | --lmk_lines FILE] [--lmk_axis I,J] [--lmk_vis LO,HI]]
+        [--mask_lmk [--mask_tri FILE] [--mask_margin R]] [--mask_dir DIR] [--mask_mesh] CHECKPOINT IMAGE [IMAGE ...]
 
 For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with inversion.LatentInverter(fit_shape=True)
 — the W+ latent, a rigid pose and the 3DMM shape / expression coefficients are fitted together (op.morph on the device)
@@ -41,6 +42,18 @@ whose vertices span the face's up direction.  --lmk_vis LO,HI fades a landmark o
 (normal z from HI down to LO; 0,0.2 is a starting value, untuned like --lmk_weight).  The pose start then takes two
 closed-form passes, and <stem>.npz also holds `contour_vertices` [C] (the vertex every line selected) and `lmk_visibility`
 [L] (the gate; 1 without --lmk_vis).  Without these options nothing changes.
+
+With --mask_lmk, --mask_dir or --mask_mesh the image terms of the loss see only a region of the picture (op.region: the
+loss runs on target + m (render - target), so hair, a hand, a microphone or the background no longer pull the fit).
+--mask_lmk fills the polygon of --lmk's landmarks, scaled to the generator's size as they are for the landmark term: their
+convex hull, or with --mask_tri FILE the triangles of a landmark triangulation (an .obj whose `f` lines name landmarks
+1-based, or an .npy / .txt of [T, 3] 0-based); --mask_margin R grows (R > 0) or shrinks (R < 0) it by R pixels of that size.
+--mask_dir DIR reads <stem>.png or <stem>.npy (grey, scaled to [0, 1], soft values allowed), resized as the picture is; a
+picture without a file gets all ones and is counted in the last line of the output; with --mask_lmk the two are
+multiplied.  --mask_mesh gates the region in every step by the fitted mesh's coverage of the picture.  A picture the
+landmark file does not list gets all ones from --mask_lmk.  DIR then also receives <stem>_mask.png, the region of the last
+step (m times the gate), and <stem>.npz `mask_area`, its mean.  The pixel term is not renormalised by the region's area.
+Without these options nothing changes.
 
 Images are PNG / JPG (PIL) or .npy in [-1, 1] (HWC or CHW), resized on the host.  The 3DMM is the Basel Face Model with
 --bfm (face_model.load_bfm), FLAME with --flame (face_model.load_flame, op.skin), the FaceWarehouse bilinear blendshape
@@ -202,6 +215,111 @@ class LandmarkGuide:
             self.missing, self.seen, self.file)
 
 
+def read_triangulation(path):
+    """int64 [T, 3], 0-based landmark numbers: the `f` lines of an .obj (1-based, their first three entries; `a/b/c`
+    entries count by their vertex), or an .npy / .txt of [T, 3] (0-based)."""
+    if not os.path.isfile(path):
+        raise SystemExit("reconstruct: --mask_tri file %s not found" % path)
+    try:
+        if path.lower().endswith(".obj"):
+            rows = [[int(tok.split("/")[0]) - 1 for tok in line.split()[1:4]]
+                    for line in open(path) if line.split()[:1] == ["f"]]
+            tri = np.asarray(rows, np.int64).reshape(-1, 3)
+        else:
+            raw = np.load(path) if path.lower().endswith(".npy") else np.loadtxt(path, ndmin=2)
+            if not np.all(np.round(raw) == raw):
+                raise ValueError("not whole numbers")
+            tri = np.asarray(raw, np.int64).reshape(-1, 3)
+    except (ValueError, IndexError) as e:
+        raise SystemExit("reconstruct: --mask_tri %s does not hold triangles [T, 3]: %s" % (path, e))
+    if tri.shape[0] == 0 or tri.min() < 0:
+        raise SystemExit("reconstruct: --mask_tri %s holds no triangle, or a landmark number below its first" % path)
+    return tri
+
+
+def load_mask(path, size):
+    """[1, 1, size, size] float32 in [0, 1] of a grey .png (0-255) or .npy ([0, 1]; whole-number types 0-255), resized by
+    the resize load_image applies to the picture."""
+    if path.lower().endswith(".npy"):
+        a = np.load(path)
+        scale = 255.0 if a.dtype.kind in "ui" else 1.0
+        a = a.astype(np.float32) / scale
+        a = a.reshape(a.shape[-2:]) if a.ndim > 2 and a.size == a.shape[-2] * a.shape[-1] else a
+        if a.ndim != 2:
+            raise SystemExit("reconstruct: mask %s is not a grey picture [H, W]" % path)
+    else:
+        from PIL import Image
+
+        a = np.asarray(Image.open(path).convert("L"), np.float32) / 255.0
+    x = torch.from_numpy(np.ascontiguousarray(a))[None, None]
+    if tuple(x.shape[-2:]) != (size, size):
+        x = torch.nn.functional.interpolate(x, size=(size, size), mode="bilinear", align_corners=False, antialias=True)
+    if not bool(torch.isfinite(x).all()):
+        raise SystemExit("reconstruct: mask %s is not finite" % path)
+    return x.clamp(0, 1).contiguous()
+
+
+class MaskGuide:
+    """The region options of one run; `lookup` gives the mask the inverter takes for a picture, or None when only the mesh
+    gate is on."""
+
+    def __init__(self, use_lmk=False, tri_file=None, margin=0, mask_dir=None, mesh=False, count=None):
+        self.use_lmk, self.margin, self.dir, self.mesh = bool(use_lmk), int(margin), mask_dir, bool(mesh)
+        if abs(self.margin) > 32:
+            raise SystemExit("reconstruct: --mask_margin lies in [-32, 32]")
+        self.tri = read_triangulation(tri_file) if tri_file else None
+        if self.tri is not None and count is not None and self.tri.max() >= count:
+            raise SystemExit("reconstruct: --mask_tri names landmark %d, the model's embedding has %d"
+                             % (int(self.tri.max()) + 1, count))
+        if mask_dir and not os.path.isdir(mask_dir):
+            raise SystemExit("reconstruct: --mask_dir %s is not a directory" % mask_dir)
+        self.missing = self.seen = 0
+
+    per_picture = property(lambda self: self.use_lmk or bool(self.dir))
+
+    def lookup(self, path, look, size):
+        """look: LandmarkGuide.lookup's triple (the landmarks in the size x size target's pixels, conf, the file's)."""
+        from .op.region import landmark_region
+
+        if not self.per_picture:
+            return None
+        mask = torch.ones(1, 1, size, size)
+        if self.use_lmk:
+            listed = look[2] is not None                 # (every listed landmark counts, whatever --lmk_contour weighs)
+            mask = landmark_region(np.asarray(look[0], np.float64)[None], np.full((1, len(look[0])), float(listed)),
+                                   (size, size), tris=self.tri, margin=self.margin)
+        if self.dir:
+            self.seen += 1
+            stem = os.path.splitext(os.path.basename(path))[0]
+            found = [f for f in (os.path.join(self.dir, stem + ext) for ext in (".png", ".npy")) if os.path.isfile(f)]
+            if found:
+                mask = mask * load_mask(found[0], size)
+            else:
+                self.missing += 1
+        return mask
+
+    def inverter_args(self, masks):
+        return dict(mask=None if masks[0] is None else torch.cat(masks, 0), mask_mesh=self.mesh)
+
+    def summary(self):
+        return "masks: %d of %d images have no file in %s and were fitted without one" % (self.missing, self.seen, self.dir)
+
+
+def mask_outputs(inv, index, out_dir, stem):
+    """Writes <stem>_mask.png, the region of the last step's forward (the mask, times the mesh gate), and returns the
+    .npz entry `mask_area`, its mean."""
+    m = inv.mask_fit[index, 0].detach().cpu().numpy().astype(np.float64)
+    pix = np.round(m * 255.0).astype(np.uint8)
+    try:
+        from PIL import Image
+
+        Image.fromarray(pix).save(os.path.join(out_dir, stem + "_mask.png"))
+    except ImportError:
+        with open(os.path.join(out_dir, stem + "_mask.pgm"), "wb") as f:
+            f.write(b"P5 %d %d 255\n" % (pix.shape[1], pix.shape[0]) + pix.tobytes())
+    return {"mask_area": np.float64(m.mean())}
+
+
 def landmark_outputs(inv, index, conf, listed, shape):
     """The landmark entries of sample `index`'s .npz: the fit's landmarks and the file's in pixel indices of the input
     picture (H, W) = shape, and their mean distance over the landmarks with a positive weight."""
@@ -239,7 +357,7 @@ def landmark_outputs(inv, index, conf, listed, shape):
 def reconstruct(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr=0.01, shape_reg=0.0,
                 n_mean_latent=4096, **landmark_args):
     """Fits one image; returns the inverter (w, pose, coeff, image, fitted_mesh()) and the loss history (host).
-    landmark_args: LatentInverter's landmark keywords."""
+    landmark_args: LatentInverter's landmark and mask keywords."""
     inv = inversion.LatentInverter(g, percept, target, None, lr=lr, pose_lr=pose_lr, n_mean_latent=n_mean_latent,
                                    face=face, fit_shape=True, coeff_lr=coeff_lr, shape_reg=shape_reg, **landmark_args)
     hist = inv.run(steps)
@@ -250,12 +368,13 @@ def reconstruct_batch(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, co
                       n_mean_latent=4096, inv=None, **landmark_args):
     """Fits the B images of target [B, 3, H, W] together; `inv` (an inverter of the same batch from an earlier call) is
     re-targeted instead of built anew.  Returns the inverter and the loss history [steps, B] (host).  landmark_args:
-    LatentInverter's landmark keywords."""
+    LatentInverter's landmark and mask keywords."""
     if inv is None:
         inv = inversion.LatentInverter(g, percept, target, None, lr=lr, pose_lr=pose_lr, n_mean_latent=n_mean_latent,
                                        face=face, fit_shape=True, coeff_lr=coeff_lr, shape_reg=shape_reg, **landmark_args)
     elif landmark_args:
-        inv.reset(target, landmark_args["landmarks"], landmark_args["landmark_conf"])
+        inv.reset(target, landmark_args.get("landmarks"), landmark_args.get("landmark_conf"),
+                  **({"mask": landmark_args["mask"]} if landmark_args.get("mask") is not None else {}))
     else:
         inv.reset(target)
     hist = inv.run(steps)
@@ -333,6 +452,17 @@ def main(argv=None):
     ap.add_argument("--lmk_vis", default=None, metavar="LO,HI",
                     help="fade a landmark out as the z of its normal falls from HI to LO (turned away from the camera); off "
                          "unless given; 0,0.2 is a starting value, untuned like --lmk_weight")
+    ap.add_argument("--mask_lmk", action="store_true",
+                    help="the image loss sees only the filled polygon of --lmk's landmarks (their convex hull)")
+    ap.add_argument("--mask_tri", default=None, metavar="FILE",
+                    help="with --mask_lmk: a landmark triangulation to fill instead of the hull: .obj (f lines, 1-based) or "
+                         ".npy / .txt of [T, 3] (0-based)")
+    ap.add_argument("--mask_margin", type=int, default=0, metavar="R",
+                    help="with --mask_lmk: grow (R > 0) or shrink (R < 0) the polygon by R pixels, |R| <= 32 [%(default)d]")
+    ap.add_argument("--mask_dir", default=None, metavar="DIR",
+                    help="masks of the pictures: DIR/<stem>.png or .npy, grey in [0, 1]; a missing file is all ones")
+    ap.add_argument("--mask_mesh", action="store_true",
+                    help="gate the region in every step by the fitted mesh's coverage of the picture")
     ap.add_argument("--gpu", type=int, default=0, help="use gpu id")
     ap.add_argument("--seed", type=int, default=0, help="random seed (mean latent, noise)")
     ap.add_argument("--out", default="reconstruct", metavar="DIR", help="output directory [%(default)s]")
@@ -345,6 +475,10 @@ def main(argv=None):
         ap.error("--lmk_index needs --lmk")
     if (args.lmk_dynamic or args.lmk_lines or args.lmk_axis or args.lmk_vis) and not args.lmk:
         ap.error("--lmk_dynamic, --lmk_lines, --lmk_axis and --lmk_vis need --lmk")
+    if args.mask_lmk and not args.lmk:
+        ap.error("--mask_lmk needs --lmk")
+    if (args.mask_tri or args.mask_margin) and not args.mask_lmk:
+        ap.error("--mask_tri and --mask_margin need --mask_lmk")
     torch.manual_seed(args.seed)
     if torch.cuda.is_available() and 0 <= args.gpu < torch.cuda.device_count():
         device = torch.device("cuda:%d" % args.gpu)
@@ -364,15 +498,32 @@ def main(argv=None):
                       beta_shape=args.beta_shape)
     guide = (LandmarkGuide(args.lmk, face, args.lmk_index, args.lmk_weight, args.lmk_beta, args.lmk_contour,
                            args.lmk_dynamic, args.lmk_lines, args.lmk_axis, args.lmk_vis) if args.lmk else None)
+    masker = (MaskGuide(args.mask_lmk, args.mask_tri, args.mask_margin, args.mask_dir, args.mask_mesh,
+                        guide.count if guide else None)
+              if (args.mask_lmk or args.mask_dir or args.mask_mesh) else None)
     os.makedirs(args.out, exist_ok=True)
     results = []
 
     def load(path):
-        """(target on the host, what the landmark file says about the picture: LandmarkGuide.lookup's triple, or None)."""
+        """(target on the host, what the landmark file says about the picture: LandmarkGuide.lookup's triple, or None,
+        the picture's mask or None)."""
         if guide is None:
-            return load_image(path, args.size), None
+            return load_image(path, args.size), None, masker.lookup(path, None, args.size) if masker else None
         x, shape = load_image(path, args.size, with_shape=True)
-        return x, guide.lookup(path, shape, args.size) + (shape,)
+        look = guide.lookup(path, shape, args.size) + (shape,)
+        return x, look, masker.lookup(path, look, args.size) if masker else None
+
+    def more(inv, index, stem, extras):
+        """The .npz entries with the region's (and its picture written), when there is one."""
+        if masker is None:
+            return extras
+        return dict(extras or {}, **mask_outputs(inv, index, args.out, stem))
+
+    def closing():
+        if guide:
+            print(guide.summary(), flush=True)
+        if masker and masker.dir:
+            print(masker.summary(), flush=True)
 
     def tail(extras):
         if extras is None:
@@ -382,40 +533,44 @@ def main(argv=None):
     if args.batch == 1:
         for path in args.images:
             stem = os.path.splitext(os.path.basename(path))[0]
-            target, look = load(path)
+            target, look, mask = load(path)
             lmk_args = guide.inverter_args([look[0]], [look[1]]) if guide else {}
+            if masker:
+                lmk_args.update(masker.inverter_args([mask]))
             inv, hist = reconstruct(g, percept, face, target.to(device), args.steps, args.lr, args.pose_lr, args.coeff_lr,
                                     args.shape_reg, args.n_mean_latent, **lmk_args)
             extras = landmark_outputs(inv, 0, look[1], look[2], look[3]) if guide else None
-            write_outputs(inv, hist, args.out, stem, extras=extras)
+            write_outputs(inv, hist, args.out, stem, extras=more(inv, 0, stem, extras))
             print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f%s" % (
                 path, float(hist[0]), float(hist[-1]), len(hist), float(inv.coeff.detach().norm()), tail(extras)),
                 flush=True)
             results.append((stem, hist))
-        if guide:
-            print(guide.summary(), flush=True)
+        closing()
         return results
     inv = None
     for start in range(0, len(args.images), args.batch):
         group = args.images[start:start + args.batch]
         loaded = [load(path) for path in group]
-        targets = [x for x, _ in loaded]
+        targets = [x for x, _, _ in loaded]
         targets += targets[-1:] * (args.batch - len(group))          # padding: fitted, then discarded
-        looks = [look for _, look in loaded]
+        looks = [look for _, look, _ in loaded]
         looks += looks[-1:] * (args.batch - len(group))
+        masks = [m for _, _, m in loaded]
+        masks += masks[-1:] * (args.batch - len(group))
         lmk_args = guide.inverter_args([k[0] for k in looks], [k[1] for k in looks]) if guide else {}
+        if masker:
+            lmk_args.update(masker.inverter_args(masks))
         inv, hist = reconstruct_batch(g, percept, face, torch.cat(targets, 0).to(device), args.steps, args.lr,
                                       args.pose_lr, args.coeff_lr, args.shape_reg, args.n_mean_latent, inv=inv, **lmk_args)
         for i, path in enumerate(group):
             stem = os.path.splitext(os.path.basename(path))[0]
             h = np.ascontiguousarray(hist[:, i])
             extras = landmark_outputs(inv, i, looks[i][1], looks[i][2], looks[i][3]) if guide else None
-            write_outputs(inv, h, args.out, stem, index=i, extras=extras)
+            write_outputs(inv, h, args.out, stem, index=i, extras=more(inv, i, stem, extras))
             print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f%s" % (
                 path, float(h[0]), float(h[-1]), len(h), float(inv.coeff.detach()[i].norm()), tail(extras)), flush=True)
             results.append((stem, h))
-    if guide:
-        print(guide.summary(), flush=True)
+    closing()
     return results
 
 

@@ -1,0 +1,583 @@
+"""CPU: the region-weighted image loss — the host definitions of op.region (hull, fill, grow, the landmark polygon, the
+blend), the inverter with mask= / mask_mesh= and `reconstruct --mask_*`."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from stylerenderer_amd import inversion, lpips, synth
+from stylerenderer_amd.op import region
+from test_landmark_cpu import TRUE_POSE, project_np, tiny_landmarks, tiny_problem
+from test_reconstruct_cpu import _env
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ---- fill: an independent restatement on Python integers --------------------------------------------------------------
+def trunc_int(v):
+    return int(v)                                                          # Python's int() truncates toward zero
+
+
+def fill_py(points, tris, h, w):
+    """[B][H][W] lists of 0 / 1: the issue's definition, one pixel and one triangle at a time, Python ints only."""
+    out = []
+    for s, pts in enumerate(points):
+        ip = [(trunc_int(x), trunc_int(y)) for x, y in pts]
+        tl = tris[s] if isinstance(tris[0][0], (list, tuple)) else tris
+        img = [[0] * w for _ in range(h)]
+        for y in range(h):
+            for x in range(w):
+                for ia, ib, ic in tl:
+                    (ax, ay), (bx, by), (cx, cy) = ip[ia], ip[ib], ip[ic]
+                    if not (min(ax, bx, cx) <= x <= max(ax, bx, cx) and min(ay, by, cy) <= y <= max(ay, by, cy)):
+                        continue
+                    e = ((bx - ax) * (y - ay) - (by - ay) * (x - ax), (cx - bx) * (y - by) - (cy - by) * (x - bx),
+                         (ax - cx) * (y - cy) - (ay - cy) * (x - cx))
+                    if all(v >= 0 for v in e) or all(v <= 0 for v in e):
+                        img[y][x] = 1
+                        break
+        out.append(img)
+    return out
+
+
+def many_triangles(n, seed, span=(-6, 40)):
+    """n triangles over 3 n points: (points [3 n, 2] float with fractions, tris [n, 3])."""
+    pts = synth.det_uniform((3 * n, 2), seed).astype(np.float64) * (span[1] - span[0]) / 2 + (span[1] + span[0]) / 2
+    return pts, np.arange(3 * n).reshape(n, 3)
+
+
+FILL_CASES = {
+    # name: (points [P, 2] as lists, tris, (H, W))
+    "ccw": ([[1, 1], [9, 2], [4, 8]], [[0, 1, 2]], (10, 12)),
+    "cw": ([[1, 1], [9, 2], [4, 8]], [[0, 2, 1]], (10, 12)),
+    "segment": ([[1, 1], [9, 5], [9, 5]], [[0, 1, 2]], (10, 12)),
+    "segment_diagonal": ([[2, 2], [7, 7], [4, 4]], [[0, 1, 2]], (10, 12)),
+    "point": ([[3, 4], [3, 4], [3, 4]], [[0, 1, 2]], (10, 12)),
+    "all_outside_5x7": ([[-4, -3], [12, 1], [2, 11]], [[0, 1, 2]], (5, 7)),
+    "misses_5x7": ([[-4, -3], [-1, -1], [-2, -9]], [[0, 1, 2]], (5, 7)),
+    "negative": ([[-5, -2], [6, 3], [-1, 7]], [[0, 1, 2]], (9, 9)),
+    "fractions": ([[-0.9, 0.9], [7.99, -0.5], [3.5, 6.7], [0.2, -0.2]], [[0, 1, 2], [3, 1, 2]], (8, 9)),
+    "overlap": ([[0, 0], [8, 1], [2, 7], [3, 2], [10, 9], [1, 9]], [[0, 1, 2], [3, 4, 5]], (11, 12)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(FILL_CASES))
+def test_fill_triangles_is_the_closed_integer_polygon(name):
+    pts, tris, (h, w) = FILL_CASES[name]
+    got = region.fill_triangles(torch.tensor([pts], dtype=torch.float64), torch.tensor(tris), (h, w))
+    assert got.dtype == torch.uint8 and got.shape == (1, 1, h, w)
+    want = np.array(fill_py([pts], tris, h, w), np.uint8)
+    assert np.array_equal(got[0].numpy(), want), (got[0, 0], want[0])
+    if name in ("ccw", "negative", "all_outside_5x7", "overlap"):
+        assert 0 < int(want.sum()) < h * w or name == "all_outside_5x7"
+    if name == "point":
+        assert int(want.sum()) == 1 and want[0, 4, 3] == 1
+    if name == "segment_diagonal":
+        assert int(want.sum()) == 6
+    if name == "misses_5x7":
+        assert int(want.sum()) == 0
+    if name == "fractions":                                                 # -0.9 -> 0, not -1; 7.99 -> 7
+        assert want[0, 0, 0] == 1 and want[0, 0, 7] == 1 and want[0, 0, 8] == 0
+    if name == "all_outside_5x7":
+        assert int(want.sum()) > 0
+
+
+def test_fill_both_windings_agree_and_float32_points_truncate_alike():
+    a = region.fill_triangles(torch.tensor([FILL_CASES["ccw"][0]], dtype=torch.float32), torch.tensor([[0, 1, 2]]), (10, 12))
+    b = region.fill_triangles(np.array([FILL_CASES["cw"][0]]), np.array([[0, 2, 1]]), (10, 12))
+    assert torch.equal(a, b)
+
+
+def test_fill_seventy_triangles_shared_and_per_sample():
+    pts, tris = many_triangles(70, 5)
+    pts2, _ = many_triangles(70, 6)
+    both = np.stack([pts, pts2])
+    got = region.fill_triangles(both, tris, (33, 35))
+    assert np.array_equal(got[:, 0].numpy(), np.array(fill_py(both.tolist(), tris.tolist(), 33, 35), np.uint8))
+    per = np.stack([tris, tris[::-1][:, [0, 2, 1]]])
+    got2 = region.fill_triangles(both, per, (33, 35))
+    assert np.array_equal(got2[:, 0].numpy(), np.array(fill_py(both.tolist(), per.tolist(), 33, 35), np.uint8))
+    assert torch.equal(got, got2)                                           # the union does not depend on order or winding
+
+
+def test_fill_refuses_what_it_cannot_index():
+    tri = torch.tensor([[0, 1, 2]])
+    with pytest.raises(ValueError, match="2\\^20"):
+        region.fill_triangles(torch.tensor([[[0.0, 0.0], [2.0 ** 20 + 1, 0.0], [1.0, 1.0]]]), tri, 8)
+    with pytest.raises(ValueError):
+        region.fill_triangles(torch.tensor([[[0.0, 0.0], [float("nan"), 0.0], [1.0, 1.0]]]), tri, 8)
+    with pytest.raises(ValueError):
+        region.fill_triangles(torch.zeros(1, 3, 2), torch.tensor([[0, 1, 3]]), 8)
+    ok = region.fill_triangles(torch.tensor([[[0.0, 0.0], [2.0 ** 20, 0.0], [0.0, -(2.0 ** 20)]]]), tri, 4)
+    assert ok[0, 0, 0].tolist() == [1, 1, 1, 1] and int(ok[0, 0, 1:].sum()) == 0
+
+
+# ---- hull ------------------------------------------------------------------------------------------------------------
+def supporting_lines(pts):
+    """Every ordered pair of distinct points whose line has all points on its closed left side."""
+    return [(a, b) for a in pts for b in pts if a != b
+            and all((b[0] - a[0]) * (py - a[1]) - (b[1] - a[1]) * (px - a[0]) >= 0 for px, py in pts)]
+
+
+def in_hull_brute(pts, lines, x, y):
+    """Is (x, y) in the convex hull of the integer points?  Inside their bounding box (which settles collinear points) and
+    on the closed left side of every supporting line."""
+    if not (min(p[0] for p in pts) <= x <= max(p[0] for p in pts) and min(p[1] for p in pts) <= y <= max(p[1] for p in pts)):
+        return False
+    return all((b[0] - a[0]) * (y - a[1]) - (b[1] - a[1]) * (x - a[0]) >= 0 for a, b in lines)
+
+
+def test_hull_fan_covers_exactly_the_hull_of_68_points():
+    pts = np.trunc(synth.det_uniform((68, 2), 21) * 14 + 15).astype(np.int64)
+    tris = region.hull_triangles(pts)
+    assert tris.dtype == torch.int32 and tris.shape[1] == 3 and 1 <= tris.shape[0] <= 66
+    got = region.fill_triangles(pts[None], tris, (32, 34))[0, 0].numpy()
+    plist = [tuple(int(v) for v in p) for p in pts]
+    lines = supporting_lines(plist)
+    want = np.array([[in_hull_brute(plist, lines, x, y) for x in range(34)] for y in range(32)], np.uint8)
+    assert np.array_equal(got, want) and 0 < int(want.sum()) < want.size
+
+
+def test_hull_of_collinear_points_and_of_one_point():
+    line = np.array([[2, 2], [8, 5], [4, 3], [6, 4], [4, 3]])
+    t = region.hull_triangles(line)
+    assert t.tolist() == [[0, 1, 1]]
+    got = region.fill_triangles(line[None], t, (8, 10))[0, 0].numpy()
+    assert sorted(zip(*np.nonzero(got))) == [(2, 2), (3, 4), (4, 6), (5, 8)]
+    one = region.hull_triangles(np.array([[3, 1], [3, 1]]))
+    assert one.tolist() == [[0, 0, 0]]
+    assert int(region.fill_triangles(np.array([[[3, 1], [3, 1]]]), one, (4, 5)).sum()) == 1
+    # duplicates and interior points of a square do not change its fan's union
+    sq = np.array([[0, 0], [4, 0], [4, 4], [0, 4], [2, 2], [4, 0], [2, 0]])
+    assert int(region.fill_triangles(sq[None], region.hull_triangles(sq), (6, 6)).sum()) == 25
+    with pytest.raises(ValueError):
+        region.hull_triangles(np.array([[0.5, 1.0]]))
+
+
+# ---- grow ------------------------------------------------------------------------------------------------------------
+def grow_brute(m, r):
+    h, w = m.shape
+    a = abs(r)
+    out = np.zeros_like(m)
+    for y in range(h):
+        for x in range(w):
+            win = [m[yy, xx] for yy in range(max(y - a, 0), min(y + a, h - 1) + 1)
+                   for xx in range(max(x - a, 0), min(x + a, w - 1) + 1)]
+            out[y, x] = any(win) if r > 0 else all(win)
+    return out
+
+
+def grow_case(h=21, w=29):
+    m = np.zeros((h, w), np.uint8)
+    m[6:14, 8:18] = 1                                                       # something an erosion by 3 leaves
+    m[7, 9] = 0                                                             # ... with a hole
+    m[0, :3] = 1                                                            # set pixels on the border
+    m[:4, w - 1] = 1
+    m[h - 1, 0] = 1
+    m[h - 7:, w - 9:] = 1                                                   # a block in the corner: the border does not erode
+    return m
+
+
+@pytest.mark.parametrize("r", [1, -1, 3, -3])
+def test_grow_against_a_brute_force_window(r):
+    m = grow_case()
+    got = region.grow(torch.from_numpy(m)[None, None], r)
+    assert got.dtype == torch.uint8 and got.shape == (1, 1) + m.shape
+    want = grow_brute(m, r)
+    assert np.array_equal(got[0, 0].numpy(), want) and 0 < int(want.sum()) < want.size
+
+
+def test_grow_border_does_not_erode_and_limits():
+    ones = torch.ones(2, 1, 5, 6, dtype=torch.uint8)
+    assert torch.equal(region.grow(ones, -3), ones)
+    assert region.grow(ones, 0) is ones
+    with pytest.raises(ValueError):
+        region.grow(ones, 33)
+    with pytest.raises(ValueError):
+        region.grow(ones.float(), 1)
+
+
+# ---- the landmark polygon --------------------------------------------------------------------------------------------
+def test_landmark_region_leaves_out_missing_landmarks_and_fills_unlisted_samples_with_ones():
+    lmk = np.array([[[2.5, 2.2], [12.9, 3.0], [13.0, 12.0], [2.0, 11.0], [25.0, 25.0]]] * 3)
+    conf = np.array([[1, 1, 1, 1, 0], [1, 1, 1, 1, 0.5], [0, 0, 0, 0, 0]], np.float64)
+    lmk[0, 4] = np.nan                                                      # a missing landmark may hold anything
+    m = region.landmark_region(lmk, conf, (28, 30))
+    assert m.dtype == torch.float32 and m.shape == (3, 1, 28, 30)
+    assert set(np.unique(m.numpy())) == {0.0, 1.0}
+    quad = region.fill_triangles(np.trunc(lmk[1:2, :4]), region.hull_triangles(np.trunc(lmk[1, :4])), (28, 30))
+    assert torch.equal(m[0], quad[0].float()) and float(m[0, 0, 25, 25]) == 0.0
+    assert float(m[1, 0, 25, 25]) == 1.0 and float(m[1].sum()) > float(m[0].sum())      # the fifth landmark widens it
+    assert float(m[2].min()) == 1.0                                         # no landmark at all: fitted as today
+    # conf None: every landmark; margin grows afterwards
+    full = region.landmark_region(lmk[1:2], None, (28, 30))
+    assert torch.equal(full, m[1:2])
+    wide = region.landmark_region(lmk[:1], conf[:1], (28, 30), margin=2)
+    assert torch.equal(wide, region.grow(quad, 2).float())
+    tight = region.landmark_region(lmk[:1], conf[:1], (28, 30), margin=-2)
+    assert torch.equal(tight, region.grow(quad, -2).float()) and 0 < float(tight.sum()) < float(quad.sum())
+
+
+def test_landmark_region_with_a_triangulation_drops_triangles_that_touch_a_missing_landmark():
+    lmk = np.array([[[2, 2], [12, 3], [13, 12], [2, 11], [20, 6]]] * 3, np.float64)
+    tris = np.array([[0, 1, 2], [0, 2, 3], [1, 4, 2]])
+    conf = np.array([[1, 1, 1, 1, 1], [1, 1, 1, 1, 0], [1, 0, 1, 1, 1]], np.float64)
+    m = region.landmark_region(lmk, conf, (16, 24), tris=tris)
+    ip = lmk[:1].astype(np.int64)
+    for s, keep in enumerate(([0, 1, 2], [0, 1], [1])):
+        assert torch.equal(m[s], region.fill_triangles(ip, tris[keep], (16, 24))[0].float()), s
+    assert float(m[0].sum()) > float(m[1].sum()) > float(m[2].sum()) > 0
+    # every triangle dropped, landmarks present: an empty region, not all ones
+    none = region.landmark_region(lmk[:1], np.array([[0, 0, 0, 0, 1.0]]), (16, 24), tris=tris)
+    assert float(none.max()) == 0.0
+    with pytest.raises(ValueError):
+        region.landmark_region(lmk, conf, (16, 24), tris=np.array([[0, 1, 5]]))
+
+
+# ---- the blend -------------------------------------------------------------------------------------------------------
+def blend_case(b=2, c=3, h=5, w=6, dtype=torch.float64):
+    t = lambda shape, key: torch.from_numpy(synth.det_normal(shape, key)).to(dtype)   # noqa: E731
+    img, target = t((b, c, h, w), 51), t((b, c, h, w), 52)
+    mask = (torch.from_numpy(synth.det_uniform((b, 1, h, w), 53)).to(dtype) + 1) / 2
+    mask[:, :, 0] = 0.0
+    mask[:, :, 1] = 1.0
+    n = t((b, 3, h, w), 54) * 0.05
+    n[:, :, :, 0] = 0.0                                                     # a column the mesh does not cover
+    return img, target, mask, n
+
+
+def test_region_blend_passes_gradcheck_and_gradgradcheck():
+    img, target, mask, n = blend_case()
+    img.requires_grad_(True)
+    for nm in (None, n):
+        f = lambda x: region.region_blend(x, target, mask, nm)[0]           # noqa: E731
+        assert torch.autograd.gradcheck(f, (img,), eps=1e-6, atol=1e-8)
+        assert torch.autograd.gradgradcheck(f, (img,), eps=1e-6, atol=1e-8)
+    # the gradient reaches img only, as m_eff * g_y
+    tg, mg = target.clone().requires_grad_(True), mask.clone().requires_grad_(True)
+    y, m_eff = region.region_blend(img, tg, mg, n)
+    assert not m_eff.requires_grad
+    gy = torch.from_numpy(synth.det_normal(tuple(y.shape), 55))
+    (gi,) = torch.autograd.grad(y, img, gy)
+    assert torch.equal(gi, m_eff * gy)
+    with pytest.raises(RuntimeError):
+        torch.autograd.grad(region.region_blend(img.detach(), tg, mg, n)[0].sum(), (tg, mg))
+
+
+def test_region_blend_is_the_written_definition_and_keeps_the_target_where_the_mask_is_zero():
+    img, target, mask, n = blend_case(dtype=torch.float32)
+    y, m_eff = region.region_blend(img, target, mask)
+    assert torch.equal(m_eff, mask) and torch.equal(y, target + mask * (img - target))
+    assert torch.equal(y[:, :, 0], target[:, :, 0])                        # bit for bit
+    assert torch.equal(y[:, :, 1], target[:, :, 1] + (img[:, :, 1] - target[:, :, 1]))
+    zero = region.region_blend(img, target, torch.zeros_like(mask))[0]
+    assert torch.equal(zero, target)
+    # the gate: (n . n over the three channels) > thresh, on a contiguous map and on the rasterizer's permuted view
+    gate = ((n * n).sum(1, keepdim=True) > 1e-3).float()
+    assert 0 < float(gate.sum()) < gate.numel() and float(gate[..., 0].max()) == 0.0
+    view = n.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    assert not view.is_contiguous()
+    for nm in (n, view):
+        y2, m2 = region.region_blend(img, target, mask, nm)
+        assert torch.equal(m2, mask * gate) and torch.equal(y2, target + m2 * (img - target))
+    y3, m3 = region.region_blend(img, target, mask, n, thresh=1e9)
+    assert float(m3.max()) == 0.0 and torch.equal(y3, target)
+    with pytest.raises(ValueError):
+        region.region_blend(img, target, mask[:, 0])
+    with pytest.raises(ValueError):
+        region.region_blend(img, target, mask, n[:, :2])
+
+
+def test_kernel_order_normalisation_is_normalize_tensor_to_the_last_bits():
+    from stylerenderer_amd.op import lpips_layer
+
+    for c in (64, 70, 512):
+        f = torch.from_numpy(synth.det_normal((2, c, 5, 7), 70 + c))
+        got, want = lpips_layer.normalize_in_kernel_order(f), lpips.normalize_tensor(f)
+        assert got.shape == want.shape and float((got - want).abs().max()) <= 2e-7 * float(want.abs().max())
+        # in float64 the order of the sum shows at the 16th digit only
+        d = lpips_layer.normalize_in_kernel_order(f.double()) - lpips.normalize_tensor(f.double())
+        assert float(d.abs().max()) <= 1e-15
+    # on the host the loss takes `features`, and so do the target's
+    net = lpips.PNetLin()
+    x = torch.from_numpy(synth.det_uniform((1, 3, 16, 16), 3))
+    with torch.no_grad():
+        for a, b in zip(net.target_features(x), net.features(x)):
+            assert torch.equal(a, b)
+        assert float(net.distance_to(net.target_features(x), x).abs().max()) == 0.0
+
+
+# ---- the inverter ----------------------------------------------------------------------------------------------------
+def _inverter(problem, **kw):
+    g, _, face, noise, target = problem
+    kw.setdefault("shape_reg", 1e-3)
+    torch.manual_seed(3)
+    return inversion.LatentInverter(g, lpips.PNetLin(), target, None, lr=0.05, pose_lr=0.02, noise=noise,
+                                    n_mean_latent=64, face=face, fit_shape=True, coeff_lr=0.05, **kw)
+
+
+class single_thread:
+    """The CPU path's threaded reductions are not run-to-run identical."""
+
+    def __enter__(self):
+        self.n = torch.get_num_threads()
+        torch.set_num_threads(1)
+
+    def __exit__(self, *exc):
+        torch.set_num_threads(self.n)
+
+
+def _state(inv, hist):
+    return [hist.clone()] + [t.detach().clone() for t in (inv.w, inv.pose, inv.coeff)]
+
+
+def test_without_the_arguments_the_blend_is_never_reached(monkeypatch):
+    problem = tiny_problem()
+    with single_thread():
+        before = _inverter(problem)
+        want = _state(before, before.run(3))
+
+        def boom(*a, **k):
+            raise AssertionError("region_blend reached without mask / mask_mesh")
+
+        monkeypatch.setattr(region, "region_blend", boom)
+        inv = _inverter(problem, mask=None, mask_mesh=False)
+        got = _state(inv, inv.run(3))
+    assert not inv.with_mask and inv.mask_fit is None
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+    with pytest.raises(AssertionError, match="reached"):
+        _inverter(problem, mask=torch.ones(1, 1, 16, 16)).run(1)            # (the patch does guard the call)
+
+
+def true_state(problem):
+    """(w, pose, coeff) of tiny_problem's target."""
+    g, _, face, _, _ = problem
+    with torch.no_grad():
+        c = torch.from_numpy(synth.det_normal((1, 14), 3)) * face[0].sigma
+        w = g.style(torch.from_numpy(synth.det_normal((1, 32), 5))).unsqueeze(1).repeat(1, g.n_latent, 1)
+    return w, torch.tensor(TRUE_POSE), c
+
+
+def put(inv, state):
+    """The test's own setter."""
+    with torch.no_grad():
+        for var, value in zip((inv.w, inv.pose, inv.coeff), state):
+            var.copy_(value.view(var.shape))
+
+
+def stationarity(make, state, occluder=(slice(3, 8), slice(9, 14)), mask_mesh=False):
+    """(masked loss, masked gradients, unmasked loss, unmasked gradients) at `state`, the true state of a target with a
+    patch painted in; the mask clears the patch.  make(target, **kw) builds an inverter (target None: any)."""
+    first = make(None)
+    put(first, state)
+    clean = first.render().detach()                                         # the inverter's own render of that state
+    painted = clean.clone()
+    painted[:, :, occluder[0], occluder[1]] = 1.0
+    mask = torch.ones_like(clean[:, :1])
+    mask[:, :, occluder[0], occluder[1]] = 0.0
+    out = []
+    for kw in (dict(mask=mask, mask_mesh=mask_mesh), {}):
+        inv = make(painted, **kw)
+        put(inv, state)
+        value = inv.loss(inv.render())
+        value.backward()
+        out += [float(value.detach().sum()), [x.grad.detach().clone() for x in (inv.w, inv.pose, inv.coeff)]]
+        if kw and not mask_mesh:
+            assert torch.equal(inv.mask_fit, mask)
+    return out
+
+
+def _make(problem):
+    g, mesh, face, noise, target = problem
+    return lambda t, **kw: _inverter((g, mesh, face, noise, target if t is None else t), shape_reg=0.0, **kw)
+
+
+def test_exact_stationarity_with_the_occluder_masked_out():
+    with single_thread():
+        problem = tiny_problem()
+        loss_m, grads_m, loss_u, grads_u = stationarity(_make(problem), true_state(problem))
+    assert loss_m == 0.0 and all(float(g.abs().max()) == 0.0 for g in grads_m)
+    assert loss_u > 0.0 and all(float(g.abs().max()) > 0.0 for g in grads_u)
+
+
+def test_mask_mesh_gates_the_region_by_the_rendered_normal_map():
+    problem = tiny_problem()
+    with single_thread():
+        inv = _inverter(problem, mask_mesh=True)
+        assert inv.with_mask and float(inv._mask.min()) == 1.0
+        inv.run(1)
+        n = inv._normal_map
+        assert tuple(n.shape) == (1, 3, 16, 16)
+        want = ((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1] + n[:, 2] * n[:, 2]) > 1e-3).float().unsqueeze(1)
+        assert torch.equal(inv.mask_fit, want) and 0 < float(want.sum()) < want.numel()
+        assert inv.image.shape == (1, 3, 16, 16)
+        half = torch.ones(16, 16)
+        half[:, 8:] = 0.25
+        both = _inverter(problem, mask=half, mask_mesh=True)
+        both.run(1)
+        assert torch.equal(both.mask_fit, want * half.view(1, 1, 16, 16))
+    g, mesh, _, noise, target = problem
+    from test_inversion_cpu import tiny_setup
+
+    plain_g, plain_mesh = tiny_setup(with_map=False)
+    with pytest.raises(ValueError, match="GeneratorWithMap"):
+        inversion.LatentInverter(plain_g, lpips.PNetLin(), target, plain_mesh, n_mean_latent=8, mask_mesh=True)
+
+
+def test_reset_with_a_mask_equals_a_fresh_inverter_and_masks_are_checked():
+    g, mesh, face, noise, target = tiny_problem()
+    targets = torch.cat([target, target.flip(3)], 0).contiguous()
+    m_a = (torch.from_numpy(synth.det_uniform((2, 1, 16, 16), 61)) > 0).float()
+    m_b = (torch.from_numpy(synth.det_uniform((2, 1, 16, 16), 62)) + 1) / 2          # soft
+    with single_thread():
+        inv = _inverter((g, mesh, face, noise, targets), mask=m_a)
+        assert inv.run(1).shape == (1, 2) and torch.equal(inv.mask_fit, m_a)
+        inv.reset(targets.flip(0).contiguous(), mask=m_b)
+        got = _state(inv, inv.run(2))
+        fresh = _inverter((g, mesh, face, noise, targets.flip(0).contiguous()), mask=m_b)
+        want = _state(fresh, fresh.run(2))
+        for a, b in zip(got, want):
+            assert torch.equal(a, b)
+        assert torch.equal(inv.mask_fit, m_b)
+        # reset without a mask: all ones
+        inv.reset(targets)
+        assert float(inv._mask.min()) == 1.0
+    one = _inverter((g, mesh, face, noise, target), mask=torch.zeros(16, 16))
+    assert one._mask.shape == (1, 1, 16, 16) and float(one._mask.max()) == 0.0
+    # a refused mask leaves the inverter as it was
+    for bad in (torch.full((1, 1, 16, 16), 1.5), torch.full((1, 1, 16, 16), float("nan")), torch.ones(1, 1, 8, 8),
+                -torch.ones(16, 16), torch.ones(2, 1, 16, 16)):
+        with pytest.raises(ValueError):
+            one.reset(target, mask=bad)
+        assert float(one._mask.max()) == 0.0
+    for shape in ((16, 16), (1, 16, 16), (1, 1, 16, 16)):
+        one.reset(target, mask=torch.full(shape, 0.5))
+        assert float(one._mask.min()) == 0.5
+    # an all-zero region: loss 0 and gradient 0, no division anywhere
+    one.reset(target, mask=torch.zeros(16, 16))
+    value = one.loss(one.render())
+    value.backward()
+    assert float(value.detach()) == float(one._reg.detach()) and float(one.w.grad.abs().max()) == 0.0
+    plain = _inverter((g, mesh, face, noise, target))
+    with pytest.raises(ValueError, match="built without a mask"):
+        plain.reset(target, mask=torch.ones(1, 1, 16, 16))
+
+
+OCCLUDER = (slice(2, 10), slice(1, 7))                                     # chosen on the CPU: the unmasked fit drifts
+
+
+def test_masking_an_occluder_keeps_the_pose_closer():
+    """A bright patch over the face's left side; both fits start at the closed-form pose of the landmarks (weight 0: the
+    start only) and run 10 steps.  Measured here: pose error (max over the 7 entries) 0.39 unmasked, 0.13 masked, 0.13 on
+    the clean target, 0.24 at the start."""
+    g, mesh, face, noise, target = tiny_problem()
+    c_true = torch.from_numpy(synth.det_normal((1, 14), 3)) * face[0].sigma.detach()
+    emb, lmk = tiny_landmarks(face, coeff=c_true)
+    painted = target.clone()
+    painted[:, :, OCCLUDER[0], OCCLUDER[1]] = 1.0
+    mask = torch.ones(1, 1, 16, 16)
+    mask[:, :, OCCLUDER[0], OCCLUDER[1]] = 0.0
+    true = torch.tensor(TRUE_POSE)
+    err = {}
+    for key, kw in (("unmasked", {}), ("masked", {"mask": mask})):
+        inv = _inverter((g, mesh, face, noise, painted), landmarks=lmk, landmark_embedding=emb, landmark_weight=0.0, **kw)
+        hist = inv.run(10)
+        assert torch.isfinite(hist).all()
+        err[key] = float((inv.pose.detach() - true).abs().max())
+    print("pose error after 10 steps: unmasked %.4f, masked %.4f" % (err["unmasked"], err["masked"]))
+    assert err["masked"] < err["unmasked"]
+
+
+# ---- command line ----------------------------------------------------------------------------------------------------
+def test_reconstruct_cli_with_masks(tmp_path):
+    from PIL import Image
+
+    from stylerenderer_amd import align, model, reconstruct
+
+    g = model.GeneratorWithMap(16, 512, 8)
+    synth.fill_state_dict(g.state_dict(), salt=5)
+    ckpt = str(tmp_path / "g.pt")
+    torch.save({"g_ema": g.state_dict()}, ckpt)
+    imgs = []
+    for k, name in enumerate(("face_a", "face_b", "face_c")):
+        path = str(tmp_path / (name + ".png"))
+        pix = (127.5 * (synth.det_uniform((24, 32, 3), 9 + k) + 1)).clip(0, 255).astype(np.uint8)
+        Image.fromarray(pix).save(path)                                  # 24 x 32, resized to 16 on the host
+        imgs.append(path)
+    v0, _ = synth.face_sized_mesh()
+    verts = np.linspace(0, len(v0) - 1, 9).round().astype(np.int64)
+    index = str(tmp_path / "index.txt")
+    np.savetxt(index, verts, fmt="%d")
+    pose = (0.2, -0.1, 0.05, 0.05, -0.04, 0.0, -0.1)
+    lmk16 = project_np(v0[verts].astype(np.float64), pose, (16, 16))
+    lmk_file = str(tmp_path / "lmk.txt")
+    with open(lmk_file, "w") as f:
+        for name in ("face_a", "face_c"):                                # face_b is not listed
+            pts = align.scale_landmarks(lmk16, (16, 16), (24, 32))
+            f.write(name + ".png " + " ".join("%.6f" % x for x in pts.reshape(-1)) + "\n")
+    # a triangulation of the landmarks, 1-based in an .obj (and a vertex line that is not a face)
+    tri_obj = str(tmp_path / "lmk9.obj")
+    with open(tri_obj, "w") as f:
+        f.write("v 0 0 0\nf 1 2 3\nf 3 4 5\n# f 7 8 9\nf  6 7 9\n")
+    mask_dir = tmp_path / "masks"
+    mask_dir.mkdir()
+    grey = np.zeros((24, 32), np.uint8)
+    grey[:, :16] = 255
+    Image.fromarray(grey).save(str(mask_dir / "face_c.png"))
+    np.save(str(mask_dir / "face_a.npy"), np.full((24, 32), 0.5, np.float32))
+    base = [sys.executable, "-m", "stylerenderer_amd.reconstruct", "--size", "16", "--steps", "2", "--n_mean_latent", "64",
+            "--lmk", lmk_file, "--lmk_index", index]
+
+    def run(extra, out, pics=imgs):
+        res = subprocess.run(base + extra + ["--out", out, ckpt] + pics, env=_env(), cwd=str(tmp_path),
+                             capture_output=True, text=True, timeout=900)
+        assert res.returncode == 0, res.stderr[-3000:]
+        return res.stdout
+
+    def outputs(out, name):
+        r = np.load(os.path.join(out, name + ".npz"))
+        png = np.asarray(Image.open(os.path.join(out, name + "_mask.png")))
+        assert png.shape == (16, 16) and png.dtype == np.uint8
+        assert r["mask_area"].shape == () and abs(float(r["mask_area"]) - png.mean() / 255.0) <= 0.5 / 255.0
+        return r, png
+
+    # 1) the landmark polygon, with the triangulation read 1-based, at --batch 2
+    out = str(tmp_path / "out_lmk")
+    run(["--batch", "2", "--mask_lmk", "--mask_tri", tri_obj, "--mask_margin", "1"], out, imgs[:2])
+    ip = np.trunc(lmk16)[None]
+    want = region.grow(region.fill_triangles(ip, np.array([[0, 1, 2], [2, 3, 4], [5, 6, 8]]), (16, 16)), 1)[0, 0].numpy()
+    r, png = outputs(out, "face_a")
+    assert np.array_equal(png, want * 255) and 0 < float(r["mask_area"]) < 1
+    r, png = outputs(out, "face_b")                                         # not listed: all ones
+    assert float(r["mask_area"]) == 1.0 and int(png.min()) == 255
+    # 2) masks from files, multiplied with the hull; a missing file is all ones and is counted
+    out = str(tmp_path / "out_dir")
+    stdout = run(["--mask_dir", str(mask_dir), "--mask_lmk"], out, imgs[1:])
+    assert "masks: 1 of 2 images have no file in" in stdout, stdout
+    hull = region.landmark_region(lmk16[None], None, (16, 16))[0, 0].numpy()
+    _, png = outputs(out, "face_c")
+    # (the file's edge at x = 16 of 32 is blurred over columns 7 and 8 by the antialiased resize the picture gets too)
+    assert np.array_equal(png[:, :7], (hull[:, :7] * 255).astype(np.uint8)) and int(png[:, 9:].max()) == 0
+    assert int(hull[:, :7].sum()) > 0
+    half = reconstruct.load_mask(str(mask_dir / "face_a.npy"), 16)
+    assert half.shape == (1, 1, 16, 16) and float((half - 0.5).abs().max()) <= 1e-6
+    r, _ = outputs(out, "face_b")
+    assert float(r["mask_area"]) == 1.0
+    # 3) the mesh gate alone, in this process (--gpu -1: on the host)
+    out = str(tmp_path / "out_mesh")
+    reconstruct.main(base[3:] + ["--gpu", "-1", "--mask_mesh", "--out", out, ckpt, imgs[0]])
+    r, png = outputs(out, "face_a")
+    assert set(np.unique(png)) == {0, 255} and 0 < float(r["mask_area"]) < 1
+    # refusals name the option
+    for argv, word in ((["--mask_lmk", ckpt, imgs[0]], "--lmk"), (["--mask_margin", "2", ckpt, imgs[0]], "--mask_lmk")):
+        with pytest.raises(SystemExit):
+            reconstruct.main(["--size", "16"] + argv)
+    with pytest.raises(SystemExit, match="mask_margin"):
+        reconstruct.MaskGuide(use_lmk=True, margin=40)
+    assert reconstruct.read_triangulation(tri_obj).tolist() == [[0, 1, 2], [2, 3, 4], [5, 6, 8]]
+    np.savetxt(str(tmp_path / "tri.txt"), np.array([[0, 1, 2], [5, 6, 8]]), fmt="%d")
+    assert reconstruct.read_triangulation(str(tmp_path / "tri.txt")).tolist() == [[0, 1, 2], [5, 6, 8]]
