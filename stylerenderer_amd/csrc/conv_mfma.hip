@@ -37,6 +37,7 @@
 #include "common.h"
 #include "conv1x1_gemm.h"
 #include "conv_s2_bf16x3.h"
+#include "conv_s2_wino.h"
 #include "conv_wgrad_bf16x3.h"
 #include "conv_wino.h"
 
@@ -1041,6 +1042,17 @@ bool wino_enabled() {
     return !(e && e[0] == '0');
 }
 
+// Polyphase 25-product form of the non-transposed stride-2 3x3 convolution (csrc/conv_s2_wino.hip):
+// SR_CONV_S2_WINO=0 keeps k_conv_mfma, =force ignores the workgroup threshold (tests).  0 off, 1 on, 2 forced.
+int s2_wino_mode() {
+    const char* e = std::getenv("SR_CONV_S2_WINO");  // read per call: tests flip it at run time
+    if (e && e[0] == '0') return 0;
+    return (e && e[0] == 'f') ? 2 : 1;
+}
+// The kernel has no K slices: launches with fewer workgroups stay on k_conv_mfma, whose split-K serves them (the
+// threshold k_convt_fused uses for the same reason; measurements in DESIGN.md 4.1y).
+constexpr int64_t S2_WINO_MIN_BLOCKS = 192;
+
 // SR_CONV_ROT=0 keeps the 4-byte halo DMA of the stride-2 kernels (A/B measurements)
 bool rot_enabled() {
     const char* e = std::getenv("SR_CONV_ROT");
@@ -1114,6 +1126,11 @@ extern "C" int64_t sr_conv2d_scratch_floats(int64_t B, int64_t C, int64_t N, int
         if (ksize == 3 && stride == 2 && pad == 0 && sr_wgrad_bf16x3_enabled('c') &&
             sr_conv_s2_bf16x3_eligible(B, C, N, IH, IW, OH, OW)) {
             const int64_t w = sr_conv_s2_bf16x3_scratch_floats(C, N);
+            need = need > w ? need : w;
+        }
+        // (whatever the switch says: it is read per call, the scratch may be sized before it flips)
+        if (ksize == 3 && stride == 2 && pad == 0 && sr_conv_s2_wino_eligible(B, C, N, IH, IW, OH, OW, nullptr, nullptr)) {
+            const int64_t w = sr_conv_s2_wino_scratch_floats(C, N);
             need = need > w ? need : w;
         }
         if (ksize == 3 && stride == 1 && pad == 1 && wino_enabled() &&
@@ -1191,6 +1208,12 @@ extern "C" int sr_conv2d_mfma_ex(float* out, const float* in, const float* wt, c
             // opt-in spike (SR_CONV_SPLIT_BF16=1): split-bf16 matrix path for the down-sampling convolution and the
             // data gradient of the up-sampling one
             return sr_conv_s2_bf16x3_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, OH, OW, scratch, st);
+        if (ksize == 3 && stride == 2 && pad == 0 && scratch) {
+            const int mode = s2_wino_mode();
+            if (mode && sr_conv_s2_wino_eligible(B, C, N, IH, IW, OH, OW, in, out) &&
+                (mode == 2 || sr_conv_s2_wino_blocks(B, N, OH, OW) >= S2_WINO_MIN_BLOCKS))
+                return sr_conv_s2_wino_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, OH, OW, scratch, st);
+        }
         if (ksize == 3 && stride == 1) rc = launch_by_patch<1, 3, 3>(p, st);
         else if (ksize == 3 && stride == 2) rc = launch_by_patch<2, 3, 3>(p, st);
         else if (ksize == 1 && stride == 1) {
