@@ -895,6 +895,35 @@ int sr_region_blend_fwd(float* y, float* m_eff, const float* img, const float* t
 int sr_region_blend_bwd(float* g_img, const float* g_y, const float* m_eff, int64_t B, int64_t C, int64_t H, int64_t W,
                         sr_stream_t stream);
 
+/* UV texture baking of face reconstruction (definition: stylerenderer_amd/op/texture.py), csrc/texture.hip.  A texel map
+ * face int32 [Th, Tw] (-1: empty), coeff [Th, Tw, 3] names the mesh face under every texel and its barycentric weights
+ * (row 0 is the top of the texture); it is shared by the batch.
+ * sr_texture_bake: tex [B, C, Th, Tw] and weight [B, 1, Th, Tw] from the posed mesh v, n [B, nv, 3], tri int64 [nf, 3],
+ *   the picture image [B, C, Hs, Ws] and the z-buffer zbuf [B, Hz, Wz] of the same posed mesh (the rasterizer's: greater z
+ *   is nearer, -FLT_MAX is empty).  For a texel with f = face >= 0, every step one float32 operation in this order:
+ *     P = (c0 v[i0] + c1 v[i1]) + c2 v[i2], i_k = tri[f, k]; N likewise from n;  m = N.z / max(|N|, 1e-12)
+ *     g = smoothstep(clamp((m - lo) / (hi - lo), 0, 1))  (hi == lo: 1 where m > lo, else 0)
+ *     q = ((1 + P.x) Wz / 2 - 1/2, (1 - P.y) Hz / 2 - 1/2); ix = floor(q.x + 1/2), iy = floor(q.y + 1/2)
+ *     vis = 0 <= ix < Wz and 0 <= iy < Hz and P.z >= zbuf[b, iy, ix] - z_bias
+ *     s = the same projection onto (Hs, Ws); inside = -1/2 <= s.x <= Ws - 1/2 and -1/2 <= s.y <= Hs - 1/2
+ *     colour = the bilinear sample of image[b, c] at s, indices clamped to the picture
+ *     weight = g if vis and inside, else 0;  tex = colour where weight > 0, else 0
+ *   An empty texel, and one whose face or vertices lie outside [0, nf) / [0, nv), writes zeros.  One launch; a lane owns
+ *   four consecutive texels of a row, reads their map entries once and walks the B samples; every plane is written with
+ *   16-byte stores when Tw % 4 == 0 and tex, weight are 16-byte aligned, with scalar stores otherwise.
+ * sr_texture_pad: one pass of texture padding, out of place (tex_out != tex_in, filled_out != filled_in).  filled uint8
+ *   [B, 1, Th, Tw].  A filled texel is copied; an unfilled one with at least one filled 8-neighbour becomes filled with the
+ *   sum of those neighbours' colours (added in the order rows top to bottom, left to right) divided by their count; any
+ *   other texel is copied and stays unfilled.  One launch, one lane per texel.
+ * NULL pointers and non-positive sizes are SR_EINVAL before any launch; B, Th or Tw of 0 returns 0.  No atomics, no
+ * scratch, no memset, no allocation, no host read: both run under graph capture on `stream`; reruns are bit-identical. */
+int sr_texture_bake(float* tex, float* weight, const float* v, const float* n, const int64_t* tri, const int32_t* face,
+                    const float* coeff, const float* image, const float* zbuf, int64_t B, int64_t C, int64_t nv,
+                    int64_t nf, int64_t Th, int64_t Tw, int64_t Hs, int64_t Ws, int64_t Hz, int64_t Wz, float facing_lo,
+                    float facing_hi, float z_bias, sr_stream_t stream);
+int sr_texture_pad(float* tex_out, uint8_t* filled_out, const float* tex_in, const uint8_t* filled_in, int64_t B,
+                   int64_t C, int64_t Th, int64_t Tw, sr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

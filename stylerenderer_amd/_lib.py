@@ -151,6 +151,8 @@ SIGNATURES = {
     "sr_region_grow": (_i, [_p, _p, _l, _l, _l, _i, _p]),
     "sr_region_blend_fwd": (_i, [_p] * 6 + [_l] * 4 + [_f] + [_l] * 4 + [_p]),
     "sr_region_blend_bwd": (_i, [_p] * 3 + [_l] * 4 + [_p]),
+    "sr_texture_bake": (_i, [_p] * 9 + [_l] * 10 + [_f, _f, _f, _p]),
+    "sr_texture_pad": (_i, [_p] * 4 + [_l] * 4 + [_p]),
     "sr_signal_bump": (_i, [_p, _p]),
     "sr_signal_wait": (_i, [_p, ctypes.c_uint32, _p]),
     "sr_signal_set": (_i, [_p, _p, _p]),

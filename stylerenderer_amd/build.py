@@ -37,6 +37,7 @@ SOURCES = [
     ("mesh.hip", EXACT),
     ("landmark.hip", EXACT),
     ("region.hip", EXACT),
+    ("texture.hip", EXACT),
     ("morph.hip", []),
     ("skin.hip", []),
     ("blend.hip", []),

@@ -1,0 +1,245 @@
+// UV texture baking of face reconstruction (C ABI: sr_texture_bake / sr_texture_pad; definition:
+// stylerenderer_amd/op/texture.py, bake_composite and pad_host).  A texel map (face int32 [Th, Tw], coeff [Th, Tw, 3],
+// built once per layout by the rasterizer) names for every texel the mesh face under it and its barycentric weights.
+//
+//   k_texture_bake   a gather over texels.  A lane owns four consecutive texels of one row; it reads their map entries
+//                    once and then walks the B samples: the surface point and normal from the posed mesh, the facing
+//                    gate (landmark.hip's smoothstep), the depth test against the sample's z-buffer, the bilinear sample
+//                    of the picture.  Every plane is written with one 16-byte store per lane (V = 4: Tw % 4 == 0 and the
+//                    planes 16-byte aligned) or with scalar stores (V = 1: any width, the tail of a row included).
+//                    An empty texel (face < 0) writes zeros and reads nothing else.  The reads are gathers by nature
+//                    (neighbouring texels share a face or neighbouring faces, neighbouring samples of the picture share
+//                    cache lines); the stores are the coalesced side.
+//   k_texture_pad    one pass of texture padding, one lane per texel: a filled texel is copied, an unfilled one with a
+//                    filled 8-neighbour takes their mean (fixed order: rows top to bottom, left to right) and becomes
+//                    filled.  Out of place: a pass reads the previous pass's state only.
+//
+// The arithmetic is the definition's, one float32 operation per step in the same order: compiled with -ffp-contract=off
+// and correctly rounded division and square root, the results are the host's bit for bit.  Vector stores and plain C++
+// only: no atomics, no scratch, no memset, no host read, so both run under graph capture on the caller's stream.
+#include "common.h"
+
+namespace {
+
+constexpr int TX_BLOCK = 256;
+constexpr float TX_TINY = 1e-12f;
+
+struct BakeArgs {
+    float* tex;            // [B, C, Th, Tw]
+    float* weight;         // [B, 1, Th, Tw]
+    const float* v;        // [B, nv, 3]
+    const float* n;        // [B, nv, 3]
+    const int64_t* tri;    // [nf, 3]
+    const int32_t* face;   // [Th, Tw]
+    const float* coeff;    // [Th, Tw, 3]
+    const float* image;    // [B, C, Hs, Ws]
+    const float* zbuf;     // [B, Hz, Wz]
+    int64_t nv, nf;
+    int B, C, Th, Tw, Hs, Ws, Hz, Wz;
+    float lo, hi, z_bias;
+};
+
+// what one texel of one sample needs to colour its C planes
+struct Tap {
+    int o00, o01, o10, o11;      // offsets into one plane of the picture
+    float fx, fy, w;
+};
+
+template <int V>
+__device__ __forceinline__ void store_group(float* p, const float* x, int count) {
+    if constexpr (V == 4) {
+        *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < count) p[j] = x[j];
+    }
+}
+
+template <int V>
+__global__ __launch_bounds__(TX_BLOCK) void k_texture_bake(BakeArgs a) {
+    const int groups = (a.Tw + 3) >> 2;                                   // lanes per row
+    const int64_t item = (int64_t)blockIdx.x * TX_BLOCK + threadIdx.x;
+    if (item >= (int64_t)a.Th * groups) return;
+    const int ty = (int)(item / groups), tx0 = (int)(item % groups) * 4;
+    const int count = min(4, a.Tw - tx0);
+    const int64_t t0 = (int64_t)ty * a.Tw + tx0;                           // first texel of the lane
+    const int64_t plane = (int64_t)a.Th * a.Tw;
+
+    // the map: read once per texel, shared by the batch.  A face or a vertex outside the mesh counts as empty.
+    int i0[4], i1[4], i2[4];                                             // 3 * vertex: nv < 2^31 / 3 (the entry point checks)
+    float c0[4], c1[4], c2[4];
+    bool live[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        live[j] = false;
+        i0[j] = i1[j] = i2[j] = 0;
+        c0[j] = c1[j] = c2[j] = 0.f;
+        if (j < count) {
+            const int f = a.face[t0 + j];
+            if (f >= 0 && f < a.nf) {
+                const int64_t t0v = a.tri[3 * (int64_t)f], t1v = a.tri[3 * (int64_t)f + 1], t2v = a.tri[3 * (int64_t)f + 2];
+                live[j] = t0v >= 0 && t0v < a.nv && t1v >= 0 && t1v < a.nv && t2v >= 0 && t2v < a.nv;
+                if (live[j]) i0[j] = 3 * (int)t0v, i1[j] = 3 * (int)t1v, i2[j] = 3 * (int)t2v;
+                c0[j] = a.coeff[3 * (t0 + j)];
+                c1[j] = a.coeff[3 * (t0 + j) + 1];
+                c2[j] = a.coeff[3 * (t0 + j) + 2];
+            }
+        }
+    }
+    const float half_ws = 0.5f * (float)a.Ws, half_hs = 0.5f * (float)a.Hs;
+    const float half_wz = 0.5f * (float)a.Wz, half_hz = 0.5f * (float)a.Hz;
+    const float span = a.hi - a.lo;
+
+    for (int b = 0; b < a.B; ++b) {
+        const float* vb = a.v + (int64_t)b * a.nv * 3;
+        const float* nb = a.n + (int64_t)b * a.nv * 3;
+        const float* zb = a.zbuf + (int64_t)b * a.Hz * a.Wz;
+        Tap tap[4];
+        float wt[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            tap[j].o00 = tap[j].o01 = tap[j].o10 = tap[j].o11 = 0;
+            tap[j].fx = tap[j].fy = tap[j].w = 0.f;
+            wt[j] = 0.f;
+            if (!live[j]) continue;
+            const float *pa = vb + i0[j], *pb = vb + i1[j], *pc = vb + i2[j];
+            const float px = (c0[j] * pa[0] + c1[j] * pb[0]) + c2[j] * pc[0];
+            const float py = (c0[j] * pa[1] + c1[j] * pb[1]) + c2[j] * pc[1];
+            const float pz = (c0[j] * pa[2] + c1[j] * pb[2]) + c2[j] * pc[2];
+            const float *na = nb + i0[j], *nbv = nb + i1[j], *nc = nb + i2[j];
+            const float nx = (c0[j] * na[0] + c1[j] * nbv[0]) + c2[j] * nc[0];
+            const float ny = (c0[j] * na[1] + c1[j] * nbv[1]) + c2[j] * nc[1];
+            const float nz = (c0[j] * na[2] + c1[j] * nbv[2]) + c2[j] * nc[2];
+            // the facing gate
+            const float m = nz / fmaxf(sqrtf((nx * nx + ny * ny) + nz * nz), TX_TINY);
+            float g;
+            if (a.hi > a.lo) {
+                const float t = fminf(fmaxf((m - a.lo) / span, 0.f), 1.f);
+                g = t * t * (3.f - 2.f * t);
+            } else {
+                g = m > a.lo ? 1.f : 0.f;
+            }
+            // the depth test at the nearest pixel of the z-buffer (it keeps the greater z)
+            const float qx = floorf(((1.f + px) * half_wz - 0.5f) + 0.5f);
+            const float qy = floorf(((1.f - py) * half_hz - 0.5f) + 0.5f);
+            bool vis = qx >= 0.f && qx < (float)a.Wz && qy >= 0.f && qy < (float)a.Hz;
+            if (vis) vis = pz >= zb[(int64_t)(int)qy * a.Wz + (int)qx] - a.z_bias;
+            // the picture
+            const float sx = (1.f + px) * half_ws - 0.5f, sy = (1.f - py) * half_hs - 0.5f;
+            const bool inside = sx >= -0.5f && sx <= (float)a.Ws - 0.5f && sy >= -0.5f && sy <= (float)a.Hs - 0.5f;
+            const float w = (vis && inside) ? g : 0.f;
+            wt[j] = w;
+            if (w > 0.f) {
+                const float x0f = floorf(sx), y0f = floorf(sy);
+                const int x0 = (int)x0f, y0 = (int)y0f;                    // in [-1, Ws - 1] x [-1, Hs - 1]: inside
+                const int xa = max(x0, 0), xb = min(x0 + 1, a.Ws - 1), ya = max(y0, 0), yb = min(y0 + 1, a.Hs - 1);
+                tap[j].o00 = ya * a.Ws + xa;
+                tap[j].o01 = ya * a.Ws + xb;
+                tap[j].o10 = yb * a.Ws + xa;
+                tap[j].o11 = yb * a.Ws + xb;
+                tap[j].fx = sx - x0f;
+                tap[j].fy = sy - y0f;
+                tap[j].w = w;
+            }
+        }
+        store_group<V>(a.weight + (int64_t)b * plane + t0, wt, count);
+        for (int c = 0; c < a.C; ++c) {
+            const float* img = a.image + ((int64_t)b * a.C + c) * a.Hs * a.Ws;
+            float col[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                col[j] = 0.f;
+                if (tap[j].w > 0.f) {
+                    const float fx = tap[j].fx, fy = tap[j].fy;
+                    const float top = (1.f - fx) * img[tap[j].o00] + fx * img[tap[j].o01];
+                    const float bot = (1.f - fx) * img[tap[j].o10] + fx * img[tap[j].o11];
+                    col[j] = top * (1.f - fy) + bot * fy;
+                }
+            }
+            store_group<V>(a.tex + ((int64_t)b * a.C + c) * plane + t0, col, count);
+        }
+    }
+}
+
+__global__ __launch_bounds__(TX_BLOCK) void k_texture_pad(float* __restrict__ tex_out, uint8_t* __restrict__ filled_out,
+                                                          const float* __restrict__ tex_in,
+                                                          const uint8_t* __restrict__ filled_in, int C, int Th, int Tw,
+                                                          int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * TX_BLOCK + threadIdx.x;       // over B Th Tw
+    if (i >= total) return;
+    const int64_t plane = (int64_t)Th * Tw;
+    const int64_t b = i / plane, pix = i % plane;
+    const int ty = (int)(pix / Tw), tx = (int)(pix % Tw);
+    const uint8_t* fin = filled_in + b * plane;
+    const float* tin = tex_in + b * C * plane;
+    float* tout = tex_out + b * C * plane;
+    if (fin[pix]) {
+        for (int c = 0; c < C; ++c) tout[c * plane + pix] = tin[c * plane + pix];
+        filled_out[i] = 1;
+        return;
+    }
+    // the filled 8-neighbours inside the picture, rows top to bottom, left to right
+    unsigned mask = 0;                                                    // bit k: neighbour k counts
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int s = k < 4 ? k : k + 1;                                  // (the window's slot: the centre is skipped)
+        const int y = ty + s / 3 - 1, x = tx + s % 3 - 1;
+        if (y >= 0 && y < Th && x >= 0 && x < Tw && fin[(int64_t)y * Tw + x]) mask |= 1u << k;
+    }
+    const int count = __popc(mask);
+    for (int c = 0; c < C; ++c) {
+        const float* src = tin + c * plane;
+        float out = src[pix];
+        if (count > 0) {
+            float acc = 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int s = k < 4 ? k : k + 1;
+                if (mask >> k & 1u) acc += src[pix + (int64_t)(s / 3 - 1) * Tw + (s % 3 - 1)];
+            }
+            out = acc / (float)count;
+        }
+        tout[c * plane + pix] = out;
+    }
+    filled_out[i] = count > 0 ? 1 : 0;
+}
+
+}  // namespace
+
+extern "C" int sr_texture_bake(float* tex, float* weight, const float* v, const float* n, const int64_t* tri,
+                               const int32_t* face, const float* coeff, const float* image, const float* zbuf, int64_t B,
+                               int64_t C, int64_t nv, int64_t nf, int64_t Th, int64_t Tw, int64_t Hs, int64_t Ws,
+                               int64_t Hz, int64_t Wz, float facing_lo, float facing_hi, float z_bias,
+                               sr_stream_t stream) {
+    if (B < 0 || C < 1 || nv < 1 || nf < 1 || Th < 0 || Tw < 0 || Hs < 1 || Ws < 1 || Hz < 1 || Wz < 1) return SR_EINVAL;
+    if (!(facing_lo <= facing_hi) || !(z_bias >= 0.f)) return SR_EINVAL;
+    if (B == 0 || Th == 0 || Tw == 0) return SR_OK;
+    if (!tex || !weight || !v || !n || !tri || !face || !coeff || !image || !zbuf) return SR_EINVAL;
+    if (B > 65535 || C > 65535 || Th > (1 << 20) || Tw > (1 << 20) || Hs * Ws >= (1LL << 31) || Hz * Wz >= (1LL << 31) ||
+        3 * nv >= (1LL << 31) || nf >= (1LL << 31))
+        return SR_ERANGE;
+    BakeArgs a;
+    a.tex = tex, a.weight = weight, a.v = v, a.n = n, a.tri = tri, a.face = face, a.coeff = coeff, a.image = image;
+    a.zbuf = zbuf, a.nv = nv, a.nf = nf, a.B = (int)B, a.C = (int)C, a.Th = (int)Th, a.Tw = (int)Tw, a.Hs = (int)Hs;
+    a.Ws = (int)Ws, a.Hz = (int)Hz, a.Wz = (int)Wz, a.lo = facing_lo, a.hi = facing_hi, a.z_bias = z_bias;
+    const int64_t items = Th * ((Tw + 3) / 4);
+    const dim3 grid((unsigned)sr_ceil_div(items, TX_BLOCK));
+    if (Tw % 4 == 0 && sr_aligned16(tex) && sr_aligned16(weight))
+        hipLaunchKernelGGL(k_texture_bake<4>, grid, dim3(TX_BLOCK), 0, sr_stream(stream), a);
+    else
+        hipLaunchKernelGGL(k_texture_bake<1>, grid, dim3(TX_BLOCK), 0, sr_stream(stream), a);
+    return sr_launch_status();
+}
+
+extern "C" int sr_texture_pad(float* tex_out, uint8_t* filled_out, const float* tex_in, const uint8_t* filled_in,
+                              int64_t B, int64_t C, int64_t Th, int64_t Tw, sr_stream_t stream) {
+    if (B < 0 || C < 1 || Th < 0 || Tw < 0) return SR_EINVAL;
+    if (B == 0 || Th == 0 || Tw == 0) return SR_OK;
+    if (!tex_out || !filled_out || !tex_in || !filled_in || tex_out == tex_in || filled_out == filled_in) return SR_EINVAL;
+    if (Th > (1 << 20) || Tw > (1 << 20) || C > 65535 || B * Th * Tw > (int64_t)0x7fffffff * TX_BLOCK) return SR_ERANGE;
+    const int64_t total = B * Th * Tw;
+    hipLaunchKernelGGL(k_texture_pad, dim3((unsigned)sr_ceil_div(total, TX_BLOCK)), dim3(TX_BLOCK), 0, sr_stream(stream),
+                       tex_out, filled_out, tex_in, filled_in, (int)C, (int)Th, (int)Tw, total);
+    return sr_launch_status();
+}

@@ -22,7 +22,8 @@ What the fitting loop (inversion.LatentInverter, reconstruct) asks of a model, t
     landmarks                      (idx int32 [L, 3], bary float32 [L, 3]) of `landmark_embedding`, or None: the model's own
                                    landmarks (load_bfm: the file's `landmarks68`), for the landmark term of the fit
 `contour_lines` builds, from any model's mean shape, the candidate lines along which the jaw landmarks of that term slide
-with the pose (op.landmark); `load_contour_lines` reads hand-made ones."""
+with the pose (op.landmark); `load_contour_lines` reads hand-made ones.  `uv_layout` computes a texture layout from a mean
+shape and `load_uv` reads one from a file, for op.texture."""
 import numpy as np
 import torch
 from torch import nn
@@ -183,6 +184,80 @@ def landmark_vertices(embedding):
     """The main vertex [L] (int64, host) of every landmark of an embedding: the one of its largest weight."""
     idx, bary = (host_array(t) for t in embedding)
     return idx.astype(np.int64)[np.arange(len(idx)), np.argmax(bary, 1)]
+
+
+# ---- texture layouts (op.texture) ------------------------------------------------------------------------------------
+def uv_layout(v_mean, tri, margin=1.0 / 64):
+    """(uv float32 [nv, 2], tri_uv int64 [nf, 3], keep bool [nf]): a cylindrical unwrap of the mean shape v_mean [nv, 3]
+    about the vertical axis through its centroid (cx, ., cz), for op.texture.texel_map:
+        theta = atan2(x - cx, z - cz)      u = theta / 2 pi + 1/2      v = (y - y_min) / (y_max - y_min)
+    both then mapped affinely from [0, 1] into [margin, 1 - margin]; one texture coordinate per vertex, so tri_uv = tri.
+    keep[f] is false for the faces that straddle the seam at the back (max u - min u > 1/2 before the margin map): they
+    would smear across the whole texture and are left out of it.  No file of the supported models carries a layout (a
+    Basel file has none); this one is meant for face patches and convex heads, where a ray from the axis meets the
+    surface once; a vertex on the axis itself (the pole of a closed head) has no angle of its own and lands wherever the
+    centroid's rounding puts it.  A template's own layout (FLAME's) comes in through `load_uv`."""
+    raw = host_array(v_mean).reshape(-1, 3)
+    v = raw.astype(np.float64)
+    t = host_array(tri).astype(np.int64).reshape(-1, 3)
+    if not 0 <= float(margin) < 0.5:
+        raise ValueError("uv_layout: margin lies in [0, 1/2)")
+    if t.size and (t.min() < 0 or t.max() >= len(v)):
+        raise ValueError("uv_layout: triangle index out of range [0, %d)" % len(v))
+    c = raw.mean(0).astype(np.float64)                      # (the centroid in the mean shape's own float type)
+    u = np.arctan2(v[:, 0] - c[0], v[:, 2] - c[2]) / (2 * np.pi) + 0.5
+    span = v[:, 1].max() - v[:, 1].min()
+    w = (v[:, 1] - v[:, 1].min()) / (span if span > 0 else 1.0)
+    ut = u[t]
+    keep = (ut.max(1) - ut.min(1)) <= 0.5
+    uv = float(margin) + np.stack((u, w), 1) * (1 - 2 * float(margin))
+    return (torch.from_numpy(uv.astype(np.float32)), torch.from_numpy(t.copy()), torch.from_numpy(keep))
+
+
+def load_uv(path, tri):
+    """(uv float32 [nt, 2], tri_uv int64 [nf, 3]) of a layout file for the mesh `tri` [nf, 3]: a Wavefront .obj with `vt`
+    lines and `f a/t[/n]` records (1-based; the `a` columns must equal tri row by row), or an .npz with `vt` [nt, 2] and
+    `ft` [nf, 3] (0-based).  This is how a template's own layout (FLAME's head_template.obj) comes in."""
+    path = str(path)
+    t = host_array(tri).astype(np.int64).reshape(-1, 3)
+    if path.lower().endswith(".npz"):
+        with np.load(path, allow_pickle=False) as z:
+            missing = [k for k in ("vt", "ft") if k not in z.files]
+            if missing:
+                raise ValueError("load_uv: %s lacks %s" % (path, ", ".join(missing)))
+            vt, ft = np.asarray(z["vt"], np.float64), np.asarray(z["ft"])
+        if not np.all(np.round(ft) == ft):
+            raise ValueError("load_uv: %s: ft holds whole numbers" % path)
+        ft = ft.astype(np.int64)
+    else:
+        vt, fa, ft = [], [], []
+        with open(path) as f:
+            for line in f:
+                tok = line.split()
+                if not tok:
+                    continue
+                if tok[0] == "vt":
+                    vt.append([float(x) for x in tok[1:3]])
+                elif tok[0] == "f":
+                    parts = [c.split("/") for c in tok[1:]]
+                    if len(parts) != 3 or any(len(p) < 2 or not p[1] for p in parts):
+                        raise ValueError("load_uv: %s: every face must be a triangle of a/t[/n] records, got %r"
+                                         % (path, line.strip()))
+                    fa.append([int(p[0]) - 1 for p in parts])
+                    ft.append([int(p[1]) - 1 for p in parts])
+        vt = np.asarray(vt, np.float64).reshape(-1, 2)
+        fa, ft = np.asarray(fa, np.int64).reshape(-1, 3), np.asarray(ft, np.int64).reshape(-1, 3)
+        if fa.shape != t.shape or not np.array_equal(fa, t):
+            raise ValueError("load_uv: the faces of %s differ from the mesh's tri (%d faces against %d, or other vertices): "
+                             "the layout must list the model's triangles row by row" % (path, len(fa), len(t)))
+    if vt.ndim != 2 or vt.shape[1] != 2 or ft.shape != t.shape:
+        raise ValueError("load_uv: %s: vt [nt, 2] and one texture triangle per face (%d) are needed, got %s and %s"
+                         % (path, len(t), vt.shape, ft.shape))
+    if ft.size and (ft.min() < 0 or ft.max() >= len(vt)):
+        raise ValueError("load_uv: %s: texture coordinate index out of range [0, %d)" % (path, len(vt)))
+    if vt.size and not (np.isfinite(vt).all() and vt.min() >= 0 and vt.max() <= 1):
+        raise ValueError("load_uv: %s: texture coordinates must lie in [0, 1]" % path)
+    return torch.from_numpy(vt.astype(np.float32)), torch.from_numpy(np.ascontiguousarray(ft))
 
 
 class LinearMorphableModel(nn.Module):

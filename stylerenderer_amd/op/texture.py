@@ -1,0 +1,364 @@
+"""UV texture baking of face reconstruction: the picture's colours carried onto the fitted surface (csrc/texture.hip).
+
+A layout gives the mesh texture coordinates: uv [nt, 2] in [0, 1] with v pointing up and tri_uv [nf, 3], row-parallel to
+the mesh's tri (face_model.uv_layout computes one, face_model.load_uv reads one).  Texel (ty, tx) of a (Th, Tw) texture
+has its centre at u = (tx + 1/2) / Tw, v = 1 - (ty + 1/2) / Th: row 0 is the top of the image, as OBJ viewers expect.
+
+  texel_map   (face int32 [Th, Tw], coeff float32 [Th, Tw, 3]): the face under every texel centre (-1: none) and its
+              barycentric weights, drawn by op.rasterize's forward (no second rasterizer) and cached per layout and size.
+  bake        (tex [B, C, Th, Tw], weight [B, 1, Th, Tw]).  For sample b and a texel with f = face >= 0, every step one
+              operation of the tensors' float type, in this order:
+                  P  = (c0 v[i0] + c1 v[i1]) + c2 v[i2]         i_k = tri[f, k];  N likewise from n
+                  m  = N.z / max(|N|, 1e-12)                    |N| = sqrt((N.x^2 + N.y^2) + N.z^2)
+                  g  = smoothstep(clamp((m - lo) / (hi - lo), 0, 1))     hi == lo: a step at m > lo (op.landmark's gate)
+                  q  = project(P, (Hz, Wz));  ix = floor(q.x + 1/2), iy = floor(q.y + 1/2)
+                  vis = 0 <= ix < Wz and 0 <= iy < Hz and P.z >= zbuf[b, iy, ix] - z_bias
+                  s  = project(P, (Hs, Ws));  inside = -1/2 <= s.x <= Ws - 1/2 and -1/2 <= s.y <= Hs - 1/2
+                  x0 = floor(s.x), fx = s.x - x0, likewise y;  indices clamped to the picture (replicate)
+                  colour = ((1 - fx) I[y0, x0] + fx I[y0, x1]) (1 - fy) + ((1 - fx) I[y1, x0] + fx I[y1, x1]) fy
+                  weight = g where vis and inside, else 0;   tex = colour where weight > 0, else 0
+              project is op.landmark's, the picture's pixel convention.  The rasterizer keeps the greater z; an empty
+              z-buffer pixel holds -FLT_MAX and occludes nothing.  An empty texel gives tex = 0 and weight = 0.
+  pad         texture padding, so that a renderer's bilinear filter does not bleed black across chart borders.
+  fill_mean   what is still unfilled gets the sample's weight-weighted mean colour.
+
+CPU tensors and float64 take the torch composites `bake_composite` and `pad_host`, which are the definition.  Float32
+device tensors take sr_texture_bake / sr_texture_pad through the C ABI: one launch per bake and one per padding pass,
+nothing allocated by the launch and nothing read back, so the calls can be captured.  The kernels are compiled without
+contraction and with correctly rounded division and square root: weight, tex and the padding are the host float32
+definition's bit for bit.  Under SR_STRICT_NATIVE=1 nothing falls to a library: a device tensor the kernels do not take
+(float64) raises.
+
+Non-square sizes.  op.rasterize reproduces the reference's call convention, which swaps the two extents of a non-square
+picture: only square pictures come out right.  `texel_map` and `depth_buffer` therefore draw a non-square
+(H, W) inside a square of side max(H, W), with the vertices scaled so that pixel (y, x) of the top left H x W block is
+the pixel `project(., (H, W))` means, and crop.  For a square size the vertices are the plain (2u - 1, 2v - 1, 0).
+
+z_bias defaults to 4 / max(Hz, Wz); like the command line's facing = (0.1, 0.4) it is a starting value, not tuned on any
+trained checkpoint.
+"""
+import numpy as np
+import torch
+
+from .. import _lib
+from ._dispatch import DerivedCache, is_device_tensor, on_device_of, stream_of, strict_native
+from .landmark import _hw, project
+from .rasterize import forward as _raster_forward, forward_with_depth as _raster_depth
+
+TINY = 1e-12
+MAX_PASSES = 64
+
+
+# ---- the texel map ---------------------------------------------------------------------------------------------------
+_MAP_CACHE = DerivedCache(8)
+
+
+def _square_vertices(x, y, size):
+    """Model coordinates (x, y in [-1, 1], y up) of an (H, W) picture -> the same points in the square picture of side
+    S = max(H, W) whose top left H x W block is that picture; the identity for a square size."""
+    h, w = size
+    s = max(h, w)
+    if h == w:
+        return x, y
+    return (1 + x) * (w / s) - 1, 1 - (1 - y) * (h / s)
+
+
+def texel_map(uv, tri_uv, size, keep=None):
+    """(face int32 [Th, Tw], coeff float32 [Th, Tw, 3]) of the layout uv [nt, 2], tri_uv [nf, 3] at size = T or (Th, Tw),
+    on uv's device.  face is the face whose uv triangle covers the texel's centre, -1 where there is none (all three
+    coefficients 0: the rasterizer's convention for an uncovered pixel); coeff[..., k] belongs to corner k of that face.
+    Drawn are the faces with keep[f] true (default: all) and a non-zero uv area; where faces overlap in uv, the one drawn
+    first (the lowest face number) wins.  The rasterizer culls one winding, so a face with the culled sign is drawn with
+    corners 1 and 2 swapped and its two coefficients are swapped back.  Cached per layout tensors and size."""
+    th, tw = _hw(size)
+    if th < 1 or tw < 1:
+        raise ValueError("texel_map: size must be positive, got (%d, %d)" % (th, tw))
+    if uv.dim() != 2 or uv.shape[1] != 2 or tri_uv.dim() != 2 or tri_uv.shape[1] != 3:
+        raise ValueError("texel_map: uv [nt, 2] and tri_uv [nf, 3], got %s and %s" % (tuple(uv.shape), tuple(tri_uv.shape)))
+    key = (uv.data_ptr(), tri_uv.data_ptr(), tuple(uv.shape), tuple(tri_uv.shape), uv._version, tri_uv._version,
+           str(uv.device), str(tri_uv.device), uv.dtype, th, tw,
+           None if keep is None else (keep.data_ptr(), keep._version, str(keep.device)))
+    hit = _MAP_CACHE.get(key)
+    if hit is not None:
+        return hit[0], hit[1]
+    dev = uv.device
+    uvh = uv.detach().cpu().numpy().astype(np.float32)
+    th_ = tri_uv.detach().cpu().numpy().astype(np.int64)
+    nf, nt = th_.shape[0], uvh.shape[0]
+    if th_.size and (th_.min() < 0 or th_.max() >= nt):
+        raise ValueError("texel_map: texture coordinate index out of range [0, %d)" % nt)
+    if uvh.size and not (np.isfinite(uvh).all() and uvh.min() >= 0 and uvh.max() <= 1):
+        raise ValueError("texel_map: uv must lie in [0, 1]")
+    kh = np.ones(nf, bool) if keep is None else keep.detach().cpu().numpy().astype(bool).reshape(-1)
+    if kh.shape[0] != nf:
+        raise ValueError("texel_map: keep must have one entry per face (%d), got %d" % (nf, kh.shape[0]))
+    p = uvh.astype(np.float64)[th_]                                             # [nf, 3, 2]
+    area = ((p[:, 1, 0] - p[:, 0, 0]) * (p[:, 2, 1] - p[:, 0, 1])
+            - (p[:, 2, 0] - p[:, 0, 0]) * (p[:, 1, 1] - p[:, 0, 1]))            # twice the signed uv area
+    drawn = np.nonzero(kh & (area != 0))[0]
+    flip = area[drawn] < 0                                                      # the winding the rasterizer culls
+    corners = th_[drawn]
+    corners[flip] = corners[flip][:, [0, 2, 1]]
+    nd = drawn.shape[0]
+    face = torch.full((th, tw), -1, dtype=torch.int32, device=dev)
+    coeff = torch.zeros((th, tw, 3), dtype=torch.float32, device=dev)
+    if nd:
+        pts = uvh[corners.reshape(-1)]                                          # [3 nd, 2] float32
+        x, y = _square_vertices(2 * pts[:, 0] - 1, 2 * pts[:, 1] - 1, (th, tw))
+        verts = np.stack((x, y, np.zeros_like(x)), 1).astype(np.float32)
+        s = max(th, tw)
+        vt = torch.from_numpy(verts).to(dev)
+        tt = torch.arange(3 * nd, dtype=torch.int64, device=dev).view(nd, 3)
+        index, c = _raster_forward(vt, tt, s, s)
+        index, c = index[:th, :tw], c[:th, :tw]
+        covered = (c != 0).any(-1)
+        slot = torch.div(index[..., 0], 3, rounding_mode="floor")                # the drawn face: index holds vertex ids
+        drawn_t = torch.from_numpy(drawn).to(dev)
+        flip_t = torch.from_numpy(flip).to(dev)
+        face = torch.where(covered, drawn_t[slot], torch.full_like(slot, -1)).to(torch.int32)
+        swapped = flip_t[slot] & covered
+        coeff = torch.where(swapped.unsqueeze(-1), c[..., [0, 2, 1]], c)
+        coeff = torch.where(covered.unsqueeze(-1), coeff, torch.zeros_like(coeff)).contiguous()
+        face = face.contiguous()
+    _MAP_CACHE.put(key, (face, coeff, uv, tri_uv, keep))                         # (the key holds their addresses)
+    return face, coeff
+
+
+def texel_centres(size, dtype=torch.float64):
+    """uv [Th, Tw, 2] of the texel centres."""
+    th, tw = _hw(size)
+    u = (torch.arange(tw, dtype=dtype) + 0.5) / tw
+    v = 1 - (torch.arange(th, dtype=dtype) + 0.5) / th
+    return torch.stack((u.view(1, tw).expand(th, tw), v.view(th, 1).expand(th, tw)), -1)
+
+
+def depth_buffer(v, tri, size):
+    """zbuf [B, Hz, Wz] of the posed mesh v [B, nv, 3], tri [nf, 3] in the pixels `project(., (Hz, Wz))` means: the
+    rasterizer's z-buffer (`forward_with_depth`; greater z is nearer, -FLT_MAX is empty).  A non-square size is drawn
+    in a square and cropped (see the module's note)."""
+    hz, wz = _hw(size)
+    if hz != wz:
+        x, y = _square_vertices(v[..., 0], v[..., 1], (hz, wz))
+        v = torch.stack((x, y, v[..., 2]), -1)
+    s = max(hz, wz)
+    zbuf = _raster_depth(v.contiguous(), tri.contiguous(), s, s)[2]
+    return zbuf[:, :hz, :wz].contiguous()
+
+
+# ---- bake ------------------------------------------------------------------------------------------------------------
+def _facing(facing, dtype):
+    """(lo, hi, hi - lo) as Python floats that hold the values of the tensors' float type: float32 takes the difference of
+    the rounded ends, as the kernel does."""
+    lo, hi = float(facing[0]), float(facing[1])
+    if not lo <= hi:
+        raise ValueError("bake: facing = (lo, hi) needs lo <= hi, got (%g, %g)" % (lo, hi))
+    if dtype == torch.float32:
+        lo32, hi32 = np.float32(lo), np.float32(hi)
+        return float(lo32), float(hi32), float(np.float32(hi32 - lo32))
+    return lo, hi, hi - lo
+
+
+def _check_bake(v, n, tri, face, coeff, image, zbuf):
+    if v.dim() != 3 or v.shape[2] != 3 or tuple(n.shape) != tuple(v.shape):
+        raise ValueError("bake: v and n must both be [B, nv, 3], got %s and %s" % (tuple(v.shape), tuple(n.shape)))
+    if tri.dim() != 2 or tri.shape[1] != 3 or tri.dtype != torch.int64:
+        raise ValueError("bake: tri must be int64 [nf, 3]")
+    if face.dim() != 2 or face.dtype != torch.int32 or tuple(coeff.shape) != tuple(face.shape) + (3,):
+        raise ValueError("bake: face int32 [Th, Tw] and coeff [Th, Tw, 3] of texel_map, got %s and %s"
+                         % (tuple(face.shape), tuple(coeff.shape)))
+    b = v.shape[0]
+    if image.dim() != 4 or image.shape[0] != b or zbuf.dim() != 3 or zbuf.shape[0] != b:
+        raise ValueError("bake: %d samples need image [B, C, Hs, Ws] and zbuf [B, Hz, Wz], got %s and %s"
+                         % (b, tuple(image.shape), tuple(zbuf.shape)))
+    if min(image.shape[1:]) < 1 or min(zbuf.shape[1:]) < 1 or v.shape[1] < 1 or tri.shape[0] < 1:
+        raise ValueError("bake: empty mesh, picture or z-buffer")
+
+
+def _div(a, b):
+    """a / b rounded once to the tensors' float type.  For float32 the quotient is taken in float64 and rounded: with 53
+    bits against 24 that is the correctly rounded float32 quotient, whatever the host's vector library does."""
+    if a.dtype == torch.float32:
+        return (a.double() / (b.double() if isinstance(b, torch.Tensor) else float(b))).float()
+    return a / b
+
+
+def _sqrt(a):
+    """sqrt rounded once to the tensor's float type (float32: through float64, as `_div`; torch's vectorised float32
+    sqrt on the host is not correctly rounded on every CPU)."""
+    return torch.sqrt(a.double()).float() if a.dtype == torch.float32 else torch.sqrt(a)
+
+
+def bake_composite(v, n, tri, face, coeff, image, zbuf, facing, z_bias, parts=False):
+    """The defining tensor algebra, in v's float type: (tex [B, C, Th, Tw], weight [B, 1, Th, Tw]); with parts=True also
+    (vis, inside) bool [B, Th, Tw], the two decisions (False on empty texels)."""
+    dt, dev = v.dtype, v.device
+    lo, hi, span = _facing(facing, dt)
+    b, c_n, hs, ws = image.shape
+    hz, wz = int(zbuf.shape[1]), int(zbuf.shape[2])
+    th, tw = face.shape
+    live = face >= 0
+    f = face.long().clamp_min(0).reshape(-1)
+    corner = tri.to(dev)[f]                                                      # [T, 3]
+    cf = coeff.to(dt).reshape(-1, 3)
+
+    def mix(a):                                                                  # [B, nv, 3] -> [B, T, 3]
+        return (cf[:, 0:1] * a[:, corner[:, 0]] + cf[:, 1:2] * a[:, corner[:, 1]]) + cf[:, 2:3] * a[:, corner[:, 2]]
+
+    p, nn = mix(v), mix(n.to(dt))
+    length = _sqrt((nn[..., 0] * nn[..., 0] + nn[..., 1] * nn[..., 1]) + nn[..., 2] * nn[..., 2])
+    m = _div(nn[..., 2], length.clamp_min(TINY))
+    if hi > lo:
+        t = _div(m - lo, span).clamp(0.0, 1.0)
+        g = t * t * (3.0 - 2.0 * t)
+    else:
+        g = (m > lo).to(dt)
+    q = project(p, (hz, wz))
+    qx, qy = torch.floor(q[..., 0] + 0.5), torch.floor(q[..., 1] + 0.5)
+    on = (qx >= 0) & (qx < wz) & (qy >= 0) & (qy < hz)
+    zero = torch.zeros_like(qx)
+    at = torch.where(on, qy, zero).long() * wz + torch.where(on, qx, zero).long()
+    depth = torch.gather(zbuf.to(dt).reshape(b, -1), 1, at)
+    vis = on & (p[..., 2] >= depth - float(z_bias))
+    s = project(p, (hs, ws))
+    sx, sy = s[..., 0], s[..., 1]
+    inside = (sx >= -0.5) & (sx <= ws - 0.5) & (sy >= -0.5) & (sy <= hs - 0.5)
+    lv = live.reshape(1, -1)
+    vis, inside = vis & lv, inside & lv
+    weight = torch.where(vis & inside, g, torch.zeros_like(g))
+    take = weight > 0
+    x0f, y0f = torch.floor(torch.where(take, sx, zero)), torch.floor(torch.where(take, sy, zero))
+    fx, fy = torch.where(take, sx, zero) - x0f, torch.where(take, sy, zero) - y0f
+    x0, y0 = x0f.long(), y0f.long()
+    xa, xb = x0.clamp(0, ws - 1), (x0 + 1).clamp(0, ws - 1)
+    ya, yb = y0.clamp(0, hs - 1), (y0 + 1).clamp(0, hs - 1)
+    flat = image.to(dt).reshape(b, c_n, hs * ws)
+
+    def tap(yy, xx):
+        return torch.gather(flat, 2, (yy * ws + xx).unsqueeze(1).expand(-1, c_n, -1))
+
+    fx, fy = fx.unsqueeze(1), fy.unsqueeze(1)
+    top = (1.0 - fx) * tap(ya, xa) + fx * tap(ya, xb)
+    bot = (1.0 - fx) * tap(yb, xa) + fx * tap(yb, xb)
+    colour = top * (1.0 - fy) + bot * fy
+    tex = torch.where(take.unsqueeze(1), colour, torch.zeros_like(colour))
+    out = tex.view(b, c_n, th, tw), weight.view(b, 1, th, tw)
+    if parts:
+        return out + (vis.view(b, th, tw), inside.view(b, th, tw))
+    return out
+
+
+def native_ok(*tensors):
+    return all(is_device_tensor(t) and t.dtype == torch.float32 for t in tensors)
+
+
+def bake(v, n, tri, face, coeff, image, zbuf, facing=(0.1, 0.4), z_bias=None):
+    """(tex [B, C, Th, Tw], weight [B, 1, Th, Tw]): the picture image [B, C, Hs, Ws] (any resolution) carried onto the
+    texels of the map (face, coeff) of `texel_map` through the posed mesh v, n [B, nv, 3], tri [nf, 3] and its z-buffer
+    zbuf [B, Hz, Wz] (`depth_buffer`, or `forward_with_depth` at a square size).  weight in [0, 1] fades a texel out as
+    its normal turns away from the camera (facing = (lo, hi) on the normal's z) and is 0 where the surface is hidden,
+    outside the picture or the texel is empty; z_bias (default 4 / max(Hz, Wz)) is the slack of the depth test.  Both
+    defaults are starting values, not tuned on any trained checkpoint.  Device float32 runs sr_texture_bake, one launch;
+    everything else `bake_composite`.  tri, face and coeff must be valid for the mesh (texel_map's are for its layout)."""
+    _check_bake(v, n, tri, face, coeff, image, zbuf)
+    hz, wz = int(zbuf.shape[1]), int(zbuf.shape[2])
+    if z_bias is None:
+        z_bias = 4.0 / max(hz, wz)
+    z_bias = float(np.float32(z_bias)) if v.dtype == torch.float32 else float(z_bias)
+    if not z_bias >= 0:
+        raise ValueError("bake: z_bias must not be negative")
+    if not native_ok(v, n, coeff, image, zbuf):
+        if is_device_tensor(v) and strict_native():
+            raise RuntimeError("bake: SR_STRICT_NATIVE=1 and the kernels take float32 device tensors only")
+        return bake_composite(v, n, tri, face, coeff, image, zbuf, facing, z_bias)
+    lo, hi, _ = _facing(facing, v.dtype)
+    vc, nc, tc, fc, cc, ic, zc = (t.contiguous() for t in (v, n, tri.to(v.device), face.to(v.device), coeff, image, zbuf))
+    b, nv = int(vc.shape[0]), int(vc.shape[1])
+    c_n, hs, ws = (int(x) for x in ic.shape[1:])
+    th, tw = (int(x) for x in fc.shape)
+    tex = torch.empty((b, c_n, th, tw), dtype=vc.dtype, device=vc.device)
+    weight = torch.empty((b, 1, th, tw), dtype=vc.dtype, device=vc.device)
+    ptr = _lib.ptr
+    with on_device_of(vc):
+        _lib.check(_lib.lib().sr_texture_bake(ptr(tex), ptr(weight), ptr(vc), ptr(nc), ptr(tc), ptr(fc), ptr(cc), ptr(ic),
+                                              ptr(zc), b, c_n, nv, int(tc.shape[0]), th, tw, hs, ws, hz, wz, lo, hi,
+                                              z_bias, stream_of(vc)), "sr_texture_bake")
+    return tex, weight
+
+
+# ---- padding ---------------------------------------------------------------------------------------------------------
+def _shift(a, dy, dx):
+    """a [..., H, W] moved so that out[y, x] = a[y + dy, x + dx], zeros from outside."""
+    h, w = a.shape[-2:]
+    out = torch.zeros_like(a)
+    ys, yd = slice(max(dy, 0), h + min(dy, 0)), slice(max(-dy, 0), h + min(-dy, 0))
+    xs, xd = slice(max(dx, 0), w + min(dx, 0)), slice(max(-dx, 0), w + min(-dx, 0))
+    if ys.start < ys.stop and xs.start < xs.stop:
+        out[..., yd, xd] = a[..., ys, xs]
+    return out
+
+
+def pad_host(tex, filled):
+    """One padding pass, the definition: (tex', filled') of tex [B, C, Th, Tw] and filled bool [B, 1, Th, Tw]."""
+    acc = torch.zeros_like(tex)
+    count = torch.zeros(filled.shape, dtype=tex.dtype, device=tex.device)
+    for dy in (-1, 0, 1):                                                        # rows top to bottom, left to right
+        for dx in (-1, 0, 1):
+            if dy == 0 and dx == 0:
+                continue
+            nf = _shift(filled, dy, dx)
+            acc = acc + torch.where(nf, _shift(tex, dy, dx), torch.zeros_like(tex))
+            count = count + nf.to(tex.dtype)
+    grow = ~filled & (count > 0)
+    return torch.where(grow, acc / count.clamp_min(1), tex), filled | grow
+
+
+def pad(tex, weight, passes=8):
+    """Texture padding: (tex_padded, filled uint8 [B, 1, Th, Tw]).  Initially filled = weight > 0; in each of `passes`
+    passes (0..64) every unfilled texel with at least one filled 8-neighbour becomes filled with the sum of its filled
+    neighbours' colours (added rows top to bottom, left to right) divided by their count.  All of a pass reads the
+    previous pass's state; weight is not changed.  Device float32 runs sr_texture_pad once per pass."""
+    passes = int(passes)
+    if not 0 <= passes <= MAX_PASSES:
+        raise ValueError("pad: 0 <= passes <= %d, got %d" % (MAX_PASSES, passes))
+    if tex.dim() != 4 or weight.dim() != 4 or weight.shape[1] != 1 or weight.shape[0] != tex.shape[0] or (
+            tuple(weight.shape[2:]) != tuple(tex.shape[2:])):
+        raise ValueError("pad: tex [B, C, Th, Tw] and weight [B, 1, Th, Tw], got %s and %s"
+                         % (tuple(tex.shape), tuple(weight.shape)))
+    filled = weight > 0
+    if not native_ok(tex, weight):
+        if is_device_tensor(tex) and strict_native():
+            raise RuntimeError("pad: SR_STRICT_NATIVE=1 and the kernels take float32 device tensors only")
+        out = tex
+        for _ in range(passes):
+            out, filled = pad_host(out, filled)
+        return (out.clone() if out is tex else out), filled.to(torch.uint8)
+    b, c_n, th, tw = (int(x) for x in tex.shape)
+    cur, cur_f = tex.contiguous(), filled.to(torch.uint8)
+    if passes == 0:
+        return cur.clone(), cur_f
+    bufs = [(torch.empty_like(cur), torch.empty_like(cur_f)) for _ in range(min(passes, 2))]
+    ptr = _lib.ptr
+    with on_device_of(cur):
+        for k in range(passes):
+            nxt, nxt_f = bufs[k % 2]
+            _lib.check(_lib.lib().sr_texture_pad(ptr(nxt), ptr(nxt_f), ptr(cur), ptr(cur_f), b, c_n, th, tw,
+                                                 stream_of(cur)), "sr_texture_pad")
+            cur, cur_f = nxt, nxt_f
+    return cur, cur_f
+
+
+def fill_mean(tex, weight, filled):
+    """tex with every texel that is still unfilled (filled == 0) set to its sample's weight-weighted mean colour
+    sum(weight tex) / sum(weight) per channel; a sample with total weight 0 stays as it is (0).  Plain tensor ops: this
+    runs once per picture."""
+    total = weight.sum((2, 3), keepdim=True)
+    mean = (tex * weight).sum((2, 3), keepdim=True) / total.clamp_min(TINY)
+    mean = torch.where(total > 0, mean, torch.zeros_like(mean))
+    return torch.where(filled.bool(), tex, mean.expand_as(tex))
+
+
+def coverage(face, weight):
+    """The share of the non-empty texels with weight > 0, per sample: [B] float64."""
+    live = (face >= 0).view(1, 1, *face.shape)
+    n = live.sum().clamp_min(1).double()
+    return ((weight > 0) & live).sum((1, 2, 3)).double() / n

@@ -5,7 +5,9 @@ for it):
         [--bfm BFM.mat | --flame FLAME.{pkl,mat} | --facewarehouse FW.mat [--beta_shape X]] [--lpips-trunk VGG16.pth] [--batch N] [--gpu 0] [--seed S] [--out DIR]
         [--lmk LANDMARKS.txt [--lmk_index FILE] [--lmk_weight 1.0] [--lmk_beta 1.0] [--lmk_contour 1.0]
          [--lmk_dynamic | --lmk_lines FILE] [--lmk_axis I,J] [--lmk_vis LO,HI]]
-        [--mask_lmk [--mask_tri FILE] [--mask_margin R]] [--mask_dir DIR] [--mask_mesh] CHECKPOINT IMAGE [IMAGE ...]
+        [--mask_lmk [--mask_tri FILE] [--mask_margin R]] [--mask_dir DIR] [--mask_mesh]
+        [--texture [T] [--uv FILE] [--texture_from picture|render] [--texture_facing LO,HI] [--texture_pad N]
+         [--texture_fill mean|none]] CHECKPOINT IMAGE [IMAGE ...]
 
 For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with inversion.LatentInverter(fit_shape=True)
 — the W+ latent, a rigid pose and the 3DMM shape / expression coefficients are fitted together (op.morph on the device)
@@ -55,6 +57,21 @@ landmark file does not list gets all ones from --mask_lmk.  DIR then also receiv
 step (m times the gate), and <stem>.npz `mask_area`, its mean.  The pixel term is not renormalised by the region's area.
 Without these options nothing changes.
 
+With --texture [T] (default 512) the picture's colours are carried onto the fitted surface (op.texture): DIR also receives
+<stem>_texture.png (T x T), <stem>_texture_weight.png (grey, weight x 255: how much every texel saw of the picture),
+<stem>_textured.obj with <stem>_textured.mtl (the posed vertices of <stem>.obj with texture coordinates and the material
+that names the texture), and <stem>.npz `texture_coverage`, the share of the layout's texels with a positive weight before
+padding.  The layout is --uv FILE (face_model.load_uv: an .obj with vt lines and f a/t records over the model's faces, or an
+.npz with vt and ft; FLAME's template comes in this way) or, without it, the cylindrical unwrap of the model's mean shape
+(face_model.uv_layout, meant for face patches and convex heads).  --texture_from picture (the default) samples the file's
+picture at its own resolution (the resized target covers the whole picture, so the same model coordinates project onto
+it); render samples the generator's image of the fit.  A texel counts while it faces the camera (--texture_facing LO,HI on
+the z of its normal; 0.1,0.4 and the depth slack 4 / side of the z-buffer are starting values, not tuned on any trained
+checkpoint, like --lmk_weight) and is not hidden (the posed mesh's z-buffer, square, of side min(1024, max(size, T))).
+--texture_pad N (default 8, at most 64) grows the charts by N texels so that a renderer's filter finds no black beside
+them; --texture_fill mean (the default) paints what is left with the mean colour, none leaves it black.  Without --texture
+nothing changes.
+
 Images are PNG / JPG (PIL) or .npy in [-1, 1] (HWC or CHW), resized on the host.  The 3DMM is the Basel Face Model with
 --bfm (face_model.load_bfm), FLAME with --flame (face_model.load_flame, op.skin), the FaceWarehouse bilinear blendshape
 model with --facewarehouse (face_model.load_facewarehouse, op.blend), else the synthetic model `train --mesh` trains with (train.SyntheticFaceSource).  Without
@@ -71,8 +88,9 @@ import torch
 from . import checkpoint, generate, inversion, lpips, utils_3d
 
 
-def load_image(path, size, with_shape=False):
-    """[1, 3, size, size] float32 in [-1, 1] on the host (with_shape: and the (H, W) of the file's picture)."""
+def load_picture(path):
+    """[1, 3, H, W] float32 of the file's picture at its own resolution, on the host (in [-1, 1] for PNG / JPG; an .npy
+    as it is)."""
     if path.lower().endswith(".npy"):
         a = np.load(path).astype(np.float32)
         if a.ndim == 4:
@@ -89,7 +107,12 @@ def load_image(path, size, with_shape=False):
         x = torch.from_numpy(np.asarray(im, np.float32) / 127.5 - 1.0).permute(2, 0, 1)[None]
     if x.shape[1] == 1:
         x = x.expand(-1, 3, -1, -1)
-    x = x[:, :3]
+    return x[:, :3]
+
+
+def load_image(path, size, with_shape=False):
+    """[1, 3, size, size] float32 in [-1, 1] on the host (with_shape: and the (H, W) of the file's picture)."""
+    x = load_picture(path)
     shape = (int(x.shape[-2]), int(x.shape[-1]))
     if shape != (size, size):
         x = torch.nn.functional.interpolate(x, size=(size, size), mode="bilinear", align_corners=False, antialias=True)
@@ -354,6 +377,79 @@ def landmark_outputs(inv, index, conf, listed, shape):
     return dict(more, landmarks=fit, landmarks_target=np.asarray(listed, np.float64), lmk_error=np.float64(err))
 
 
+class TextureGuide:
+    """The texture options of one run: the layout and its texel map (built once), and `outputs`, which bakes one fitted
+    sample and writes its files."""
+
+    def __init__(self, face, size, uv_file=None, source="picture", facing="0.1,0.4", passes=8, fill="mean"):
+        from .face_model import load_uv, uv_layout
+        from .op import texture
+
+        model, tri = face
+        self.size = int(size)
+        if not 1 <= self.size <= 8192:
+            raise SystemExit("reconstruct: --texture T lies in [1, 8192]")
+        try:
+            lo, hi = (float(x) for x in facing.split(","))
+        except ValueError:
+            raise SystemExit("reconstruct: --texture_facing takes LO,HI")
+        if not lo <= hi:
+            raise SystemExit("reconstruct: --texture_facing needs LO <= HI")
+        self.facing, self.source, self.fill = (lo, hi), source, fill
+        self.passes = int(passes)
+        if not 0 <= self.passes <= texture.MAX_PASSES:
+            raise SystemExit("reconstruct: --texture_pad lies in [0, %d]" % texture.MAX_PASSES)
+        dev = tri.device
+        try:
+            if uv_file:
+                if not os.path.isfile(uv_file):
+                    raise SystemExit("reconstruct: --uv file %s not found" % uv_file)
+                uv, tri_uv = load_uv(uv_file, tri)
+                keep = None
+            else:
+                with torch.no_grad():
+                    v = model.mesh(torch.zeros(1, model.n_coeff, device=dev), torch.zeros(1, 7, device=dev), tri)[0]
+                uv, tri_uv, keep = uv_layout(v[0].cpu(), tri)
+            self.uv, self.tri_uv = uv, tri_uv                            # (on the host: what the .obj lists)
+            self._layout = (uv.to(dev), tri_uv, keep)                    # (kept: the map's cache key holds their addresses)
+            self.face, self.coeff = texture.texel_map(self._layout[0], tri_uv, self.size, keep)
+        except (ValueError, OSError) as e:
+            raise SystemExit("reconstruct: %s" % e)
+
+    def outputs(self, inv, index, out_dir, stem, path):
+        """Writes the four texture files of sample `index` and returns the .npz entry `texture_coverage`."""
+        from .op import texture
+
+        k = slice(index, index + 1)
+        v, n, tri = inv.fitted_mesh()
+        v, n = v[k].contiguous(), n[k].contiguous()
+        if self.source == "render":
+            picture = inv.image[k]
+        else:
+            picture = load_picture(path).to(v.device)                    # its own resolution, uploaded once
+        side = min(1024, max(int(inv.target.shape[-1]), self.size))
+        with torch.no_grad():
+            zbuf = texture.depth_buffer(v, tri, side)
+            tex, weight = texture.bake(v, n, tri, self.face, self.coeff, picture.to(v.dtype).contiguous(), zbuf,
+                                       facing=self.facing)
+            cover = float(texture.coverage(self.face, weight)[0])
+            out, filled = texture.pad(tex, weight, self.passes)
+            if self.fill == "mean":
+                out = texture.fill_mean(out, weight, filled)
+        generate.save_image(out.clamp(-1, 1).cpu(), os.path.join(out_dir, stem + "_texture.png"))
+        grey = np.round(weight[0, 0].cpu().numpy().astype(np.float64) * 255.0).astype(np.uint8)
+        try:
+            from PIL import Image
+
+            Image.fromarray(grey).save(os.path.join(out_dir, stem + "_texture_weight.png"))
+        except ImportError:
+            with open(os.path.join(out_dir, stem + "_texture_weight.pgm"), "wb") as f:
+                f.write(b"P5 %d %d 255\n" % (grey.shape[1], grey.shape[0]) + grey.tobytes())
+        utils_3d.save_textured_obj(os.path.join(out_dir, stem + "_textured.obj"), v[0].cpu().numpy(), tri.cpu().numpy(),
+                                   self.uv.numpy(), self.tri_uv.numpy(), n[0].cpu().numpy(), stem + "_texture.png")
+        return {"texture_coverage": np.float64(cover)}
+
+
 def reconstruct(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr=0.01, shape_reg=0.0,
                 n_mean_latent=4096, **landmark_args):
     """Fits one image; returns the inverter (w, pose, coeff, image, fitted_mesh()) and the loss history (host).
@@ -463,6 +559,22 @@ def main(argv=None):
                     help="masks of the pictures: DIR/<stem>.png or .npy, grey in [0, 1]; a missing file is all ones")
     ap.add_argument("--mask_mesh", action="store_true",
                     help="gate the region in every step by the fitted mesh's coverage of the picture")
+    ap.add_argument("--texture", type=int, nargs="?", const=512, default=None, metavar="T",
+                    help="bake a T x T texture of the picture on the fitted mesh and write a textured .obj [512 when given "
+                         "without a number]")
+    ap.add_argument("--uv", default=None, metavar="FILE",
+                    help="with --texture: the layout, an .obj with vt lines and f a/t records over the model's faces, or an "
+                         ".npz with vt and ft; default: a cylindrical unwrap of the model's mean shape")
+    ap.add_argument("--texture_from", default=None, choices=("picture", "render"),
+                    help="with --texture: sample the file's picture at its own resolution, or the generator's image of the "
+                         "fit [picture]")
+    ap.add_argument("--texture_facing", default=None, metavar="LO,HI",
+                    help="with --texture: a texel fades out as the z of its normal falls from HI to LO; 0.1,0.4 is a "
+                         "starting value, untuned like --lmk_weight [0.1,0.4]")
+    ap.add_argument("--texture_pad", type=int, default=None, metavar="N",
+                    help="with --texture: grow the charts by N texels (0..64) [8]")
+    ap.add_argument("--texture_fill", default=None, choices=("mean", "none"),
+                    help="with --texture: paint the texels still unfilled with the mean colour, or leave them black [mean]")
     ap.add_argument("--gpu", type=int, default=0, help="use gpu id")
     ap.add_argument("--seed", type=int, default=0, help="random seed (mean latent, noise)")
     ap.add_argument("--out", default="reconstruct", metavar="DIR", help="output directory [%(default)s]")
@@ -479,6 +591,9 @@ def main(argv=None):
         ap.error("--mask_lmk needs --lmk")
     if (args.mask_tri or args.mask_margin) and not args.mask_lmk:
         ap.error("--mask_tri and --mask_margin need --mask_lmk")
+    if args.texture is None and (args.uv or args.texture_from or args.texture_facing or args.texture_pad is not None
+                                 or args.texture_fill):
+        ap.error("--uv, --texture_from, --texture_facing, --texture_pad and --texture_fill need --texture")
     torch.manual_seed(args.seed)
     if torch.cuda.is_available() and 0 <= args.gpu < torch.cuda.device_count():
         device = torch.device("cuda:%d" % args.gpu)
@@ -501,6 +616,9 @@ def main(argv=None):
     masker = (MaskGuide(args.mask_lmk, args.mask_tri, args.mask_margin, args.mask_dir, args.mask_mesh,
                         guide.count if guide else None)
               if (args.mask_lmk or args.mask_dir or args.mask_mesh) else None)
+    painter = (TextureGuide(face, args.texture, args.uv, args.texture_from or "picture", args.texture_facing or "0.1,0.4",
+                            8 if args.texture_pad is None else args.texture_pad, args.texture_fill or "mean")
+               if args.texture is not None else None)
     os.makedirs(args.out, exist_ok=True)
     results = []
 
@@ -513,11 +631,13 @@ def main(argv=None):
         look = guide.lookup(path, shape, args.size) + (shape,)
         return x, look, masker.lookup(path, look, args.size) if masker else None
 
-    def more(inv, index, stem, extras):
-        """The .npz entries with the region's (and its picture written), when there is one."""
-        if masker is None:
-            return extras
-        return dict(extras or {}, **mask_outputs(inv, index, args.out, stem))
+    def more(inv, index, stem, extras, path):
+        """The .npz entries with the region's and the texture's (and their files written), when there are any."""
+        if masker is not None:
+            extras = dict(extras or {}, **mask_outputs(inv, index, args.out, stem))
+        if painter is not None:
+            extras = dict(extras or {}, **painter.outputs(inv, index, args.out, stem, path))
+        return extras
 
     def closing():
         if guide:
@@ -540,7 +660,7 @@ def main(argv=None):
             inv, hist = reconstruct(g, percept, face, target.to(device), args.steps, args.lr, args.pose_lr, args.coeff_lr,
                                     args.shape_reg, args.n_mean_latent, **lmk_args)
             extras = landmark_outputs(inv, 0, look[1], look[2], look[3]) if guide else None
-            write_outputs(inv, hist, args.out, stem, extras=more(inv, 0, stem, extras))
+            write_outputs(inv, hist, args.out, stem, extras=more(inv, 0, stem, extras, path))
             print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f%s" % (
                 path, float(hist[0]), float(hist[-1]), len(hist), float(inv.coeff.detach().norm()), tail(extras)),
                 flush=True)
@@ -566,7 +686,7 @@ def main(argv=None):
             stem = os.path.splitext(os.path.basename(path))[0]
             h = np.ascontiguousarray(hist[:, i])
             extras = landmark_outputs(inv, i, looks[i][1], looks[i][2], looks[i][3]) if guide else None
-            write_outputs(inv, h, args.out, stem, index=i, extras=more(inv, i, stem, extras))
+            write_outputs(inv, h, args.out, stem, index=i, extras=more(inv, i, stem, extras, path))
             print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f%s" % (
                 path, float(h[0]), float(h[-1]), len(h), float(inv.coeff.detach()[i].norm()), tail(extras)), flush=True)
             results.append((stem, h))

@@ -7,6 +7,7 @@ meaning as reference utils_3d.py / layers.py:
     random_apply_pose3D(p=[...], v=None)                   utils_3d.py:360-378
     mesh_point_normal(v, tri)                              utils_3d.py:379-404
     save_obj(file_name, v, tri, vt, trit, vn, trin)        utils_3d.py:405-444
+`save_textured_obj` adds what a textured mesh needs on top of save_obj's records: a material file and its two lines.
 
 `mesh_point_normal` on device tensors runs ONE gather kernel (csrc/mesh.hip, C ABI
 sr_vertex_normals_f32) over a per-topology incidence list built once and cached, instead of three
@@ -292,6 +293,13 @@ def save_obj(file_name, v, tri=[], vt=[], trit=[], vn=[], trin=[]):
     or arrays are accepted.  Returns whether the file exists."""
     import os
 
+    with open(file_name, "w") as f:
+        f.write("".join(line + "\n" for line in _obj_records(v, tri, vt, trit, vn, trin)))
+    return os.path.exists(file_name)
+
+
+def _obj_records(v, tri=[], vt=[], trit=[], vn=[], trin=[]):
+    """The lines of `save_obj`'s file."""
     def rows(a):
         if isinstance(a, torch.Tensor):
             a = a.detach().cpu()
@@ -322,9 +330,22 @@ def save_obj(file_name, v, tri=[], vt=[], trit=[], vn=[], trin=[]):
         else:
             corners = ["%d" % (face[j] + 1) for j in range(len(face))]
         out.append("f " + " ".join(corners) if corners else "f")
+    return out
+
+
+def save_textured_obj(file_name, v, tri, vt, trit, vn, texture_file):
+    """`save_obj`'s records (v, vt, vn, f a/t/n) behind `mtllib <stem>.mtl` and `usemtl face`, and beside the file the
+    material <stem>.mtl: `newmtl face`, `Kd 1 1 1`, `map_Kd <texture_file>` (a file name relative to the .obj).  Returns
+    whether both files exist."""
+    import os
+
+    stem = os.path.splitext(file_name)[0]
+    head = ["mtllib %s.mtl" % os.path.basename(stem), "usemtl face"]
     with open(file_name, "w") as f:
-        f.write("".join(line + "\n" for line in out))
-    return os.path.exists(file_name)
+        f.write("".join(line + "\n" for line in head + _obj_records(v, tri, vt, trit, vn)))
+    with open(stem + ".mtl", "w") as f:
+        f.write("newmtl face\nKd 1 1 1\nmap_Kd %s\n" % texture_file)
+    return os.path.exists(file_name) and os.path.exists(stem + ".mtl")
 
 
 # ---- ADA augmentation (reference utils_3d.py:155-188, 189-349 cam=None branch, 350-359) ------------
