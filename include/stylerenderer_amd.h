@@ -915,14 +915,34 @@ int sr_region_blend_bwd(float* g_img, const float* g_y, const float* m_eff, int6
  *   [B, 1, Th, Tw].  A filled texel is copied; an unfilled one with at least one filled 8-neighbour becomes filled with the
  *   sum of those neighbours' colours (added in the order rows top to bottom, left to right) divided by their count; any
  *   other texel is copied and stays unfilled.  One launch, one lane per texel.
+ * sr_texture_merge: V bakes tex_in [V, C, Th, Tw], weight_in [V, 1, Th, Tw] of one subject in one layout -> tex
+ *   [1, C, Th, Tw], weight [1, 1, Th, Tw], best uint8 [Th, Tw], out of place.  Per texel, one float32 operation per step:
+ *     wmax = max_v w_v, best = the first v that attains it; wmax <= 0: colour 0, weight 0, best 255
+ *     r_v = w_v / wmax, then `sharpness` times r_v = r_v r_v; after the division and after every squaring a value below
+ *       2^-63 becomes 0 (no operand or result is subnormal)
+ *     den = ((r_0 + r_1) + ...), num_c = ((r_0 t_0c + r_1 t_1c) + ...) from 0, product and sum rounded separately; a view
+ *       with r_v = 0 is skipped, not multiplied (what stands in an unweighted texel cannot leak)
+ *     tex_c = num_c / den, weight = wmax
+ *   1 <= V <= 64, 0 <= sharpness <= 4.  One launch; a lane owns four consecutive texels of a row; 16-byte loads and stores
+ *   when Tw % 4 == 0 and all four float planes are 16-byte aligned (best 4-byte aligned), scalar ones otherwise.
  * NULL pointers and non-positive sizes are SR_EINVAL before any launch; B, Th or Tw of 0 returns 0.  No atomics, no
- * scratch, no memset, no allocation, no host read: both run under graph capture on `stream`; reruns are bit-identical. */
+ * scratch, no memset, no allocation, no host read: all three run under graph capture on `stream`; reruns are
+ * bit-identical. */
 int sr_texture_bake(float* tex, float* weight, const float* v, const float* n, const int64_t* tri, const int32_t* face,
                     const float* coeff, const float* image, const float* zbuf, int64_t B, int64_t C, int64_t nv,
                     int64_t nf, int64_t Th, int64_t Tw, int64_t Hs, int64_t Ws, int64_t Hz, int64_t Wz, float facing_lo,
                     float facing_hi, float z_bias, sr_stream_t stream);
 int sr_texture_pad(float* tex_out, uint8_t* filled_out, const float* tex_in, const uint8_t* filled_in, int64_t B,
                    int64_t C, int64_t Th, int64_t Tw, sr_stream_t stream);
+int sr_texture_merge(float* tex, float* weight, uint8_t* best, const float* tex_in, const float* weight_in, int64_t V,
+                     int64_t C, int64_t Th, int64_t Tw, int sharpness, sr_stream_t stream);
+
+/* The shared identity of a multi-view fit (definition: stylerenderer_amd/op/share.py), csrc/share.hip.
+ * sr_share_rows: g [B, d] in place: s[j] = ((g[0, j] + g[1, j]) + g[2, j]) + ... in row order, then g[b, j] = s[j] for
+ *   every b, for the columns j < k (1 <= k <= d); the other columns are not touched.  One launch, one lane per column.  No
+ *   atomics, no LDS, no scratch, no allocation, no host read: it runs under graph capture on `stream`; reruns on the same
+ *   input are bit-identical.  B <= 65535. */
+int sr_share_rows(float* g, int64_t B, int64_t d, int64_t k, sr_stream_t stream);
 
 #ifdef __cplusplus
 }

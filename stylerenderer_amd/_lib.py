@@ -153,6 +153,8 @@ SIGNATURES = {
     "sr_region_blend_bwd": (_i, [_p] * 3 + [_l] * 4 + [_p]),
     "sr_texture_bake": (_i, [_p] * 9 + [_l] * 10 + [_f, _f, _f, _p]),
     "sr_texture_pad": (_i, [_p] * 4 + [_l] * 4 + [_p]),
+    "sr_texture_merge": (_i, [_p] * 5 + [_l] * 4 + [_i, _p]),
+    "sr_share_rows": (_i, [_p] + [_l] * 3 + [_p]),
     "sr_signal_bump": (_i, [_p, _p]),
     "sr_signal_wait": (_i, [_p, ctypes.c_uint32, _p]),
     "sr_signal_set": (_i, [_p, _p, _p]),

@@ -38,6 +38,7 @@ SOURCES = [
     ("landmark.hip", EXACT),
     ("region.hip", EXACT),
     ("texture.hip", EXACT),
+    ("share.hip", EXACT),
     ("morph.hip", []),
     ("skin.hip", []),
     ("blend.hip", []),

@@ -1,6 +1,7 @@
-// UV texture baking of face reconstruction (C ABI: sr_texture_bake / sr_texture_pad; definition:
-// stylerenderer_amd/op/texture.py, bake_composite and pad_host).  A texel map (face int32 [Th, Tw], coeff [Th, Tw, 3],
-// built once per layout by the rasterizer) names for every texel the mesh face under it and its barycentric weights.
+// UV texture baking of face reconstruction (C ABI: sr_texture_bake / sr_texture_pad / sr_texture_merge; definition:
+// stylerenderer_amd/op/texture.py, bake_composite, pad_host and merge_composite).  A texel map (face int32 [Th, Tw],
+// coeff [Th, Tw, 3], built once per layout by the rasterizer) names for every texel the mesh face under it and its
+// barycentric weights.
 //
 //   k_texture_bake   a gather over texels.  A lane owns four consecutive texels of one row; it reads their map entries
 //                    once and then walks the B samples: the surface point and normal from the posed mesh, the facing
@@ -13,10 +14,15 @@
 //   k_texture_pad    one pass of texture padding, one lane per texel: a filled texel is copied, an unfilled one with a
 //                    filled 8-neighbour takes their mean (fixed order: rows top to bottom, left to right) and becomes
 //                    filled.  Out of place: a pass reads the previous pass's state only.
+//   k_texture_merge  V bakes of one subject in one layout become one texture.  A lane owns four consecutive texels as in
+//                    the bake and walks the V views twice: the largest weight and the first view that has it, then the
+//                    sums of r_v and r_v t_v with r_v = (w_v / wmax)^(2^sharpness).  Up to four channels ride along in
+//                    registers, so an RGB stack is read once (the weight planes a second time, out of cache).  The same
+//                    two forms as the bake: 16-byte loads and stores, or scalar ones for any width.
 //
 // The arithmetic is the definition's, one float32 operation per step in the same order: compiled with -ffp-contract=off
 // and correctly rounded division and square root, the results are the host's bit for bit.  Vector stores and plain C++
-// only: no atomics, no scratch, no memset, no host read, so both run under graph capture on the caller's stream.
+// only: no atomics, no scratch, no memset, no host read, so all three run under graph capture on the caller's stream.
 #include "common.h"
 
 namespace {
@@ -205,7 +211,141 @@ __global__ __launch_bounds__(TX_BLOCK) void k_texture_pad(float* __restrict__ te
     filled_out[i] = count > 0 ? 1 : 0;
 }
 
+struct MergeArgs {
+    float* tex;            // [1, C, Th, Tw]
+    float* weight;         // [1, 1, Th, Tw]
+    uint8_t* best;         // [Th, Tw]
+    const float* tex_in;   // [V, C, Th, Tw]
+    const float* w_in;     // [V, 1, Th, Tw]
+    int V, C, Th, Tw, sharpness;
+};
+
+constexpr float MG_FLUSH = 0x1p-63f;                                      // below it a ratio counts as 0
+constexpr int MG_CH = 4;                                                  // channels a lane carries at a time
+
+template <int V>
+__device__ __forceinline__ void load_group(float* x, const float* p, int count) {
+    if constexpr (V == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        x[0] = q.x, x[1] = q.y, x[2] = q.z, x[3] = q.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) x[j] = j < count ? p[j] : 0.f;
+    }
+}
+
+// (w / wmax)^(2^sharpness), flushed to 0 below 2^-63 after the division and after every squaring
+__device__ __forceinline__ float merge_ratio(float w, float wmax, int sharpness) {
+    float r = w / wmax;
+    if (r < MG_FLUSH) r = 0.f;
+    for (int s = 0; s < sharpness; ++s) {
+        r = r * r;
+        if (r < MG_FLUSH) r = 0.f;
+    }
+    return r;
+}
+
+template <int V>
+__global__ __launch_bounds__(TX_BLOCK) void k_texture_merge(MergeArgs a) {
+    const int groups = (a.Tw + 3) >> 2;                                   // lanes per row, as in k_texture_bake
+    const int64_t item = (int64_t)blockIdx.x * TX_BLOCK + threadIdx.x;
+    if (item >= (int64_t)a.Th * groups) return;
+    const int ty = (int)(item / groups), tx0 = (int)(item % groups) * 4;
+    const int count = min(4, a.Tw - tx0);
+    const int64_t t0 = (int64_t)ty * a.Tw + tx0;
+    const int64_t plane = (int64_t)a.Th * a.Tw;
+
+    // the largest weight and the first view that attains it
+    float wmax[4], w[4];
+    int first[4];
+    load_group<V>(wmax, a.w_in + t0, count);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) first[j] = 0;
+    for (int v = 1; v < a.V; ++v) {
+        load_group<V>(w, a.w_in + (int64_t)v * plane + t0, count);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (w[j] > wmax[j]) wmax[j] = w[j], first[j] = v;
+    }
+    bool live[4];
+    float wout[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        live[j] = wmax[j] > 0.f;
+        wout[j] = live[j] ? wmax[j] : 0.f;
+        if (!live[j]) first[j] = 255;
+    }
+    store_group<V>(a.weight + t0, wout, count);
+    if constexpr (V == 4) {
+        *reinterpret_cast<uchar4*>(a.best + t0) = make_uchar4((unsigned char)first[0], (unsigned char)first[1],
+                                                              (unsigned char)first[2], (unsigned char)first[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < count) a.best[t0 + j] = (uint8_t)first[j];
+    }
+
+    // the colours, MG_CH channels at a time: with C <= 4 every plane is read once (the weights a second time, from cache)
+    for (int c0 = 0; c0 < a.C; c0 += MG_CH) {
+        const int nc = min(MG_CH, a.C - c0);
+        float num[MG_CH][4], den[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            den[j] = 0.f;
+#pragma unroll
+            for (int cc = 0; cc < MG_CH; ++cc) num[cc][j] = 0.f;
+        }
+        for (int v = 0; v < a.V; ++v) {
+            float r[4];
+            load_group<V>(w, a.w_in + (int64_t)v * plane + t0, count);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                r[j] = live[j] ? merge_ratio(w[j], wmax[j], a.sharpness) : 0.f;
+                if (r[j] > 0.f) den[j] = den[j] + r[j];
+            }
+#pragma unroll
+            for (int cc = 0; cc < MG_CH; ++cc) {
+                if (cc < nc) {
+                    float t[4];
+                    load_group<V>(t, a.tex_in + ((int64_t)v * a.C + c0 + cc) * plane + t0, count);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        if (r[j] > 0.f) num[cc][j] = num[cc][j] + r[j] * t[j];      // a view without weight is skipped
+                }
+            }
+        }
+#pragma unroll
+        for (int cc = 0; cc < MG_CH; ++cc) {
+            if (cc < nc) {
+                float out[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) out[j] = live[j] ? num[cc][j] / den[j] : 0.f;
+                store_group<V>(a.tex + (int64_t)(c0 + cc) * plane + t0, out, count);
+            }
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int sr_texture_merge(float* tex, float* weight, uint8_t* best, const float* tex_in, const float* weight_in,
+                                int64_t V, int64_t C, int64_t Th, int64_t Tw, int sharpness, sr_stream_t stream) {
+    if (V < 1 || V > 64 || C < 1 || Th < 0 || Tw < 0 || sharpness < 0 || sharpness > 4) return SR_EINVAL;
+    if (Th == 0 || Tw == 0) return SR_OK;
+    if (!tex || !weight || !best || !tex_in || !weight_in || tex == tex_in || weight == weight_in) return SR_EINVAL;
+    if (C > 65535 || Th > (1 << 20) || Tw > (1 << 20)) return SR_ERANGE;
+    MergeArgs a;
+    a.tex = tex, a.weight = weight, a.best = best, a.tex_in = tex_in, a.w_in = weight_in;
+    a.V = (int)V, a.C = (int)C, a.Th = (int)Th, a.Tw = (int)Tw, a.sharpness = sharpness;
+    const int64_t items = Th * ((Tw + 3) / 4);
+    const dim3 grid((unsigned)sr_ceil_div(items, TX_BLOCK));
+    if (Tw % 4 == 0 && sr_aligned16(tex) && sr_aligned16(weight) && sr_aligned16(tex_in) && sr_aligned16(weight_in) &&
+        (reinterpret_cast<uintptr_t>(best) & 3) == 0)
+        hipLaunchKernelGGL(k_texture_merge<4>, grid, dim3(TX_BLOCK), 0, sr_stream(stream), a);
+    else
+        hipLaunchKernelGGL(k_texture_merge<1>, grid, dim3(TX_BLOCK), 0, sr_stream(stream), a);
+    return sr_launch_status();
+}
 
 extern "C" int sr_texture_bake(float* tex, float* weight, const float* v, const float* n, const int64_t* tri,
                                const int32_t* face, const float* coeff, const float* image, const float* zbuf, int64_t B,

@@ -13,6 +13,11 @@ face_model.py:75-146 and 363-377; on the device its forward is the blendshape no
 What the fitting loop (inversion.LatentInverter, reconstruct) asks of a model, the same for all three:
     kind                           "linear" | "skinned" | "blended"
     n_coeff                        length of a coefficient vector
+    n_identity                     how many leading coefficients describe the person rather than the moment: what the views
+                                   of a multi-view fit share (LatentInverter's shared_identity).  dim[0] for all three
+                                   (shape before expression, identity logits before expression logits, shape before the
+                                   joints' rotations); load_flame lowers it where the file's shape basis carries
+                                   expression columns behind the identity columns
     mesh(coeff, pose, tri, reg_weight=0.0)
                                    (v, n, reg, prior_rows) of the model's node (op.morph / op.skin / op.blend); prior_rows
                                    [B] is every sample's share of reg, or None where the prior is a diagonal Gaussian
@@ -324,6 +329,10 @@ class LinearMorphableModel(nn.Module):
     def n_coeff(self):
         return self.sigma.numel()
 
+    @property
+    def n_identity(self):
+        return self.dim[0]
+
     def mesh(self, coeff, pose, tri, reg_weight=0.0):
         from .op.morph import morph_mesh
 
@@ -452,6 +461,10 @@ class BlendShapeModel(nn.Module):
     @property
     def n_coeff(self):
         return self.dim[0] + self.dim[1]
+
+    @property
+    def n_identity(self):
+        return self.dim[0]
 
     def mesh(self, coeff, pose, tri, reg_weight=0.0):
         from .op.blend import blend_mesh
@@ -668,6 +681,12 @@ class LinearBlendSkinningModel(nn.Module):
     def n_coeff(self):
         return self.sigma.numel()
 
+    @property
+    def n_identity(self):
+        """dim[0], unless a loader set `identity_dim` (load_flame: the shape basis' identity columns)."""
+        k = getattr(self, "identity_dim", None)
+        return self.dim[0] if k is None else min(int(k), self.dim[0])
+
     def mesh(self, coeff, pose, tri, reg_weight=0.0):
         from .op.skin import skin_mesh
 
@@ -683,12 +702,21 @@ class LinearBlendSkinningModel(nn.Module):
         return {"joints": coeff[0, self.dim[0]:].view(-1, 3).cpu().numpy()}
 
 
+FLAME_IDENTITY_DIMS = 300                         # of the 400 columns of a published FLAME file's shapedirs
+
+
 def load_flame(file_name="/data/flame/generic_model.mat"):
     """FLAME -> (LinearBlendSkinningModel, tri int64 [nf, 3]) with the reference's contract (face_model.py:378-408):
     `file_name` is a `.pkl` (pickle, latin1), a `.mat`, or an already loaded dict with the keys `v_template` [nv, 3],
     `shapedirs` [nv, 3, ds], `posedirs` [nv, 3, 9 (nj - 1)], `J_regressor` [nj, nv] (dense or scipy sparse),
     `kintree_table` [2, nj], `weights` [nv, nj] and `f` [nf, 3].  The pose prior's sigmas are the reference's neck / jaw /
-    eye values in degrees (pitch, yaw, roll).  The licensed file is not distributed."""
+    eye values in degrees (pitch, yaw, roll).  The licensed file is not distributed.
+
+    `n_identity` of the model (what the views of a multi-view fit share).  FLAME's files keep identity and expression in one
+    `shapedirs`: the published models have 400 columns, 300 of identity followed by 100 of expression, and nothing in the
+    file marks the border.  The rule here is that layout's: a shape basis of more than FLAME_IDENTITY_DIMS = 300 columns has
+    its first 300 as identity and the rest as expression; a basis of up to 300 columns (a truncated or synthetic file) is
+    identity throughout, n_identity = dim[0]."""
     if isinstance(file_name, str):
         if file_name.endswith(".pkl"):
             import pickle
@@ -710,6 +738,8 @@ def load_flame(file_name="/data/flame/generic_model.mat"):
                                      np.asarray(data["shapedirs"]).shape[-1], v_template, data["J_regressor"],
                                      data["kintree_table"], data["weights"], data["posedirs"], data["shapedirs"], 1,
                                      sigma_pose)
+    if model.dim[0] > FLAME_IDENTITY_DIMS:
+        model.identity_dim = FLAME_IDENTITY_DIMS
     f = np.asarray(data["f"])
     tri = (f - f.min()).astype(np.int64)
     if tri.shape[0] == 3 and tri.shape[1] != 3:

@@ -35,6 +35,16 @@ the LPIPS layers, the pixel term and the prior); `loss_value` is [B] and `run` r
 shapes and launches above.  `reset(target)` re-targets an inverter whose graph is captured: the next `run` computes
 exactly what a fresh inverter on that target would, with no new warm-up or capture.
 
+With shared_identity=K (fit_shape=True, 1 <= K <= the model's n_coeff; the models name their own K as `n_identity`) the B
+rows are B views of ONE subject: the leading K columns of coeff are one variable shared by all rows, and everything else
+(w, pose, the remaining columns: expression, FLAME's joints, the landmarks and masks) stays per view.  coeff keeps its
+shape [B, d]; between backward and the optimiser's step the leading K columns of every row of coeff.grad are replaced by
+their sum over the rows (op.share.share_rows_, one launch inside the captured step), which is the gradient of sum_b L_b
+with respect to the shared variable.  All rows start equal (zero, also after `reset`), see the same gradient and pass
+through the same element-wise Adam, so coeff[:, :K] stays equal across the rows bit for bit, with no copy and no second
+parameter.  Every row keeps its own prior term, as in the batched fit: the objective is the sum of the V single-view
+objectives under the constraint, so the shared columns' prior enters V times; it is not rescaled.
+
 The pose gradient reaches the vertices only through the rasterizer's backward (deterministic gather, so two
 runs from the same state produce bit-identical trajectories).  On a GPU the whole iteration — forward, backward,
 Adam — is one hipGraph (batch 1 is launch-latency bound: ~2 000 kernels per step), replayed `steps` times; the
@@ -70,7 +80,7 @@ class LatentInverter:
                  n_mean_latent=4096, use_graph=None, optimise_pose=True, *, face=None, fit_shape=False, coeff_lr=0.01,
                  shape_reg=0.0, landmarks=None, landmark_conf=None, landmark_weight=1.0, landmark_beta=1.0,
                  landmark_embedding=None, landmark_lines=None, landmark_axis=None, landmark_vis=None, mask=None,
-                 mask_mesh=False):
+                 mask_mesh=False, shared_identity=None):
         self.g = generator.eval()
         self.perceptual = perceptual.eval()
         for p in list(self.g.parameters()) + list(self.perceptual.parameters()):
@@ -97,6 +107,16 @@ class LatentInverter:
             self.v0 = self.n0 = None
         else:
             self.v0, self.n0, self.tri = (t.detach() for t in mesh)
+        # the rows are views of one subject: the leading columns of coeff are tied in every step (None: off)
+        self.shared_identity = None
+        if shared_identity is not None:
+            if not self.fit_shape:
+                raise ValueError("LatentInverter: shared_identity needs fit_shape=True and face=(model, tri)")
+            if isinstance(shared_identity, bool) or not isinstance(shared_identity, int) or not (
+                    1 <= shared_identity <= self.face_model.n_coeff):
+                raise ValueError("LatentInverter: shared_identity is an int in [1, %d] (the model's coefficients), got %r"
+                                 % (self.face_model.n_coeff, shared_identity))
+            self.shared_identity = int(shared_identity)
         self.pixel_weight = float(pixel_weight)
         self.with_map = hasattr(self.g, "norm_to_style")
         with torch.no_grad():
@@ -382,6 +402,13 @@ class LatentInverter:
         img = self.render()
         value = self.loss(img)
         value.backward()
+        if self.shared_identity is not None:
+            # the gradient of the shared variable: the rows' sum, written into every row
+            from .op.share import share_rows_
+
+            if not self.coeff.grad.is_contiguous():
+                self.coeff.grad = self.coeff.grad.contiguous()
+            share_rows_(self.coeff.grad, self.shared_identity)
         self.optim.step()
         self.loss_value.copy_(value.detach() if self.batch == 1 else self._rows)
         self.image = img.detach()

@@ -21,13 +21,27 @@ has its centre at u = (tx + 1/2) / Tw, v = 1 - (ty + 1/2) / Th: row 0 is the top
               z-buffer pixel holds -FLT_MAX and occludes nothing.  An empty texel gives tex = 0 and weight = 0.
   pad         texture padding, so that a renderer's bilinear filter does not bleed black across chart borders.
   fill_mean   what is still unfilled gets the sample's weight-weighted mean colour.
+  merge       (tex [1, C, Th, Tw], weight [1, 1, Th, Tw], best uint8 [Th, Tw]) of V bakes of one subject in one layout
+              (tex [V, C, Th, Tw], weight [V, 1, Th, Tw]: several views of one head).  Per texel, every step one operation
+              of the float type, no fused multiply-add:
+                  wmax = max_v w_v;  best = the first v that attains it;  wmax <= 0: colour 0, weight 0, best = 255
+                  r_v  = w_v / wmax, correctly rounded; then `sharpness` times r_v = r_v r_v.  After the division and
+                         after every squaring a value below 2^-63 becomes 0, so that no operand or result is subnormal
+                         whatever the float mode of host or device
+                  den  = ((r_0 + r_1) + ...) and num_c = ((r_0 t_0c + r_1 t_1c) + ...) over the views in order, both
+                         from 0, the product and the sum rounded separately.  A view with r_v = 0 is skipped, not
+                         multiplied: whatever stands in an unweighted texel (NaN included) cannot leak
+                  tex_c = num_c / den, correctly rounded;  weight = wmax
+              sharpness 0 is the weight-weighted mean; every step up squares the ratios, so the best view takes over
+              and a seam between two views narrows; with weights (1, 2^-4) sharpness 4 gives the first view exactly.
+              Weights are expected finite and not negative (a negative one counts as 0).
 
-CPU tensors and float64 take the torch composites `bake_composite` and `pad_host`, which are the definition.  Float32
-device tensors take sr_texture_bake / sr_texture_pad through the C ABI: one launch per bake and one per padding pass,
-nothing allocated by the launch and nothing read back, so the calls can be captured.  The kernels are compiled without
-contraction and with correctly rounded division and square root: weight, tex and the padding are the host float32
-definition's bit for bit.  Under SR_STRICT_NATIVE=1 nothing falls to a library: a device tensor the kernels do not take
-(float64) raises.
+CPU tensors and float64 take the torch composites `bake_composite`, `pad_host` and `merge_composite`, which are the
+definition.  Float32 device tensors take sr_texture_bake / sr_texture_pad / sr_texture_merge through the C ABI: one launch
+per bake, per padding pass and per merge, nothing allocated by the launch and nothing read back, so the calls can be
+captured.  The kernels are compiled without contraction and with correctly rounded division and square root: weight, tex,
+the padding and the merge are the host float32 definition's bit for bit.  Under SR_STRICT_NATIVE=1 nothing falls to a
+library: a device tensor the kernels do not take (float64) raises.
 
 Non-square sizes.  op.rasterize reproduces the reference's call convention, which swaps the two extents of a non-square
 picture: only square pictures come out right.  `texel_map` and `depth_buffer` therefore draw a non-square
@@ -355,6 +369,78 @@ def fill_mean(tex, weight, filled):
     mean = (tex * weight).sum((2, 3), keepdim=True) / total.clamp_min(TINY)
     mean = torch.where(total > 0, mean, torch.zeros_like(mean))
     return torch.where(filled.bool(), tex, mean.expand_as(tex))
+
+
+# ---- merging several views --------------------------------------------------------------------------------------------
+MAX_VIEWS = 64
+MAX_SHARPNESS = 4
+FLUSH = 2.0 ** -63
+
+
+def _check_merge(tex, weight, sharpness):
+    if tex.dim() != 4 or weight.dim() != 4 or weight.shape[1] != 1 or weight.shape[0] != tex.shape[0] or (
+            tuple(weight.shape[2:]) != tuple(tex.shape[2:])) or weight.dtype != tex.dtype or weight.device != tex.device:
+        raise ValueError("merge: tex [V, C, Th, Tw] and weight [V, 1, Th, Tw] of one float type on one device, got %s "
+                         "and %s" % (tuple(tex.shape), tuple(weight.shape)))
+    if not tex.is_floating_point() or tex.shape[1] < 1:
+        raise ValueError("merge: tex must be floating point with at least one channel")
+    if not 1 <= tex.shape[0] <= MAX_VIEWS:
+        raise ValueError("merge: 1 <= V <= %d views, got %d" % (MAX_VIEWS, tex.shape[0]))
+    if isinstance(sharpness, bool) or int(sharpness) != sharpness or not 0 <= int(sharpness) <= MAX_SHARPNESS:
+        raise ValueError("merge: sharpness is an int in 0..%d, got %r" % (MAX_SHARPNESS, sharpness))
+    return int(sharpness)
+
+
+def merge_composite(tex, weight, sharpness=2):
+    """The defining tensor algebra of `merge`, in tex's float type."""
+    n_v = int(tex.shape[0])
+    w = weight[:, 0]                                                             # [V, Th, Tw]
+    wmax, best = w[0], torch.zeros(w.shape[1:], dtype=torch.int64, device=w.device)
+    for v in range(1, n_v):
+        more = w[v] > wmax
+        wmax = torch.where(more, w[v], wmax)
+        best = torch.where(more, torch.full_like(best, v), best)
+    live = wmax > 0
+    safe = torch.where(live, wmax, torch.ones_like(wmax))
+    zero = torch.zeros_like(wmax)
+    den = zero
+    num = torch.zeros_like(tex[0])                                               # [C, Th, Tw]
+    for v in range(n_v):
+        r = _div(w[v], safe)
+        r = torch.where(r < FLUSH, zero, r)
+        for _ in range(sharpness):
+            r = r * r
+            r = torch.where(r < FLUSH, zero, r)
+        take = live & (r > 0)
+        den = torch.where(take, den + r, den)
+        num = torch.where(take.unsqueeze(0), num + r.unsqueeze(0) * tex[v], num)
+    out = torch.where(live.unsqueeze(0), _div(num, torch.where(live, den, torch.ones_like(den)).unsqueeze(0)),
+                      torch.zeros_like(num))
+    best = torch.where(live, best, torch.full_like(best, 255)).to(torch.uint8)
+    return out.unsqueeze(0), torch.where(live, wmax, zero).view(1, 1, *wmax.shape), best
+
+
+def merge(tex, weight, sharpness=2):
+    """(tex [1, C, Th, Tw], weight [1, 1, Th, Tw], best uint8 [Th, Tw]): the V bakes tex [V, C, Th, Tw] with their weights
+    [V, 1, Th, Tw] (one subject, one layout, 1 <= V <= 64) blended per texel with the weights (w_v / max_v w_v)^(2^sharpness),
+    sharpness an int in 0..4; the merged weight is the largest of the views', best the first view that has it (255 where
+    no view saw the texel; colour and weight are 0 there).  The module's note has the definition step by step.  Device
+    float32 runs sr_texture_merge, one launch; everything else `merge_composite`.  The inputs are not changed."""
+    sharpness = _check_merge(tex, weight, sharpness)
+    if not native_ok(tex, weight):
+        if is_device_tensor(tex) and strict_native():
+            raise RuntimeError("merge: SR_STRICT_NATIVE=1 and the kernels take float32 device tensors only")
+        return merge_composite(tex, weight, sharpness)
+    tc, wc = tex.contiguous(), weight.contiguous()
+    n_v, c_n, th, tw = (int(x) for x in tc.shape)
+    out = torch.empty((1, c_n, th, tw), dtype=tc.dtype, device=tc.device)
+    wout = torch.empty((1, 1, th, tw), dtype=tc.dtype, device=tc.device)
+    best = torch.empty((th, tw), dtype=torch.uint8, device=tc.device)
+    ptr = _lib.ptr
+    with on_device_of(tc):
+        _lib.check(_lib.lib().sr_texture_merge(ptr(out), ptr(wout), ptr(best), ptr(tc), ptr(wc), n_v, c_n, th, tw,
+                                               sharpness, stream_of(tc)), "sr_texture_merge")
+    return out, wout, best
 
 
 def coverage(face, weight):

@@ -3,6 +3,7 @@ for it):
 
     python -m stylerenderer_amd.reconstruct [--size 256] [--steps 400] [--lr] [--pose_lr] [--coeff_lr] [--shape_reg]
         [--bfm BFM.mat | --flame FLAME.{pkl,mat} | --facewarehouse FW.mat [--beta_shape X]] [--lpips-trunk VGG16.pth] [--batch N] [--gpu 0] [--seed S] [--out DIR]
+        [--multiview V [--identity_dims K] [--subject NAME] [--merge_sharpness S]]
         [--lmk LANDMARKS.txt [--lmk_index FILE] [--lmk_weight 1.0] [--lmk_beta 1.0] [--lmk_contour 1.0]
          [--lmk_dynamic | --lmk_lines FILE] [--lmk_axis I,J] [--lmk_vis LO,HI]]
         [--mask_lmk [--mask_tri FILE] [--mask_margin R]] [--mask_dir DIR] [--mask_mesh]
@@ -71,6 +72,27 @@ checkpoint, like --lmk_weight) and is not hidden (the posed mesh's z-buffer, squ
 --texture_pad N (default 8, at most 64) grows the charts by N texels so that a renderer's filter finds no black beside
 them; --texture_fill mean (the default) paints what is left with the mean colour, none leaves it black.  Without --texture
 nothing changes.
+
+With --multiview V the IMAGE arguments are taken in consecutive groups of V, each group V pictures of one subject (their
+count must be a multiple of V).  It implies --batch V: a group is fitted as one batched LatentInverter with
+shared_identity=K, so the views share the leading K coefficients (K = the face model's n_identity: shape before
+expression, FLAME's 300 identity columns, FaceWarehouse's identity logits; --identity_dims K overrides it) while latent,
+pose, expression / joints, landmarks and masks stay per view; the first group builds the inverter, the following ones
+`reset` it.  Every view keeps its own prior term, so the shared coefficients' prior enters V times (the objective is the
+sum of the V single-view objectives under the constraint).  Per view, the files are those of --batch, and every .npz also
+holds `subject` and `view`.  Per subject NAME (--subject for a single group, else the stem of the group's first view) DIR
+also receives NAME_identity.obj, the model's mesh at the shared coefficients with every other coefficient and the pose at
+0, with normals, and NAME_identity.npz with `identity` [K], `views` (the stems) and `loss` (the views' summed history).
+With --texture the V bakes are merged per texel (op.texture.merge: weights (w_v / max w)^(2^S), --merge_sharpness S in 0..4,
+default 2), then padded and filled as a single bake is: NAME_merged_texture.png, NAME_merged_texture_weight.png,
+NAME_merged_texture_views.png (grey: the view every texel took most from, 255 where no view saw it) and NAME_merged.obj
+with NAME_merged.mtl, the identity mesh carrying the merged texture.  NAME_identity.npz then also holds
+`merged_coverage` beside `texture_coverage` [V], the views' own (the gain of the merge is their difference), and the
+merge before padding: `merged_texture` [C, T, T], `merged_weight` [T, T] and `merged_best` [T, T]; every view's .npz
+holds its bake before padding, `texture` [C, T, T] and `texture_weight` [T, T] (float32; 4 MB per view at T = 512), so a
+merge can be repeated at another sharpness without a new fit.  Not built: exposure or colour matching between the views,
+mirror fill, a differentiable texture, per-view intrinsics or perspective, choosing the views automatically.  Without
+--multiview nothing changes.
 
 Images are PNG / JPG (PIL) or .npy in [-1, 1] (HWC or CHW), resized on the host.  The 3DMM is the Basel Face Model with
 --bfm (face_model.load_bfm), FLAME with --flame (face_model.load_flame, op.skin), the FaceWarehouse bilinear blendshape
@@ -416,8 +438,29 @@ class TextureGuide:
         except (ValueError, OSError) as e:
             raise SystemExit("reconstruct: %s" % e)
 
-    def outputs(self, inv, index, out_dir, stem, path):
-        """Writes the four texture files of sample `index` and returns the .npz entry `texture_coverage`."""
+    def finish(self, tex, weight):
+        """The texture as it is written: padded and filled (tex [1, C, T, T] of a bake or a merge, with its weight)."""
+        from .op import texture
+
+        out, filled = texture.pad(tex, weight, self.passes)
+        if self.fill == "mean":
+            out = texture.fill_mean(out, weight, filled)
+        return out
+
+    @staticmethod
+    def save_grey(grey, path):
+        try:
+            from PIL import Image
+
+            Image.fromarray(grey).save(path)
+        except ImportError:
+            with open(os.path.splitext(path)[0] + ".pgm", "wb") as f:
+                f.write(b"P5 %d %d 255\n" % (grey.shape[1], grey.shape[0]) + grey.tobytes())
+
+    def outputs(self, inv, index, out_dir, stem, path, keep=None):
+        """Writes the four texture files of sample `index` and returns the .npz entry `texture_coverage`.  keep: a list
+        that receives the bake before padding, (tex [1, C, T, T], weight [1, 1, T, T]), and makes the returned entries
+        hold it too (`texture`, `texture_weight`): the views of --multiview, merged afterwards."""
         from .op import texture
 
         k = slice(index, index + 1)
@@ -433,9 +476,7 @@ class TextureGuide:
             tex, weight = texture.bake(v, n, tri, self.face, self.coeff, picture.to(v.dtype).contiguous(), zbuf,
                                        facing=self.facing)
             cover = float(texture.coverage(self.face, weight)[0])
-            out, filled = texture.pad(tex, weight, self.passes)
-            if self.fill == "mean":
-                out = texture.fill_mean(out, weight, filled)
+            out = self.finish(tex, weight)
         generate.save_image(out.clamp(-1, 1).cpu(), os.path.join(out_dir, stem + "_texture.png"))
         grey = np.round(weight[0, 0].cpu().numpy().astype(np.float64) * 255.0).astype(np.uint8)
         try:
@@ -447,7 +488,30 @@ class TextureGuide:
                 f.write(b"P5 %d %d 255\n" % (grey.shape[1], grey.shape[0]) + grey.tobytes())
         utils_3d.save_textured_obj(os.path.join(out_dir, stem + "_textured.obj"), v[0].cpu().numpy(), tri.cpu().numpy(),
                                    self.uv.numpy(), self.tri_uv.numpy(), n[0].cpu().numpy(), stem + "_texture.png")
+        if keep is not None:
+            keep.append((tex, weight))
+            return {"texture_coverage": np.float64(cover), "texture": tex[0].cpu().numpy(),
+                    "texture_weight": weight[0, 0].cpu().numpy()}
         return {"texture_coverage": np.float64(cover)}
+
+    def merged_outputs(self, bakes, sharpness, out_dir, name, v, n, tri):
+        """Merges the views' bakes (`outputs`' keep list), writes the subject's NAME_merged_texture.png, _weight.png,
+        _views.png and NAME_merged.obj / .mtl on the mesh v, n [1, nv, 3], and returns the entries of NAME_identity.npz."""
+        from .op import texture
+
+        with torch.no_grad():
+            tex, weight, best = texture.merge(torch.cat([t for t, _ in bakes], 0), torch.cat([w for _, w in bakes], 0),
+                                              sharpness)
+            cover = float(texture.coverage(self.face, weight)[0])
+            out = self.finish(tex, weight)
+        generate.save_image(out.clamp(-1, 1).cpu(), os.path.join(out_dir, name + "_merged_texture.png"))
+        grey = np.round(weight[0, 0].cpu().numpy().astype(np.float64) * 255.0).astype(np.uint8)
+        self.save_grey(grey, os.path.join(out_dir, name + "_merged_texture_weight.png"))
+        self.save_grey(np.ascontiguousarray(best.cpu().numpy()), os.path.join(out_dir, name + "_merged_texture_views.png"))
+        utils_3d.save_textured_obj(os.path.join(out_dir, name + "_merged.obj"), v[0].cpu().numpy(), tri.cpu().numpy(),
+                                   self.uv.numpy(), self.tri_uv.numpy(), n[0].cpu().numpy(), name + "_merged_texture.png")
+        return {"merged_coverage": np.float64(cover), "merged_texture": tex[0].cpu().numpy(),
+                "merged_weight": weight[0, 0].cpu().numpy(), "merged_best": best.cpu().numpy()}
 
 
 def reconstruct(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr=0.01, shape_reg=0.0,
@@ -461,13 +525,16 @@ def reconstruct(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr
 
 
 def reconstruct_batch(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr=0.01, shape_reg=0.0,
-                      n_mean_latent=4096, inv=None, **landmark_args):
+                      n_mean_latent=4096, inv=None, shared_identity=None, **landmark_args):
     """Fits the B images of target [B, 3, H, W] together; `inv` (an inverter of the same batch from an earlier call) is
     re-targeted instead of built anew.  Returns the inverter and the loss history [steps, B] (host).  landmark_args:
-    LatentInverter's landmark and mask keywords."""
+    LatentInverter's landmark and mask keywords.  shared_identity=K: the images are views of one subject and share the
+    leading K coefficients (a re-targeted inverter keeps the K it was built with)."""
     if inv is None:
+        more = {} if shared_identity is None else {"shared_identity": shared_identity}
         inv = inversion.LatentInverter(g, percept, target, None, lr=lr, pose_lr=pose_lr, n_mean_latent=n_mean_latent,
-                                       face=face, fit_shape=True, coeff_lr=coeff_lr, shape_reg=shape_reg, **landmark_args)
+                                       face=face, fit_shape=True, coeff_lr=coeff_lr, shape_reg=shape_reg, **more,
+                                       **landmark_args)
     elif landmark_args:
         inv.reset(target, landmark_args.get("landmarks"), landmark_args.get("landmark_conf"),
                   **({"mask": landmark_args["mask"]} if landmark_args.get("mask") is not None else {}))
@@ -501,6 +568,27 @@ def write_outputs(inv, hist, out_dir, stem, index=0, extras=None):
              pose=pose.cpu().numpy(), loss=hist, **inv.face_model.fit_extras(coeff), **(extras or {}))
 
 
+def subject_outputs(inv, hist, out_dir, name, stems, covers=None, painter=None, bakes=None, sharpness=2):
+    """The per-subject files of a --multiview group: NAME_identity.obj (the model's mesh at the shared coefficients, every
+    other coefficient and the pose 0) and NAME_identity.npz; with a painter also the merged texture's files.  hist
+    [steps, V]: the views' loss histories; covers: the views' `texture_coverage`."""
+    k = inv.shared_identity
+    coeff = inv.coeff.detach()
+    shared = coeff[0, :k]
+    with torch.no_grad():
+        only = torch.zeros_like(coeff[:1])
+        only[0, :k] = shared
+        v, n = inv.face_model.mesh(only, torch.zeros(1, 7, device=coeff.device, dtype=coeff.dtype), inv.tri)[:2]
+    utils_3d.save_obj(os.path.join(out_dir, name + "_identity.obj"), v[0].cpu().numpy(), inv.tri.cpu().numpy(),
+                      vn=n[0].cpu().numpy())
+    entries = {"identity": shared.cpu().numpy(), "views": np.asarray(stems), "loss": hist.sum(1)}
+    if painter is not None:
+        entries.update(painter.merged_outputs(bakes, sharpness, out_dir, name, v.contiguous(), n.contiguous(), inv.tri))
+        entries["texture_coverage"] = np.asarray(covers, np.float64)
+    np.savez(os.path.join(out_dir, name + "_identity.npz"), **entries)
+    return entries
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Face reconstruction: fit W+, pose and 3DMM coefficients to images")
     ap.add_argument("--size", type=int, default=256, help="output image size of the generator [%(default)d]")
@@ -524,8 +612,18 @@ def main(argv=None):
     ap.add_argument("--lpips-trunk", default=None, metavar="PATH",
                     help="torchvision vgg16 (or vgg16().features) state dict for the LPIPS trunk")
     ap.add_argument("--n_mean_latent", type=int, default=4096, help="latents averaged for the starting W+ [%(default)d]")
-    ap.add_argument("--batch", type=int, default=1,
-                    help="images fitted together in one batched inverter (one captured graph) [%(default)d]")
+    ap.add_argument("--batch", type=int, default=None,
+                    help="images fitted together in one batched inverter (one captured graph) [1]")
+    ap.add_argument("--multiview", type=int, default=None, metavar="V",
+                    help="the images are consecutive groups of V views of one subject each: a group is fitted together "
+                         "(as --batch V) with the identity coefficients shared by its views")
+    ap.add_argument("--identity_dims", type=int, default=None, metavar="K",
+                    help="with --multiview: how many leading coefficients the views share [the face model's n_identity]")
+    ap.add_argument("--subject", default=None, metavar="NAME",
+                    help="with --multiview and a single group: the name of the subject's files [the first view's stem]")
+    ap.add_argument("--merge_sharpness", type=int, default=None, metavar="S",
+                    help="with --multiview and --texture: the views' textures are blended with the weights "
+                         "(w / max w)^(2^S), S in 0..4 [2]")
     ap.add_argument("--lmk", default=None, metavar="LANDMARKS.txt",
                     help="landmark file (one picture per line: its name and x y pairs in its pixels): guides the fit")
     ap.add_argument("--lmk_index", default=None, metavar="FILE",
@@ -581,6 +679,26 @@ def main(argv=None):
     ap.add_argument("ckpt", metavar="CHECKPOINT", help="checkpoint holding g_ema of a GeneratorWithMap")
     ap.add_argument("images", metavar="IMAGE", nargs="+", help="PNG / JPG, or .npy in [-1, 1] (HWC or CHW)")
     args = ap.parse_args(argv)
+    if args.multiview is None:
+        if args.identity_dims is not None or args.subject is not None or args.merge_sharpness is not None:
+            ap.error("--identity_dims, --subject and --merge_sharpness need --multiview")
+    else:
+        if args.multiview < 1:
+            ap.error("--multiview must be at least 1")
+        if args.batch is not None and args.batch != args.multiview:
+            ap.error("--multiview V implies --batch V and conflicts with --batch %d" % args.batch)
+        if len(args.images) % args.multiview:
+            raise SystemExit("reconstruct: --multiview %d takes the images in groups of %d views, got %d images"
+                             % (args.multiview, args.multiview, len(args.images)))
+        if args.subject is not None and len(args.images) != args.multiview:
+            ap.error("--subject names the files of a single group; with several groups each takes its first view's stem")
+        if args.merge_sharpness is not None and args.texture is None:
+            ap.error("--merge_sharpness needs --texture")
+        if args.merge_sharpness is not None and not 0 <= args.merge_sharpness <= 4:
+            ap.error("--merge_sharpness lies in 0..4")
+        args.batch = args.multiview
+    if args.batch is None:
+        args.batch = 1
     if args.batch < 1:
         ap.error("--batch must be at least 1")
     if args.lmk_index and not args.lmk:
@@ -619,6 +737,12 @@ def main(argv=None):
     painter = (TextureGuide(face, args.texture, args.uv, args.texture_from or "picture", args.texture_facing or "0.1,0.4",
                             8 if args.texture_pad is None else args.texture_pad, args.texture_fill or "mean")
                if args.texture is not None else None)
+    shared = None
+    if args.multiview is not None:
+        shared = face[0].n_identity if args.identity_dims is None else args.identity_dims
+        if not 1 <= shared <= face[0].n_coeff:
+            raise SystemExit("reconstruct: the views share K coefficients with 1 <= K <= %d (the model's), got %d: pass "
+                             "--identity_dims K" % (face[0].n_coeff, shared))
     os.makedirs(args.out, exist_ok=True)
     results = []
 
@@ -631,12 +755,12 @@ def main(argv=None):
         look = guide.lookup(path, shape, args.size) + (shape,)
         return x, look, masker.lookup(path, look, args.size) if masker else None
 
-    def more(inv, index, stem, extras, path):
+    def more(inv, index, stem, extras, path, keep=None):
         """The .npz entries with the region's and the texture's (and their files written), when there are any."""
         if masker is not None:
             extras = dict(extras or {}, **mask_outputs(inv, index, args.out, stem))
         if painter is not None:
-            extras = dict(extras or {}, **painter.outputs(inv, index, args.out, stem, path))
+            extras = dict(extras or {}, **painter.outputs(inv, index, args.out, stem, path, keep))
         return extras
 
     def closing():
@@ -650,7 +774,7 @@ def main(argv=None):
             return ""
         return ", landmarks %s" % ("not listed" if np.isnan(extras["lmk_error"]) else "%.3f px" % float(extras["lmk_error"]))
 
-    if args.batch == 1:
+    if args.batch == 1 and shared is None:
         for path in args.images:
             stem = os.path.splitext(os.path.basename(path))[0]
             target, look, mask = load(path)
@@ -681,15 +805,32 @@ def main(argv=None):
         if masker:
             lmk_args.update(masker.inverter_args(masks))
         inv, hist = reconstruct_batch(g, percept, face, torch.cat(targets, 0).to(device), args.steps, args.lr,
-                                      args.pose_lr, args.coeff_lr, args.shape_reg, args.n_mean_latent, inv=inv, **lmk_args)
+                                      args.pose_lr, args.coeff_lr, args.shape_reg, args.n_mean_latent, inv=inv,
+                                      shared_identity=shared, **lmk_args)
+        stems = [os.path.splitext(os.path.basename(path))[0] for path in group]
+        name = (args.subject or stems[0]) if shared is not None else None
+        bakes = [] if shared is not None and painter is not None else None
+        covers = []
         for i, path in enumerate(group):
-            stem = os.path.splitext(os.path.basename(path))[0]
+            stem = stems[i]
             h = np.ascontiguousarray(hist[:, i])
-            extras = landmark_outputs(inv, i, looks[i][1], looks[i][2], looks[i][3]) if guide else None
-            write_outputs(inv, h, args.out, stem, index=i, extras=more(inv, i, stem, extras, path))
+            lmk = landmark_outputs(inv, i, looks[i][1], looks[i][2], looks[i][3]) if guide else None
+            extras = more(inv, i, stem, lmk, path, bakes)
+            if shared is not None:
+                extras = dict(extras or {}, subject=np.asarray(name), view=np.int64(i))
+                if painter is not None:
+                    covers.append(float(extras["texture_coverage"]))
+            write_outputs(inv, h, args.out, stem, index=i, extras=extras)
             print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f%s" % (
-                path, float(h[0]), float(h[-1]), len(h), float(inv.coeff.detach()[i].norm()), tail(extras)), flush=True)
+                path, float(h[0]), float(h[-1]), len(h), float(inv.coeff.detach()[i].norm()), tail(lmk)), flush=True)
             results.append((stem, h))
+        if shared is not None:
+            entries = subject_outputs(inv, hist[:, :len(group)], args.out, name, stems, covers, painter, bakes,
+                                      2 if args.merge_sharpness is None else args.merge_sharpness)
+            print("%s: %d views share %d coefficients, |identity| %.4f%s" % (
+                name, len(group), shared, float(np.linalg.norm(entries["identity"])),
+                ", merged texture covers %.3f (views: %s)" % (float(entries["merged_coverage"]), " ".join(
+                    "%.3f" % c for c in covers)) if painter is not None else ""), flush=True)
     closing()
     return results
 
