@@ -944,6 +944,29 @@ int sr_texture_merge(float* tex, float* weight, uint8_t* best, const float* tex_
  *   input are bit-identical.  B <= 65535. */
 int sr_share_rows(float* g, int64_t B, int64_t d, int64_t k, sr_stream_t stream);
 
+/* The perspective camera of face reconstruction (definition: stylerenderer_amd/op/camera.py), csrc/camera.hip.  v, v', n,
+ * n_view, gv, gv' are [B, nv, 3], kappa and gkappa [B]; kappa[b] = 1 / the camera's distance from the plane z = 0 in
+ * half-picture-widths.  Per vertex (x, y, z) of row b with k = kappa[b], every step one float32 operation in this order:
+ *     q0 = 1 - k z;  clamped = q0 < 1/16;  q = clamped ? 1/16 : q0;  v' = (x / q, y / q, z / q)
+ *     a = (k x', k y');  len = sqrt(1 + (a.x a.x + a.y a.y));  d = (-a.x / len, -a.y / len, 1 / len)
+ *     c = (N.x d.x + N.y d.y) + N.z d.z;  e = (c + N.z) / (1 + d.z)
+ *     n_view = (N.x - e d.x, N.y - e d.y, (N.z - e (d.z + 1)) + 2 c);  k == 0: n_view = N
+ * sr_camera_fwd: v' and, when n_view and n are given (both or neither), n_view.  One launch for the batch; a lane owns four
+ *   vertices (three 16-byte loads and stores) where the row's offset allows and all tensors are 16-byte aligned, the at most
+ *   six other vertices of a row and unaligned tensors go one vertex per lane.
+ * sr_camera_bwd: gv and, when gkappa is given, gkappa from gv' (n_view is a constant of the backward pass):
+ *     u = (x' gx' + y' gy') + z' gz';  t = u / q;  gv = gv' / q;  gv.z = gv.z + k t unless clamped
+ *     gkappa[b] = sum_i z_i t_i, a clamped vertex adding 0
+ *   vp is v' of the forward call or NULL (recomputed, the same bits).  One launch; with gkappa one workgroup of 1024 lanes per
+ *   row: a lane adds the terms of its items (item j, j + 1024, ... of the row; a group's four vertices in order), then a
+ *   fixed-order tree of depth 10 in LDS.
+ * B <= 65535.  No atomics, no scratch, no memset, no allocation, no host read: both run under graph capture on `stream`;
+ * reruns are bit-identical. */
+int sr_camera_fwd(float* vp, float* n_view, const float* v, const float* n, const float* kappa, int64_t B, int64_t nv,
+                  sr_stream_t stream);
+int sr_camera_bwd(float* gv, float* gkappa, const float* v, const float* vp, const float* gvp, const float* kappa,
+                  int64_t B, int64_t nv, sr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,8 @@ SIGNATURES = {
     "sr_texture_pad": (_i, [_p] * 4 + [_l] * 4 + [_p]),
     "sr_texture_merge": (_i, [_p] * 5 + [_l] * 4 + [_i, _p]),
     "sr_share_rows": (_i, [_p] + [_l] * 3 + [_p]),
+    "sr_camera_fwd": (_i, [_p] * 5 + [_l, _l, _p]),
+    "sr_camera_bwd": (_i, [_p] * 6 + [_l, _l, _p]),
     "sr_signal_bump": (_i, [_p, _p]),
     "sr_signal_wait": (_i, [_p, ctypes.c_uint32, _p]),
     "sr_signal_set": (_i, [_p, _p, _p]),

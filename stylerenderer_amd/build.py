@@ -39,6 +39,7 @@ SOURCES = [
     ("region.hip", EXACT),
     ("texture.hip", EXACT),
     ("share.hip", EXACT),
+    ("camera.hip", EXACT),
     ("morph.hip", []),
     ("skin.hip", []),
     ("blend.hip", []),

@@ -45,6 +45,18 @@ through the same element-wise Adam, so coeff[:, :K] stays equal across the rows 
 parameter.  Every row keeps its own prior term, as in the batched fit: the objective is the sum of the V single-view
 objectives under the constraint, so the shared columns' prior enters V times; it is not rescaled.
 
+With camera= (a float or [B] of kappa = 1 / distance, the camera's distance from the plane z = 0 of pose space in
+half-picture-widths) the posed mesh passes through op.camera.project before the landmark term and the generator see it: one
+node, one launch each way, after the model's node (or the fixed mesh's pose).  The consumers stay orthographic; with
+landmark_vis the same launch writes n_view, the normals as a facing gate must read them under a camera, while the generator
+keeps the camera-space normals.  fit_camera=True makes kappa a variable [B] with its own Adam group (camera_lr, a starting
+value, not tuned): one value per row, per view under shared_identity, unconstrained (a negative fit is reported as it is).
+`fitted_mesh()` returns what the consumers saw, `fitted_mesh(projected=False)` the camera-space mesh; `reset` puts kappa
+back at its start.  With camera=None there is no node and no parameter: the iteration and its captured graph are unchanged.
+Known degeneracy: for image-plane positions, (e^s, t_xy, t_z, kappa) and (e^s / (1 - kappa t_z), t_xy / (1 - kappa t_z), 0,
+kappa) project identically, so t_z and the scale trade off along a flat direction; compare projections, kappa and angles
+between fits, never raw t_z or s.  kappa is only weakly determined by the image terms alone: it wants landmarks.
+
 The pose gradient reaches the vertices only through the rasterizer's backward (deterministic gather, so two
 runs from the same state produce bit-identical trajectories).  On a GPU the whole iteration — forward, backward,
 Adam — is one hipGraph (batch 1 is launch-latency bound: ~2 000 kernels per step), replayed `steps` times; the
@@ -60,13 +72,18 @@ class _FlatAdamSet:
     """The per-variable optim.FlatAdam instances of the device path behind torch.optim's two calls (scripts and callers
     written against `inverter.optim.step()` keep working: ADVICE r4)."""
 
-    def __init__(self, adams):
+    def __init__(self, adams, direct=()):
         self.adams = adams
+        # variables whose backward node writes the gradient into the optimiser's buffer itself (op.camera's gkappa_out):
+        # no p.grad, no copy
+        self.direct = tuple(direct)
 
     @torch.no_grad()
     def step(self):
         for p, adam in self.adams:
-            if p.grad is not None:
+            if any(p is q for q in self.direct):
+                adam.step()
+            elif p.grad is not None:
                 adam.flat_g[:p.numel()].copy_(p.grad.reshape(-1))
                 adam.step()
 
@@ -80,7 +97,7 @@ class LatentInverter:
                  n_mean_latent=4096, use_graph=None, optimise_pose=True, *, face=None, fit_shape=False, coeff_lr=0.01,
                  shape_reg=0.0, landmarks=None, landmark_conf=None, landmark_weight=1.0, landmark_beta=1.0,
                  landmark_embedding=None, landmark_lines=None, landmark_axis=None, landmark_vis=None, mask=None,
-                 mask_mesh=False, shared_identity=None):
+                 mask_mesh=False, shared_identity=None, camera=None, fit_camera=False, camera_lr=0.01):
         self.g = generator.eval()
         self.perceptual = perceptual.eval()
         for p in list(self.g.parameters()) + list(self.perceptual.parameters()):
@@ -155,12 +172,21 @@ class LatentInverter:
         self.coeff = (torch.zeros(self.batch, self.face_model.n_coeff, device=self.device, requires_grad=True)
                       if self.fit_shape else None)
         self.noise = noise if noise is not None else [n.detach() for n in self.g.make_noise()]
+        # the perspective camera (op.camera): not part of the iteration at all with camera=None
+        self.camera = self._camera_start = self._camera_grad = None
+        self.fit_camera = bool(fit_camera)
+        if camera is not None:
+            self._init_camera(camera)
+        elif self.fit_camera:
+            raise ValueError("LatentInverter: fit_camera=True needs camera=, the start value of kappa = 1 / distance")
         on_gpu = self.device.type == "cuda"
         groups = [{"params": [self.w], "lr": lr}]
         if optimise_pose:
             groups.append({"params": [self.pose], "lr": pose_lr})
         if self.fit_shape:
             groups.append({"params": [self.coeff], "lr": coeff_lr})
+        if self.fit_camera:
+            groups.append({"params": [self.camera], "lr": camera_lr})
         if on_gpu:
             # one sr_adam_flat launch per variable (optim.FlatAdam, the training loop's optimiser) instead of the ~30
             # multi-tensor passes of torch's capturable foreach Adam: at batch 1 every launch is ~5 us of an 8 ms step
@@ -170,8 +196,14 @@ class LatentInverter:
             for g_ in groups:
                 p = g_["params"][0]
                 flat_g = torch.zeros((p.numel() + ALIGN - 1) // ALIGN * ALIGN, device=self.device)
-                self._adams.append((p, FlatAdam([p], flat_g, lr=g_["lr"], betas=(0.9, 0.999))))
-            self.optim = _FlatAdamSet(self._adams)       # `.optim.step()` / `.zero_grad()` like torch's optimiser
+                # kappa's Adam counts its steps on the latent's counter (they step together, the latent first): with the
+                # gradient written into flat_g by the camera's backward, the variable costs one launch per step
+                own = p is self.camera
+                self._adams.append((p, FlatAdam([p], flat_g, lr=g_["lr"], betas=(0.9, 0.999),
+                                                step_from=self._adams[0][1] if own else None)))
+                if own:
+                    self._camera_grad = flat_g
+            self.optim = _FlatAdamSet(self._adams, [self.camera] if self.fit_camera else [])
         else:
             self._adams = None
             self.optim = optim.Adam(groups, betas=(0.9, 0.999))
@@ -183,6 +215,41 @@ class LatentInverter:
     # ---- model ----------------------------------------------------------------------------------------
     skinned = property(lambda self: self.fit_shape and self.face_model.kind == "skinned")       # FLAME: op.skin
     blended = property(lambda self: self.fit_shape and self.face_model.kind == "blended")       # FaceWarehouse: op.blend
+
+    # ---- camera --------------------------------------------------------------------------------------
+    def _init_camera(self, camera):
+        """camera: a float or [B] of kappa = 1 / distance, the start values (kept for reset)."""
+        import math
+
+        if isinstance(camera, torch.Tensor):
+            k = camera.detach().to(device="cpu", dtype=torch.float64).reshape(-1)
+        elif isinstance(camera, (int, float)) and not isinstance(camera, bool):
+            k = torch.full((self.batch,), float(camera), dtype=torch.float64)
+        else:
+            try:
+                k = torch.as_tensor([float(x) for x in camera], dtype=torch.float64)
+            except (TypeError, ValueError):
+                raise ValueError("LatentInverter: camera is a float or %d floats, got %r" % (self.batch, camera))
+        if k.numel() == 1 and self.batch > 1 and not isinstance(camera, (int, float)):
+            k = k.expand(self.batch).clone()
+        if k.numel() != self.batch:
+            raise ValueError("LatentInverter: %d images need camera [%d] (or one float), got %d values"
+                             % (self.batch, self.batch, k.numel()))
+        if not all(math.isfinite(x) for x in k.tolist()):
+            raise ValueError("LatentInverter: camera (kappa = 1 / distance) must be finite")
+        self._camera_start = k.to(device=self.device, dtype=torch.float32)
+        self.camera = self._camera_start.clone().requires_grad_(self.fit_camera)
+
+    def _project(self, v, n, gate=False):
+        """The mesh the consumers see: (v', n_view or None) of the camera-space mesh (op.camera.project: one launch each
+        way on the device).  gate: a facing gate will read the normals, so the same launch writes n_view."""
+        from .op.camera import project
+
+        # (on the device a fitted kappa's gradient goes straight into its Adam's buffer)
+        out = self._camera_grad if torch.is_grad_enabled() else None
+        if gate:
+            return project(v, self.camera, normals=n, gkappa_out=out)
+        return project(v, self.camera, gkappa_out=out), None
 
     # ---- landmarks -----------------------------------------------------------------------------------
     def _init_landmarks(self, landmarks, conf, weight, beta, embedding, lines=None, axis=None, vis=None):
@@ -313,7 +380,15 @@ class LatentInverter:
         v, n, reg, self._prior_rows = self.face_model.mesh(self.coeff, self.pose.view(-1, 7), self.tri, self.shape_reg)
         return v, n, self.tri, reg
 
-    def posed_mesh(self):
+    def posed_mesh(self, projected=True):
+        """(v, n, tri) of the current variables.  With a camera and projected=True, v is what the consumers see (v' of
+        op.camera.project) and n stays the camera-space normal; projected=False gives the camera-space mesh."""
+        v, n, tri = self._camera_space_mesh()
+        if self.camera is not None and projected:
+            v = self._project(v, n)[0]
+        return v, n, tri
+
+    def _camera_space_mesh(self):
         if self.fit_shape:
             return self._shape_mesh()[:3]
         lin, rot = utils_3d.pose_matrices(self.pose)                                    # [B, 3, 3] each
@@ -323,10 +398,14 @@ class LatentInverter:
         n = utils_3d.affine3(self.n0, rot)
         return v.contiguous(), n.contiguous(), self.tri
 
-    def fitted_mesh(self):
-        """(v, n, tri) of the current fit, posed and detached."""
+    def fitted_mesh(self, projected=True):
+        """(v, n, tri) of the current fit, posed and detached.  With a camera this is what the consumers saw: the
+        projected vertices v' and n_view, the normals as the facing gates read them (op.camera); projected=False returns
+        the camera-space mesh.  Without a camera the two are the same."""
         with torch.no_grad():
-            v, n, tri = self.posed_mesh()
+            v, n, tri = self._camera_space_mesh()
+            if self.camera is not None and projected:
+                v, n = self._project(v.contiguous(), n.contiguous(), gate=True)
         return v.detach(), n.detach(), tri
 
     def render(self):
@@ -334,9 +413,14 @@ class LatentInverter:
         if self.with_map:
             if self.fit_shape:
                 v, n, tri, self._reg = self._shape_mesh()
-                mesh = (v, n, tri)
+                n_gate = n
+                if self.camera is not None:
+                    gate = self.with_landmarks and self._lmk_vis is not None
+                    v, n_view = self._project(v, n, gate)
+                    n_gate = n_view if gate else n
+                mesh = (v, n, tri)                       # (the generator keeps the camera-space normals)
                 if self.with_landmarks:
-                    self._landmark_term(v, n)
+                    self._landmark_term(v, n_gate)
             else:
                 mesh = self.posed_mesh()
             if self.mask_mesh:
@@ -351,7 +435,12 @@ class LatentInverter:
                 img, _, _ = self.g([self.w], mesh, input_is_latent=True, noise=self.noise)
         else:
             if self.with_landmarks:
-                self._landmark_term(*self._shape_mesh()[:2])
+                v, n = self._shape_mesh()[:2]
+                if self.camera is not None:
+                    gate = self._lmk_vis is not None
+                    v, n_view = self._project(v, n, gate)
+                    n = n_view if gate else n
+                self._landmark_term(v, n)
             img, _ = self.g([self.w], input_is_latent=True, noise=self.noise)
         return img
 
@@ -399,6 +488,8 @@ class LatentInverter:
         self.pose.grad = None
         if self.coeff is not None:
             self.coeff.grad = None
+        if self.camera is not None:
+            self.camera.grad = None
         img = self.render()
         value = self.loss(img)
         value.backward()
@@ -462,6 +553,8 @@ class LatentInverter:
             self.pose.zero_()
         if self.coeff is not None:
             self.coeff.zero_()
+        if self.camera is not None:
+            self.camera.copy_(self._camera_start)
         if self._adams is not None:
             for _, adam in self._adams:
                 for t in (adam.m, adam.v, adam.step_t, adam.flat_g):

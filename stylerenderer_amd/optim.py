@@ -32,7 +32,9 @@ def flat_views(flat, params, offs):
 
 
 class FlatAdam:
-    def __init__(self, params, flat_grad, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, offs=None):
+    def __init__(self, params, flat_grad, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, offs=None, step_from=None):
+        """step_from: another FlatAdam that steps before this one in every iteration; this one then reads that one's step
+        count instead of keeping (and incrementing) its own: one launch less per step."""
         self.params = list(params)
         p0 = self.params[0]
         if any(p.dtype != torch.float32 for p in self.params):
@@ -45,7 +47,8 @@ class FlatAdam:
         self.flat_p = torch.zeros(self.total, device=p0.device)
         self.m = torch.zeros_like(self.flat_p)
         self.v = torch.zeros_like(self.flat_p)
-        self.step_t = torch.zeros((), device=p0.device)
+        self.own_step = step_from is None
+        self.step_t = torch.zeros((), device=p0.device) if self.own_step else step_from.step_t
         with torch.no_grad():
             for p, view in zip(self.params, flat_views(self.flat_p, self.params, self.offs)):
                 view.copy_(p)
@@ -81,10 +84,12 @@ class FlatAdam:
             if self.guards is not None and bool(torch.isnan(self.flat_g[list(self.guards)]).any()):
                 self.skipped.fill_(1)          # refused: p / m / v AND the step count stay as they were
                 return
-            self.step_t.add_(1.0)
+            if self.own_step:
+                self.step_t.add_(1.0)
             return self._step_host(g)
         # (device: the guarded kernel takes this increment back when it refuses the step)
-        self.step_t.add_(1.0)
+        if self.own_step:
+            self.step_t.add_(1.0)
         if self.guards is not None:
             rc = _lib.lib().sr_adam_flat_guarded(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.m.data_ptr(),
                                                  self.v.data_ptr(), self.total, g["lr"], g["betas"][0], g["betas"][1],

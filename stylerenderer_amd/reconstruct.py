@@ -8,7 +8,8 @@ for it):
          [--lmk_dynamic | --lmk_lines FILE] [--lmk_axis I,J] [--lmk_vis LO,HI]]
         [--mask_lmk [--mask_tri FILE] [--mask_margin R]] [--mask_dir DIR] [--mask_mesh]
         [--texture [T] [--uv FILE] [--texture_from picture|render] [--texture_facing LO,HI] [--texture_pad N]
-         [--texture_fill mean|none]] CHECKPOINT IMAGE [IMAGE ...]
+         [--texture_fill mean|none]]
+        [--camera_distance D | --camera_fov DEG] [--fit_camera] [--camera_lr 0.01] CHECKPOINT IMAGE [IMAGE ...]
 
 For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with inversion.LatentInverter(fit_shape=True)
 — the W+ latent, a rigid pose and the 3DMM shape / expression coefficients are fitted together (op.morph on the device)
@@ -91,8 +92,21 @@ with NAME_merged.mtl, the identity mesh carrying the merged texture.  NAME_ident
 merge before padding: `merged_texture` [C, T, T], `merged_weight` [T, T] and `merged_best` [T, T]; every view's .npz
 holds its bake before padding, `texture` [C, T, T] and `texture_weight` [T, T] (float32; 4 MB per view at T = 512), so a
 merge can be repeated at another sharpness without a new fit.  Not built: exposure or colour matching between the views,
-mirror fill, a differentiable texture, per-view intrinsics or perspective, choosing the views automatically.  Without
---multiview nothing changes.
+mirror fill, a differentiable texture, choosing the views automatically.  Without --multiview nothing changes.
+
+With --camera_distance D (D > 0: the camera's distance from the plane z = 0 of pose space in half-picture-widths, which is
+the focal length in that unit) or --camera_fov DEG (the full field of view across the picture) the fit sees the mesh through
+a perspective camera with kappa = 1 / D = tan(DEG / 2) (op.camera: one node between the posed mesh and every consumer; a
+close-up taken from 35 cm and cropped to 1.5 face widths has D near 3).  --fit_camera fits kappa together with the pose, one
+value per picture (per view with --multiview), with the learning rate --camera_lr (a starting value, not tuned); kappa is not
+constrained and a negative fit is reported as it is.  kappa is only weakly determined by the image terms alone: it wants
+--lmk.  <stem>.obj, <stem>_textured.obj and the merged .obj then hold the camera-space mesh (pose applied, not projected),
+while <stem>_normal.png, the landmarks, the mask, the depth buffer and the bake use the projected mesh the fit saw;
+<stem>.npz also holds `camera` (kappa) and `camera_distance` (1 / kappa), NAME_identity.npz the views' `camera` [V].  The
+depth translation and the scale trade off along a flat direction under a camera (inversion.LatentInverter's note), so
+compare projections, kappa and angles between fits, not raw t_z or scale.  Not built: a principal-point offset (the crop is
+assumed centred on the optical axis), a closed-form perspective pose start (the orthographic one is the start), lens
+distortion.  Without these options nothing changes.
 
 Images are PNG / JPG (PIL) or .npy in [-1, 1] (HWC or CHW), resized on the host.  The 3DMM is the Basel Face Model with
 --bfm (face_model.load_bfm), FLAME with --flame (face_model.load_flame, op.skin), the FaceWarehouse bilinear blendshape
@@ -466,6 +480,8 @@ class TextureGuide:
         k = slice(index, index + 1)
         v, n, tri = inv.fitted_mesh()
         v, n = v[k].contiguous(), n[k].contiguous()
+        # (under a camera the bake reads the projected mesh and the .obj lists the camera-space one)
+        vo, no = (t[k] for t in inv.fitted_mesh(projected=False)[:2]) if inv.camera is not None else (v, n)
         if self.source == "render":
             picture = inv.image[k]
         else:
@@ -486,8 +502,8 @@ class TextureGuide:
         except ImportError:
             with open(os.path.join(out_dir, stem + "_texture_weight.pgm"), "wb") as f:
                 f.write(b"P5 %d %d 255\n" % (grey.shape[1], grey.shape[0]) + grey.tobytes())
-        utils_3d.save_textured_obj(os.path.join(out_dir, stem + "_textured.obj"), v[0].cpu().numpy(), tri.cpu().numpy(),
-                                   self.uv.numpy(), self.tri_uv.numpy(), n[0].cpu().numpy(), stem + "_texture.png")
+        utils_3d.save_textured_obj(os.path.join(out_dir, stem + "_textured.obj"), vo[0].cpu().numpy(), tri.cpu().numpy(),
+                                   self.uv.numpy(), self.tri_uv.numpy(), no[0].cpu().numpy(), stem + "_texture.png")
         if keep is not None:
             keep.append((tex, weight))
             return {"texture_coverage": np.float64(cover), "texture": tex[0].cpu().numpy(),
@@ -549,21 +565,28 @@ def write_outputs(inv, hist, out_dir, stem, index=0, extras=None):
     from .op.rasterize import rasterize
 
     k = slice(index, index + 1)
-    v, n, tri = inv.fitted_mesh()
+    # the camera-space mesh is what is written; the normal map draws what the generator saw: under a camera the projected
+    # vertices with the camera-space normals
+    v, n, tri = inv.fitted_mesh(projected=False)
     v, n = v[k], n[k]
+    vd = inv.fitted_mesh()[0][k] if inv.camera is not None else v
     coeff = inv.coeff.detach()[k]
     pose = inv.pose.detach().view(-1, 7)[index]
     with torch.no_grad():
         zero = torch.zeros_like(pose).view(1, 7)
         vc, nc = inv.face_model.mesh(coeff, zero, tri)[:2]
         size = int(inv.target.shape[-1])
-        normal_map = rasterize(v.contiguous(), n.contiguous(), tri, size, size, channel_major=True)
+        normal_map = rasterize(vd.contiguous(), n.contiguous(), tri, size, size, channel_major=True)
     tri_h = tri.cpu().numpy()
     utils_3d.save_obj(os.path.join(out_dir, stem + ".obj"), v[0].cpu().numpy(), tri_h, vn=n[0].cpu().numpy())
     utils_3d.save_obj(os.path.join(out_dir, stem + "_canonical.obj"), vc[0].cpu().numpy(), tri_h,
                       vn=nc[0].cpu().numpy())
     generate.save_image(inv.image[k].cpu(), os.path.join(out_dir, stem + "_render.png"))
     generate.save_image(normal_map.cpu(), os.path.join(out_dir, stem + "_normal.png"))
+    if inv.camera is not None:
+        kappa = float(inv.camera.detach()[index])
+        extras = dict(extras or {}, camera=np.float64(kappa),
+                      camera_distance=np.float64(1.0 / kappa if kappa != 0 else np.inf))
     np.savez(os.path.join(out_dir, stem + ".npz"), w=inv.w.detach()[k].cpu().numpy(), coeff=coeff.cpu().numpy(),
              pose=pose.cpu().numpy(), loss=hist, **inv.face_model.fit_extras(coeff), **(extras or {}))
 
@@ -582,6 +605,8 @@ def subject_outputs(inv, hist, out_dir, name, stems, covers=None, painter=None, 
     utils_3d.save_obj(os.path.join(out_dir, name + "_identity.obj"), v[0].cpu().numpy(), inv.tri.cpu().numpy(),
                       vn=n[0].cpu().numpy())
     entries = {"identity": shared.cpu().numpy(), "views": np.asarray(stems), "loss": hist.sum(1)}
+    if inv.camera is not None:
+        entries["camera"] = inv.camera.detach()[:len(stems)].cpu().numpy().astype(np.float64)
     if painter is not None:
         entries.update(painter.merged_outputs(bakes, sharpness, out_dir, name, v.contiguous(), n.contiguous(), inv.tri))
         entries["texture_coverage"] = np.asarray(covers, np.float64)
@@ -673,6 +698,17 @@ def main(argv=None):
                     help="with --texture: grow the charts by N texels (0..64) [8]")
     ap.add_argument("--texture_fill", default=None, choices=("mean", "none"),
                     help="with --texture: paint the texels still unfilled with the mean colour, or leave them black [mean]")
+    cam = ap.add_mutually_exclusive_group()
+    cam.add_argument("--camera_distance", type=float, default=None, metavar="D",
+                     help="perspective camera at distance D > 0 from the plane z = 0 of pose space, in half-picture-widths "
+                          "(the focal length in that unit): kappa = 1 / D; default: orthographic")
+    cam.add_argument("--camera_fov", type=float, default=None, metavar="DEG",
+                     help="perspective camera by its full field of view across the picture, 0 <= DEG < 180: kappa = tan(DEG / 2)")
+    ap.add_argument("--fit_camera", action="store_true",
+                    help="fit kappa = 1 / distance with the pose, one value per picture, from the start --camera_distance or "
+                         "--camera_fov gives; it wants --lmk")
+    ap.add_argument("--camera_lr", type=float, default=None,
+                    help="learning rate of kappa; a starting value, not tuned [0.01]")
     ap.add_argument("--gpu", type=int, default=0, help="use gpu id")
     ap.add_argument("--seed", type=int, default=0, help="random seed (mean latent, noise)")
     ap.add_argument("--out", default="reconstruct", metavar="DIR", help="output directory [%(default)s]")
@@ -712,6 +748,20 @@ def main(argv=None):
     if args.texture is None and (args.uv or args.texture_from or args.texture_facing or args.texture_pad is not None
                                  or args.texture_fill):
         ap.error("--uv, --texture_from, --texture_facing, --texture_pad and --texture_fill need --texture")
+    camera_args = {}
+    if args.camera_distance is not None or args.camera_fov is not None:
+        if args.camera_distance is not None:
+            if not (args.camera_distance > 0 and np.isfinite(args.camera_distance)):
+                ap.error("--camera_distance must be positive")
+            kappa = 1.0 / args.camera_distance
+        else:
+            if not 0 <= args.camera_fov < 180:
+                ap.error("--camera_fov lies in [0, 180) degrees")
+            kappa = float(np.tan(np.deg2rad(args.camera_fov) / 2))
+        camera_args = dict(camera=kappa, fit_camera=args.fit_camera,
+                           camera_lr=0.01 if args.camera_lr is None else args.camera_lr)
+    elif args.fit_camera or args.camera_lr is not None:
+        ap.error("--fit_camera and --camera_lr need --camera_distance or --camera_fov (the start of the fit)")
     torch.manual_seed(args.seed)
     if torch.cuda.is_available() and 0 <= args.gpu < torch.cuda.device_count():
         device = torch.device("cuda:%d" % args.gpu)
@@ -781,6 +831,7 @@ def main(argv=None):
             lmk_args = guide.inverter_args([look[0]], [look[1]]) if guide else {}
             if masker:
                 lmk_args.update(masker.inverter_args([mask]))
+            lmk_args.update(camera_args)
             inv, hist = reconstruct(g, percept, face, target.to(device), args.steps, args.lr, args.pose_lr, args.coeff_lr,
                                     args.shape_reg, args.n_mean_latent, **lmk_args)
             extras = landmark_outputs(inv, 0, look[1], look[2], look[3]) if guide else None
@@ -804,6 +855,7 @@ def main(argv=None):
         lmk_args = guide.inverter_args([k[0] for k in looks], [k[1] for k in looks]) if guide else {}
         if masker:
             lmk_args.update(masker.inverter_args(masks))
+        lmk_args.update(camera_args)
         inv, hist = reconstruct_batch(g, percept, face, torch.cat(targets, 0).to(device), args.steps, args.lr,
                                       args.pose_lr, args.coeff_lr, args.shape_reg, args.n_mean_latent, inv=inv,
                                       shared_identity=shared, **lmk_args)
