@@ -574,6 +574,32 @@ int sr_conv2d_nba(float* out, const float* in, const float* wt, const float* isc
  * served by the Winograd kernel, 0 when by the direct one — what a caller that keeps a scratch for SR_CONV_U_READY
  * must ask before it marks the scratch's weight block as written. */
 int sr_conv2d_uses_winograd(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, const float* in, const float* out);
+/* Which kernel family serves a sr_conv2d_mfma(_ex) call — the decision the launch itself makes (one dispatch plan,
+ * DESIGN.md 4.0), for callers that keep state per path and for tests.  Shape arguments as sr_conv2d_scratch_floats;
+ * in / out / wt / wt_ld as the call would pass them (alignment is part of several rules; NULL = assume aligned);
+ * have_scratch: 0 when the call passes scratch = NULL (no path that needs scratch is taken then).  Nothing is launched.
+ * Returns SR_CONV_PATH_INVALID for a geometry sr_conv2d_mfma rejects, else one of the values below, with
+ * SR_CONV_PATH_STRIPS or-ed in when the transposed convolution's border (output row 2*IH, column 2*IW) runs as the
+ * two strip launches behind an interior kernel (otherwise as per-phase launches of the direct kernel). */
+#define SR_CONV_PATH_INVALID (-1)
+#define SR_CONV_PATH_DIRECT 0         /* k_conv_mfma; transposed: its per-phase launches */
+#define SR_CONV_PATH_WINO 1           /* 3x3 s1 p1: Winograd F(2x2,3x3), k_conv_wino */
+#define SR_CONV_PATH_S2_BF16 2        /* 3x3 s2 p0: split-bf16 (SR_CONV_SPLIT_BF16) */
+#define SR_CONV_PATH_S2_WINO 3        /* 3x3 s2 p0: polyphase 25-product form, k_conv_s2_wino */
+#define SR_CONV_PATH_GEMM1X1 4        /* 1x1 s1 p0: plain GEMM, k_conv1x1_gemm */
+#define SR_CONV_PATH_CONVT_TAPS 5     /* transposed: tap-split, nine shifted 1x1 convolutions + k_convt_tap_reduce */
+#define SR_CONV_PATH_CONVT_BF16 6     /* transposed: interior by split-bf16 (SR_CONV_SPLIT_BF16) */
+#define SR_CONV_PATH_CONVT_FUSED_KS 7 /* transposed: interior by k_convt_fused in K slices + k_convt_fused_reduce */
+#define SR_CONV_PATH_CONVT_FUSED 8    /* transposed: interior by k_convt_fused */
+#define SR_CONV_PATH_STRIPS 0x100
+int sr_conv2d_path(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW, int ksize, int stride,
+                   int pad, int transposed, const float* in, const float* out, const float* wt, int64_t wt_ld,
+                   int have_scratch);
+/* Scratch floats the path sr_conv2d_path returns cannot run without (for SR_CONV_PATH_DIRECT: what its split-K would use;
+ * it takes what it is given) — never more than sr_conv2d_scratch_floats of the same shape.  -1 for an invalid geometry. */
+int64_t sr_conv2d_path_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW, int ksize,
+                              int stride, int pad, int transposed, const float* in, const float* out, const float* wt,
+                              int64_t wt_ld, int have_scratch);
 
 /* Generic-geometry convolution (csrc/conv_generic.hip): any kernel extent kh x kw, stride (sy, sx) and zero padding
  * (py, px), dilation 1, one group, weights in the reference's layout [N, C, kh, kw] — what the reference's EqualConv2d
@@ -624,6 +650,17 @@ int sr_conv2d_wgrad_mfma(float* dwt, const float* x, const float* gy, const floa
                          const float* gscale, int64_t B, int64_t C, int64_t N, int64_t IH,
                          int64_t IW, int64_t OH, int64_t OW, int ksize, int stride, int pad,
                          int transposed, float* scratch, sr_stream_t stream);
+/* Which kernel serves a sr_conv2d_wgrad_mfma call with these sizes and buffers (NULL = assume aligned), mirroring
+ * sr_conv2d_path; SR_WGRAD_PATH_INVALID for a geometry the call rejects. */
+#define SR_WGRAD_PATH_INVALID (-1)
+#define SR_WGRAD_PATH_DIRECT 0   /* k_wgrad_mfma */
+#define SR_WGRAD_PATH_SMALL3 1   /* 3x3 s1 p1 with <= 4 x <= 4 channels: streaming k_wgrad_small3 */
+#define SR_WGRAD_PATH_WINO 2     /* 3x3 s1 p1: Winograd, k_wgrad_wino */
+#define SR_WGRAD_PATH_BF16_1X1 3 /* 1x1 s1 p0: split-bf16 (SR_CONV_SPLIT_BF16) */
+#define SR_WGRAD_PATH_BF16_S2 4  /* 3x3 s2 p0, either direction: split-bf16 (SR_CONV_SPLIT_BF16) */
+#define SR_WGRAD_PATH_S2_DMA 5   /* 3x3 s2 p0, either direction: k_wgrad_s2_dma */
+int sr_conv2d_wgrad_path(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW, int ksize,
+                         int stride, int pad, int transposed, const float* x, const float* gy);
 
 /* ---- signalling out of a replayed hipGraph (overlapped gradient all-reduce) -----------------------------------
  * The reference overlaps the gradient all-reduce with the backward through torch DDP's bucket hooks

@@ -115,6 +115,9 @@ SIGNATURES = {
     "sr_conv2d_scratch_floats": (_l, [_l] * 7 + [_i] * 4),
     "sr_conv2d_mfma": (_i, [_p] * 6 + [_l] * 8 + [_i] * 4 + [_p, _p]),
     "sr_conv2d_uses_winograd": (_i, [_l] * 5 + [_p, _p]),
+    "sr_conv2d_path": (_i, [_l] * 7 + [_i] * 4 + [_p, _p, _p, _l, _i]),
+    "sr_conv2d_path_floats": (_l, [_l] * 7 + [_i] * 4 + [_p, _p, _p, _l, _i]),
+    "sr_conv2d_wgrad_path": (_i, [_l] * 7 + [_i] * 4 + [_p, _p]),
     "sr_conv2d_mfma_ex": (_i, [_p] * 6 + [_l] * 8 + [_i] * 5 + [_p, _p]),
     "sr_conv1x1_add_supported": (_i, [_l] * 5 + [_p] * 4),
     "sr_conv1x1_add": (_i, [_p] * 5 + [_l] * 5 + [_p]),
@@ -166,6 +169,13 @@ SIGNATURES = {
     "sr_graph_replace_memset_nodes": (_i, [_p, ctypes.POINTER(_i)]),
     "sr_graph_node_count": (_i, [_p, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
 }
+
+# sr_conv2d_path / sr_conv2d_wgrad_path values (SR_CONV_PATH_* / SR_WGRAD_PATH_* of the header)
+(CONV_PATH_DIRECT, CONV_PATH_WINO, CONV_PATH_S2_BF16, CONV_PATH_S2_WINO, CONV_PATH_GEMM1X1, CONV_PATH_CONVT_TAPS,
+ CONV_PATH_CONVT_BF16, CONV_PATH_CONVT_FUSED_KS, CONV_PATH_CONVT_FUSED) = range(9)
+CONV_PATH_STRIPS = 0x100
+(WGRAD_PATH_DIRECT, WGRAD_PATH_SMALL3, WGRAD_PATH_WINO, WGRAD_PATH_BF16_1X1, WGRAD_PATH_BF16_S2,
+ WGRAD_PATH_S2_DMA) = range(6)
 
 _lib = None
 

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
+
 #include "../../include/stylerenderer_amd.h"
 
 #define SR_WAVE 64          // CDNA wavefront width
@@ -28,6 +30,15 @@ static inline int sr_stream_grid(int64_t work_items, int per_block) {
     if (g < 1) g = 1;
     return static_cast<int>(g);
 }
+
+// Run-time switches live in the environment and are read per call (tests flip them between calls).
+// First character of a switch's value: -1 when it is not set, 0 when it is set to the empty string.
+static inline int sr_env_char(const char* name) {
+    const char* e = std::getenv(name);
+    return e ? (unsigned char)e[0] : -1;
+}
+// A switch is off when its value starts with '0'.
+static inline bool sr_env_off(const char* name) { return sr_env_char(name) == '0'; }
 
 static inline bool sr_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 

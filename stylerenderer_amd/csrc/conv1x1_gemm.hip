@@ -261,10 +261,8 @@ __global__ __launch_bounds__(256, 2) void k_convt_taps_gemm(const TapParams q) {
 
 // SR_CONV1X1_GEMM: "0" off, "force" also below the tile count that fills the chip (tests)
 int mode() {
-    const char* e = std::getenv("SR_CONV1X1_GEMM");
-    if (e && e[0] == '0') return 0;
-    if (e && e[0] == 'f') return 2;
-    return 1;
+    const int e = sr_env_char("SR_CONV1X1_GEMM");
+    return e == '0' ? 0 : (e == 'f' ? 2 : 1);
 }
 
 }  // namespace
@@ -296,11 +294,11 @@ int sr_conv1x1_gemm_launch(float* out, const float* in, const float* wt, int64_t
 
 bool sr_convt_taps_gemm_eligible(int64_t B, int64_t C, int64_t N, int64_t IW, int64_t ldw, int c_per_slice,
                                  const void* wt) {
-    const char* e = std::getenv("SR_CONVT_TAPS_GEMM");
-    if (e && e[0] == '0') return false;
+    const int e = sr_env_char("SR_CONVT_TAPS_GEMM");
+    if (e == '0') return false;
     // maps up to 32 wide: their (2^k + 1)-wide grids fill half of a 32-wide patch row; from 64 up the patch form's
     // aligned 16-byte DMA wins (batch 1, scripts/bench_convt_small.py: 0.169 against 0.180 ms at 64^2, 0.172 / 0.188 at 128^2)
-    if (IW > 32 && !(e && e[0] == 'f')) return false;
+    if (IW > 32 && e != 'f') return false;
     return B > 0 && C % KC == 0 && c_per_slice % KC == 0 && N % TN == 0 && ldw % 4 == 0 &&
            (reinterpret_cast<uintptr_t>(wt) & 15) == 0;
 }

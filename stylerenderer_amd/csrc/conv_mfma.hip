@@ -41,6 +41,7 @@
 #include "conv_wgrad_bf16x3.h"
 #include "conv_wino.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 namespace {
@@ -717,11 +718,20 @@ extern "C" int sr_debug_convt_stamps(long long* host, int n) {
 }
 #endif
 
-bool convt_fused_eligible(const ConvParams& p) {
+// One dense-convolution call as the dispatch sees it: the shape and, for the alignment rules, the buffers.  A NULL
+// buffer means "alignment unknown, assume aligned" (as the *_eligible functions of the other files treat it).
+struct ConvCall {
+    int64_t B, C, N, IH, IW, OH, OW;
+    int ksize, stride, pad, transposed;
+    const void *in, *out, *wt;
+    int64_t ldw;
+    bool is3x3(int s, int pd) const { return ksize == 3 && stride == s && pad == pd; }
+};
+
+bool convt_fused_eligible(const ConvCall& c) {
     // buffer addressing: byte offsets inside one sample / the weight tensor below 2^31 - 16
-    if ((int64_t)p.C * p.IH * p.IW >= (1LL << 29) - 4 || 9LL * p.C * p.ldw >= (1LL << 29) - 4) return false;
-    return p.IH % TFused::PH == 0 && p.IW % TFused::PW == 0 && p.C % TFused::KC == 0 && p.C <= 2048 &&
-           (reinterpret_cast<uintptr_t>(p.in) & 15) == 0;
+    if (c.C * c.IH * c.IW >= (1LL << 29) - 4 || 9 * c.C * c.ldw >= (1LL << 29) - 4) return false;
+    return c.IH % TFused::PH == 0 && c.IW % TFused::PW == 0 && c.C % TFused::KC == 0 && c.C <= 2048 && sr_aligned16(c.in);
 }
 
 // interior outputs (rows < 2 IH, columns < 2 IW) = the slices of k_convt_fused<true> added in order, then scale / bias
@@ -753,14 +763,9 @@ int convt_fused_slices(int64_t fused_blocks, int C) {
     return 1;
 }
 
-int64_t convt_fused_split_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW) {
-    const int64_t blocks = (IW / TFused::PW) * (IH / TFused::PH) * ((N + BN - 1) / BN) * B;
-    if (IW % TFused::PW || IH % TFused::PH || blocks >= 192 || C <= 256) return 0;
-    const int ks = convt_fused_slices(blocks, (int)C);
-    return ks > 1 ? ks * B * N * (2 * IH + 1) * (2 * IW + 1) : 0;
-}
-
-int launch_convt_fused(ConvParams p, hipStream_t st) {
+// ks > 1: the K slices the plan chose (convt_fused_slices)
+int launch_convt_fused(ConvParams p, int ks, hipStream_t st) {
+    if (ks > 1) { p.ks = ks; p.c_per_slice = p.C / ks; }
     p.tiles_x = p.IW / TFused::PW;
     p.tiles_y = p.IH / TFused::PH;
     p.tiles_n = (p.N + BN - 1) / BN;
@@ -847,12 +852,6 @@ __global__ __launch_bounds__(256) void k_convt_tap_reduce(const ConvParams p) {
     }
 }
 
-// SR_CONVT_TAPS=0 keeps the per-phase launches for small maps (A/B measurements); =1 forces the tap-split form for any size
-int convt_taps_mode() {
-    const char* e = std::getenv("SR_CONVT_TAPS");
-    return !e ? 2 : (e[0] == '0' ? 0 : 1);
-}
-
 // K slices of the tap-split launch: enough workgroups for ~2 per CU (the nine taps already multiply the tiles by 9),
 // >= 32 channels (a multiple of 16) per slice
 void convt_taps_plan(int IH, int IW, int B, int N, int C, int& ks, int& c_per_slice) {
@@ -892,36 +891,32 @@ void convt_taps_plan(int IH, int IW, int B, int N, int C, int& ks, int& c_per_sl
     ks = (C + per - 1) / per;
 }
 
-int64_t convt_taps_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW) {
-    int ks, per;
-    convt_taps_plan((int)IH, (int)IW, (int)B, (int)N, (int)C, ks, per);
-    return (int64_t)ks * 9 * B * N * (IH + 1) * (IW + 1);
-}
-
 // Small problems only: measured inside captured graphs (scripts/bench_convt_small.py, profiles/r05_notes.md) the
 // tap-split form wins up to ~10 GFLOP per call (4^2 .. 16^2 maps at batch 4, 32^2 .. 128^2 at batch 1: 0.042 / 0.069 /
 // 0.128 / 0.135 / 0.168 / 0.172 ms against 0.071 / 0.095 / 0.218 / 0.226 / 0.258 / 0.231; 32^2 at batch 2 and 16^2 at
 // batch 8, 9.7 GFLOP: 0.241 against 0.259 / 0.270) and loses above (its 1x1 workgroups top out at 45-60 TFLOP/s; 32^2
 // at batch 4: 0.429 against 0.352 per-phase).
+// SR_CONVT_TAPS=0 keeps the per-phase launches for small maps (A/B measurements); =1 forces the tap-split form for any size
 bool convt_taps_wanted(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW) {
-    const int mode = convt_taps_mode();
-    return mode == 1 || (mode == 2 && 18.0 * (double)B * (double)C * (double)N * (double)IH * (double)IW < 1.05e10);
+    const int sw = sr_env_char("SR_CONVT_TAPS");
+    if (sw >= 0) return sw != '0';
+    return 18.0 * (double)B * (double)C * (double)N * (double)IH * (double)IW < 1.05e10;
 }
 
 // 16-byte halo DMAs for a tap-split launch: aligned rows and an aligned tile origin (one sample per patch is checked
 // by the caller's choice of the patch shape); SR_CONVT_TAPS_V4=0 keeps the 4-byte form (A/B, tests)
 bool taps_v4(const ConvParams& p) {
-    const char* e = std::getenv("SR_CONVT_TAPS_V4");
-    return !(e && e[0] == '0') && p.IW % 4 == 0 && p.gx_base % 4 == 0 && (reinterpret_cast<uintptr_t>(p.in) & 15) == 0;
+    return !sr_env_off("SR_CONVT_TAPS_V4") && p.IW % 4 == 0 && p.gx_base % 4 == 0 && sr_aligned16(p.in);
 }
 
-int launch_convt_taps(ConvParams p, hipStream_t st) {
+// ks / c_per_slice: convt_taps_plan's; gemm: the flattened-pixel form (sr_convt_taps_gemm_eligible for this call's weights)
+int launch_convt_taps(ConvParams p, int ks, int c_per_slice, bool gemm, hipStream_t st) {
     p.GH = p.IH + 1; p.GW = p.IW + 1;                // common grid of the four phases
     p.gy_base = p.gx_base = 0;
     p.osy = p.osx = 2; p.ooy = p.oox = 0;
     p.dy0 = p.dx0 = 0;
     p.tap_first = 0; p.tap_step = 1; p.tap_count = 9;
-    convt_taps_plan(p.IH, p.IW, p.B, p.N, p.C, p.ks, p.c_per_slice);
+    p.ks = ks; p.c_per_slice = c_per_slice;
     int pw, ph, pb;
     patch_shape(p.GW, pw, ph, pb);
     p.tiles_x = (p.GW + pw - 1) / pw;
@@ -933,7 +928,7 @@ int launch_convt_taps(ConvParams p, hipStream_t st) {
     const dim3 grid((unsigned)blocks);
     const bool v4 = taps_v4(p);
     int rc;
-    if (sr_convt_taps_gemm_eligible(p.B, p.C, p.N, p.IW, p.ldw, p.c_per_slice, p.wt))
+    if (gemm)
         // pixels = the flattened (sample, grid point) index instead of 32 x 4 patches of a (2^k + 1)-wide grid
         rc = sr_convt_taps_gemm_launch(p.partial, p.in, p.wt, p.ldw, p.iscale, p.B, p.C, p.N, p.IH, p.IW, p.ks, p.c_per_slice, st);
     else if (pw == 32) rc = v4 ? launch_one<1, 1, 1, 32, 4, 1, true, true>(p, grid, st)
@@ -1035,29 +1030,10 @@ int launch_convt_strips(ConvParams p, hipStream_t st) {
     return sr_launch_status();
 }
 
-// Winograd F(2x2,3x3) for the stride-1 3x3 convolution (csrc/conv_wino.hip); SR_WINOGRAD=0 keeps the
-// direct implicit GEMM (A/B measurements, exact-fma-chain numerics).
-bool wino_enabled() {
-    const char* e = std::getenv("SR_WINOGRAD");      // read per call: tests flip it at run time
-    return !(e && e[0] == '0');
-}
-
-// Polyphase 25-product form of the non-transposed stride-2 3x3 convolution (csrc/conv_s2_wino.hip):
-// SR_CONV_S2_WINO=0 keeps k_conv_mfma, =force ignores the workgroup threshold (tests).  0 off, 1 on, 2 forced.
-int s2_wino_mode() {
-    const char* e = std::getenv("SR_CONV_S2_WINO");  // read per call: tests flip it at run time
-    if (e && e[0] == '0') return 0;
-    return (e && e[0] == 'f') ? 2 : 1;
-}
+// Polyphase 25-product form of the non-transposed stride-2 3x3 convolution (csrc/conv_s2_wino.hip).
 // The kernel has no K slices: launches with fewer workgroups stay on k_conv_mfma, whose split-K serves them (the
 // threshold k_convt_fused uses for the same reason; measurements in DESIGN.md 4.1y).
 constexpr int64_t S2_WINO_MIN_BLOCKS = 192;
-
-// SR_CONV_ROT=0 keeps the 4-byte halo DMA of the stride-2 kernels (A/B measurements)
-bool rot_enabled() {
-    const char* e = std::getenv("SR_CONV_ROT");
-    return !(e && e[0] == '0');
-}
 
 template <int IS, int TY, int TX>
 int launch_by_patch(ConvParams& p, hipStream_t st) {
@@ -1081,13 +1057,13 @@ int launch_by_patch(ConvParams& p, hipStream_t st) {
     if (blocks > 0x7FFFFFFFLL) return SR_ERANGE;
     const dim3 grid((unsigned)blocks);
     // 16-byte halo DMAs: stride 1, one sample per tile, aligned rows, window origin dx0 = -(TX > 1)
-    const bool v4 = IS == 1 && pb == 1 && p.IW % 4 == 0 && (reinterpret_cast<uintptr_t>(p.in) & 15) == 0 &&
+    const bool v4 = IS == 1 && pb == 1 && p.IW % 4 == 0 && sr_aligned16(p.in) &&
                     p.gx_base % 4 == 0 && p.dx0 == (TX > 1 ? -1 : 0);
     // rotating-lead 16-byte DMAs for stride 2 (see Geo): (2^k+1)-sized maps, window inside the image, whole tiles
     const bool rot = IS == 2 && pb == 1 && (p.IW & 3) == 1 && ((p.IH * p.IW) & 3) == 1 && p.C % 4 == 0 &&
-                     (reinterpret_cast<uintptr_t>(p.in) & 15) == 0 && p.dx0 >= 0 && p.dy0 >= 0 && p.gx_base == 0 &&
+                     sr_aligned16(p.in) && p.dx0 >= 0 && p.dy0 >= 0 && p.gx_base == 0 &&
                      p.gy_base == 0 && (p.GW - 1) * 2 + p.dx0 + TX <= p.IW && (p.GH - 1) * 2 + p.dy0 + TY <= p.IH &&
-                     ext_w % pw == 0 && ext_h % ph == 0 && rot_enabled();
+                     ext_w % pw == 0 && ext_h % ph == 0 && !sr_env_off("SR_CONV_ROT");   // =0: the 4-byte halo DMA (A/B)
     int rc;
     if (IS == 1 && v4) {
         if (pw == 32) rc = launch_one<1, TY, TX, 32, 4, 1, true>(p, grid, st);
@@ -1105,180 +1081,130 @@ int launch_by_patch(ConvParams& p, hipStream_t st) {
     return sr_launch_status();
 }
 
-}  // namespace
+// ---- dispatch plan: which kernel serves a call is decided ONCE, by make_conv_plan (DESIGN.md 4.0 has the table) ------------
 
-extern "C" int64_t sr_conv2d_scratch_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW,
-                                            int64_t OH, int64_t OW, int ksize, int stride, int pad,
-                                            int transposed) {
-    (void)ksize; (void)stride; (void)pad;
-    if (B <= 0 || C <= 0 || N <= 0 || OH <= 0 || OW <= 0) return 0;
-    // regions a launch may split: the whole output grid (small maps) or, for the transposed conv,
-    // its border strips.  Upper bound: ks * B * N * region for the largest split region.
+// Scratch the direct kernel's split-K would use: ks * B * N * region for the largest region a launch may split — the
+// whole output grid or, transposed, the phase grids and their border strips.  A wish, not a need: launch_by_patch drops
+// to one slice when the slab does not fit.
+int64_t direct_floats(const ConvCall& c) {
     int ks, per;
     int64_t need = 0;
     auto consider = [&](int64_t gh, int64_t gw) {
         if (gh <= 0 || gw <= 0) return;
-        choose_split((int)gh, (int)gw, (int)B, (int)N, (int)C, ks, per);
-        if (ks > 1) need = need > ks * B * N * gh * gw ? need : ks * B * N * gh * gw;
+        choose_split((int)gh, (int)gw, (int)c.B, (int)c.N, (int)c.C, ks, per);
+        if (ks > 1) need = std::max(need, ks * c.B * c.N * gh * gw);
     };
-    if (!transposed) {
-        consider(OH, OW);
-        if (ksize == 3 && stride == 2 && pad == 0 && sr_wgrad_bf16x3_enabled('c') &&
-            sr_conv_s2_bf16x3_eligible(B, C, N, IH, IW, OH, OW)) {
-            const int64_t w = sr_conv_s2_bf16x3_scratch_floats(C, N);
-            need = need > w ? need : w;
-        }
-        // (whatever the switch says: it is read per call, the scratch may be sized before it flips)
-        if (ksize == 3 && stride == 2 && pad == 0 && sr_conv_s2_wino_eligible(B, C, N, IH, IW, OH, OW, nullptr, nullptr)) {
-            const int64_t w = sr_conv_s2_wino_scratch_floats(C, N);
-            need = need > w ? need : w;
-        }
-        if (ksize == 3 && stride == 1 && pad == 1 && wino_enabled() &&
-            sr_wino_eligible(B, C, N, IH, IW, nullptr, nullptr)) {
-            const int64_t w = sr_wino_scratch_floats(C, N) + sr_wino_partial_floats(B, C, N, IH, IW);
-            need = need > w ? need : w;
-        }
-    } else {
-        consider(IH + 1, IW + 1);
-        consider(IH, IW);
-        consider(1, IW + 1);
-        consider(IH, 1);
-        if (ksize == 3 && stride == 2 && pad == 0 && convt_taps_wanted(B, C, N, IH, IW)) {
-            const int64_t w = convt_taps_floats(B, C, N, IH, IW);
-            need = need > w ? need : w;
-        }
-        if (ksize == 3 && stride == 2 && pad == 0) {
-            const int64_t w = convt_strip_floats(B, N, IH, IW), f = convt_fused_split_floats(B, C, N, IH, IW);
-            need = need > w ? need : w;
-            need = need > f ? need : f;
-        }
-        if (ksize == 3 && stride == 2 && pad == 0 && sr_wgrad_bf16x3_enabled('t') && sr_convt_bf16x3_eligible(B, C, N, IH, IW)) {
-            const int64_t w = sr_convt_bf16x3_scratch_floats(C, N);
-            need = need > w ? need : w;
-        }
-    }
+    if (!c.transposed) consider(c.OH, c.OW);
+    else consider(c.IH + 1, c.IW + 1), consider(c.IH, c.IW), consider(1, c.IW + 1), consider(c.IH, 1);
     return need;
 }
 
-// 1 when a stride-1 3x3 convolution call with these sizes AND these buffers runs the Winograd kernel (and therefore
-// writes / reads the Winograd-domain weights at the head of its scratch), 0 when it takes the direct kernel.
-extern "C" int sr_conv2d_uses_winograd(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, const float* in,
-                                       const float* out) {
-    return (wino_enabled() && sr_wino_eligible(B, C, N, IH, IW, in, out)) ? 1 : 0;
+bool convt_interior(int path) {
+    return path == SR_CONV_PATH_CONVT_BF16 || path == SR_CONV_PATH_CONVT_FUSED_KS || path == SR_CONV_PATH_CONVT_FUSED;
 }
 
-extern "C" int sr_conv2d_mfma_ex(float* out, const float* in, const float* wt, const float* iscale,
-                              const float* oscale, const float* obias, int64_t B, int64_t C,
-                              int64_t N, int64_t wt_ld, int64_t IH, int64_t IW, int64_t OH, int64_t OW,
-                              int ksize, int stride, int pad, int transposed, int flags, float* scratch,
-                              sr_stream_t stream) {
-    if (B < 0 || C <= 0 || N <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return SR_EINVAL;
-    if (wt_ld < N || wt_ld % 4 != 0 || (reinterpret_cast<uintptr_t>(wt) & 15)) return SR_EINVAL;
-    if (B == 0) return SR_OK;
-    if (!out || !in || !wt) return SR_EINVAL;
-    // 32-bit element offsets inside the kernel
-    if (B * C * IH * IW >= (1LL << 31) || B * N * OH * OW >= (1LL << 40) ||
-        (int64_t)ksize * ksize * C * wt_ld >= (1LL << 31))
-        return SR_ERANGE;
-    hipStream_t st = sr_stream(stream);
-    ConvParams p;
-    p.in = in; p.wt = wt; p.iscale = iscale; p.oscale = oscale; p.obias = obias; p.out = out;
-    p.B = (int)B; p.C = (int)C; p.N = (int)N; p.ldw = (int)wt_ld;
-    p.IH = (int)IH; p.IW = (int)IW; p.OH = (int)OH; p.OW = (int)OW;
-    p.partial = scratch;
-    p.partial_floats = scratch ? sr_conv2d_scratch_floats(B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed) : 0;
-    for (int i = 0; i < 9; ++i) p.wmap[i] = 0;
-    p.ks = 1; p.c_per_slice = (p.C + 15) / 16 * 16;
-    p.tap_first = 0; p.tap_step = 1; p.tap_count = 9;
-    if (!transposed) {
-        if (OH != (IH + 2 * pad - ksize) / stride + 1 || OW != (IW + 2 * pad - ksize) / stride + 1)
-            return SR_EINVAL;
-        p.GH = p.OH; p.GW = p.OW;
-        p.gy_base = p.gx_base = 0;
-        p.osy = p.osx = 1; p.ooy = p.oox = 0;
-        p.dy0 = p.dx0 = -pad;
-        for (int i = 0; i < ksize * ksize; ++i) p.wmap[i] = i;
-        int rc;
-        if (ksize == 3 && stride == 1 && pad == 1 && scratch && wino_enabled() &&
-            sr_wino_eligible(B, C, N, IH, IW, in, out))
-            return sr_wino_conv3x3(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, scratch, st, nullptr,
-                                   (flags & SR_CONV_U_READY) != 0);
-        if (ksize == 3 && stride == 2 && pad == 0 && scratch && sr_wgrad_bf16x3_enabled('c') &&
-            sr_conv_s2_bf16x3_eligible(B, C, N, IH, IW, OH, OW))
-            // opt-in spike (SR_CONV_SPLIT_BF16=1): split-bf16 matrix path for the down-sampling convolution and the
-            // data gradient of the up-sampling one
-            return sr_conv_s2_bf16x3_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, OH, OW, scratch, st);
-        if (ksize == 3 && stride == 2 && pad == 0 && scratch) {
-            const int mode = s2_wino_mode();
-            if (mode && sr_conv_s2_wino_eligible(B, C, N, IH, IW, OH, OW, in, out) &&
-                (mode == 2 || sr_conv_s2_wino_blocks(B, N, OH, OW) >= S2_WINO_MIN_BLOCKS))
-                return sr_conv_s2_wino_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, OH, OW, scratch, st);
+struct ConvPlan {
+    int path = SR_CONV_PATH_DIRECT; // the direct kernel (per-phase launches when transposed) takes what nobody else does
+    bool strips = false;            // transposed: launch_convt_strips follows the interior kernel
+    int ks = 1, c_per_slice = 0;    // K slices of the fused / tap-split launch (c_per_slice: tap-split only)
+    bool taps_gemm = false;         // tap-split in its flattened-pixel GEMM form
+    int64_t floats = 0;             // scratch of the chosen path (direct: what its split-K would use)
+    int64_t sized = 0;              // sr_conv2d_scratch_floats of the call
+    int code() const { return path | (strips ? SR_CONV_PATH_STRIPS : 0); }
+};
+
+// THE path list: every path of a call's geometry goes through candidate(), in priority order.
+//   reach   the SHAPE can get here: with some buffer alignment, below or above a launch-size bar, and with the on / off
+//           switches (SR_CONV_S2_WINO, SR_CONVT_FUSED, SR_CONVT_FUSED_KS, SR_CONVT_STRIPS, SR_CONV1X1_GEMM) in either
+//           position — they are read per call, the scratch may be sized before one flips.  SR_WINOGRAD, SR_CONVT_TAPS and
+//           SR_CONV_SPLIT_BF16 count as they stand.  `sized` is the largest `floats` within reach,
+//   take    THIS call takes it (its buffers, the switches now) unless an earlier candidate did
+//   floats  scratch the path cannot run without — so with a scratch (of `sized` floats: the interface has no other
+//           size) whatever is taken fits, and without one only paths that need none are taken
+ConvPlan make_conv_plan(const ConvCall& c, bool have_scratch) {
+    ConvPlan plan;
+    const int64_t B = c.B, C = c.C, N = c.N, IH = c.IH, IW = c.IW, OH = c.OH, OW = c.OW;
+    if (B <= 0 || C <= 0 || N <= 0 || OH <= 0 || OW <= 0) return plan;
+    plan.sized = plan.floats = direct_floats(c);
+    auto candidate = [&](int path, bool reach, bool take, int64_t floats, int ks = 1) {
+        if (!reach) return;
+        plan.sized = std::max(plan.sized, floats);
+        if (plan.path != SR_CONV_PATH_DIRECT || !take || (floats > 0 && !have_scratch)) return;
+        plan.path = path; plan.floats = floats; plan.ks = ks;
+    };
+    if (!c.transposed && c.is3x3(1, 1)) {
+        if (sr_winograd_enabled() && sr_wino_eligible(B, C, N, IH, IW, nullptr, nullptr))
+            candidate(SR_CONV_PATH_WINO, true, sr_wino_eligible(B, C, N, IH, IW, c.in, c.out),
+                      sr_wino_scratch_floats(C, N) + sr_wino_partial_floats(B, C, N, IH, IW));
+    } else if (!c.transposed && c.is3x3(2, 0)) {
+        // opt-in spike (SR_CONV_SPLIT_BF16=1): split-bf16 matrix path for the down-sampling convolution and the data
+        // gradient of the up-sampling one
+        candidate(SR_CONV_PATH_S2_BF16, sr_wgrad_bf16x3_enabled('c') && sr_conv_s2_bf16x3_eligible(B, C, N, IH, IW, OH, OW),
+                  true, sr_conv_s2_bf16x3_scratch_floats(C, N));
+        const int sw = sr_env_char("SR_CONV_S2_WINO");      // =0 keeps k_conv_mfma, =force ignores the workgroup bar (tests)
+        candidate(SR_CONV_PATH_S2_WINO, sr_conv_s2_wino_eligible(B, C, N, IH, IW, OH, OW, nullptr, nullptr),
+                  sw != '0' && sr_conv_s2_wino_eligible(B, C, N, IH, IW, OH, OW, c.in, c.out) &&
+                      (sw == 'f' || sr_conv_s2_wino_blocks(B, N, OH, OW) >= S2_WINO_MIN_BLOCKS),
+                  sr_conv_s2_wino_scratch_floats(C, N));
+    } else if (!c.transposed && c.ksize == 1 && c.stride == 1) {
+        // no window: a plain GEMM with both operands K-major (csrc/conv1x1_gemm.hip) where its tiles fill the chip
+        candidate(SR_CONV_PATH_GEMM1X1, true,
+                  c.pad == 0 && sr_conv1x1_gemm_eligible(B, C, N, c.ldw, IH * IW, c.in, c.wt, c.out), 0);
+    } else if (c.transposed && c.is3x3(2, 0)) {
+        // opt-in spike (SR_CONV_SPLIT_BF16=1): the interior of the map on the bf16 matrix cores (three-way operand
+        // split); it keeps the tap-split form out, the border stays on the exact-fp32 kernels
+        const bool bf = sr_wgrad_bf16x3_enabled('t') && sr_convt_bf16x3_eligible(B, C, N, IH, IW);
+        // small problems: nine shifted 1x1 convolutions in one launch + one reduction (k_conv_mfma<..., TAP9>)
+        if (convt_taps_wanted(B, C, N, IH, IW)) {
+            int ks;
+            convt_taps_plan((int)IH, (int)IW, (int)B, (int)N, (int)C, ks, plan.c_per_slice);
+            candidate(SR_CONV_PATH_CONVT_TAPS, true, !bf, (int64_t)ks * 9 * B * N * (IH + 1) * (IW + 1), ks);
         }
-        if (ksize == 3 && stride == 1) rc = launch_by_patch<1, 3, 3>(p, st);
-        else if (ksize == 3 && stride == 2) rc = launch_by_patch<2, 3, 3>(p, st);
-        else if (ksize == 1 && stride == 1) {
-            // no window: a plain GEMM with both operands K-major (csrc/conv1x1_gemm.hip) where its tiles fill the chip
-            if (pad == 0 && sr_conv1x1_gemm_eligible(B, C, N, wt_ld, IH * IW, in, wt, out))
-                return sr_conv1x1_gemm_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH * IW, st);
-            rc = launch_by_patch<1, 1, 1>(p, st);
-        }
-        else if (ksize == 1 && stride == 2) rc = launch_by_patch<2, 1, 1>(p, st);
-        else return SR_EINVAL;
-        return rc;
-    }
-    // transposed 3x3 stride 2, no padding: out[2y + ky, 2x + kx] += in[y, x] * W[ky][kx].
-    // Output phase (py, px) of grid point (j, i) = output (2j + py, 2i + px); window position ty
-    // reads input row j + ty - (TY - 1) and pairs with ky = py + 2 * (TY - 1 - ty).
-    if (ksize != 3 || stride != 2 || pad != 0 || OH != 2 * IH + 1 || OW != 2 * IW + 1) return SR_EINVAL;
-    // The phase grids have 2^k + 1 points per side: the 2^k x 2^k interior tiles the 32-wide
-    // patches exactly, the last grid row / column (output row 2*IH, column 2*IW: even phases only)
-    // runs as thin strip launches instead of padding every tile row by up to 50 %.
-    // interior of the map: all four phases in one workgroup (k_convt_fused); SR_CONVT_FUSED=0 keeps the
-    // per-phase launches
-    // small problems: nine shifted 1x1 convolutions in one launch + one reduction (k_conv_mfma<..., TAP9>)
-    if (scratch && convt_taps_wanted(B, C, N, IH, IW) && convt_taps_floats(B, C, N, IH, IW) <= p.partial_floats &&
-        !(sr_wgrad_bf16x3_enabled('t') && sr_convt_bf16x3_eligible(B, C, N, IH, IW)))
-        return launch_convt_taps(p, st);
-    bool fused_ok = false;
-    {
-        const char* e = std::getenv("SR_CONVT_FUSED");
+        candidate(SR_CONV_PATH_CONVT_BF16, bf, true, sr_convt_bf16x3_scratch_floats(C, N));
+        // interior of the map: all four phases in one workgroup (k_convt_fused); SR_CONVT_FUSED=0 keeps the per-phase
+        // launches, =1 takes it whatever the size
+        const int sw = sr_env_char("SR_CONVT_FUSED");
+        const bool fused_ok = sw != '0' && IW >= 16 && convt_fused_eligible(c);
         // the fused kernel has no split-K: when its workgroups cover less than ~3/4 of the CUs AND the channel loop is
         // long (C > 256: 64 chunks, ~0.38 ms whatever the batch), each one walks the whole loop alone and the per-phase
         // launches, which split K, are faster — in-graph, scripts/bench_convt_small.py: 32^2 512->512 at batch 1 / 2 / 4
         // 0.23 / 0.26 / 0.35 ms against 0.38 / 0.39 / 0.40 fused (batch 8: 0.56 against 0.43, fused stays);
         // 64^2 512->256 at batch 1 / 2 0.26 / 0.33 against 0.39; 128^2 256->128 (32 chunks) is fused from batch 1 on
-        const int64_t fused_blocks = (int64_t)(p.IW / TFused::PW) * (p.IH / TFused::PH) * ((p.N + BN - 1) / BN) * p.B;
-        bool fused_pays = fused_blocks >= 192 || p.C <= 256;
-        if (!fused_pays && scratch && !(e && e[0] == '0')) {
-            // few tiles, long channel loop: K slices inside the fused kernel (SR_CONVT_FUSED_KS=0: the per-phase launches)
-            const char* k = std::getenv("SR_CONVT_FUSED_KS");
-            const int ks = (k && k[0] == '0') ? 1 : convt_fused_slices(fused_blocks, p.C);
-            if (ks > 1 && convt_fused_eligible(p) && (int64_t)ks * B * N * OH * OW <= p.partial_floats) {
-                p.ks = ks;
-                p.c_per_slice = p.C / ks;
-                fused_pays = true;
-            }
-        }
-        if (scratch && sr_wgrad_bf16x3_enabled('t') && sr_convt_bf16x3_eligible(B, C, N, IH, IW)) {
-            // opt-in spike (SR_CONV_SPLIT_BF16=1): the interior of the map on the bf16 matrix cores (three-way operand
-            // split); the border strips below stay on the exact-fp32 kernels
-            const int rc = sr_convt_bf16x3_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, scratch, st);
-            if (rc != SR_OK) return rc;
-            fused_ok = true;
-        } else if (!(e && e[0] == '0') && p.IW >= 16 && convt_fused_eligible(p) && (fused_pays || (e && e[0] == '1'))) {
-            for (int i = 0; i < 9; ++i) p.wmap[i] = i;
-            const int rc = launch_convt_fused(p, st);
-            p.ks = 1; p.c_per_slice = (p.C + 15) / 16 * 16;          // (the strips below plan their own)
-            if (rc != SR_OK) return rc;
-            fused_ok = true;
-        }
-    }
-    if (fused_ok && scratch && convt_strip_floats(B, N, IH, IW) <= p.partial_floats) {
-        // the interior is done: output row 2*IH and column 2*IW as two three-tap launches + one reduction
+        const int64_t blocks = (IW / TFused::PW) * (IH / TFused::PH) * ((N + BN - 1) / BN) * B;
+        const bool pays = blocks >= 192 || C <= 256;
+        // few tiles, long channel loop: K slices inside the fused kernel (SR_CONVT_FUSED_KS=0: the per-phase launches)
+        const int ks = (IW % TFused::PW || IH % TFused::PH || pays) ? 1 : convt_fused_slices(blocks, (int)C);
+        candidate(SR_CONV_PATH_CONVT_FUSED_KS, ks > 1, fused_ok && !sr_env_off("SR_CONVT_FUSED_KS"),
+                  ks * B * N * (2 * IH + 1) * (2 * IW + 1), ks);
+        candidate(SR_CONV_PATH_CONVT_FUSED, true, fused_ok && (pays || sw == '1'), 0);
+        // behind an interior kernel the output row 2*IH and column 2*IW run as two three-tap launches + one reduction
         // (SR_CONVT_STRIPS=0: the four thin per-phase launches and their split-K reductions)
-        const char* e = std::getenv("SR_CONVT_STRIPS");
-        if (!(e && e[0] == '0')) return launch_convt_strips(p, st);
+        const int64_t strip = convt_strip_floats(B, N, IH, IW);
+        plan.sized = std::max(plan.sized, strip);
+        if (convt_interior(plan.path) && have_scratch && !sr_env_off("SR_CONVT_STRIPS")) {
+            plan.strips = true;
+            plan.floats = std::max(plan.floats, strip);
+        }
     }
+    if (plan.path == SR_CONV_PATH_CONVT_TAPS)
+        plan.taps_gemm = sr_convt_taps_gemm_eligible(B, C, N, IW, c.ldw, plan.c_per_slice, c.wt);
+    return plan;
+}
+
+// The geometries the matrix-core kernels serve (SR_EINVAL otherwise).
+bool conv_call_valid(const ConvCall& c) {
+    if (c.B < 0 || c.C <= 0 || c.N <= 0 || c.IH <= 0 || c.IW <= 0 || c.OH <= 0 || c.OW <= 0) return false;
+    if (c.transposed) return c.is3x3(2, 0) && c.OH == 2 * c.IH + 1 && c.OW == 2 * c.IW + 1;
+    return (c.ksize == 3 || c.ksize == 1) && (c.stride == 1 || c.stride == 2) &&
+           c.OH == (c.IH + 2 * c.pad - c.ksize) / c.stride + 1 && c.OW == (c.IW + 2 * c.pad - c.ksize) / c.stride + 1;
+}
+
+// The transposed convolution as its four output phases.  Output phase (py, px) of grid point (j, i) = output
+// (2j + py, 2i + px); window position ty reads input row j + ty - (TY - 1) and pairs with ky = py + 2 * (TY - 1 - ty).
+// The phase grids have 2^k + 1 points per side: the 2^k x 2^k interior tiles the 32-wide patches exactly, the last grid
+// row / column (output row 2*IH, column 2*IW: even phases only) runs as thin strip launches instead of padding every
+// tile row by up to 50 %.  interior_done: an interior kernel has written the interior already.
+int launch_convt_phases(ConvParams p, bool interior_done, hipStream_t st) {
     for (int py = 0; py < 2; ++py)
         for (int px = 0; px < 2; ++px) {
             const int TYp = py == 0 ? 2 : 1, TXp = px == 0 ? 2 : 1;
@@ -1300,7 +1226,7 @@ extern "C" int sr_conv2d_mfma_ex(float* out, const float* in, const float* wt, c
                 regions[0][1] = gh_full;
                 regions[0][3] = gw_full;
             }
-            const bool fused = split_border && fused_ok;
+            const bool fused = split_border && interior_done;
             for (int rg = fused ? 1 : 0; rg < (split_border ? 3 : 1); ++rg) {
                 p.gy_base = regions[rg][0]; p.GH = regions[rg][1];
                 p.gx_base = regions[rg][2]; p.GW = regions[rg][3];
@@ -1314,6 +1240,100 @@ extern "C" int sr_conv2d_mfma_ex(float* out, const float* in, const float* wt, c
             }
         }
     return SR_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t sr_conv2d_scratch_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW,
+                                            int64_t OH, int64_t OW, int ksize, int stride, int pad,
+                                            int transposed) {
+    const ConvCall c{B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, nullptr, nullptr, nullptr, 0};
+    return make_conv_plan(c, true).sized;
+}
+
+extern "C" int sr_conv2d_path(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW, int ksize,
+                              int stride, int pad, int transposed, const float* in, const float* out, const float* wt,
+                              int64_t wt_ld, int have_scratch) {
+    const ConvCall c{B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, in, out, wt, wt_ld};
+    return conv_call_valid(c) ? make_conv_plan(c, have_scratch != 0).code() : SR_CONV_PATH_INVALID;
+}
+
+extern "C" int64_t sr_conv2d_path_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW,
+                                         int ksize, int stride, int pad, int transposed, const float* in, const float* out,
+                                         const float* wt, int64_t wt_ld, int have_scratch) {
+    const ConvCall c{B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, in, out, wt, wt_ld};
+    return conv_call_valid(c) ? make_conv_plan(c, have_scratch != 0).floats : -1;
+}
+
+// 1 when a stride-1 3x3 convolution call with these sizes AND these buffers runs the Winograd kernel (and therefore
+// writes / reads the Winograd-domain weights at the head of its scratch), 0 when it takes the direct kernel.
+extern "C" int sr_conv2d_uses_winograd(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, const float* in,
+                                       const float* out) {
+    return make_conv_plan(ConvCall{B, C, N, IH, IW, IH, IW, 3, 1, 1, 0, in, out, nullptr, 0}, true).path == SR_CONV_PATH_WINO;
+}
+
+extern "C" int sr_conv2d_mfma_ex(float* out, const float* in, const float* wt, const float* iscale,
+                              const float* oscale, const float* obias, int64_t B, int64_t C,
+                              int64_t N, int64_t wt_ld, int64_t IH, int64_t IW, int64_t OH, int64_t OW,
+                              int ksize, int stride, int pad, int transposed, int flags, float* scratch,
+                              sr_stream_t stream) {
+    const ConvCall c{B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, in, out, wt, wt_ld};
+    if (B < 0 || C <= 0 || N <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return SR_EINVAL;
+    if (wt_ld < N || wt_ld % 4 != 0 || !sr_aligned16(wt)) return SR_EINVAL;
+    if (B == 0) return SR_OK;
+    if (!out || !in || !wt) return SR_EINVAL;
+    // 32-bit element offsets inside the kernel
+    if (B * C * IH * IW >= (1LL << 31) || B * N * OH * OW >= (1LL << 40) ||
+        (int64_t)ksize * ksize * C * wt_ld >= (1LL << 31))
+        return SR_ERANGE;
+    if (!conv_call_valid(c)) return SR_EINVAL;
+    const ConvPlan plan = make_conv_plan(c, scratch != nullptr);
+    hipStream_t st = sr_stream(stream);
+    ConvParams p;
+    p.in = in; p.wt = wt; p.iscale = iscale; p.oscale = oscale; p.obias = obias; p.out = out;
+    p.B = (int)B; p.C = (int)C; p.N = (int)N; p.ldw = (int)wt_ld;
+    p.IH = (int)IH; p.IW = (int)IW; p.OH = (int)OH; p.OW = (int)OW;
+    p.partial = scratch;
+    p.partial_floats = scratch ? plan.sized : 0;
+    for (int i = 0; i < 9; ++i) p.wmap[i] = 0;
+    p.ks = 1; p.c_per_slice = (p.C + 15) / 16 * 16;
+    p.tap_first = 0; p.tap_step = 1; p.tap_count = 9;
+    int rc = SR_OK;
+    switch (plan.path) {
+    case SR_CONV_PATH_WINO:
+        return sr_wino_conv3x3(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, scratch, st, nullptr,
+                               (flags & SR_CONV_U_READY) != 0);
+    case SR_CONV_PATH_S2_BF16:
+        return sr_conv_s2_bf16x3_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, OH, OW, scratch, st);
+    case SR_CONV_PATH_S2_WINO:
+        return sr_conv_s2_wino_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, OH, OW, scratch, st);
+    case SR_CONV_PATH_GEMM1X1:
+        return sr_conv1x1_gemm_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH * IW, st);
+    case SR_CONV_PATH_CONVT_TAPS:
+        return launch_convt_taps(p, plan.ks, plan.c_per_slice, plan.taps_gemm, st);
+    case SR_CONV_PATH_CONVT_BF16:
+        rc = sr_convt_bf16x3_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, scratch, st);
+        break;
+    case SR_CONV_PATH_CONVT_FUSED_KS:
+    case SR_CONV_PATH_CONVT_FUSED:
+        for (int i = 0; i < 9; ++i) p.wmap[i] = i;
+        rc = launch_convt_fused(p, plan.ks, st);
+        break;
+    default:    // SR_CONV_PATH_DIRECT
+        if (transposed) break;
+        p.GH = p.OH; p.GW = p.OW;
+        p.gy_base = p.gx_base = 0;
+        p.osy = p.osx = 1; p.ooy = p.oox = 0;
+        p.dy0 = p.dx0 = -pad;
+        for (int i = 0; i < ksize * ksize; ++i) p.wmap[i] = i;
+        if (ksize == 3) return stride == 1 ? launch_by_patch<1, 3, 3>(p, st) : launch_by_patch<2, 3, 3>(p, st);
+        return stride == 1 ? launch_by_patch<1, 1, 1>(p, st) : launch_by_patch<2, 1, 1>(p, st);
+    }
+    // transposed 3x3 stride 2, no padding: out[2y + ky, 2x + kx] += in[y, x] * W[ky][kx]; the interior is done or left to
+    // the per-phase launches, the border follows
+    if (rc != SR_OK) return rc;
+    if (plan.strips) return launch_convt_strips(p, st);
+    return launch_convt_phases(p, convt_interior(plan.path), st);
 }
 
 extern "C" int sr_conv2d_mfma(float* out, const float* in, const float* wt, const float* iscale,
@@ -1333,10 +1353,10 @@ extern "C" int sr_conv2d_nba_ex(float* out, const float* in, const float* wt, co
                                 int64_t B, int64_t C, int64_t N, int64_t wt_ld, int64_t H, int64_t W,
                                 int64_t noise_bstride, int flags, float* scratch, sr_stream_t stream) {
     if (B < 0 || C <= 0 || N <= 0 || H <= 0 || W <= 0) return SR_EINVAL;
-    if (wt_ld < N || wt_ld % 4 != 0 || (reinterpret_cast<uintptr_t>(wt) & 15)) return SR_EINVAL;
+    if (wt_ld < N || wt_ld % 4 != 0 || !sr_aligned16(wt)) return SR_EINVAL;
     if (B == 0) return SR_OK;
     if (!out || !in || !wt || !scratch || (noise && !noise_w)) return SR_EINVAL;
-    if (!wino_enabled() || !sr_wino_eligible(B, C, N, H, W, in, out)) return SR_EINVAL;
+    if (!sr_conv2d_uses_winograd(B, C, N, H, W, in, out)) return SR_EINVAL;
     const WinoNba nba{noise, noise_w, abias, noise_bstride, alpha, gain};
     return sr_wino_conv3x3(out, in, wt, wt_ld, iscale, oscale, nullptr, B, C, N, H, W, scratch, sr_stream(stream), &nba,
                            (flags & SR_CONV_U_READY) != 0);

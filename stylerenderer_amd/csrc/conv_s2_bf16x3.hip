@@ -24,11 +24,8 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "bf16x3.h"
+
 typedef const void __attribute__((address_space(1)))* gptr_t;
 typedef void __attribute__((address_space(3)))* lptr_t;
 
@@ -47,19 +44,6 @@ static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
 constexpr int W_INSTR = W_DWORDS / 256;          // 54 DMA instructions of 1 KB per chunk
 constexpr int X_ITEMS = KC * 9 / 4;              // (channel, row) pairs per wave: 18
 
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float bf16_lo(unsigned pk) { return __builtin_bit_cast(float, pk << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned pk) { return __builtin_bit_cast(float, pk & 0xFFFF0000u); }
-__device__ __forceinline__ void split2(float x0, float x1, unsigned& p1, unsigned& p2, unsigned& p3) {
-    p1 = pack_bf16(x0, x1);
-    const float r0 = x0 - bf16_lo(p1), r1 = x1 - bf16_hi(p1);
-    p2 = pack_bf16(r0, r1);
-    const float q0 = r0 - bf16_lo(p2), q1 = r1 - bf16_hi(p2);
-    p3 = pack_bf16(q0, q1);
-}
 __device__ __forceinline__ void split8(const float (&x)[8], u32x4& h1, u32x4& h2, u32x4& h3) {
     unsigned a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3;
     split2(x[0], x[1], a0, b0, c0);
@@ -69,9 +53,6 @@ __device__ __forceinline__ void split8(const float (&x)[8], u32x4& h1, u32x4& h2
     h1 = u32x4{a0, a1, a2, a3};
     h2 = u32x4{b0, b1, b2, b3};
     h3 = u32x4{c0, c1, c2, c3};
-}
-__device__ __forceinline__ f32x16 mma(const u32x4 a, const u32x4 b, const f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
 // ---- weights: fp32 [9][C][ldw] -> bf16 pieces in staging order ------------------------------------------------------

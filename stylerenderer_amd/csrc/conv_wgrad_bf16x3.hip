@@ -27,9 +27,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+#include "bf16x3.h"
 
 namespace s1 {
 constexpr int UT = 128, VT = 128, KC = 32, PITCH = 36, THREADS = 256;
@@ -51,29 +49,9 @@ struct P3 {
     int tiles_u, tiles_v, UP, VP;
 };
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 struct Split3 {
     u32x4 h1, h2, h3;          // 8 bf16 each (bit patterns, two per dword: element 2i in the low half)
 };
-
-// two floats -> one dword of two round-to-nearest bf16 (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float bf16_lo(unsigned pk) { return __builtin_bit_cast(float, pk << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned pk) { return __builtin_bit_cast(float, pk & 0xFFFF0000u); }
-
-// a pair of floats -> its three bf16 pieces (see the header: exact three-way split): 11 VALU operations per pair
-__device__ __forceinline__ void split2(float x0, float x1, unsigned& p1, unsigned& p2, unsigned& p3) {
-    p1 = pack_bf16(x0, x1);
-    const float r0 = x0 - bf16_lo(p1), r1 = x1 - bf16_hi(p1);
-    p2 = pack_bf16(r0, r1);
-    const float q0 = r0 - bf16_lo(p2), q1 = r1 - bf16_hi(p2);
-    p3 = pack_bf16(q0, q1);
-}
 
 __device__ __forceinline__ Split3 split8(const float4 lo, const float4 hi) {
     unsigned a0, a1, a2, a3, b0, b1, b2, b3, c0, c1, c2, c3;
@@ -86,10 +64,6 @@ __device__ __forceinline__ Split3 split8(const float4 lo, const float4 hi) {
     s.h2 = u32x4{b0, b1, b2, b3};
     s.h3 = u32x4{c0, c1, c2, c3};
     return s;
-}
-
-__device__ __forceinline__ f32x16 mma(const u32x4 a, const u32x4 b, const f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
 __global__ __launch_bounds__(s1::THREADS, 2) void k_wgrad1_bf16x3(const P3 p) {
@@ -419,10 +393,10 @@ __global__ __launch_bounds__(512) void k_wgrad_s2_bf16x3(const P9 p) {
 // SR_CONV_SPLIT_BF16=1: all four kernel families; or a subset by letter (probes: which family moves a result):
 //   w  1x1 weight gradient    g  stride-2 3x3 weight gradient    c  stride-2 3x3 convolution    t  its transposed form
 bool sr_wgrad_bf16x3_enabled(char kind) {
-    const char* e = std::getenv("SR_CONV_SPLIT_BF16");
-    if (!e || !e[0] || e[0] == '0') return false;
-    if (e[0] == '1') return true;
-    for (; *e; ++e)
+    const int first = sr_env_char("SR_CONV_SPLIT_BF16");
+    if (first <= 0 || first == '0') return false;
+    if (first == '1') return true;
+    for (const char* e = std::getenv("SR_CONV_SPLIT_BF16"); *e; ++e)
         if (*e == kind) return true;
     return false;
 }

@@ -31,6 +31,7 @@
 #include "conv_wgrad_bf16x3.h"
 #include "conv_wino.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 namespace {
@@ -568,18 +569,18 @@ int launch_wgrad_s1(const WgradParams& p, const Plan& pl, hipStream_t st) {
 }
 // k_wgrad_s2_dma serves full 16 x 4 patches of whole channel tiles whose windows stay inside U (pad-0 stride-2 layers
 // of 2G + 1 pixels: every up- / down-sampling convolution from 16^2 up); SR_WGRAD_DMA=0 keeps the dword staging.
-bool s2_dma_ok(const WgradParams& p, const Plan& pl) {
-    const char* e = std::getenv("SR_WGRAD_DMA");
-    if (e && e[0] == '0') return false;
-    return pl.pw == 16 && pl.ph == 4 && pl.pb == 1 && pl.ut == 32 && pl.vt == 128 && p.CU % 32 == 0 && p.CV % 128 == 0 &&
-           p.GW % 16 == 0 && p.GH % 4 == 0 && p.dy0 == 0 && p.dx0 == 0 && p.UH >= 2 * p.GH + 1 && p.UW >= 2 * p.GW + 1 &&
-           (int64_t)p.B * p.CU * p.UH * p.UW < (1LL << 29) && (int64_t)p.B * p.CV * p.GH * p.GW < (1LL << 29);
+bool s2_dma_ok(const Plan& pl, int64_t B, int CU, int CV, int UH, int UW, int GH, int GW, int d0) {
+    if (sr_env_off("SR_WGRAD_DMA")) return false;
+    return pl.pw == 16 && pl.ph == 4 && pl.pb == 1 && pl.ut == 32 && pl.vt == 128 && CU % 32 == 0 && CV % 128 == 0 &&
+           GW % 16 == 0 && GH % 4 == 0 && d0 == 0 && UH >= 2 * GH + 1 && UW >= 2 * GW + 1 &&
+           B * CU * UH * UW < (1LL << 29) && B * CV * GH * GW < (1LL << 29);
 }
 
+// dma: the plan chose k_wgrad_s2_dma (3x3 only)
 template <int TY, int TX>
-int launch_wgrad_s2(const WgradParams& p, const Plan& pl, hipStream_t st) {
+int launch_wgrad_s2(const WgradParams& p, const Plan& pl, bool dma, hipStream_t st) {
     const dim3 grid((unsigned)(pl.tiles_u * pl.tiles_v * pl.ks));
-    if (TY == 3 && TX == 3 && s2_dma_ok(p, pl)) {
+    if (TY == 3 && TX == 3 && dma) {
         static bool configured = false;
         if (!configured) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_s2_dma),
@@ -670,8 +671,7 @@ __global__ __launch_bounds__(4 * WS_ACC) void k_wgrad_small3_finish(float* __res
 }
 
 bool wgrad_small_ok(int64_t C, int64_t N, int ksize, int stride, int pad, int transposed) {
-    const char* e = std::getenv("SR_WGRAD_SMALL");
-    if (e && e[0] == '0') return false;
+    if (sr_env_off("SR_WGRAD_SMALL")) return false;
     return !transposed && ksize == 3 && stride == 1 && pad == 1 && C <= WS_CM && N <= WS_NM;
 }
 
@@ -681,65 +681,110 @@ int wgrad_small_blocks(int64_t B, int64_t IH, int64_t IW) {
     return (int)(nb < 1 ? 1 : (nb > 256 ? 256 : nb));
 }
 
+// ---- dispatch plan: which kernel serves a call, decided once -------------------------------------------------------------
+// sr_conv2d_wgrad_scratch_floats, sr_conv2d_wgrad_mfma and sr_conv2d_wgrad_path read the same plan.
+struct WgradPlan {
+    int path = SR_WGRAD_PATH_INVALID;
+    int64_t sized = -1;                      // sr_conv2d_wgrad_scratch_floats of the call
+    int GH, GW, UH, UW, CU, CV, d0;          // geometry(): U = the windowed operand, V = the other one
+    Plan tiles;                              // tiling of k_wgrad_mfma / k_wgrad_s2_dma
+};
+
 bool geometry(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW,
-              int ksize, int stride, int pad, int transposed, int& is, int& GH, int& GW, int& UH,
-              int& UW, int& CUc, int& CVc, int& d0) {
+              int ksize, int stride, int pad, int transposed, WgradPlan& w) {
     if (B < 0 || C <= 0 || N <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return false;
     if (!(ksize == 3 || ksize == 1) || !(stride == 1 || stride == 2)) return false;
-    is = stride;
     if (!transposed) {
         if (OH != (IH + 2 * pad - ksize) / stride + 1 || OW != (IW + 2 * pad - ksize) / stride + 1) return false;
-        GH = (int)OH; GW = (int)OW; UH = (int)IH; UW = (int)IW; CUc = (int)C; CVc = (int)N; d0 = -pad;
+        w.GH = (int)OH; w.GW = (int)OW; w.UH = (int)IH; w.UW = (int)IW; w.CU = (int)C; w.CV = (int)N; w.d0 = -pad;
     } else {
         if (ksize != 3 || stride != 2 || pad != 0 || OH != 2 * IH + 1 || OW != 2 * IW + 1) return false;
-        GH = (int)IH; GW = (int)IW; UH = (int)OH; UW = (int)OW; CUc = (int)N; CVc = (int)C; d0 = 0;
+        w.GH = (int)IH; w.GW = (int)IW; w.UH = (int)OH; w.UW = (int)OW; w.CU = (int)N; w.CV = (int)C; w.d0 = 0;
     }
     return true;
 }
 
-}  // namespace
-
-static bool wgrad_wino_enabled() {
-    const char* e = std::getenv("SR_WINOGRAD");          // "0" keeps the direct correlation kernel
-    return !(e && e[0] == '0');
+// x / gy: NULL = alignment unknown, assume aligned.  `sized` covers every path the SHAPE can take with some buffer
+// alignment; SR_WGRAD_SMALL, SR_WINOGRAD and SR_CONV_SPLIT_BF16 count as they stand (SR_WGRAD_DMA moves no size).
+WgradPlan make_wgrad_plan(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW, int ksize,
+                          int stride, int pad, int transposed, const void* x, const void* gy) {
+    WgradPlan w;
+    if (!geometry(B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, w)) return w;
+    if (wgrad_small_ok(C, N, ksize, stride, pad, transposed)) {     // takes every call of its shape: nothing else in reach
+        w.path = SR_WGRAD_PATH_SMALL3;
+        w.sized = (int64_t)wgrad_small_blocks(B, IH, IW) * WS_ACC + 4;
+        return w;
+    }
+    const Plan& pl = w.tiles = make_plan(stride, (int)B, w.CU, w.CV, w.GH, w.GW);
+    w.path = SR_WGRAD_PATH_DIRECT;
+    w.sized = (int64_t)pl.ks * NG_OF(pl.pb) * ksize * ksize * (pl.tiles_u * pl.ut) * (int64_t)(pl.tiles_v * pl.vt) + 4;
+    // The other paths in priority order.  Each `if` says whether the SHAPE can get there (then the scratch is sized for
+    // it), `take` whether this call does.
+    auto candidate = [&](int path, bool take, int64_t floats) {
+        w.sized = std::max(w.sized, floats);
+        if (take && w.path == SR_WGRAD_PATH_DIRECT) w.path = path;
+    };
+    if (!transposed && ksize == 3 && stride == 1 && pad == 1 && sr_winograd_enabled() &&
+        sr_wgrad_wino_eligible(B, C, N, IH, IW, nullptr, nullptr))
+        candidate(SR_WGRAD_PATH_WINO, sr_wgrad_wino_eligible(B, C, N, IH, IW, x, gy),
+                  sr_wgrad_wino_scratch_floats(B, C, N, IH, IW));
+    // opt-in spike (SR_CONV_SPLIT_BF16=1): split-bf16 matrix paths, same partial-slab layout and reduce
+    if (!transposed && ksize == 1 && stride == 1 && sr_wgrad_bf16x3_enabled('w'))
+        candidate(SR_WGRAD_PATH_BF16_1X1, pad == 0 && B > 0 && sr_wgrad_bf16x3_eligible(B, C, N, IH * IW, x, gy),
+                  sr_wgrad_bf16x3_scratch_floats(B, C, N, IH * IW));
+    if (ksize == 3 && stride == 2 && sr_wgrad_bf16x3_enabled('g'))
+        candidate(SR_WGRAD_PATH_BF16_S2,
+                  pad == 0 && sr_wgrad_s2_bf16x3_eligible(B, w.CU, w.CV, w.UH, w.UW, w.GH, w.GW, transposed ? x : gy),
+                  sr_wgrad_s2_bf16x3_scratch_floats(B, w.CU, w.CV, w.GH, w.GW));
+    if (w.path == SR_WGRAD_PATH_DIRECT && ksize == 3 && stride == 2 &&
+        s2_dma_ok(pl, B, w.CU, w.CV, w.UH, w.UW, w.GH, w.GW, w.d0))
+        w.path = SR_WGRAD_PATH_S2_DMA;
+    return w;
 }
+
+// Adds the K slices of partial[ks][nt][UP][VP] into dwt [nt][C][N]: a regular convolution has (u, v) = (c, n), the
+// transposed one (u, v) = (n, c).
+int reduce_slices(float* dwt, const float* partial, const WgradPlan& w, int ks, int nt, int UP, int VP, int transposed,
+                  hipStream_t st) {
+    ReduceParams r;
+    r.partial = partial; r.out = dwt;
+    r.ks = ks; r.nt = nt; r.UP = UP; r.VP = VP; r.CU = w.CU; r.CV = w.CV;
+    r.slab = (int64_t)w.CU * w.CV;
+    r.su = transposed ? 1 : w.CV;
+    r.sv = transposed ? w.CU : 1;
+    for (int t = 0; t < 9; ++t) r.tmap[t] = t;
+    launch_wgrad_reduce(r, (int64_t)nt * w.CU * w.CV, st);
+    return sr_launch_status();
+}
+
+}  // namespace
 
 extern "C" int64_t sr_conv2d_wgrad_scratch_floats(int64_t B, int64_t C, int64_t N, int64_t IH,
                                                   int64_t IW, int64_t OH, int64_t OW, int ksize,
                                                   int stride, int pad, int transposed) {
-    int is, GH, GW, UH, UW, CUc, CVc, d0;
-    if (!geometry(B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, is, GH, GW, UH, UW, CUc, CVc, d0))
-        return -1;
-    if (wgrad_small_ok(C, N, ksize, stride, pad, transposed)) return (int64_t)wgrad_small_blocks(B, IH, IW) * WS_ACC + 4;
-    const Plan pl = make_plan(is, (int)B, CUc, CVc, GH, GW);
-    int64_t need = (int64_t)pl.ks * NG_OF(pl.pb) * ksize * ksize * (pl.tiles_u * pl.ut) * (int64_t)(pl.tiles_v * pl.vt) + 4;
-    if (!transposed && ksize == 3 && stride == 1 && pad == 1 && wgrad_wino_enabled() &&
-        sr_wgrad_wino_eligible(B, C, N, IH, IW, nullptr, nullptr)) {
-        const int64_t w = sr_wgrad_wino_scratch_floats(B, C, N, IH, IW);
-        need = need > w ? need : w;
-    }
-    if (!transposed && ksize == 1 && stride == 1 && sr_wgrad_bf16x3_enabled('w')) {
-        const int64_t w = sr_wgrad_bf16x3_scratch_floats(B, C, N, IH * IW);
-        need = need > w ? need : w;
-    }
-    if (ksize == 3 && stride == 2 && sr_wgrad_bf16x3_enabled('g')) {
-        const int64_t w = sr_wgrad_s2_bf16x3_scratch_floats(B, CUc, CVc, GH, GW);
-        need = need > w ? need : w;
-    }
-    return need;
+    return make_wgrad_plan(B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, nullptr, nullptr).sized;
+}
+
+extern "C" int sr_conv2d_wgrad_path(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW,
+                                    int ksize, int stride, int pad, int transposed, const float* x, const float* gy) {
+    return make_wgrad_plan(B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, x, gy).path;
 }
 
 extern "C" int sr_conv2d_wgrad_mfma(float* dwt, const float* x, const float* gy, const float* xscale,
                                     const float* gscale, int64_t B, int64_t C, int64_t N, int64_t IH,
                                     int64_t IW, int64_t OH, int64_t OW, int ksize, int stride, int pad,
                                     int transposed, float* scratch, sr_stream_t stream) {
-    int is, GH, GW, UH, UW, CUc, CVc, d0;
-    if (!geometry(B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, is, GH, GW, UH, UW, CUc, CVc, d0))
-        return SR_EINVAL;
+    const WgradPlan w = make_wgrad_plan(B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, x, gy);
+    if (w.path == SR_WGRAD_PATH_INVALID) return SR_EINVAL;
     if (!dwt || !x || !gy || !scratch) return SR_EINVAL;
     if (B * C * IH * IW >= (1LL << 31) || B * N * OH * OW >= (1LL << 31)) return SR_ERANGE;
     hipStream_t st = sr_stream(stream);
-    if (wgrad_small_ok(C, N, ksize, stride, pad, transposed)) {
+    // U / V and their scales
+    const float *U = transposed ? gy : x, *V = transposed ? x : gy;
+    const float *uscale = transposed ? gscale : xscale, *vscale = transposed ? xscale : gscale;
+    int ks = 0, UP = 0, VP = 0, rc = SR_OK;
+    switch (w.path) {
+    case SR_WGRAD_PATH_SMALL3: {
         const int nb = B > 0 ? wgrad_small_blocks(B, IH, IW) : 0;
         if (nb > 0) {
             hipLaunchKernelGGL(k_wgrad_small3, dim3(nb, (unsigned)C), dim3(256), 0, st, scratch, x, gy, xscale, gscale, (int)B, (int)C,
@@ -748,72 +793,31 @@ extern "C" int sr_conv2d_wgrad_mfma(float* dwt, const float* x, const float* gy,
         hipLaunchKernelGGL(k_wgrad_small3_finish, dim3(1), dim3(4 * WS_ACC), 0, st, dwt, scratch, nb, (int)C, (int)N);
         return sr_launch_status();
     }
-    if (!transposed && ksize == 3 && stride == 1 && pad == 1 && wgrad_wino_enabled() &&
-        sr_wgrad_wino_eligible(B, C, N, IH, IW, x, gy))
+    case SR_WGRAD_PATH_WINO:
         return sr_wgrad_wino_3x3(dwt, x, gy, xscale, gscale, B, C, N, IH, IW, scratch, st);
-    if (!transposed && ksize == 1 && stride == 1 && pad == 0 && B > 0 && sr_wgrad_bf16x3_enabled('w') &&
-        sr_wgrad_bf16x3_eligible(B, C, N, IH * IW, x, gy)) {
-        // opt-in spike (SR_CONV_SPLIT_BF16=1): split-bf16 matrix path, same partial-slab layout and reduce
-        int ks3 = 0, UP3 = 0, VP3 = 0;
-        const int rc3 = sr_wgrad_bf16x3_launch(x, gy, xscale, gscale, scratch, B, C, N, IH * IW, &ks3, &UP3, &VP3, st);
-        if (rc3 != SR_OK) return rc3;
-        ReduceParams r;
-        r.partial = scratch; r.out = dwt;
-        r.ks = ks3; r.nt = 1; r.UP = UP3; r.VP = VP3; r.CU = CUc; r.CV = CVc;
-        r.slab = C * N; r.su = N; r.sv = 1;
-        for (int t = 0; t < 9; ++t) r.tmap[t] = t;
-        const int64_t total = (int64_t)CUc * CVc;
-        launch_wgrad_reduce(r, total, st);
-        return sr_launch_status();
+    case SR_WGRAD_PATH_BF16_1X1:
+        rc = sr_wgrad_bf16x3_launch(x, gy, xscale, gscale, scratch, B, C, N, IH * IW, &ks, &UP, &VP, st);
+        return rc != SR_OK ? rc : reduce_slices(dwt, scratch, w, ks, 1, UP, VP, transposed, st);
+    case SR_WGRAD_PATH_BF16_S2:
+        rc = sr_wgrad_s2_bf16x3_launch(U, V, uscale, vscale, scratch, B, w.CU, w.CV, w.UH, w.UW, w.GH, w.GW, &ks, &UP, &VP, st);
+        return rc != SR_OK ? rc : reduce_slices(dwt, scratch, w, ks, 9, UP, VP, transposed, st);
     }
-    if (ksize == 3 && is == 2 && pad == 0 && sr_wgrad_bf16x3_enabled('g') &&
-        sr_wgrad_s2_bf16x3_eligible(B, CUc, CVc, UH, UW, GH, GW, transposed ? x : gy)) {
-        // opt-in spike (SR_CONV_SPLIT_BF16=1): the up- / down-sampling layers' weight gradient on the bf16 matrix cores
-        int ks3 = 0, UP3 = 0, VP3 = 0;
-        const int rc3 = sr_wgrad_s2_bf16x3_launch(transposed ? gy : x, transposed ? x : gy, transposed ? gscale : xscale,
-                                                  transposed ? xscale : gscale, scratch, B, CUc, CVc, UH, UW, GH, GW, &ks3,
-                                                  &UP3, &VP3, st);
-        if (rc3 != SR_OK) return rc3;
-        ReduceParams r;
-        r.partial = scratch; r.out = dwt;
-        r.ks = ks3; r.nt = 9; r.UP = UP3; r.VP = VP3; r.CU = CUc; r.CV = CVc;
-        r.slab = C * N;
-        r.su = transposed ? 1 : N;
-        r.sv = transposed ? N : 1;
-        for (int t = 0; t < 9; ++t) r.tmap[t] = t;
-        const int64_t total = (int64_t)9 * CUc * CVc;
-        launch_wgrad_reduce(r, total, st);
-        return sr_launch_status();
-    }
-    const Plan pl = make_plan(is, (int)B, CUc, CVc, GH, GW);
+    const Plan& pl = w.tiles;
     WgradParams p;
-    p.U = transposed ? gy : x;
-    p.V = transposed ? x : gy;
-    p.uscale = transposed ? gscale : xscale;
-    p.vscale = transposed ? xscale : gscale;
+    p.U = U; p.V = V; p.uscale = uscale; p.vscale = vscale;
     p.partial = scratch;
-    p.B = (int)B; p.CU = CUc; p.CV = CVc; p.UH = UH; p.UW = UW; p.GH = GH; p.GW = GW;
-    p.dy0 = p.dx0 = d0;
+    p.B = (int)B; p.CU = w.CU; p.CV = w.CV; p.UH = w.UH; p.UW = w.UW; p.GH = w.GH; p.GW = w.GW;
+    p.dy0 = p.dx0 = w.d0;
     p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.tiles_b = pl.tiles_b;
     p.tiles_u = pl.tiles_u; p.tiles_v = pl.tiles_v; p.ks = pl.ks; p.patches_per_slice = pl.pps;
     p.UP = pl.tiles_u * pl.ut; p.VP = pl.tiles_v * pl.vt;
-    int rc = SR_OK;
     if (B > 0) {
-        if (ksize == 3 && is == 1) rc = launch_wgrad_s1<3, 3>(p, pl, st);
-        else if (ksize == 3 && is == 2) rc = launch_wgrad_s2<3, 3>(p, pl, st);
-        else if (ksize == 1 && is == 1) rc = launch_wgrad_s1<1, 1>(p, pl, st);
-        else rc = launch_wgrad_s2<1, 1>(p, pl, st);
+        const bool dma = w.path == SR_WGRAD_PATH_S2_DMA;
+        if (ksize == 3 && stride == 1) rc = launch_wgrad_s1<3, 3>(p, pl, st);
+        else if (ksize == 3 && stride == 2) rc = launch_wgrad_s2<3, 3>(p, pl, dma, st);
+        else if (ksize == 1 && stride == 1) rc = launch_wgrad_s1<1, 1>(p, pl, st);
+        else rc = launch_wgrad_s2<1, 1>(p, pl, dma, st);
         if (rc != SR_OK) return rc;
     }
-    ReduceParams r;
-    r.partial = scratch; r.out = dwt;
-    r.ks = B > 0 ? pl.ks * NG_OF(pl.pb) : 0; r.nt = ksize * ksize; r.UP = p.UP; r.VP = p.VP; r.CU = CUc; r.CV = CVc;
-    r.slab = C * N;
-    // dwt is [k*k][C][N]: regular conv has (u, v) = (c, n); transposed has (u, v) = (n, c)
-    r.su = transposed ? 1 : N;
-    r.sv = transposed ? N : 1;
-    for (int t = 0; t < 9; ++t) r.tmap[t] = t;
-    const int64_t total = (int64_t)r.nt * CUc * CVc;
-    launch_wgrad_reduce(r, total, st);
-    return sr_launch_status();
+    return reduce_slices(dwt, scratch, w, B > 0 ? pl.ks * NG_OF(pl.pb) : 0, ksize * ksize, p.UP, p.VP, transposed, st);
 }

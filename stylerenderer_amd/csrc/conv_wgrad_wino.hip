@@ -591,8 +591,7 @@ int sr_wgrad_wino_3x3(float* dwt, const float* x, const float* gy, const float* 
     p.cty = (int)(H / 2); p.ctx = (int)(W / 16);
     plan(B, C, N, H, W, p.slices, p.chunks_per_slice, p.chunks_total);
     // SR_WGW_WAVES=4: one wave per SIMD (round 2's form); default 8: two per SIMD (same bits)
-    const char* e = getenv("SR_WGW_WAVES");
-    const bool two = !(e && e[0] == '4');
+    const bool two = sr_env_char("SR_WGW_WAVES") != '4';
     static bool configured = false;
     if (!configured) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_wino<4>), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -3,6 +3,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "common.h"
+
+// SR_WINOGRAD=0 keeps the direct kernels for the stride-1 3x3 convolution and its weight gradient (A/B measurements,
+// exact-fma-chain numerics).  Read per call: tests flip it at run time.
+inline bool sr_winograd_enabled() { return !sr_env_off("SR_WINOGRAD"); }
+
 struct WinoParams {
     const float* in;
     const float* u;        // transformed weights, chunk-ordered (k_wino_weights)

@@ -590,8 +590,7 @@ int64_t sr_wino_scratch_floats(int64_t C, int64_t N) { return 16 * C * N; }
 // K slices: only when the tiles alone leave most of the chip idle; equal slices of >= 8 chunks (64 channels).
 // SR_WINO_SPLIT=0 disables (A/B measurements).
 int sr_wino_split(int64_t B, int64_t C, int64_t N, int64_t H, int64_t W) {
-    const char* e = std::getenv("SR_WINO_SPLIT");
-    if (e && e[0] == '0') return 1;
+    if (sr_env_off("SR_WINO_SPLIT")) return 1;
     const int64_t blocks = B * (W / (2 * TW)) * (H / (2 * TH)) * (N / NB), nchunks = C / 8;
     int ks = 1;
     while (blocks * ks < 192 && ks < 8 && nchunks % (2 * ks) == 0 && nchunks / (2 * ks) >= 8) ks *= 2;

@@ -47,14 +47,7 @@ def conv2d_mfma(x, wt, iscale=None, oscale=None, obias=None, ksize=3, stride=1, 
     x = x.contiguous()
     b, c, ih, iw = x.shape
     taps, cw, n = wt.shape
-    # the kernel reads weight rows as 16-byte vectors: row pitch a multiple of 4 floats (views of the
-    # padded buffers of op.weight_prep pass through untouched)
-    if (wt.stride(2) == 1 and wt.stride(1) % 4 == 0 and wt.stride(1) >= n and wt.stride(0) == cw * wt.stride(1)
-            and wt.data_ptr() % 16 == 0):
-        ldw = wt.stride(1)
-    else:
-        ldw = (n + 3) // 4 * 4
-        wt = torch.nn.functional.pad(wt, (0, ldw - n)) if ldw != n else wt.contiguous()
+    wt, ldw = _wt_pitch(wt)
     if taps != ksize * ksize or cw != c:
         raise RuntimeError("conv2d_mfma: weight must be [k*k, C, N]; got %s for C=%d k=%d"
                            % (tuple(wt.shape), c, ksize))
@@ -297,14 +290,13 @@ def _aliases(*tensors):
 
 
 def conv_nba_shape_ok(x, n, noise):
-    """Shape / layout part of `conv_nba_supported` (no weights needed)."""
-    import os
-
-    if os.environ.get("SR_WINOGRAD", "1") == "0" or x.device.type != "cuda" or x.dtype != torch.float32:
+    """Shape / layout part of `conv_nba_supported` (no weights needed): the library's dispatch takes the Winograd kernel
+    for this input (sr_conv2d_path; the output is allocated by the caller, aligned), one grid row per (sample, channel)."""
+    if x.device.type != "cuda" or x.dtype != torch.float32 or not x.is_contiguous():
         return False
     b, c, h, w = x.shape
-    ok = (h % 8 == 0 and w % 32 == 0 and c % 8 == 0 and c <= 512 and n % 64 == 0
-          and b * n <= 65535 and x.is_contiguous() and x.data_ptr() % 16 == 0)
+    ok = b * n <= 65535 and _lib.lib().sr_conv2d_path(b, c, n, h, w, h, w, 3, 1, 1, 0, _lib.ptr(x), None, None, 0,
+                                                      1) == _lib.CONV_PATH_WINO
     if noise is not None:
         ok = ok and noise.dtype == torch.float32 and noise.numel() in (h * w, b * h * w) and noise.data_ptr() % 16 == 0
     return ok
@@ -315,6 +307,8 @@ def conv_nba_supported(x, wt, noise):
 
 
 def _wt_pitch(wt):
+    """(wt, row pitch): the kernels read weight rows as 16-byte vectors — row pitch a multiple of 4 floats (views of the
+    padded buffers of op.weight_prep pass through untouched)."""
     taps, cw, n = wt.shape
     if (wt.stride(2) == 1 and wt.stride(1) % 4 == 0 and wt.stride(1) >= n and wt.stride(0) == cw * wt.stride(1)
             and wt.data_ptr() % 16 == 0):

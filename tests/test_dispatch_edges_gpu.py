@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from conv_plan_cases import FORWARD, STRIPS, SWITCHES, WGRAD, case_id, conv_args
 from util import bits_equal, kernel_ran, launched_kernels
 
 pytestmark = pytest.mark.gpu
@@ -595,3 +596,62 @@ def test_from_rgb_weight_gradient_at_256_vs_float64():
     # _dw(x, gy): the image is the "gradient" operand (N = 3), the 128 channels the rows (CH = 4)
     assert kernel_ran(names, "k_smallconv_dw", "<3, 4>") and kernel_ran(names, "k_smallconv_dw_finish"), names
     _check(got, want, mag, 2e-6, "dwt")
+
+
+# ---- the dispatch queries and the launches agree (csrc/conv_mfma.hip make_conv_plan, csrc/conv_wgrad_mfma.hip) ---------
+# kernels that tell the paths apart: a path's launch runs exactly its own of these (no numeric assertions here: the
+# float64 comparisons of the same shapes are in test_conv_gpu, test_conv_s2_wino_gpu and above).  k_conv_mfma is judged
+# apart: it is the direct path's only kernel and no other non-transposed path runs it, but the transposed paths use its
+# TAP9 / per-phase instantiations for the tap-split launch in patch form, the strips and the border.
+def _forward_kernels(path):
+    from stylerenderer_amd import _lib as P
+
+    own = {P.CONV_PATH_DIRECT: set(), P.CONV_PATH_WINO: {"k_conv_wino"}, P.CONV_PATH_S2_WINO: {"k_conv_s2_wino"},
+           P.CONV_PATH_GEMM1X1: {"k_conv1x1_gemm"}, P.CONV_PATH_CONVT_TAPS: {"k_convt_tap_reduce"},
+           P.CONV_PATH_CONVT_FUSED: {"k_convt_fused"},
+           P.CONV_PATH_CONVT_FUSED_KS: {"k_convt_fused", "k_convt_fused_reduce"}}[path & ~STRIPS]
+    return own | ({"k_convt_strip_reduce"} if path & STRIPS else set())
+
+
+FORWARD_KERNELS = ("k_conv_wino", "k_conv_s2_wino", "k_conv1x1_gemm", "k_convt_tap_reduce", "k_convt_fused",
+                   "k_convt_fused_reduce", "k_convt_strip_reduce")
+WGRAD_KERNELS = {"k_wgrad_mfma": 0, "k_wgrad_small3": 1, "k_wgrad_wino": 2, "k_wgrad_s2_dma": 5}      # SR_WGRAD_PATH_*
+
+
+@pytest.mark.parametrize("row", [r for r in FORWARD if r[-1]], ids=case_id)
+def test_forward_launch_runs_the_path_the_query_returns(row, monkeypatch):
+    from stylerenderer_amd import _lib
+    from stylerenderer_amd.op.conv import _wt_pitch, conv2d_mfma
+
+    geom, shape, env, _, _, path, _ = row
+    for name in SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    for kv in env.items():
+        monkeypatch.setenv(*kv)
+    b, c, n, ih, iw, oh, ow, k, stride, pad, tr = conv_args(geom, shape)
+    x = torch.randn(b, c, ih, iw, device=DEV)
+    wt, ldw = _wt_pitch(torch.randn(k * k, c, n, device=DEV))
+    got = _lib.lib().sr_conv2d_path(b, c, n, ih, iw, oh, ow, k, stride, pad, tr, x.data_ptr(), None, wt.data_ptr(), ldw, 1)
+    assert got == path                                   # the rule beside the row, now with real buffers
+    _, names = launched_kernels(lambda: conv2d_mfma(x, wt, None, None, None, k, stride, pad, bool(tr)))
+    assert {kn for kn in FORWARD_KERNELS if kernel_ran(names, kn)} == _forward_kernels(got), names
+    if got == _lib.CONV_PATH_DIRECT or not tr:
+        assert kernel_ran(names, "k_conv_mfma") == (got == _lib.CONV_PATH_DIRECT), names
+
+
+@pytest.mark.parametrize("row", [r for r in WGRAD if r[-1]], ids=case_id)
+def test_wgrad_launch_runs_the_path_the_query_returns(row, monkeypatch):
+    from stylerenderer_amd import _lib
+    from stylerenderer_amd.op.conv import conv2d_wgrad_mfma
+
+    geom, shape, env, _, path, _ = row
+    for name in SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    for kv in env.items():
+        monkeypatch.setenv(*kv)
+    b, c, n, ih, iw, oh, ow, k, stride, pad, tr = conv_args(geom, shape)
+    x, gy = torch.randn(b, c, ih, iw, device=DEV), torch.randn(b, n, oh, ow, device=DEV)
+    got = _lib.lib().sr_conv2d_wgrad_path(b, c, n, ih, iw, oh, ow, k, stride, pad, tr, x.data_ptr(), gy.data_ptr())
+    assert got == path
+    _, names = launched_kernels(lambda: conv2d_wgrad_mfma(x, gy, None, None, k, stride, pad, bool(tr)))
+    assert {kn for kn in WGRAD_KERNELS if kernel_ran(names, kn)} == {kn for kn, v in WGRAD_KERNELS.items() if v == got}, names
