@@ -15,16 +15,7 @@ The reference has no fitting script; its pieces are the generato
                 mean identity with every expression at sigmoid(0))
     loss        LPIPS-shaped distance(image, target) + pixel_weight * mean((image - target)^2)
                 (+ shape_reg * face_model.regulation(coeff), reference face_model.py:73-74, with fit_shape=True)
-                (+ landmark_weight * op.landmark.landmark_loss(vertices, embedding, landmarks, landmark_conf), with
-                 landmarks=: the fit's landmarks against the picture's; the pose then starts at
-                 align.pose_from_landmarks of the mean shape instead of 0; with landmark_lines= (and landmark_axis=) the
-                 jaw landmarks slide along the posed mesh's silhouette, with landmark_vis= landmarks turned away from the
-                 camera are faded out: op.landmark's pose-aware term, the pose start in two closed-form passes)
-                with mask= ([B, 1, H, W] in [0, 1]) and / or mask_mesh=True the image terms run on
-                y = target + m_eff (image - target) instead of image (op.region.region_blend; m_eff = mask, times the
-                mesh's coverage (n . n of the rendered normal map > 1e-3) with mask_mesh): outside the region the loss
-                sees the target itself.  The pixel term is then mean((m_eff (image - target))^2) over ALL pixels, not
-                renormalised by the region's area.  An all-zero region gives loss 0 and gradient 0.
+                (the optional parts below: + a landmark term; the image terms on a region; a camera before the consumers)
     update      Adam, `steps` iterations (default 400)
 
 A target [B, 3, H, W] with B > 1 fits B independent images in one iteration (one captured graph): every variable
@@ -45,17 +36,14 @@ through the same element-wise Adam, so coeff[:, :K] stays equal across the rows 
 parameter.  Every row keeps its own prior term, as in the batched fit: the objective is the sum of the V single-view
 objectives under the constraint, so the shared columns' prior enters V times; it is not rescaled.
 
-With camera= (a float or [B] of kappa = 1 / distance, the camera's distance from the plane z = 0 of pose space in
-half-picture-widths) the posed mesh passes through op.camera.project before the landmark term and the generator see it: one
-node, one launch each way, after the model's node (or the fixed mesh's pose).  The consumers stay orthographic; with
-landmark_vis the same launch writes n_view, the normals as a facing gate must read them under a camera, while the generator
-keeps the camera-space normals.  fit_camera=True makes kappa a variable [B] with its own Adam group (camera_lr, a starting
-value, not tuned): one value per row, per view under shared_identity, unconstrained (a negative fit is reported as it is).
+The optional parts are objects of fit_parts, each None when it is off, and each called at one place of the iteration:
+    landmark    fit_parts.LandmarkTerm (landmarks=): the fit's landmarks against the picture's, and the pose's start
+    region      fit_parts.Region (mask=, mask_mesh=): the image terms see the target itself outside a region
+    cam         fit_parts.Camera (camera=, fit_camera=): the consumers see the mesh through a perspective projection
+`_mesh` is the one place that builds the mesh (and applies the camera) for `render`, `posed_mesh` and `fitted_mesh`:
 `fitted_mesh()` returns what the consumers saw, `fitted_mesh(projected=False)` the camera-space mesh; `reset` puts kappa
-back at its start.  With camera=None there is no node and no parameter: the iteration and its captured graph are unchanged.
-Known degeneracy: for image-plane positions, (e^s, t_xy, t_z, kappa) and (e^s / (1 - kappa t_z), t_xy / (1 - kappa t_z), 0,
-kappa) project identically, so t_z and the scale trade off along a flat direction; compare projections, kappa and angles
-between fits, never raw t_z or s.  kappa is only weakly determined by the image terms alone: it wants landmarks.
+back at its start.  With a part off there is no node and no parameter for it: the iteration and its captured graph are
+those without it.
 
 The pose gradient reaches the vertices only through the rasterizer's backward (deterministic gather, so two
 runs from the same state produce bit-identical trajectories).  On a GPU the whole iteration — forward, backward,
@@ -66,6 +54,7 @@ import torch
 from torch import optim
 
 from . import graphs, utils_3d
+from .fit_parts import Camera, LandmarkTerm, Region
 
 
 class _FlatAdamSet:
@@ -136,49 +125,31 @@ class LatentInverter:
             self.shared_identity = int(shared_identity)
         self.pixel_weight = float(pixel_weight)
         self.with_map = hasattr(self.g, "norm_to_style")
+        # the region of the image loss (op.region): not part of the iteration at all without mask / mask_mesh
+        self.region = Region(self.target, mask, mask_mesh, self.with_map) if mask is not None or mask_mesh else None
         with torch.no_grad():
             mean_w = self.g.mean_latent(n_mean_latent)                                  # [1, D]
-            self.target_feats = [f.detach() for f in self.perceptual.features(self.target)]
+            self.target_feats = self._features_of_target()
         self._mean_w = mean_w
         self.w = mean_w.unsqueeze(1).repeat(self.batch, self.g.n_latent, 1).clone().requires_grad_(True)
         pose_shape = (7,) if self.batch == 1 else (self.batch, 7)
         self.pose = torch.zeros(pose_shape, device=self.device, requires_grad=optimise_pose)
         # the landmark term: not part of the iteration at all without landmarks
-        self.with_landmarks = landmarks is not None
-        self.landmarks_fit = None
-        # of the pose-aware term (landmark_lines / landmark_vis): the vertices the contour lines selected [B, C] and the
-        # gate on every landmark's confidence [B, L] in the last forward
-        self.contour_fit = self.landmark_visibility = None
-        if self.with_landmarks:
-            self._init_landmarks(landmarks, landmark_conf, landmark_weight, landmark_beta, landmark_embedding,
-                                 landmark_lines, landmark_axis, landmark_vis)
-        elif landmark_conf is not None:
-            raise ValueError("LatentInverter: landmark_conf without landmarks")
-        # the region of the image loss (op.region): not part of the iteration at all without mask / mask_mesh
-        self.mask_mesh = bool(mask_mesh)
-        self.with_mask = mask is not None or self.mask_mesh
-        self.mask_fit = None                             # m_eff [B, 1, H, W] of the last forward
-        self._normal_map = None
-        if self.mask_mesh and not self.with_map:
-            raise ValueError("LatentInverter: mask_mesh=True needs a GeneratorWithMap: the mesh's coverage is read off "
-                             "the normal map it renders")
-        if self.with_mask:
-            # the buffer the iteration (and its captured graph) reads; reset() rewrites it
-            self._mask = torch.ones((self.batch, 1) + tuple(self.target.shape[-2:]), device=self.device)
-            self._set_mask(mask)
+        self.landmark = None
+        if landmarks is not None or landmark_conf is not None:
+            self.landmark = LandmarkTerm((self.face_model, self.tri) if self.fit_shape else None, self.pose,
+                                         self.target.shape[-2:], landmarks, landmark_conf, landmark_weight,
+                                         landmark_beta, landmark_embedding, landmark_lines, landmark_axis, landmark_vis)
             with torch.no_grad():
-                self.target_feats = self._features_of_target()
+                self.pose.copy_(self.landmark.pose_start)
         # 3DMM coefficients [B, d], from the mean face
         self.coeff = (torch.zeros(self.batch, self.face_model.n_coeff, device=self.device, requires_grad=True)
                       if self.fit_shape else None)
         self.noise = noise if noise is not None else [n.detach() for n in self.g.make_noise()]
         # the perspective camera (op.camera): not part of the iteration at all with camera=None
-        self.camera = self._camera_start = self._camera_grad = None
-        self.fit_camera = bool(fit_camera)
-        if camera is not None:
-            self._init_camera(camera)
-        elif self.fit_camera:
-            raise ValueError("LatentInverter: fit_camera=True needs camera=, the start value of kappa = 1 / distance")
+        self.cam = Camera(camera, fit_camera, self.batch, self.device) if camera is not None or fit_camera else None
+        # what render leaves for loss: the prior of this forward (None: not added), and the per-sample losses
+        self._reg = self._prior_rows = self._rows = None
         on_gpu = self.device.type == "cuda"
         groups = [{"params": [self.w], "lr": lr}]
         if optimise_pose:
@@ -202,7 +173,7 @@ class LatentInverter:
                 self._adams.append((p, FlatAdam([p], flat_g, lr=g_["lr"], betas=(0.9, 0.999),
                                                 step_from=self._adams[0][1] if own else None)))
                 if own:
-                    self._camera_grad = flat_g
+                    self.cam.grad = flat_g
             self.optim = _FlatAdamSet(self._adams, [self.camera] if self.fit_camera else [])
         else:
             self._adams = None
@@ -216,252 +187,89 @@ class LatentInverter:
     skinned = property(lambda self: self.fit_shape and self.face_model.kind == "skinned")       # FLAME: op.skin
     blended = property(lambda self: self.fit_shape and self.face_model.kind == "blended")       # FaceWarehouse: op.blend
 
-    # ---- camera --------------------------------------------------------------------------------------
-    def _init_camera(self, camera):
-        """camera: a float or [B] of kappa = 1 / distance, the start values (kept for reset)."""
-        import math
+    # ---- the optional parts (fit_parts) ---------------------------------------------------------------
+    with_landmarks = property(lambda self: self.landmark is not None)
+    with_mask = property(lambda self: self.region is not None)
+    camera = property(lambda self: None if self.cam is None else self.cam.kappa)                # kappa [B], or None
+    fit_camera = property(lambda self: self.cam is not None and self.cam.fit)
+    # outputs of the last forward (they keep the previous picture's values after reset, until the next step)
+    landmarks_fit = property(lambda self: None if self.landmark is None else self.landmark.landmarks_fit)
+    contour_fit = property(lambda self: None if self.landmark is None else self.landmark.contour_fit)
+    landmark_visibility = property(lambda self: None if self.landmark is None else self.landmark.landmark_visibility)
+    mask_fit = property(lambda self: None if self.region is None else self.region.mask_fit)
 
-        if isinstance(camera, torch.Tensor):
-            k = camera.detach().to(device="cpu", dtype=torch.float64).reshape(-1)
-        elif isinstance(camera, (int, float)) and not isinstance(camera, bool):
-            k = torch.full((self.batch,), float(camera), dtype=torch.float64)
-        else:
-            try:
-                k = torch.as_tensor([float(x) for x in camera], dtype=torch.float64)
-            except (TypeError, ValueError):
-                raise ValueError("LatentInverter: camera is a float or %d floats, got %r" % (self.batch, camera))
-        if k.numel() == 1 and self.batch > 1 and not isinstance(camera, (int, float)):
-            k = k.expand(self.batch).clone()
-        if k.numel() != self.batch:
-            raise ValueError("LatentInverter: %d images need camera [%d] (or one float), got %d values"
-                             % (self.batch, self.batch, k.numel()))
-        if not all(math.isfinite(x) for x in k.tolist()):
-            raise ValueError("LatentInverter: camera (kappa = 1 / distance) must be finite")
-        self._camera_start = k.to(device=self.device, dtype=torch.float32)
-        self.camera = self._camera_start.clone().requires_grad_(self.fit_camera)
-
-    def _project(self, v, n, gate=False):
-        """The mesh the consumers see: (v', n_view or None) of the camera-space mesh (op.camera.project: one launch each
-        way on the device).  gate: a facing gate will read the normals, so the same launch writes n_view."""
-        from .op.camera import project
-
-        # (on the device a fitted kappa's gradient goes straight into its Adam's buffer)
-        out = self._camera_grad if torch.is_grad_enabled() else None
-        if gate:
-            return project(v, self.camera, normals=n, gkappa_out=out)
-        return project(v, self.camera, gkappa_out=out), None
-
-    # ---- landmarks -----------------------------------------------------------------------------------
-    def _init_landmarks(self, landmarks, conf, weight, beta, embedding, lines=None, axis=None, vis=None):
-        if not self.fit_shape:
-            raise ValueError("LatentInverter: landmarks need fit_shape=True and face=(model, tri): the landmarks of the "
-                             "fit are read off the model's mesh")
-        emb = embedding if embedding is not None else getattr(self.face_model, "landmarks", None)
-        if emb is None:
-            raise ValueError("LatentInverter: landmarks need a landmark embedding and the face model has none "
-                             "(model.landmarks is None): pass landmark_embedding=face_model.landmark_embedding(...)")
-        self._lmk_idx, self._lmk_bary = (t.detach().to(self.device).contiguous() for t in emb)
-        self.landmark_weight, self.landmark_beta = float(weight), float(beta)
-        n_l = int(self._lmk_idx.shape[0])
-        # the pose-aware term (op.landmark.landmark_loss_ex): contour lines that slide along the silhouette (on the host:
-        # the kernels' lists are built from them once), the two anchor vertices of the face's up direction, the gate
-        self._lmk_dynamic = lines is not None or vis is not None
-        if lines is not None and axis is None:
-            raise ValueError("LatentInverter: landmark_lines need landmark_axis=(i_up, i_down), the vertices that span "
-                             "the face's up direction")
-        if vis is not None and not float(vis[0]) <= float(vis[1]):
-            raise ValueError("LatentInverter: landmark_vis = (lo, hi) needs lo <= hi")
-        self._lmk_lines = None if lines is None else tuple(
-            (t.detach().cpu() if isinstance(t, torch.Tensor) else torch.as_tensor(t)).to(torch.int32).reshape(-1)
-            for t in lines)
-        self._lmk_axis = None if lines is None else (int(axis[0]), int(axis[1]))
-        self._lmk_vis = None if vis is None else (float(vis[0]), float(vis[1]))
-        # the buffers the iteration (and its captured graph) reads; reset() rewrites them
-        self._lmk_target = torch.zeros(self.batch, n_l, 2, device=self.device)
-        self._lmk_conf = torch.zeros(self.batch, n_l, device=self.device)
-        self._pose_start = torch.zeros_like(self.pose)
-        # the model's landmark points on its mean shape (host, float64): what the closed-form pose start is fitted to
-        with torch.no_grad():
-            v_mean = self.face_model.mesh(torch.zeros(1, self.face_model.n_coeff, device=self.device),
-                                          torch.zeros(1, 7, device=self.device), self.tri)[0]
-            from .op.landmark import landmark_points
-
-            self._lmk_points = landmark_points(v_mean.double().cpu(), self._lmk_idx.cpu(),
-                                               self._lmk_bary.double().cpu())[0].numpy()
-            self._lmk_mean = v_mean[0].double().cpu().numpy() if self._lmk_lines is not None else None
-        self._set_landmarks(landmarks, conf)
-        with torch.no_grad():
-            self.pose.copy_(self._pose_start)
-
-    @torch.no_grad()
-    def _set_landmarks(self, landmarks, conf):
-        """Target landmarks [B, L, 2] (or [L, 2]) and confidences [B, L] (None: 1; landmarks None: all missing) into the
-        buffers, and every sample's closed-form starting pose into _pose_start (0 for a sample without landmarks)."""
-        import numpy as np
-
-        from .align import pose_from_landmarks, pose_from_landmarks_contour
-        from .op._dispatch import host_array
-
-        n_l = int(self._lmk_idx.shape[0])
-        if landmarks is None:
-            lm, c = np.zeros((self.batch, n_l, 2)), np.zeros((self.batch, n_l))
-        else:
-            lm = host_array(landmarks).astype(np.float64)
-            lm = lm[None] if lm.ndim == 2 else lm
-            c = np.ones(lm.shape[:2]) if conf is None else host_array(conf).astype(np.float64).reshape(lm.shape[0], -1)
-        if lm.shape != (self.batch, n_l, 2) or c.shape != (self.batch, n_l):
-            raise ValueError("LatentInverter: %d images and %d landmarks need landmarks [B, L, 2] and landmark_conf "
-                             "[B, L], got %s and %s" % (self.batch, n_l, lm.shape, c.shape))
-        if (c < 0).any() or not np.isfinite(c).all():
-            raise ValueError("LatentInverter: landmark_conf must be finite and not negative")
-        lm = np.where(c[:, :, None] > 0, lm, 0.0)                       # a missing landmark may hold anything
-        if not np.isfinite(lm).all():
-            raise ValueError("LatentInverter: a landmark with a positive confidence is not finite")
-        size = tuple(int(x) for x in self.target.shape[-2:])
-        start = np.zeros((self.batch, 7))
-        for b in range(self.batch):
-            if c[b].sum() > 0 and self._lmk_lines is not None:
-                # the jaw landmarks follow the silhouette: a second closed-form pass on the vertices the lines select
-                start[b] = pose_from_landmarks_contour(self._lmk_mean, (self._lmk_idx.cpu(), self._lmk_bary.cpu()),
-                                                       self._lmk_lines, self._lmk_axis, lm[b], size, c[b])[0]
-            elif c[b].sum() > 0:
-                start[b] = pose_from_landmarks(self._lmk_points, lm[b], size, c[b])
-        self._lmk_target.copy_(torch.from_numpy(lm).float())
-        self._lmk_conf.copy_(torch.from_numpy(c).float())
-        self._pose_start.copy_(torch.from_numpy(start).float().view(self._pose_start.shape))
-
-    # ---- region ---------------------------------------------------------------------------------------
     def _features_of_target(self):
-        """The target's LPIPS features.  With a region a render that equals the target inside it must have distance
-        exactly 0, so they are normalised the way the loss normalises the render's (lpips.PNetLin.target_features);
-        without one they are `features`, as ever."""
-        f = self.perceptual.target_features if self.with_mask else self.perceptual.features
-        return [x.detach() for x in f(self.target)]
+        """The target's LPIPS features: `features`, or with a region the region's choice."""
+        if self.region is not None:
+            return self.region.target_features(self.perceptual, self.target)
+        return [x.detach() for x in self.perceptual.features(self.target)]
 
-    @torch.no_grad()
-    def _set_mask(self, mask):
-        """mask [B, 1, H, W] ([1, H, W] / [H, W] at B = 1; None: all ones), finite and in [0, 1], into the buffer."""
-        if mask is None:
-            self._mask.fill_(1.0)
-            return
-        m = mask.detach() if isinstance(mask, torch.Tensor) else torch.as_tensor(mask)
-        if self.batch == 1 and tuple(m.shape) in (tuple(self._mask.shape[1:]), tuple(self._mask.shape[2:])):
-            m = m.reshape(self._mask.shape)
-        if tuple(m.shape) != tuple(self._mask.shape):
-            raise ValueError("LatentInverter: mask %s, the inverter fits %s (a mask is [B, 1, H, W], or [1, H, W] / "
-                             "[H, W] for one image)" % (tuple(m.shape), tuple(self._mask.shape)))
-        m = m.to(torch.float32)
-        if not bool(torch.isfinite(m).all()) or float(m.min()) < 0.0 or float(m.max()) > 1.0:
-            raise ValueError("LatentInverter: a mask is finite and in [0, 1]")
-        self._mask.copy_(m)
-
-    def _landmark_term(self, v, n=None):
-        """landmark_weight * rows [B] of the posed vertices (one launch each way on the device); keeps the fitted
-        landmarks [B, L, 2] (pixel index coordinates of the target) as landmarks_fit: those of this forward pass, that is
-        of the mesh before the iteration's update (reconstruct projects fitted_mesh() for what it writes).  With
-        landmark_lines / landmark_vis the pose-aware term runs (the same two launches; n: the posed normals, read
-        detached) and contour_fit / landmark_visibility keep its selection and gate."""
-        from .op.landmark import landmark_loss, landmark_loss_ex
-
-        if self._lmk_dynamic:
-            self._lmk_rows, p, sel, gate = landmark_loss_ex(
-                v, self._lmk_idx, self._lmk_bary, self._lmk_target, self._lmk_conf, tuple(self.target.shape[-2:]),
-                self.landmark_beta, self.landmark_weight, normals=n.detach() if self._lmk_vis is not None else None,
-                lines=self._lmk_lines, axis=self._lmk_axis, vis=self._lmk_vis)
-            self.landmarks_fit, self.contour_fit, self.landmark_visibility = p.detach(), sel.detach(), gate.detach()
-            return
-        self._lmk_rows, p = landmark_loss(v, self._lmk_idx, self._lmk_bary, self._lmk_target, self._lmk_conf,
-                                          tuple(self.target.shape[-2:]), self.landmark_beta, self.landmark_weight)
-        self.landmarks_fit = p.detach()
-
-    def _shape_mesh(self):
-        """(v, n, tri, reg) of the fitted coefficients and pose (the model's node — op.morph / op.skin / op.blend: no
-        library GEMM on the device)."""
-        v, n, reg, self._prior_rows = self.face_model.mesh(self.coeff, self.pose.view(-1, 7), self.tri, self.shape_reg)
-        return v, n, self.tri, reg
+    def _mesh(self, projected=True, gate=False):
+        """The one mesh path: (v, n, n_gate, reg, prior_rows) of the current variables.  v is what the consumers see: the
+        camera-space vertices of the model's node (op.morph / op.skin / op.blend: no library GEMM on the device) or of the
+        posed fixed mesh, through the camera's projection if there is one (projected=False: left in camera space); the
+        projection is applied here and nowhere else.  n stays the camera-space normal, which the generator keeps; n_gate
+        is what a facing gate reads: with gate=True under a camera n_view, written by the projection's launch, else n.
+        reg, prior_rows: the prior of the model's node (None for the fixed mesh)."""
+        reg = prior_rows = None
+        if self.fit_shape:
+            v, n, reg, prior_rows = self.face_model.mesh(self.coeff, self.pose.view(-1, 7), self.tri, self.shape_reg)
+        else:
+            lin, rot = utils_3d.pose_matrices(self.pose)                                # [B, 3, 3] each
+            # [nv, 3] x [3, 3]: one streaming kernel each (utils_3d.affine3), not a 3-wide library GEMM
+            t = self.pose[3:6].view(1, 3) if self.batch == 1 else self.pose[:, 3:6]
+            v, n = utils_3d.affine3(self.v0, lin, t).contiguous(), utils_3d.affine3(self.n0, rot).contiguous()
+        n_gate = n
+        if self.cam is not None and projected:
+            v, n_gate = self.cam.project(v, n, gate)
+        return v, n, n_gate, reg, prior_rows
 
     def posed_mesh(self, projected=True):
         """(v, n, tri) of the current variables.  With a camera and projected=True, v is what the consumers see (v' of
         op.camera.project) and n stays the camera-space normal; projected=False gives the camera-space mesh."""
-        v, n, tri = self._camera_space_mesh()
-        if self.camera is not None and projected:
-            v = self._project(v, n)[0]
-        return v, n, tri
-
-    def _camera_space_mesh(self):
-        if self.fit_shape:
-            return self._shape_mesh()[:3]
-        lin, rot = utils_3d.pose_matrices(self.pose)                                    # [B, 3, 3] each
-        # [nv, 3] x [3, 3]: one streaming kernel each (utils_3d.affine3), not a 3-wide library GEMM
-        t = self.pose[3:6].view(1, 3) if self.batch == 1 else self.pose[:, 3:6]
-        v = utils_3d.affine3(self.v0, lin, t)
-        n = utils_3d.affine3(self.n0, rot)
-        return v.contiguous(), n.contiguous(), self.tri
+        v, n = self._mesh(projected)[:2]
+        return v, n, self.tri
 
     def fitted_mesh(self, projected=True):
         """(v, n, tri) of the current fit, posed and detached.  With a camera this is what the consumers saw: the
         projected vertices v' and n_view, the normals as the facing gates read them (op.camera); projected=False returns
         the camera-space mesh.  Without a camera the two are the same."""
         with torch.no_grad():
-            v, n, tri = self._camera_space_mesh()
-            if self.camera is not None and projected:
-                v, n = self._project(v.contiguous(), n.contiguous(), gate=True)
-        return v.detach(), n.detach(), tri
+            v, _, n = self._mesh(projected, gate=True)[:3]
+        return v.detach(), n.detach(), self.tri
 
     def render(self):
-        self._reg = None
-        if self.with_map:
-            if self.fit_shape:
-                v, n, tri, self._reg = self._shape_mesh()
-                n_gate = n
-                if self.camera is not None:
-                    gate = self.with_landmarks and self._lmk_vis is not None
-                    v, n_view = self._project(v, n, gate)
-                    n_gate = n_view if gate else n
-                mesh = (v, n, tri)                       # (the generator keeps the camera-space normals)
-                if self.with_landmarks:
-                    self._landmark_term(v, n_gate)
-            else:
-                mesh = self.posed_mesh()
-            if self.mask_mesh:
-                # the normal map at the image's resolution gates the region per step (the same nodes: the generator
-                # rasterises it either way)
-                img, _, maps = self.g([self.w], mesh, input_is_latent=True, noise=self.noise, return_normals=True)
-                self._normal_map = maps[-1].detach()
-                if tuple(self._normal_map.shape[-2:]) != tuple(img.shape[-2:]):
-                    raise RuntimeError("LatentInverter: mask_mesh needs the generator's last normal map at the image's "
-                                       "resolution, got %s for %s" % (tuple(self._normal_map.shape), tuple(img.shape)))
-            else:
-                img, _, _ = self.g([self.w], mesh, input_is_latent=True, noise=self.noise)
-        else:
-            if self.with_landmarks:
-                v, n = self._shape_mesh()[:2]
-                if self.camera is not None:
-                    gate = self._lmk_vis is not None
-                    v, n_view = self._project(v, n, gate)
-                    n = n_view if gate else n
-                self._landmark_term(v, n)
-            img, _ = self.g([self.w], input_is_latent=True, noise=self.noise)
+        self._reg = self._prior_rows = None
+        lmk = self.landmark
+        if self.with_map or lmk is not None:
+            v, n, n_gate, reg, prior_rows = self._mesh(gate=lmk is not None and lmk.vis is not None)
+            if lmk is not None:
+                lmk(v, n_gate)
+        if not self.with_map:
+            # a plain Generator takes no mesh: the model's mesh serves the landmark term only, and the prior is not added
+            # (_reg stays None), as it never was on this path
+            return self.g([self.w], input_is_latent=True, noise=self.noise)[0]
+        self._reg, self._prior_rows = reg, prior_rows
+        # with mask_mesh the normal map at the image's resolution gates the region in this step
+        want = self.region is not None and self.region.mask_mesh
+        img, _, maps = self.g([self.w], (v, n, self.tri), input_is_latent=True, noise=self.noise, return_normals=want)
+        if want:
+            self.region.see(maps, img)
         return img
 
     def loss(self, img):
-        if self.with_mask:
-            # the loss below runs on y = target + m_eff (img - target): outside the region it sees the target itself
-            # (target composites to itself, so target_feats stay valid)
-            from .op.region import region_blend
-
-            img, m_eff = region_blend(img, self.target, self._mask, self._normal_map)
-            self.mask_fit = m_eff.detach()
+        if self.region is not None:
+            img = self.region(img, self.target)
         if self.batch > 1:
             return self._loss_rows(img)
         from .op.lpips_layer import mse
 
         d = self.perceptual.distance_to(self.target_feats, img).mean()
         value = d + self.pixel_weight * mse(img, self.target)
-        if self.fit_shape and self.shape_reg != 0.0 and getattr(self, "_reg", None) is not None:
+        if self.fit_shape and self.shape_reg != 0.0 and self._reg is not None:
             value = value + self._reg                    # shape_reg * regulation(coeff), from the node's forward
-        if self.with_landmarks:
-            value = value + self._lmk_rows.view(())
+        if self.landmark is not None:
+            value = value + self.landmark.rows.view(())
         return value
 
     def _loss_rows(self, img):
@@ -469,7 +277,7 @@ class LatentInverter:
         from .op.lpips_layer import fit_loss_rows, mse_rows
 
         layers = self.perceptual.layer_distances(self.target_feats, img)
-        prior = self.fit_shape and self.shape_reg != 0.0 and getattr(self, "_reg", None) is not None
+        prior = self.fit_shape and self.shape_reg != 0.0 and self._reg is not None
         if prior and self._prior_rows is not None:
             self._rows, total = fit_loss_rows(layers, mse_rows(img, self.target), self.pixel_weight, reg=self._reg,
                                               prior_rows=self._prior_rows)
@@ -478,9 +286,9 @@ class LatentInverter:
                                               coeff=self.coeff if prior else None,
                                               sigma=self._prior_sigma if prior else None, shape_reg=self.shape_reg,
                                               reg=self._reg if prior else None)
-        if self.with_landmarks:
-            self._rows = self._rows + self._lmk_rows.detach()
-            total = total + self._lmk_rows.sum()
+        if self.landmark is not None:
+            self._rows = self._rows + self.landmark.rows.detach()
+            total = total + self.landmark.rows.sum()
         return total
 
     def _iteration(self):
@@ -540,21 +348,21 @@ class LatentInverter:
         if tuple(target.shape) != tuple(self.target.shape):
             raise ValueError("LatentInverter.reset: target %s, the inverter fits %s"
                              % (tuple(target.shape), tuple(self.target.shape)))
-        if self.with_mask:
-            self._set_mask(mask)
+        if self.region is not None:
+            self.region.set(mask)
         self.target.copy_(target)
         for buf, f in zip(self.target_feats, self._features_of_target()):
             buf.copy_(f)
         self.w.copy_(self._mean_w.unsqueeze(1).expand_as(self.w))
-        if self.with_landmarks:
-            self._set_landmarks(landmarks, landmark_conf)
-            self.pose.copy_(self._pose_start)
+        if self.landmark is not None:
+            self.landmark.set(landmarks, landmark_conf)
+            self.pose.copy_(self.landmark.pose_start)
         else:
             self.pose.zero_()
         if self.coeff is not None:
             self.coeff.zero_()
-        if self.camera is not None:
-            self.camera.copy_(self._camera_start)
+        if self.cam is not None:
+            self.cam.reset()
         if self._adams is not None:
             for _, adam in self._adams:
                 for t in (adam.m, adam.v, adam.step_t, adam.flat_g):

@@ -387,22 +387,22 @@ def landmark_outputs(inv, index, conf, listed, shape):
     from .op.landmark import landmark_points, project
 
     size = tuple(int(x) for x in inv.target.shape[-2:])
+    term = inv.landmark                                  # fit_parts.LandmarkTerm: the embedding and the pose-aware settings
     # of the mesh that is written (the saved pose and coeff): inv.landmarks_fit is the last forward's, one Adam step behind
     with torch.no_grad():
         v = inv.fitted_mesh()[0][index:index + 1]
-        p = project(landmark_points(v, inv._lmk_idx, inv._lmk_bary), size)[0]
+        p = project(landmark_points(v, term.index, term.bary), size)[0]
     fit = align.scale_landmarks(p.cpu().numpy().astype(np.float64), size, shape)
     more = {}
-    if getattr(inv, "_lmk_dynamic", False):
+    if term.dynamic:
         # the pose-aware term: the jaw landmarks are those the contour lines select on the written mesh
         from .op.landmark import landmark_dynamic_composite
 
         with torch.no_grad():
             n = inv.fitted_mesh()[1][index:index + 1]
             zero = torch.zeros(1, p.shape[0], device=v.device)
-            _, pd, sel, gate = landmark_dynamic_composite(v, inv._lmk_idx, inv._lmk_bary, torch.zeros_like(p)[None], zero,
-                                                          size, normals=n, lines=inv._lmk_lines, axis=inv._lmk_axis,
-                                                          vis=inv._lmk_vis)
+            _, pd, sel, gate = landmark_dynamic_composite(v, term.index, term.bary, torch.zeros_like(p)[None], zero,
+                                                          size, normals=n, lines=term.lines, axis=term.axis, vis=term.vis)
         fit = align.scale_landmarks(pd[0].cpu().numpy().astype(np.float64), size, shape)
         more = {"contour_vertices": sel[0].cpu().numpy().astype(np.int64),
                 "lmk_visibility": gate[0].cpu().numpy().astype(np.float64)}
@@ -531,29 +531,30 @@ class TextureGuide:
 
 
 def reconstruct(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr=0.01, shape_reg=0.0,
-                n_mean_latent=4096, **landmark_args):
+                n_mean_latent=4096, **inverter_args):
     """Fits one image; returns the inverter (w, pose, coeff, image, fitted_mesh()) and the loss history (host).
-    landmark_args: LatentInverter's landmark and mask keywords."""
+    inverter_args: LatentInverter's further keywords (landmarks, mask, camera)."""
     inv = inversion.LatentInverter(g, percept, target, None, lr=lr, pose_lr=pose_lr, n_mean_latent=n_mean_latent,
-                                   face=face, fit_shape=True, coeff_lr=coeff_lr, shape_reg=shape_reg, **landmark_args)
+                                   face=face, fit_shape=True, coeff_lr=coeff_lr, shape_reg=shape_reg, **inverter_args)
     hist = inv.run(steps)
     return inv, hist.cpu().numpy()
 
 
 def reconstruct_batch(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr=0.01, shape_reg=0.0,
-                      n_mean_latent=4096, inv=None, shared_identity=None, **landmark_args):
+                      n_mean_latent=4096, inv=None, shared_identity=None, **inverter_args):
     """Fits the B images of target [B, 3, H, W] together; `inv` (an inverter of the same batch from an earlier call) is
-    re-targeted instead of built anew.  Returns the inverter and the loss history [steps, B] (host).  landmark_args:
-    LatentInverter's landmark and mask keywords.  shared_identity=K: the images are views of one subject and share the
-    leading K coefficients (a re-targeted inverter keeps the K it was built with)."""
+    re-targeted instead of built anew.  Returns the inverter and the loss history [steps, B] (host).  inverter_args:
+    LatentInverter's further keywords (landmarks, mask, camera; a re-targeted inverter takes landmarks, landmark_conf and
+    mask from them and keeps the rest as it was built).  shared_identity=K: the images are views of one subject and share
+    the leading K coefficients (a re-targeted inverter keeps the K it was built with)."""
     if inv is None:
         more = {} if shared_identity is None else {"shared_identity": shared_identity}
         inv = inversion.LatentInverter(g, percept, target, None, lr=lr, pose_lr=pose_lr, n_mean_latent=n_mean_latent,
                                        face=face, fit_shape=True, coeff_lr=coeff_lr, shape_reg=shape_reg, **more,
-                                       **landmark_args)
-    elif landmark_args:
-        inv.reset(target, landmark_args.get("landmarks"), landmark_args.get("landmark_conf"),
-                  **({"mask": landmark_args["mask"]} if landmark_args.get("mask") is not None else {}))
+                                       **inverter_args)
+    elif inverter_args:
+        inv.reset(target, inverter_args.get("landmarks"), inverter_args.get("landmark_conf"),
+                  **({"mask": inverter_args["mask"]} if inverter_args.get("mask") is not None else {}))
     else:
         inv.reset(target)
     hist = inv.run(steps)

@@ -290,7 +290,7 @@ def test_inverter_starts_at_the_pose_of_the_landmarks():
     off = _inverter(problem, landmarks=lmk, landmark_conf=np.zeros((1, 10)), landmark_embedding=emb)
     assert float(off.pose.detach().abs().max()) == 0.0
     off.run(1)
-    assert float(off._lmk_rows.detach().abs().max()) == 0.0
+    assert float(off.landmark.rows.detach().abs().max()) == 0.0
 
 
 def test_inverter_refuses_landmarks_it_cannot_use():

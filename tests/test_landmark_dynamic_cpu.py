@@ -458,7 +458,7 @@ def test_inverter_without_the_new_arguments_is_bit_identical_and_empty_lines_cha
             if "landmark_axis" in extra and extra["landmark_axis"]:
                 assert inv.contour_fit.shape == (1, 0) and bool((inv.landmark_visibility == 1).all())
             else:
-                assert inv.contour_fit is None and inv.landmark_visibility is None and not inv._lmk_dynamic
+                assert inv.contour_fit is None and inv.landmark_visibility is None and not inv.landmark.dynamic
         # and without landmarks the new keywords are not looked at, like the old ones
         plain = [_inverter(problem, **kw) for kw in ({}, {"landmark_lines": empty, "landmark_vis": (0.0, 0.2)})]
         hist = [inv.run(4) for inv in plain]

@@ -408,9 +408,9 @@ def test_mask_mesh_gates_the_region_by_the_rendered_normal_map():
     problem = tiny_problem()
     with single_thread():
         inv = _inverter(problem, mask_mesh=True)
-        assert inv.with_mask and float(inv._mask.min()) == 1.0
+        assert inv.with_mask and float(inv.region.mask.min()) == 1.0
         inv.run(1)
-        n = inv._normal_map
+        n = inv.region.normal_map
         assert tuple(n.shape) == (1, 3, 16, 16)
         want = ((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1] + n[:, 2] * n[:, 2]) > 1e-3).float().unsqueeze(1)
         assert torch.equal(inv.mask_fit, want) and 0 < float(want.sum()) < want.numel()
@@ -445,18 +445,18 @@ def test_reset_with_a_mask_equals_a_fresh_inverter_and_masks_are_checked():
         assert torch.equal(inv.mask_fit, m_b)
         # reset without a mask: all ones
         inv.reset(targets)
-        assert float(inv._mask.min()) == 1.0
+        assert float(inv.region.mask.min()) == 1.0
     one = _inverter((g, mesh, face, noise, target), mask=torch.zeros(16, 16))
-    assert one._mask.shape == (1, 1, 16, 16) and float(one._mask.max()) == 0.0
+    assert one.region.mask.shape == (1, 1, 16, 16) and float(one.region.mask.max()) == 0.0
     # a refused mask leaves the inverter as it was
     for bad in (torch.full((1, 1, 16, 16), 1.5), torch.full((1, 1, 16, 16), float("nan")), torch.ones(1, 1, 8, 8),
                 -torch.ones(16, 16), torch.ones(2, 1, 16, 16)):
         with pytest.raises(ValueError):
             one.reset(target, mask=bad)
-        assert float(one._mask.max()) == 0.0
+        assert float(one.region.mask.max()) == 0.0
     for shape in ((16, 16), (1, 16, 16), (1, 1, 16, 16)):
         one.reset(target, mask=torch.full(shape, 0.5))
-        assert float(one._mask.min()) == 0.5
+        assert float(one.region.mask.min()) == 0.5
     # an all-zero region: loss 0 and gradient 0, no division anywhere
     one.reset(target, mask=torch.zeros(16, 16))
     value = one.loss(one.render())
