@@ -659,8 +659,13 @@ int sr_conv2d_wgrad_mfma(float* dwt, const float* x, const float* gy, const floa
 #define SR_WGRAD_PATH_BF16_1X1 3 /* 1x1 s1 p0: split-bf16 (SR_CONV_SPLIT_BF16) */
 #define SR_WGRAD_PATH_BF16_S2 4  /* 3x3 s2 p0, either direction: split-bf16 (SR_CONV_SPLIT_BF16) */
 #define SR_WGRAD_PATH_S2_DMA 5   /* 3x3 s2 p0, either direction: k_wgrad_s2_dma */
+#define SR_WGRAD_PATH_S2_WINO 6  /* 3x3 s2 p0, either direction: polyphase 25-product k_wgrad_s2p + k_wgrad_s2p_finish */
 int sr_conv2d_wgrad_path(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW, int ksize,
                          int stride, int pad, int transposed, const float* x, const float* gy);
+/* Scratch floats the path sr_conv2d_wgrad_path returns writes — never more than sr_conv2d_wgrad_scratch_floats of the
+ * same shape.  -1 for an invalid geometry. */
+int64_t sr_conv2d_wgrad_path_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW,
+                                    int ksize, int stride, int pad, int transposed, const float* x, const float* gy);
 
 /* ---- signalling out of a replayed hipGraph (overlapped gradient all-reduce) -----------------------------------
  * The reference overlaps the gradient all-reduce with the backward through torch DDP's bucket hooks

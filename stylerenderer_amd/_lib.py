@@ -118,6 +118,7 @@ SIGNATURES = {
     "sr_conv2d_path": (_i, [_l] * 7 + [_i] * 4 + [_p, _p, _p, _l, _i]),
     "sr_conv2d_path_floats": (_l, [_l] * 7 + [_i] * 4 + [_p, _p, _p, _l, _i]),
     "sr_conv2d_wgrad_path": (_i, [_l] * 7 + [_i] * 4 + [_p, _p]),
+    "sr_conv2d_wgrad_path_floats": (_l, [_l] * 7 + [_i] * 4 + [_p, _p]),
     "sr_conv2d_mfma_ex": (_i, [_p] * 6 + [_l] * 8 + [_i] * 5 + [_p, _p]),
     "sr_conv1x1_add_supported": (_i, [_l] * 5 + [_p] * 4),
     "sr_conv1x1_add": (_i, [_p] * 5 + [_l] * 5 + [_p]),
@@ -175,7 +176,7 @@ SIGNATURES = {
  CONV_PATH_CONVT_BF16, CONV_PATH_CONVT_FUSED_KS, CONV_PATH_CONVT_FUSED) = range(9)
 CONV_PATH_STRIPS = 0x100
 (WGRAD_PATH_DIRECT, WGRAD_PATH_SMALL3, WGRAD_PATH_WINO, WGRAD_PATH_BF16_1X1, WGRAD_PATH_BF16_S2,
- WGRAD_PATH_S2_DMA) = range(6)
+ WGRAD_PATH_S2_DMA, WGRAD_PATH_S2_WINO) = range(7)
 
 _lib = None
 

@@ -53,6 +53,7 @@ SOURCES = [
     ("conv_wgrad_wino.hip", []),
     ("conv_wgrad_mfma.hip", []),
     ("conv_wgrad_bf16x3.hip", []),
+    ("conv_wgrad_s2_wino.hip", []),
     ("conv_s2_bf16x3.hip", []),
     ("conv_s2_wino.hip", []),
     ("conv_generic.hip", []),

@@ -29,6 +29,7 @@
 // operands after the ds_read (never onto freshly loaded registers: no wait on memory in the loop).
 #include "common.h"
 #include "conv_wgrad_bf16x3.h"
+#include "conv_wgrad_s2_wino.h"
 #include "conv_wino.h"
 
 #include <algorithm>
@@ -541,6 +542,12 @@ Plan make_plan(int is, int B, int CU, int CV, int GH, int GW) {
     return pl;
 }
 
+// k_wgrad_s2p takes an eligible stride-2 call from this much direct work on, 18 B CU CV GH GW: measured (DESIGN.md 4.2h,
+// profiles/s2wgrad_wino_notes.md) a tie at 4.83e9 and 5 - 8 % ahead at 7.25e9; below, its longer prologue per slice loses.
+// Must stay above 3.63e9: tests pin k_wgrad_s2_dma's results bit for bit up to (3, 64 -> 256, 129^2) = 3.62e9.
+constexpr double SR_WGRAD_S2_WINO_MIN_WORK = 6.0e9;
+static_assert(SR_WGRAD_S2_WINO_MIN_WORK > 3.63e9, "k_wgrad_s2_dma keeps the shapes the tests pin bit for bit");
+
 constexpr int NG_OF(int pb) { return pb == 1 ? 2 : 1; }     // groups per workgroup by patch type
 
 template <int IS, int TY, int TX, int PW, int PH, int PB, int UT, int VT>
@@ -686,6 +693,7 @@ int wgrad_small_blocks(int64_t B, int64_t IH, int64_t IW) {
 struct WgradPlan {
     int path = SR_WGRAD_PATH_INVALID;
     int64_t sized = -1;                      // sr_conv2d_wgrad_scratch_floats of the call
+    int64_t needs = -1;                      // sr_conv2d_wgrad_path_floats: what the chosen path writes, <= sized
     int GH, GW, UH, UW, CU, CV, d0;          // geometry(): U = the windowed operand, V = the other one
     Plan tiles;                              // tiling of k_wgrad_mfma / k_wgrad_s2_dma
 };
@@ -712,17 +720,17 @@ WgradPlan make_wgrad_plan(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t I
     if (!geometry(B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, w)) return w;
     if (wgrad_small_ok(C, N, ksize, stride, pad, transposed)) {     // takes every call of its shape: nothing else in reach
         w.path = SR_WGRAD_PATH_SMALL3;
-        w.sized = (int64_t)wgrad_small_blocks(B, IH, IW) * WS_ACC + 4;
+        w.sized = w.needs = (int64_t)wgrad_small_blocks(B, IH, IW) * WS_ACC + 4;
         return w;
     }
     const Plan& pl = w.tiles = make_plan(stride, (int)B, w.CU, w.CV, w.GH, w.GW);
     w.path = SR_WGRAD_PATH_DIRECT;
-    w.sized = (int64_t)pl.ks * NG_OF(pl.pb) * ksize * ksize * (pl.tiles_u * pl.ut) * (int64_t)(pl.tiles_v * pl.vt) + 4;
+    w.sized = w.needs = (int64_t)pl.ks * NG_OF(pl.pb) * ksize * ksize * (pl.tiles_u * pl.ut) * (int64_t)(pl.tiles_v * pl.vt) + 4;
     // The other paths in priority order.  Each `if` says whether the SHAPE can get there (then the scratch is sized for
     // it), `take` whether this call does.
     auto candidate = [&](int path, bool take, int64_t floats) {
         w.sized = std::max(w.sized, floats);
-        if (take && w.path == SR_WGRAD_PATH_DIRECT) w.path = path;
+        if (take && w.path == SR_WGRAD_PATH_DIRECT) { w.path = path; w.needs = floats; }
     };
     if (!transposed && ksize == 3 && stride == 1 && pad == 1 && sr_winograd_enabled() &&
         sr_wgrad_wino_eligible(B, C, N, IH, IW, nullptr, nullptr))
@@ -736,6 +744,16 @@ WgradPlan make_wgrad_plan(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t I
         candidate(SR_WGRAD_PATH_BF16_S2,
                   pad == 0 && sr_wgrad_s2_bf16x3_eligible(B, w.CU, w.CV, w.UH, w.UW, w.GH, w.GW, transposed ? x : gy),
                   sr_wgrad_s2_bf16x3_scratch_floats(B, w.CU, w.CV, w.GH, w.GW));
+    // The polyphase 25-product kernel walks the direct plan's K slices and writes ONE slab of 16 positions per slice
+    // where the direct kernels write two of 9: ks * 16 <= ks * 18, so it adds nothing to `sized` (stated, and checked
+    // here: callers size their buffers from the direct plan).  SR_WGRAD_S2_WINO: 0 never, force ignores the work bar.
+    if (ksize == 3 && stride == 2 && sr_wgrad_s2_wino_eligible(B, w.CU, w.CV, w.UH, w.UW, w.GH, w.GW, w.d0)) {
+        const int sw = sr_env_char("SR_WGRAD_S2_WINO");
+        const double work = 18.0 * (double)B * w.CU * w.CV * w.GH * w.GW;
+        const int64_t floats = sr_wgrad_s2_wino_scratch_floats(pl.ks, w.CU, w.CV);
+        if (floats > w.sized) std::abort();     // one 16-position slab per slice of the direct plan always fits
+        candidate(SR_WGRAD_PATH_S2_WINO, sw != '0' && (sw == 'f' || work >= SR_WGRAD_S2_WINO_MIN_WORK), floats);
+    }
     if (w.path == SR_WGRAD_PATH_DIRECT && ksize == 3 && stride == 2 &&
         s2_dma_ok(pl, B, w.CU, w.CV, w.UH, w.UW, w.GH, w.GW, w.d0))
         w.path = SR_WGRAD_PATH_S2_DMA;
@@ -763,6 +781,12 @@ extern "C" int64_t sr_conv2d_wgrad_scratch_floats(int64_t B, int64_t C, int64_t 
                                                   int64_t IW, int64_t OH, int64_t OW, int ksize,
                                                   int stride, int pad, int transposed) {
     return make_wgrad_plan(B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, nullptr, nullptr).sized;
+}
+
+extern "C" int64_t sr_conv2d_wgrad_path_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH,
+                                               int64_t OW, int ksize, int stride, int pad, int transposed, const float* x,
+                                               const float* gy) {
+    return make_wgrad_plan(B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, x, gy).needs;
 }
 
 extern "C" int sr_conv2d_wgrad_path(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW,
@@ -801,6 +825,12 @@ extern "C" int sr_conv2d_wgrad_mfma(float* dwt, const float* x, const float* gy,
     case SR_WGRAD_PATH_BF16_S2:
         rc = sr_wgrad_s2_bf16x3_launch(U, V, uscale, vscale, scratch, B, w.CU, w.CV, w.UH, w.UW, w.GH, w.GW, &ks, &UP, &VP, st);
         return rc != SR_OK ? rc : reduce_slices(dwt, scratch, w, ks, 9, UP, VP, transposed, st);
+    case SR_WGRAD_PATH_S2_WINO:
+        rc = sr_wgrad_s2_wino_launch(U, V, uscale, vscale, scratch, B, w.CU, w.CV, w.UH, w.UW, w.GH, w.GW, w.tiles.ks,
+                                     w.tiles.pps, st);
+        return rc != SR_OK ? rc
+                           : sr_wgrad_s2_wino_finish(dwt, scratch, w.tiles.ks, w.CU, w.CV, (int64_t)w.CU * w.CV,
+                                                     transposed ? 1 : w.CV, transposed ? w.CU : 1, st);
     }
     const Plan& pl = w.tiles;
     WgradParams p;
