@@ -254,6 +254,7 @@ def bench_flame(size, steps, rounds, reps):
 def bench_facewarehouse(size, batches, steps, rounds, reps):
     from stylerenderer_amd import face_model
     from stylerenderer_amd.op import blend
+    from stylerenderer_amd.op._dispatch import native
 
     invs, _, _ = make_inverters(size)
     base = invs.pop("pose_only")
@@ -298,7 +299,7 @@ def bench_facewarehouse(size, batches, steps, rounds, reps):
         c = torch.from_numpy(synth.det_normal((b, ds + de), 8)).to(DEV)
         pose = torch.zeros(b, 7, device=DEV)
         lin = torch.eye(3, device=DEV).repeat(b, 1, 1).contiguous()
-        xs, xe, prior, z = blend._head(L, c, fm.beta.detach(), 1e-3, ds, de, st)
+        xs, xe, prior, z = blend._head(native(c), c, fm.beta.detach(), 1e-3, ds, de)
         v, vs, gvs = (torch.randn(b, nv, 3, device=DEV) for _ in range(3))
         reg = torch.empty((), device=DEV)
         gz = torch.empty(b, (ds + 1) * (de + 1), device=DEV)

@@ -1,6 +1,7 @@
 """Shared helpers of the operator wrappers."""
 import collections
 import contextlib
+import functools
 
 import numpy as np
 import torch
@@ -22,20 +23,34 @@ def require_f32(t, name):
         raise RuntimeError("%s: expected a float32 tensor, got %s" % (name, t.dtype))
 
 
-@contextlib.contextmanager
-def on_device_of(t):
-    """Makes the tensor's GPU current for the duration of a native launch (one process per GPU
-    normally makes this a no-op)."""
-    idx = t.device.index
-    if idx is None or idx == torch.cuda.current_device():
-        yield
+class native:
+    """The one way an operator wrapper calls a stream-taking function of the HIP library:
+    `native(like).sr_name(*args)` makes the device of `like` current, passes every tensor argument as its device
+    pointer (`_lib.ptr`: None and zero-size tensors are NULL) and everything else — ints, floats, raw addresses —
+    untouched, appends the current stream of that device as the last argument and raises through `_lib.check`
+    under the name that was called."""
+    __slots__ = ("device",)
+
+    def __init__(self, like):
+        self.device = like.device
+
+    def __getattr__(self, name):
+        return functools.partial(_launch, getattr(_lib.lib(), name), name, self.device)
+
+
+def _launch(fn, name, device, *args):
+    # on every launch of every operator: `_lib.ptr` is written out (a Python call per tensor argument is measurable in
+    # the eager inversion step), and the device is normally current already — no context manager on that path
+    args = [(a.data_ptr() if a.numel() else None) if isinstance(a, torch.Tensor) else a for a in args]
+    args.append(_lib.current_stream(device))
+    index = device.index
+    if index is None or index == torch.cuda.current_device():
+        rc = fn(*args)
     else:
-        with torch.cuda.device(idx):
-            yield
-
-
-def stream_of(t):
-    return _lib.current_stream(t.device)
+        with torch.cuda.device(index):
+            rc = fn(*args)
+    if rc:
+        _lib.check(rc, name)
 
 
 def strict_native():

@@ -3,8 +3,8 @@ handling and native / composite dispatch all three repeat, the composite pose, a
 the morphable and the blendshape node have in common — everything around the one model-specific contraction each way."""
 import torch
 
-from .. import _lib, utils_3d
-from ._dispatch import on_device_of, stream_of, strict_native
+from .. import utils_3d
+from ._dispatch import native, strict_native
 
 EPS = 1e-8
 
@@ -45,7 +45,7 @@ def pose_composite(vs, pose, tri):
 
 def forward(c, p, tri, nv, model_fwd):
     """The forward of a node whose model is a contraction with the pose as its epilogue: pose matrices, then
-    `model_fwd(L, st, v, vs, reg, lin)` (its launches write the posed vertices v, the unposed vs and the prior reg), the
+    `model_fwd(run, v, vs, reg, lin)` (its launches write the posed vertices v, the unposed vs and the prior reg), the
     vertex-normal gather of the unposed shape and its rotation.  Returns (v, n, reg, mesh, what model_fwd returned): mesh
     is the tensors `backward` takes, to be saved by the node."""
     b = c.shape[0]
@@ -60,41 +60,32 @@ def forward(c, p, tri, nv, model_fwd):
     n = torch.empty_like(vs)
     normc = torch.empty((b, nv), dtype=f32, device=dev)
     reg = torch.empty((), dtype=f32, device=dev)
-    L = _lib.lib()
-    st = stream_of(c)
-    ptr = _lib.ptr
-    with on_device_of(c):
-        _lib.check(L.sr_pose_batch_fwd(ptr(lin), ptr(rot), ptr(p), b, st), "sr_pose_batch_fwd")
-        kept = model_fwd(L, st, v, vs, reg, lin)
-        _lib.check(L.sr_vertex_normals_f32(ptr(ns), ptr(normc), ptr(vs), ptr(tric), ptr(off), ptr(adj), b, nv,
-                                           tric.size(0), EPS, st), "sr_vertex_normals_f32")
-        _lib.check(L.sr_affine3_fwd(ptr(n), ptr(ns), ptr(rot), None, b, nv, nv * 3, st), "sr_affine3_fwd")
+    run = native(c)
+    run.sr_pose_batch_fwd(lin, rot, p, b)
+    kept = model_fwd(run, v, vs, reg, lin)
+    run.sr_vertex_normals_f32(ns, normc, vs, tric, off, adj, b, nv, tric.size(0), EPS)
+    run.sr_affine3_fwd(n, ns, rot, None, b, nv, nv * 3)
     return v, n, reg, (p, tric, off, adj, lin, rot, vs, ns, normc), kept
 
 
 def backward(needs, mesh, gv, gn, model_bwd):
     """(gcoeff, gpose) of that node, each None unless `needs` (ctx.needs_input_grad) asks for it: the vertex-normal
-    adjoint gather into gvs and `model_bwd(L, st, gvs)` -> gcoeff; the two pose sums and the pose gradient."""
+    adjoint gather into gvs and `model_bwd(run, gvs)` -> gcoeff; the two pose sums and the pose gradient."""
     p, tric, off, adj, lin, rot, vs, ns, normc = mesh
     b, nv = vs.shape[:2]
     gv, gn = gv.contiguous(), gn.contiguous()
-    L = _lib.lib()
-    st = stream_of(p)
-    ptr = _lib.ptr
+    run = native(p)
     gcoeff = gpose = None
-    with on_device_of(p):
-        if needs[0]:
-            gvs = torch.empty_like(vs)
-            _lib.check(L.sr_vertex_normals_bwd_f32(ptr(gvs), ptr(gv), ptr(gn), ptr(lin), ptr(rot), ptr(vs), ptr(ns),
-                                                   ptr(normc), ptr(tric), ptr(off), ptr(adj), b, nv, tric.size(0),
-                                                   EPS, st), "sr_vertex_normals_bwd_f32")
-            gcoeff = model_bwd(L, st, gvs)
-        if needs[1]:
-            glin = torch.empty_like(lin)
-            grot = torch.empty_like(rot)
-            gt = torch.empty((b, 3), dtype=p.dtype, device=p.device)
-            gpose = torch.empty_like(p)
-            _lib.check(L.sr_affine3_bwd(ptr(glin), ptr(gt), ptr(vs), ptr(gv), b, nv, nv * 3, st), "sr_affine3_bwd")
-            _lib.check(L.sr_affine3_bwd(ptr(grot), None, ptr(ns), ptr(gn), b, nv, nv * 3, st), "sr_affine3_bwd")
-            _lib.check(L.sr_morph_pose_bwd(ptr(gpose), ptr(glin), ptr(grot), ptr(gt), ptr(p), b, st), "sr_morph_pose_bwd")
+    if needs[0]:
+        gvs = torch.empty_like(vs)
+        run.sr_vertex_normals_bwd_f32(gvs, gv, gn, lin, rot, vs, ns, normc, tric, off, adj, b, nv, tric.size(0), EPS)
+        gcoeff = model_bwd(run, gvs)
+    if needs[1]:
+        glin = torch.empty_like(lin)
+        grot = torch.empty_like(rot)
+        gt = torch.empty((b, 3), dtype=p.dtype, device=p.device)
+        gpose = torch.empty_like(p)
+        run.sr_affine3_bwd(glin, gt, vs, gv, b, nv, nv * 3)
+        run.sr_affine3_bwd(grot, None, ns, gn, b, nv, nv * 3)
+        run.sr_morph_pose_bwd(gpose, glin, grot, gt, p, b)
     return gcoeff, gpose

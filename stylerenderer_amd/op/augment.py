@@ -17,8 +17,7 @@ import ctypes
 import torch
 from torch.autograd import Function
 
-from .. import _lib
-from ._dispatch import on_device_of, require_f32, stream_of
+from ._dispatch import native, require_f32
 
 NDRAW = 11
 REC = 28
@@ -51,10 +50,7 @@ def params(raw, h, w, p, pose_p=POSE_P, color_p=COLOR_P):
         p_dev = p.reshape(()) if p.dtype == torch.float64 else p.reshape(()).to(torch.float64)
     else:
         p_host = float(p)
-    with on_device_of(raw):
-        rc = _lib.lib().sr_ada_params(_lib.ptr(rec), _lib.ptr(raw), raw.shape[0], _sigmas(pose_p, 6), _sigmas(color_p, 5),
-                                      _lib.ptr(p_dev), p_host, h, w, stream_of(raw))
-    _lib.check(rc, "sr_ada_params")
+    native(raw).sr_ada_params(rec, raw, raw.shape[0], _sigmas(pose_p, 6), _sigmas(color_p, 5), p_dev, p_host, h, w)
     return rec
 
 
@@ -62,9 +58,7 @@ def _launch_apply(x, rec, with_bias):
     x = x.contiguous()
     out = torch.empty_like(x)
     b, _, h, w = x.shape
-    with on_device_of(x):
-        rc = _lib.lib().sr_ada_apply(_lib.ptr(out), _lib.ptr(x), _lib.ptr(rec), b, h, w, with_bias, stream_of(x))
-    _lib.check(rc, "sr_ada_apply")
+    native(x).sr_ada_apply(out, x, rec, b, h, w, with_bias)
     return out
 
 
@@ -72,9 +66,7 @@ def _launch_grad(g, rec):
     g = g.contiguous()
     out = torch.empty_like(g)
     b, _, h, w = g.shape
-    with on_device_of(g):
-        rc = _lib.lib().sr_ada_apply_grad(_lib.ptr(out), _lib.ptr(g), _lib.ptr(rec), b, h, w, stream_of(g))
-    _lib.check(rc, "sr_ada_apply_grad")
+    native(g).sr_ada_apply_grad(out, g, rec, b, h, w)
     return out
 
 
@@ -158,10 +150,7 @@ def update(state, stat, target, length):
     if not state.is_cuda:
         return update_composite(state, stat, float(target), float(length))
     st = stat if stat.dtype == torch.float32 else stat.to(torch.float32)
-    with on_device_of(state):
-        rc = _lib.lib().sr_ada_update(_lib.ptr(state), _lib.ptr(st.contiguous()), float(target), float(length),
-                                      stream_of(state))
-    _lib.check(rc, "sr_ada_update")
+    native(state).sr_ada_update(state, st.contiguous(), float(target), float(length))
     return state
 
 

@@ -24,8 +24,7 @@ import ctypes
 import torch
 from torch.autograd import Function
 
-from .. import _lib
-from ._dispatch import mark_inputs, on_device_of, stream_of, wanted
+from ._dispatch import mark_inputs, native, wanted
 
 
 def _arr(ctype, vals):
@@ -80,13 +79,10 @@ def _mod_nt(meta, x, ws, bs):
     ws = [_dense(w) for w in ws]
     bs = [_dense(t) for t in bs] if bs else None
     base, xp = out.data_ptr(), x.data_ptr()
-    with on_device_of(x):
-        rc = _lib.lib().sr_bank_nt(
-            len(rows), _pa([base + 4 * o for o in offs]), _pa([xp + 4 * k * rr for rr in rows]),
-            _pa([w.data_ptr() for w in ws]), _pa([t.data_ptr() for t in bs]) if bs else None,
-            _la([r * k] * len(rows)), _la(widths), _la([k] * len(rows)), _la(widths), b, float(alpha), float(bscale),
-            stream_of(x))
-    _lib.check(rc, "sr_bank_nt")
+    native(x).sr_bank_nt(len(rows), _pa([base + 4 * o for o in offs]), _pa([xp + 4 * k * rr for rr in rows]),
+                         _pa([w.data_ptr() for w in ws]), _pa([t.data_ptr() for t in bs]) if bs else None,
+                         _la([r * k] * len(rows)), _la(widths), _la([k] * len(rows)), _la(widths), b, float(alpha),
+                         float(bscale))
     return out
 
 
@@ -101,13 +97,10 @@ def _mod_nn(meta, g, ws, shape):
     gp, op = g.data_ptr(), out.data_ptr()
     terms = [[p for p, rr in enumerate(rows) if rr == row] for row in used]
     flat_terms = [p for ts in terms for p in ts]
-    with on_device_of(g):
-        rc = _lib.lib().sr_bank_nn(
-            len(used), _pa([op + 4 * k * row for row in used]), _la([r * k] * len(used)), _la([k] * len(used)),
-            _arr(ctypes.c_int, [len(ts) for ts in terms]), _pa([gp + 4 * offs[p] for p in flat_terms]),
-            _pa([ws[p].data_ptr() for p in flat_terms]), _la([widths[p] for p in flat_terms]),
-            _la([widths[p] for p in flat_terms]), b, float(alpha), stream_of(g))
-    _lib.check(rc, "sr_bank_nn")
+    native(g).sr_bank_nn(len(used), _pa([op + 4 * k * row for row in used]), _la([r * k] * len(used)),
+                         _la([k] * len(used)), _arr(ctypes.c_int, [len(ts) for ts in terms]),
+                         _pa([gp + 4 * offs[p] for p in flat_terms]), _pa([ws[p].data_ptr() for p in flat_terms]),
+                         _la([widths[p] for p in flat_terms]), _la([widths[p] for p in flat_terms]), b, float(alpha))
     return out
 
 
@@ -119,12 +112,9 @@ def _mod_tn(meta, g, x, want_bias):
     gws = _flat_out(None, [(n, k) for n in widths], g.device, g.dtype)
     gbs = _flat_out(None, [(1, n) for n in widths], g.device, g.dtype) if want_bias else None
     gp, xp = g.data_ptr(), x.data_ptr()
-    with on_device_of(g):
-        rc = _lib.lib().sr_bank_tn(
-            len(rows), _pa([t.data_ptr() for t in gws]), _pa([t.data_ptr() for t in gbs]) if gbs else None,
-            _pa([gp + 4 * o for o in offs]), _pa([xp + 4 * k * rr for rr in rows]), _la(widths), _la([r * k] * len(rows)),
-            _la(widths), _la([k] * len(rows)), b, float(alpha), float(bscale), stream_of(g))
-    _lib.check(rc, "sr_bank_tn")
+    native(g).sr_bank_tn(len(rows), _pa([t.data_ptr() for t in gws]), _pa([t.data_ptr() for t in gbs]) if gbs else None,
+                         _pa([gp + 4 * o for o in offs]), _pa([xp + 4 * k * rr for rr in rows]), _la(widths),
+                         _la([r * k] * len(rows)), _la(widths), _la([k] * len(rows)), b, float(alpha), float(bscale))
     return gws, ([t.view(-1) for t in gbs] if gbs else None)
 
 
@@ -236,12 +226,10 @@ def _dem_nn(meta, a, ms):
     ms = [_dense(m) for m in ms]
     ap, op = a.data_ptr(), out.data_ptr()
     n = len(dims)
-    with on_device_of(a):
-        rc = _lib.lib().sr_bank_nn(
-            n, _pa([op + 4 * o for o in q_offs]), _la([j for _, j in dims]), _la([j for _, j in dims]),
-            _arr(ctypes.c_int, [1] * n), _pa([ap + 4 * o for o in a_offs]), _pa([m.data_ptr() for m in ms]),
-            _la([i for i, _ in dims]), _la([i for i, _ in dims]), batch, 1.0, stream_of(a))
-    _lib.check(rc, "sr_bank_nn")
+    native(a).sr_bank_nn(n, _pa([op + 4 * o for o in q_offs]), _la([j for _, j in dims]), _la([j for _, j in dims]),
+                         _arr(ctypes.c_int, [1] * n), _pa([ap + 4 * o for o in a_offs]),
+                         _pa([m.data_ptr() for m in ms]), _la([i for i, _ in dims]), _la([i for i, _ in dims]), batch,
+                         1.0)
     return out
 
 
@@ -254,12 +242,9 @@ def _dem_nt(meta, g, ms):
     ms = [_dense(m) for m in ms]
     gp, op = g.data_ptr(), out.data_ptr()
     n = len(dims)
-    with on_device_of(g):
-        rc = _lib.lib().sr_bank_nt(
-            n, _pa([op + 4 * o for o in a_offs]), _pa([gp + 4 * o for o in q_offs]), _pa([m.data_ptr() for m in ms]), None,
-            _la([j for _, j in dims]), _la([i for i, _ in dims]), _la([j for _, j in dims]), _la([i for i, _ in dims]),
-            batch, 1.0, 0.0, stream_of(g))
-    _lib.check(rc, "sr_bank_nt")
+    native(g).sr_bank_nt(n, _pa([op + 4 * o for o in a_offs]), _pa([gp + 4 * o for o in q_offs]),
+                         _pa([m.data_ptr() for m in ms]), None, _la([j for _, j in dims]), _la([i for i, _ in dims]),
+                         _la([j for _, j in dims]), _la([i for i, _ in dims]), batch, 1.0, 0.0)
     return out
 
 
@@ -270,12 +255,9 @@ def _dem_tn(meta, a, g):
     outs = _flat_out(None, list(dims), a.device, a.dtype)
     ap, gp = a.data_ptr(), g.data_ptr()
     n = len(dims)
-    with on_device_of(a):
-        rc = _lib.lib().sr_bank_tn(
-            n, _pa([t.data_ptr() for t in outs]), None, _pa([ap + 4 * o for o in a_offs]), _pa([gp + 4 * o for o in q_offs]),
-            _la([i for i, _ in dims]), _la([j for _, j in dims]), _la([i for i, _ in dims]), _la([j for _, j in dims]),
-            batch, 1.0, 0.0, stream_of(a))
-    _lib.check(rc, "sr_bank_tn")
+    native(a).sr_bank_tn(n, _pa([t.data_ptr() for t in outs]), None, _pa([ap + 4 * o for o in a_offs]),
+                         _pa([gp + 4 * o for o in q_offs]), _la([i for i, _ in dims]), _la([j for _, j in dims]),
+                         _la([i for i, _ in dims]), _la([j for _, j in dims]), batch, 1.0, 0.0)
     return outs
 
 

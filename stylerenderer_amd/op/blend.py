@@ -25,7 +25,7 @@ from torch.autograd import Function
 
 from .. import _lib
 from . import _mesh_node
-from ._dispatch import on_device_of, stream_of
+from ._dispatch import native
 
 
 def mixing_weights(x, ds):
@@ -50,16 +50,14 @@ def blend_composite(model, coeff, pose, tri, reg_weight=0.0):
     return v, n, reg_weight * model.regulation(coeff)
 
 
-def _head(L, c, beta, reg_weight, ds, de, st):
+def _head(run, c, beta, reg_weight, ds, de):
     b = c.shape[0]
     dev, f32 = c.device, c.dtype
     xs = torch.empty((b, ds + 1), dtype=f32, device=dev)
     xe = torch.empty((b, de + 1), dtype=f32, device=dev)
     prior = torch.empty((b,), dtype=f32, device=dev)
-    z = torch.empty((int(L.sr_blend_z_floats(b, ds, de)),), dtype=f32, device=dev)
-    ptr = _lib.ptr
-    _lib.check(L.sr_blend_head(ptr(xs), ptr(xe), ptr(prior), ptr(z), ptr(c), ptr(beta), float(reg_weight), b, ds, de, st),
-               "sr_blend_head")
+    z = torch.empty((int(_lib.lib().sr_blend_z_floats(b, ds, de)),), dtype=f32, device=dev)
+    run.sr_blend_head(xs, xe, prior, z, c, beta, float(reg_weight), b, ds, de)
     return xs, xe, prior, z
 
 
@@ -70,12 +68,10 @@ class _Blend(Function):
         w, bt = weight.contiguous(), beta.contiguous()
         b = c.shape[0]
         ds, de, nv = w.shape[0] - 1, w.shape[1] - 1, w.shape[2] // 3
-        ptr = _lib.ptr
 
-        def model_fwd(L, st, v, vs, reg, lin):
-            xs, xe, prior, z = _head(L, c, bt, reg_weight, ds, de, st)
-            _lib.check(L.sr_blend_fwd(ptr(v), ptr(vs), ptr(reg), ptr(w), ptr(z), ptr(prior), ptr(lin), ptr(p), b,
-                                      nv, ds, de, st), "sr_blend_fwd")
+        def model_fwd(run, v, vs, reg, lin):
+            xs, xe, prior, z = _head(run, c, bt, reg_weight, ds, de)
+            run.sr_blend_fwd(v, vs, reg, w, z, prior, lin, p, b, nv, ds, de)
             return xs, xe, prior
 
         v, n, reg, mesh, (xs, xe, prior) = _mesh_node.forward(c, p, tri, nv, model_fwd)
@@ -90,14 +86,12 @@ class _Blend(Function):
         w, bt, xs, xe, *mesh = ctx.saved_tensors
         b, ds, de, nv = ctx.dims
         greg = greg.contiguous()
-        ptr = _lib.ptr
 
-        def model_bwd(L, st, gvs):
+        def model_bwd(run, gvs):
             gz = torch.empty((b, (ds + 1) * (de + 1)), dtype=gvs.dtype, device=gvs.device)
-            _lib.check(L.sr_blend_gz(ptr(gz), ptr(w), ptr(gvs), b, nv, ds, de, st), "sr_blend_gz")
+            run.sr_blend_gz(gz, w, gvs, b, nv, ds, de)
             gcoeff = torch.empty((b, ds + de), dtype=gvs.dtype, device=gvs.device)
-            _lib.check(L.sr_blend_tail(ptr(gcoeff), ptr(gz), ptr(xs), ptr(xe), ptr(bt), ctx.reg_weight, ptr(greg), b,
-                                       ds, de, st), "sr_blend_tail")
+            run.sr_blend_tail(gcoeff, gz, xs, xe, bt, ctx.reg_weight, greg, b, ds, de)
             return gcoeff
 
         return _mesh_node.backward(ctx.needs_input_grad, mesh, gv, gn, model_bwd) + (None,) * 4
@@ -112,13 +106,9 @@ class _BlendVertices(Function):
         b = c.shape[0]
         ds, de, nv = w.shape[0] - 1, w.shape[1] - 1, w.shape[2] // 3
         vs = torch.empty((b, nv, 3), dtype=c.dtype, device=c.device)
-        L = _lib.lib()
-        st = stream_of(c)
-        ptr = _lib.ptr
-        with on_device_of(c):
-            xs, xe, _, z = _head(L, c, bt, 0.0, ds, de, st)
-            _lib.check(L.sr_blend_fwd(None, ptr(vs), None, ptr(w), ptr(z), None, None, None, b, nv, ds, de, st),
-                       "sr_blend_fwd")
+        run = native(c)
+        xs, xe, _, z = _head(run, c, bt, 0.0, ds, de)
+        run.sr_blend_fwd(None, vs, None, w, z, None, None, None, b, nv, ds, de)
         ctx.save_for_backward(w, bt, xs, xe)
         ctx.dims = (b, ds, de, nv)
         return vs
@@ -128,15 +118,11 @@ class _BlendVertices(Function):
         w, bt, xs, xe = ctx.saved_tensors
         b, ds, de, nv = ctx.dims
         gvs = gvs.contiguous()
-        L = _lib.lib()
-        st = stream_of(gvs)
-        ptr = _lib.ptr
+        run = native(gvs)
         gz = torch.empty((b, (ds + 1) * (de + 1)), dtype=gvs.dtype, device=gvs.device)
         gcoeff = torch.empty((b, ds + de), dtype=gvs.dtype, device=gvs.device)
-        with on_device_of(gvs):
-            _lib.check(L.sr_blend_gz(ptr(gz), ptr(w), ptr(gvs), b, nv, ds, de, st), "sr_blend_gz")
-            _lib.check(L.sr_blend_tail(ptr(gcoeff), ptr(gz), ptr(xs), ptr(xe), ptr(bt), 0.0, None, b, ds, de, st),
-                       "sr_blend_tail")
+        run.sr_blend_gz(gz, w, gvs, b, nv, ds, de)
+        run.sr_blend_tail(gcoeff, gz, xs, xe, bt, 0.0, None, b, ds, de)
         return gcoeff, None, None
 
 

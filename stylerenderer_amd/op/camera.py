@@ -45,8 +45,7 @@ triangle, where a true perspective rasterizer's weights are b_i = (a_i / q_i) / 
 """
 import torch
 
-from .. import _lib
-from ._dispatch import is_device_tensor, on_device_of, stream_of, strict_native
+from ._dispatch import is_device_tensor, native, strict_native
 from .texture import _div, _sqrt
 
 QMIN = 1.0 / 16.0
@@ -180,10 +179,7 @@ class _ProjectNative(torch.autograd.Function):
         b, nv = int(vc.shape[0]), int(vc.shape[1])
         vp = torch.empty_like(vc)
         n_view = None if nc is None else torch.empty_like(nc)
-        ptr = _lib.ptr
-        with on_device_of(vc):
-            _lib.check(_lib.lib().sr_camera_fwd(ptr(vp), ptr(n_view), ptr(vc), ptr(nc), ptr(kc), b, nv, stream_of(vc)),
-                       "sr_camera_fwd")
+        native(vc).sr_camera_fwd(vp, n_view, vc, nc, kc, b, nv)
         ctx.save_for_backward(vc, kc, vp)
         if n_view is None:
             return vp
@@ -202,10 +198,7 @@ class _ProjectNative(torch.autograd.Function):
         gk = ctx.gkappa_out
         if gk is None and ctx.needs_input_grad[1]:
             gk = torch.empty_like(kc)
-        ptr = _lib.ptr
-        with on_device_of(vc):
-            _lib.check(_lib.lib().sr_camera_bwd(ptr(gv), ptr(gk), ptr(vc), ptr(vp), ptr(g), ptr(kc), b, nv,
-                                                stream_of(vc)), "sr_camera_bwd")
+        native(vc).sr_camera_bwd(gv, gk, vc, vp, g, kc, b, nv)
         return gv, (None if ctx.gkappa_out is not None else gk), None, None
 
 
@@ -217,12 +210,12 @@ def project(v, kappa, normals=None, gkappa_out=None):
     into its first B elements and kappa receives no gradient through autograd (an optimiser that reads its gradients from a
     buffer of its own, inversion.LatentInverter's, then needs no copy)."""
     _check(v, kappa, normals)
-    native = native_ok(v, kappa, normals) and v.shape[0] > 0 and v.shape[1] > 0
-    if gkappa_out is not None and not (native and native_ok(gkappa_out) and gkappa_out.is_contiguous()
+    kernels = native_ok(v, kappa, normals) and v.shape[0] > 0 and v.shape[1] > 0
+    if gkappa_out is not None and not (kernels and native_ok(gkappa_out) and gkappa_out.is_contiguous()
                                        and gkappa_out.numel() >= v.shape[0] and gkappa_out.device == v.device):
         raise ValueError("project: gkappa_out is for the kernels: float32 device tensors and a contiguous float32 buffer of "
                          "at least B elements on their device")
-    if not native:
+    if not kernels:
         if is_device_tensor(v) and strict_native():
             raise RuntimeError("project: SR_STRICT_NATIVE=1 and the kernels take float32 device tensors only")
         return project_composite(v, kappa, normals)

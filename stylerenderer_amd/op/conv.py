@@ -13,9 +13,9 @@ import os
 import torch
 
 from .. import _lib
-from ._dispatch import hold_for_capture, mark_inputs, on_device_of, require_f32, stream_of, wanted
+from ._dispatch import hold_for_capture, mark_inputs, native, require_f32, wanted
 from . import weight_prep as _wp
-from .fused_elem import rowdot, rowdot_div
+from .fused_elem import noise_stride, param_grads, rowdot, rowdot_div
 
 
 # Optional per-launch timing used by bench.py's roofline leg: when PROFILE is a list, every MFMA
@@ -23,15 +23,15 @@ from .fused_elem import rowdot, rowdot_div
 PROFILE = None
 
 
-def _timed(kind, geom, flops, launch):
+def _timed(like, kind, geom, flops, launch):
     if PROFILE is None:
         return launch()
+    stream = torch.cuda.current_stream(like.device)          # the launch stream: that of the operand's device
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    rc = launch()
-    e1.record()
+    e0.record(stream)
+    launch()
+    e1.record(stream)
     PROFILE.append((kind, geom, flops, e0, e1))
-    return rc
 
 
 def conv_out_size(ih, iw, ksize, stride, pad, transposed):
@@ -60,16 +60,11 @@ def conv2d_mfma(x, wt, iscale=None, oscale=None, obias=None, ksize=3, stride=1, 
     out = torch.empty((b, n, oh, ow), dtype=x.dtype, device=x.device)
     gh, gw = (ih, iw) if transposed else (oh, ow)
     flops = 2.0 * b * gh * gw * c * n * ksize * ksize
-    L = _lib.lib()
-    nscr = L.sr_conv2d_scratch_floats(b, c, n, ih, iw, oh, ow, ksize, stride, pad, int(bool(transposed)))
+    nscr = _lib.lib().sr_conv2d_scratch_floats(b, c, n, ih, iw, oh, ow, ksize, stride, pad, int(bool(transposed)))
     scratch, flags, entry = _conv_scratch(wt, nscr, (b, c, n, ih, iw, ksize, stride, pad, bool(transposed)), x)
-    with on_device_of(x):
-        rc = _timed("conv", (ksize, stride, int(bool(transposed)), b, c, n, gh, gw), flops,
-                    lambda: L.sr_conv2d_mfma_ex(
-                        _lib.ptr(out), _lib.ptr(x), _lib.ptr(wt), _lib.ptr(iscale), _lib.ptr(oscale),
-                        _lib.ptr(obias), b, c, n, ldw, ih, iw, oh, ow, ksize, stride, pad,
-                        int(bool(transposed)), flags, _lib.ptr(scratch), stream_of(x)))
-    _lib.check(rc, "sr_conv2d_mfma")
+    _timed(x, "conv", (ksize, stride, int(bool(transposed)), b, c, n, gh, gw), flops,
+           lambda: native(x).sr_conv2d_mfma_ex(out, x, wt, iscale, oscale, obias, b, c, n, ldw, ih, iw, oh, ow, ksize,
+                                               stride, pad, int(bool(transposed)), flags, scratch))
     _scratch_written(entry, b, c, n, ih, iw, x, out)
     return out
 
@@ -144,21 +139,16 @@ def conv2d_wgrad_mfma(x, gy, xscale=None, gscale=None, ksize=3, stride=1, pad=1,
         from .smallconv import _dw
 
         return _dw(x, gy).sum(0).view(1, c, n)
-    L = _lib.lib()
-    nfl = L.sr_conv2d_wgrad_scratch_floats(b, c, n, ih, iw, oh, ow, ksize, stride, pad, int(bool(transposed)))
+    nfl = _lib.lib().sr_conv2d_wgrad_scratch_floats(b, c, n, ih, iw, oh, ow, ksize, stride, pad, int(bool(transposed)))
     if nfl < 0:
         raise RuntimeError("conv2d_wgrad_mfma: unsupported geometry")
     scratch = torch.empty(nfl, dtype=torch.float32, device=x.device)
     dwt = torch.empty((ksize * ksize, c, n), dtype=torch.float32, device=x.device)
     gh, gw = (ih, iw) if transposed else (oh, ow)
     flops = 2.0 * b * gh * gw * c * n * ksize * ksize
-    with on_device_of(x):
-        rc = _timed("wgrad", (ksize, stride, int(bool(transposed)), b, c, n, gh, gw), flops,
-                    lambda: L.sr_conv2d_wgrad_mfma(
-                        _lib.ptr(dwt), _lib.ptr(x), _lib.ptr(gy), _lib.ptr(xscale), _lib.ptr(gscale),
-                        b, c, n, ih, iw, oh, ow, ksize, stride, pad, int(bool(transposed)),
-                        _lib.ptr(scratch), stream_of(x)))
-    _lib.check(rc, "sr_conv2d_wgrad_mfma")
+    _timed(x, "wgrad", (ksize, stride, int(bool(transposed)), b, c, n, gh, gw), flops,
+           lambda: native(x).sr_conv2d_wgrad_mfma(dwt, x, gy, xscale, gscale, b, c, n, ih, iw, oh, ow, ksize, stride, pad,
+                                                  int(bool(transposed)), scratch))
     return dwt
 
 
@@ -193,6 +183,26 @@ def _bc(s):
     return s[:, :, None, None]
 
 
+def _input_grads(x, g, wt, iscale, oscale, geom, need_x, need_is, frozen=False, banked=None, fused=True):
+    """(gx, gis) of y = oscale * conv(iscale * x, wt) for the cotangent g: the data gradient through the adjoint
+    `ConvFn`, then the style gradient sum_p x*dxu and dx = iscale*dxu — in one sweep (csrc/fused_elem.hip) where
+    `fused` and both are wanted.  `need_is` implies an `iscale`: `needs_input_grad` is False for a None input."""
+    if not (need_x or need_is):
+        return None, None
+    if geom == "c1s2":
+        inner = ConvFn.apply(g, adjoint_weight(wt, "c1", frozen, banked), oscale, None, None, "c1")
+        dxu = torch.zeros_like(x)
+        dxu[:, :, ::2, ::2] = inner
+    else:
+        dxu = ConvFn.apply(g, adjoint_weight(wt, geom, frozen, banked), oscale, None, None, _ADJOINT[geom])
+    if fused and need_is and need_x:
+        gis, gx = rowdot(x, dxu, iscale)
+        return gx, gis
+    gis = rowdot(x, dxu) if need_is else None
+    gx = (dxu * _bc(iscale) if iscale is not None else dxu) if need_x else None
+    return gx, gis
+
+
 class ConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, wt, iscale, oscale, bias, geom):
@@ -212,22 +222,8 @@ class ConvFn(torch.autograd.Function):
         need_x, need_w, need_is, need_os, need_b = wanted(ctx)[:5]      # minus what this pass would discard
         geom = ctx.geom
         g = g.contiguous()
-        gx = gw = gis = gos = gb = None
-        if need_x or need_is:
-            if geom == "c1s2":
-                inner = ConvFn.apply(g, adjoint_weight(wt, "c1", ctx.frozen, ctx.adj), oscale, None, None, "c1")
-                dxu = torch.zeros_like(x)
-                dxu[:, :, ::2, ::2] = inner
-            else:
-                dxu = ConvFn.apply(g, adjoint_weight(wt, geom, ctx.frozen, ctx.adj), oscale, None, None, _ADJOINT[geom])
-            # style gradient sum_p x*dxu and dx = s*dxu in one sweep (csrc/fused_elem.hip)
-            if need_is and need_x and iscale is not None:
-                gis, gx = rowdot(x, dxu, iscale)
-            else:
-                if need_is:
-                    gis = rowdot(x, dxu)
-                if need_x:
-                    gx = dxu * _bc(iscale) if iscale is not None else dxu
+        gw = gos = gb = None
+        gx, gis = _input_grads(x, g, wt, iscale, oscale, geom, need_x, need_is, ctx.frozen, ctx.adj)
         if need_w:
             gw = WgradFn.apply(x, g, iscale, oscale, geom)
         if need_os:
@@ -254,18 +250,8 @@ class WgradFn(torch.autograd.Function):
         need_x, need_g, need_is, need_os = wanted(ctx)[:4]
         geom = ctx.geom
         gg = gg.contiguous()
-        gx = g_g = gis = gos = None
-        if need_x or need_is:
-            if geom == "c1s2":
-                inner = ConvFn.apply(g, adjoint_weight(gg, "c1"), oscale, None, None, "c1")
-                dxu = torch.zeros_like(x)
-                dxu[:, :, ::2, ::2] = inner
-            else:
-                dxu = ConvFn.apply(g, adjoint_weight(gg, geom), oscale, None, None, _ADJOINT[geom])
-            if need_is:
-                gis = rowdot(x, dxu)
-            if need_x:
-                gx = dxu * _bc(iscale) if iscale is not None else dxu
+        g_g = gos = None
+        gx, gis = _input_grads(x, g, gg, iscale, oscale, geom, need_x, need_is, fused=False)
         if need_g or need_os:
             dgu = ConvFn.apply(x, gg, iscale, None, None, geom)
             if need_os:
@@ -287,6 +273,19 @@ def _aliases(*tensors):
     history that links them OUTSIDE the node (the demodulation scale is a function of the style) and count
     those paths twice.  Gradients w.r.t. the aliases stop at the node boundary, and stay differentiable."""
     return [t.view_as(t) if t is not None else None for t in tensors]
+
+
+def _recorded_backward(saved, needs, gy, rebuild):
+    """Backward of a fused node while that backward is itself recorded (create_graph): the output is rebuilt from the
+    separate differentiable operators — `rebuild(*aliases)` of `saved`, the node's leading inputs (None where one takes
+    no gradient) — and its VJP taken for the inputs that `needs` one.  One gradient per forward input."""
+    with torch.enable_grad():
+        ins = _aliases(*saved)
+        y = rebuild(*ins)
+        sel = [t for t, nd in zip(ins, needs) if nd and t is not None]
+        got = iter(torch.autograd.grad(y, sel, gy, create_graph=True, allow_unused=True)) if sel else iter(())
+        grads = [next(got) if (nd and t is not None) else None for t, nd in zip(ins, needs)]
+    return tuple(grads) + (None,) * (len(needs) - len(ins))
 
 
 def conv_nba_shape_ok(x, n, noise):
@@ -325,18 +324,13 @@ class ConvNBAFn(torch.autograd.Function):
         n = wt.shape[2]
         wtp, ldw = _wt_pitch(wt)
         out = torch.empty((b, n, h, w), dtype=x.dtype, device=x.device)
-        L = _lib.lib()
-        nscr = L.sr_conv2d_scratch_floats(b, c, n, h, w, h, w, 3, 1, 1, 0)
+        nscr = _lib.lib().sr_conv2d_scratch_floats(b, c, n, h, w, h, w, 3, 1, 1, 0)
         scratch, flags, entry = _conv_scratch(wt if wtp is wt else wtp, max(nscr, 1), (b, c, n, h, w, 3, 1, 1, False), x)
-        bstride = 0 if noise is None or noise.numel() == h * w else h * w
         flops = 2.0 * b * h * w * c * n * 9
-        with on_device_of(x):
-            rc = _timed("conv", (3, 1, 0, b, c, n, h, w), flops,
-                        lambda: L.sr_conv2d_nba_ex(_lib.ptr(out), _lib.ptr(x), _lib.ptr(wtp), _lib.ptr(iscale),
-                                                   _lib.ptr(oscale), _lib.ptr(noise), _lib.ptr(noise_w), _lib.ptr(abias),
-                                                   float(slope), float(gain), b, c, n, ldw, h, w, bstride, flags,
-                                                   _lib.ptr(scratch), stream_of(x)))
-        _lib.check(rc, "sr_conv2d_nba")
+        _timed(x, "conv", (3, 1, 0, b, c, n, h, w), flops,
+               lambda: native(x).sr_conv2d_nba_ex(out, x, wtp, iscale, oscale, noise, noise_w, abias, float(slope),
+                                                  float(gain), b, c, n, ldw, h, w, noise_stride(noise, h * w), flags,
+                                                  scratch))
         _scratch_written(entry, b, c, n, h, w, x, out)
         ctx.save_for_backward(x, wt, iscale, oscale, noise, noise_w, abias, out)
         ctx.cfg = (float(slope), float(gain))
@@ -356,15 +350,10 @@ class ConvNBAFn(torch.autograd.Function):
             # demodulation gradient is sum_p g * y0): re-derived from the separate operators.  Without demodulation (the
             # discriminator's layers under R1, the LPIPS trunk) nothing below reads y0 — the operators of the plain
             # branch are differentiable themselves and record the same pass without convolving again
-            with torch.enable_grad():
-                xa, wa, sa, da, nwa, aba = _aliases(x, wt, iscale, oscale, noise_w, abias)
-                y0 = ConvFn.apply(xa, wa, sa, da, None, "c3")
-                y = _NBA.apply(y0, noise, nwa, aba, slope, gain, out.detach())
-                ins = (xa, wa, sa, da, None, nwa, aba)
-                sel = [t for t, nd in zip(ins, needs[:7]) if nd and t is not None]
-                got = iter(torch.autograd.grad(y, sel, gy, create_graph=True, allow_unused=True)) if sel else iter(())
-                grads = [next(got) if (nd and t is not None) else None for t, nd in zip(ins, needs[:7])]
-            return tuple(grads) + (None, None)
+            return _recorded_backward(
+                (x, wt, iscale, oscale, None, noise_w, abias), needs, gy,
+                lambda xa, wa, sa, da, _, nwa, aba: _NBA.apply(ConvFn.apply(xa, wa, sa, da, None, "c3"), noise, nwa, aba,
+                                                               slope, gain, out.detach()))
         want_p = bool(needs[6] or (noise is not None and needs[5]))
         if oscale is None:
             # no demodulation (the LPIPS trunk's plain convolution + bias + ReLU): nothing to row-dot — and with slope 0
@@ -375,16 +364,8 @@ class ConvNBAFn(torch.autograd.Function):
             rdot = None
         else:
             g, gb, gnw, rdot = _nba_bwd_dot(gy, out, noise, noise_w, abias, slope, gain, want_p)
-        gx = gw = gis = gos = None
-        if needs[0] or needs[2]:
-            dxu = ConvFn.apply(g, adjoint_weight(wt, "c3", ctx.frozen, ctx.adj), oscale, None, None, "c3")
-            if needs[2] and needs[0] and iscale is not None:
-                gis, gx = rowdot(x, dxu, iscale)
-            else:
-                if needs[2] and iscale is not None:
-                    gis = rowdot(x, dxu)
-                if needs[0]:
-                    gx = dxu * _bc(iscale) if iscale is not None else dxu
+        gw = gos = None
+        gx, gis = _input_grads(x, g, wt, iscale, oscale, "c3", needs[0], needs[2], ctx.frozen, ctx.adj)
         if needs[1]:
             gw = WgradFn.apply(x, g, iscale, oscale, "c3")
         if needs[3] and oscale is not None:
@@ -399,21 +380,13 @@ def _nba_bwd_dot(gy, out, noise, noise_w, abias, slope, gain, want_params=True):
     gy = gy.contiguous()
     b, n, h, w = out.shape
     inner = h * w
-    L = _lib.lib()
     g = torch.empty_like(out)
-    gb = (torch.zeros if out.numel() == 0 else torch.empty)(n if want_params else 0, dtype=out.dtype, device=out.device)
-    # written by the finish kernel whenever there is noise; a fill launch only for the cases that need the zero
-    gnw = (torch.empty if (noise is not None and out.numel() > 0) else torch.zeros)(1 if want_params else 0,
-                                                                                        dtype=out.dtype, device=out.device)
+    gb, gnw = param_grads(out, noise, want_params)
     rdot = torch.empty((b, n), dtype=out.dtype, device=out.device)
-    scratch = torch.empty(L.sr_noise_bias_act_bwd_dot_scratch_floats(b, n, inner), dtype=out.dtype, device=out.device)
-    bstride = 0 if noise is None or noise.numel() == inner else inner
-    with on_device_of(out):
-        rc = L.sr_noise_bias_act_bwd_dot(_lib.ptr(g), _lib.ptr(gb) if want_params else None,
-                                         _lib.ptr(gnw) if want_params else None, _lib.ptr(rdot), _lib.ptr(gy),
-                                         _lib.ptr(out), _lib.ptr(noise), _lib.ptr(noise_w), _lib.ptr(abias), slope, gain,
-                                         b, n, inner, bstride, _lib.ptr(scratch), stream_of(out))
-    _lib.check(rc, "sr_noise_bias_act_bwd_dot")
+    scratch = torch.empty(_lib.lib().sr_noise_bias_act_bwd_dot_scratch_floats(b, n, inner), dtype=out.dtype,
+                          device=out.device)
+    native(out).sr_noise_bias_act_bwd_dot(g, gb, gnw, rdot, gy, out, noise, noise_w, abias, slope, gain, b, n, inner,
+                                          noise_stride(noise, inner), scratch)
     return g, gb, gnw, rdot
 
 
@@ -428,20 +401,13 @@ def _blur_nba_bwd(gy, out, k_flipped, p0, shape257, noise, noise_w, abias, slope
     """csrc/upfirdn2d.hip k_fir4_nba_bwd: gradient w.r.t. the blur's input plus what `_nba_bwd_dot` returns."""
     gy = gy.contiguous()
     b, n, oh, ow = out.shape
-    L = _lib.lib()
     g257 = torch.empty(shape257, dtype=out.dtype, device=out.device)
-    gb = torch.empty(n if want_params else 0, dtype=out.dtype, device=out.device)
-    gnw = (torch.empty if noise is not None else torch.zeros)(1 if want_params else 0, dtype=out.dtype, device=out.device)
+    gb, gnw = param_grads(out, noise, want_params, zero_empty=False)
     rdot = torch.empty((b, n), dtype=out.dtype, device=out.device)
-    scratch = torch.empty(L.sr_blur_nba_bwd_scratch_floats(b, n, shape257[2], shape257[3]), dtype=out.dtype,
+    scratch = torch.empty(_lib.lib().sr_blur_nba_bwd_scratch_floats(b, n, shape257[2], shape257[3]), dtype=out.dtype,
                           device=out.device)
-    bstride = 0 if noise is None or noise.numel() == oh * ow else oh * ow
-    with on_device_of(out):
-        rc = L.sr_blur_nba_bwd(_lib.ptr(g257), _lib.ptr(gb) if want_params else None,
-                               _lib.ptr(gnw) if want_params else None, _lib.ptr(rdot), _lib.ptr(gy), _lib.ptr(out),
-                               _lib.ptr(k_flipped), _lib.ptr(noise), _lib.ptr(noise_w), _lib.ptr(abias), slope, gain, b, n,
-                               oh, ow, shape257[2], shape257[3], p0, bstride, _lib.ptr(scratch), stream_of(out))
-    _lib.check(rc, "sr_blur_nba_bwd")
+    native(out).sr_blur_nba_bwd(g257, gb, gnw, rdot, gy, out, k_flipped, noise, noise_w, abias, slope, gain, b, n, oh, ow,
+                                shape257[2], shape257[3], p0, noise_stride(noise, oh * ow), scratch)
     return g257, gb, gnw, rdot
 
 
@@ -483,15 +449,10 @@ class UpConvNBAFn(torch.autograd.Function):
         pad, slope, gain, shape257 = ctx.cfg
         needs = wanted(ctx)
         if torch.is_grad_enabled():
-            with torch.enable_grad():
-                xa, wa, sa, da, nwa, aba = _aliases(x, wt, iscale, oscale, noise_w, abias)
-                y = ConvFn.apply(xa, wa, sa, da, None, "t3s2")
-                o = _BlurNBA.apply(y, kernel, pad, noise, nwa, aba, slope, gain, out.detach())
-                ins = (xa, wa, sa, da, None, None, None, nwa, aba)
-                sel = [t for t, nd in zip(ins, needs[:9]) if nd and t is not None]
-                got = iter(torch.autograd.grad(o, sel, gy, create_graph=True, allow_unused=True)) if sel else iter(())
-                grads = [next(got) if (nd and t is not None) else None for t, nd in zip(ins, needs[:9])]
-            return tuple(grads) + (None, None)
+            return _recorded_backward(
+                (x, wt, iscale, oscale, None, None, None, noise_w, abias), needs, gy,
+                lambda xa, wa, sa, da, _k, _p, _n, nwa, aba: _BlurNBA.apply(
+                    ConvFn.apply(xa, wa, sa, da, None, "t3s2"), kernel, pad, noise, nwa, aba, slope, gain, out.detach()))
         want_p = bool(needs[8] or (noise is not None and needs[7]))
         p0 = pad[0]
         oh, ow = out.shape[2], out.shape[3]
@@ -504,16 +465,8 @@ class UpConvNBAFn(torch.autograd.Function):
             g, gb, gnw, rdot = _nba_bwd_dot(gy, out, noise, noise_w, abias, slope, gain, want_p)
             g257 = upfirdn2d_op(g.reshape(-1, oh, ow, 1), flipped(kernel), 1, 1, 1, 1, 3 - p0,
                                 shape257[3] - ow + p0, 3 - p0, shape257[2] - oh + p0).view(shape257)
-        gx = gw = gis = gos = None
-        if needs[0] or needs[2]:
-            dxu = ConvFn.apply(g257, adjoint_weight(wt, "t3s2", ctx.frozen, ctx.adj), oscale, None, None, "c3s2")
-            if needs[2] and needs[0] and iscale is not None:
-                gis, gx = rowdot(x, dxu, iscale)
-            else:
-                if needs[2] and iscale is not None:
-                    gis = rowdot(x, dxu)
-                if needs[0]:
-                    gx = dxu * _bc(iscale) if iscale is not None else dxu
+        gw = gos = None
+        gx, gis = _input_grads(x, g257, wt, iscale, oscale, "t3s2", needs[0], needs[2], ctx.frozen, ctx.adj)
         if needs[1]:
             gw = WgradFn.apply(x, g257, iscale, oscale, "t3s2")
         if needs[3] and oscale is not None:
@@ -550,10 +503,7 @@ class Conv1x1AddFn(torch.autograd.Function):
         b, c, h, w = x.shape
         n = wt.shape[2]
         out = torch.empty((b, n, h, w), dtype=x.dtype, device=x.device)
-        with on_device_of(x):
-            rc = _lib.lib().sr_conv1x1_add(_lib.ptr(out), _lib.ptr(x), _lib.ptr(wt), _lib.ptr(oscale), _lib.ptr(addend),
-                                           b, c, n, wt.stride(1), h * w, stream_of(x))
-        _lib.check(rc, "sr_conv1x1_add")
+        native(x).sr_conv1x1_add(out, x, wt, oscale, addend, b, c, n, wt.stride(1), h * w)
         ctx.frozen = bool(getattr(wt, "_sr_frozen", False))
         ctx.adj = getattr(wt, "_sr_adj", None)
         ctx.save_for_backward(x, wt, oscale)

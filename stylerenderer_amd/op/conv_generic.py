@@ -14,8 +14,7 @@ two — so the Functions below are differentiable to any order (R1 / path-length
 import torch
 from torch.autograd import Function
 
-from .. import _lib
-from ._dispatch import on_device_of, stream_of
+from ._dispatch import native
 
 
 def _pair(v):
@@ -62,9 +61,7 @@ def _fwd(x, w, bias, geo):
     x, w = x.contiguous(), w.contiguous()
     bias = bias.contiguous() if bias is not None else None
     y = torch.empty((b, n, oh, ow), dtype=x.dtype, device=x.device)
-    with on_device_of(x):
-        rc = _lib.lib().sr_conv2d_generic(_lib.ptr(y), _lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), *geo, stream_of(x))
-    _lib.check(rc, "sr_conv2d_generic")
+    native(x).sr_conv2d_generic(y, x, w, bias, *geo)
     return y
 
 
@@ -73,9 +70,7 @@ def _dgrad(g, w, geo):
     _check("conv2d_generic_dgrad", g, w)
     g, w = g.contiguous(), w.contiguous()
     dx = torch.empty((b, c, ih, iw), dtype=g.dtype, device=g.device)
-    with on_device_of(g):
-        rc = _lib.lib().sr_conv2d_generic_dgrad(_lib.ptr(dx), _lib.ptr(g), _lib.ptr(w), *geo, stream_of(g))
-    _lib.check(rc, "sr_conv2d_generic_dgrad")
+    native(g).sr_conv2d_generic_dgrad(dx, g, w, *geo)
     return dx
 
 
@@ -85,9 +80,7 @@ def _wgrad(x, g, geo):
     _check("conv2d_generic_wgrad", x, g)
     x, g = x.contiguous(), g.contiguous()
     dw = torch.empty((n, c, kh, kw), dtype=x.dtype, device=x.device)
-    with on_device_of(x):
-        rc = _lib.lib().sr_conv2d_generic_wgrad(_lib.ptr(dw), _lib.ptr(x), _lib.ptr(g), *geo, stream_of(x))
-    _lib.check(rc, "sr_conv2d_generic_wgrad")
+    native(x).sr_conv2d_generic_wgrad(dw, x, g, *geo)
     return dw
 
 

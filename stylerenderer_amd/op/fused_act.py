@@ -17,7 +17,7 @@ from torch.autograd import Function
 from torch.nn import functional as F
 
 from .. import _lib
-from ._dispatch import is_device_tensor, mark_inputs, on_device_of, require_f32, stream_of, wanted
+from ._dispatch import is_device_tensor, mark_inputs, native, require_f32, wanted
 
 
 def fused_bias_act(input, bias, refer, act, grad, alpha, scale):
@@ -41,12 +41,8 @@ def fused_bias_act(input, bias, refer, act, grad, alpha, scale):
     for i in range(2, x.dim()):
         step_b *= x.size(i)
     y = torch.empty_like(x)
-    with on_device_of(x):
-        rc = _lib.lib().sr_fused_bias_act(
-            _lib.ptr(y), _lib.ptr(x), _lib.ptr(b) if use_bias else None,
-            _lib.ptr(ref) if use_ref else None, int(act), int(grad), float(alpha), float(scale),
-            x.numel(), step_b, b.numel() if use_bias else 0, use_bias, use_ref, stream_of(x))
-    _lib.check(rc, "sr_fused_bias_act")
+    native(x).sr_fused_bias_act(y, x, b if use_bias else None, ref if use_ref else None, int(act), int(grad), float(alpha),
+                                float(scale), x.numel(), step_b, b.numel() if use_bias else 0, use_bias, use_ref)
     return y
 
 
@@ -64,14 +60,9 @@ def _act_backward(grad_output, out, negative_slope, scale, want_bias=True):
     gx = torch.empty_like(o)
     # an empty input launches nothing: its bias gradient is the empty sum, not uninitialised memory
     gb = (torch.zeros if o.numel() == 0 else torch.empty)(c if want_bias else 0, dtype=o.dtype, device=o.device)
-    L = _lib.lib()
-    scratch = (torch.empty(L.sr_fused_act_bwd_scratch_floats(n, c, inner), dtype=o.dtype, device=o.device)
+    scratch = (torch.empty(_lib.lib().sr_fused_act_bwd_scratch_floats(n, c, inner), dtype=o.dtype, device=o.device)
                if want_bias else None)
-    with on_device_of(o):
-        rc = L.sr_fused_act_bwd(_lib.ptr(gx), _lib.ptr(gb) if want_bias else None, _lib.ptr(g), _lib.ptr(o),
-                                float(negative_slope), float(scale), n, c, inner,
-                                _lib.ptr(scratch), stream_of(o))
-    _lib.check(rc, "sr_fused_act_bwd")
+    native(o).sr_fused_act_bwd(gx, gb, g, o, float(negative_slope), float(scale), n, c, inner, scratch)
     return gx, gb
 
 

@@ -9,7 +9,7 @@ import torch
 from torch.autograd import Function
 
 from .. import _lib
-from ._dispatch import mark_inputs, on_device_of, stream_of, wanted
+from ._dispatch import mark_inputs, native, wanted
 from .fused_act import fused_leaky_relu
 
 
@@ -34,15 +34,30 @@ def _fusable(x, noise):
     return True
 
 
+def noise_stride(noise, inner):
+    """Batch stride of the noise plane [B or 1, 1, H, W]: 0 without noise or with one plane for the whole batch."""
+    return 0 if noise is None or noise.numel() == inner else inner
+
+
+def param_grads(out, noise, want_params, zero_empty=True):
+    """(gb [C], gnw [1]) for an activation backward kernel to fill; zero-size (NULL to the kernel, no reduction
+    launches) when bias and noise strength are frozen.  gnw is written by the finish kernel whenever there is noise: a
+    fill launch only for the cases that need the zero.  `zero_empty`: nothing is launched over an empty output, so
+    both are zero-filled then.  With False there is never a fill for gb, and both are unspecified for an empty output:
+    for a caller whose kernel writes them whenever it is given a non-empty output and which is not used on empty ones
+    (op.conv's blur backward)."""
+    live = out.numel() > 0 or not zero_empty
+    gb = (torch.empty if live else torch.zeros)(out.shape[1] if want_params else 0, dtype=out.dtype, device=out.device)
+    gnw = (torch.empty if (noise is not None and live) else torch.zeros)(1 if want_params else 0, dtype=out.dtype,
+                                                                          device=out.device)
+    return gb, gnw
+
+
 def _launch_fwd(x, noise, noise_w, bias, ref, slope, scale):
     n, c, inner = _geometry(x)
     y = torch.empty_like(x)
-    bstride = 0 if noise is None or noise.numel() == inner else inner
-    with on_device_of(x):
-        rc = _lib.lib().sr_noise_bias_act(_lib.ptr(y), _lib.ptr(x), _lib.ptr(noise), _lib.ptr(noise_w),
-                                          _lib.ptr(bias), _lib.ptr(ref), float(slope), float(scale), n, c,
-                                          inner, bstride, stream_of(x))
-    _lib.check(rc, "sr_noise_bias_act")
+    native(x).sr_noise_bias_act(y, x, noise, noise_w, bias, ref, float(slope), float(scale), n, c, inner,
+                                noise_stride(noise, inner))
     return y
 
 
@@ -54,21 +69,11 @@ class _NBABackward(Function):
         n, c, inner = _geometry(out)
         gy = gy.contiguous()
         gx = torch.empty_like(out)
-        gb = (torch.zeros if out.numel() == 0 else torch.empty)(c if want_params else 0, dtype=out.dtype,
-                                                                device=out.device)
-        gnw = (torch.empty if (noise is not None and out.numel() > 0) else torch.zeros)(1 if want_params else 0,
-                                                                                            dtype=out.dtype,
-                                                                                            device=out.device)
-        L = _lib.lib()
-        scratch = torch.empty(L.sr_noise_bias_act_bwd_scratch_floats(n, c, inner), dtype=out.dtype,
+        gb, gnw = param_grads(out, noise, want_params)
+        scratch = torch.empty(_lib.lib().sr_noise_bias_act_bwd_scratch_floats(n, c, inner), dtype=out.dtype,
                               device=out.device)
-        bstride = 0 if noise is None or noise.numel() == inner else inner
-        with on_device_of(out):
-            rc = L.sr_noise_bias_act_bwd(_lib.ptr(gx), _lib.ptr(gb) if want_params else None,
-                                         _lib.ptr(gnw) if want_params else None, _lib.ptr(gy),
-                                         _lib.ptr(out), _lib.ptr(noise), float(slope), float(scale), n, c,
-                                         inner, bstride, _lib.ptr(scratch), stream_of(out))
-        _lib.check(rc, "sr_noise_bias_act_bwd")
+        native(out).sr_noise_bias_act_bwd(gx, gb, gnw, gy, out, noise, float(slope), float(scale), n, c, inner,
+                                          noise_stride(noise, inner), scratch)
         ctx.save_for_backward(out, noise)
         ctx.slope, ctx.scale = slope, scale
         return gx, gb, gnw
@@ -131,22 +136,12 @@ class _NBAAffineBackward(Function):
         gx = torch.empty_like(out)
         gmap = torch.empty((2, n) + tuple(out.shape[2:]), dtype=out.dtype, device=out.device)   # [a | s] planes
         # want_params False: bias and noise strength are frozen (inversion, sampling) — no reduction launches
-        gb = (torch.zeros if out.numel() == 0 else torch.empty)(c if want_params else 0, dtype=out.dtype,
-                                                                device=out.device)
-        gnw = (torch.empty if (noise is not None and out.numel() > 0) else torch.zeros)(1 if want_params else 0,
-                                                                                            dtype=out.dtype,
-                                                                                            device=out.device)
-        L = _lib.lib()
-        scratch = torch.empty(L.sr_noise_bias_act_affine_bwd_scratch_floats(n, c, inner), dtype=out.dtype,
+        gb, gnw = param_grads(out, noise, want_params)
+        scratch = torch.empty(_lib.lib().sr_noise_bias_act_affine_bwd_scratch_floats(n, c, inner), dtype=out.dtype,
                               device=out.device)
-        bstride = 0 if noise is None or noise.numel() == inner else inner
-        with on_device_of(out):
-            rc = L.sr_noise_bias_act_affine_bwd(
-                _lib.ptr(gx), gmap.data_ptr(), gmap.data_ptr() + 4 * n * inner, _lib.ptr(gb) if want_params else None,
-                _lib.ptr(gnw) if want_params else None,
-                _lib.ptr(gy), _lib.ptr(out), _lib.ptr(x), _lib.ptr(smap2), smap2.stride(0), _lib.ptr(noise),
-                float(slope), float(scale), n, c, inner, bstride, _lib.ptr(scratch), stream_of(out))
-        _lib.check(rc, "sr_noise_bias_act_affine_bwd")
+        native(out).sr_noise_bias_act_affine_bwd(gx, gmap.data_ptr(), gmap.data_ptr() + 4 * n * inner, gb, gnw, gy, out, x,
+                                                 smap2, smap2.stride(0), noise, float(slope), float(scale), n, c, inner,
+                                                 noise_stride(noise, inner), scratch)
         ctx.save_for_backward(gy, out, x, smap2, noise)
         # absent cotangents (frozen bias / noise strength, a plane nobody differentiated) arrive as None, not as
         # zero-filled tensors: two fill launches less per layer of the recorded backward
@@ -167,17 +162,11 @@ class _NBAAffineBackward(Function):
         G_gmap = G_gmap.contiguous() if G_gmap is not None else None                  # [n, 2, H, W]
         G_gb = G_gb.contiguous() if (G_gb is not None and G_gb.numel() == c) else None
         G_gnw = G_gnw.contiguous() if (G_gnw is not None and G_gnw.numel() == 1 and noise is not None) else None
-        L = _lib.lib()
-        scratch = torch.empty(L.sr_noise_bias_act_affine_bwd2_scratch_floats(n, c, inner), dtype=out.dtype,
+        scratch = torch.empty(_lib.lib().sr_noise_bias_act_affine_bwd2_scratch_floats(n, c, inner), dtype=out.dtype,
                               device=out.device)
-        bstride = 0 if noise is None or noise.numel() == inner else inner
-        with on_device_of(out):
-            rc = L.sr_noise_bias_act_affine_bwd2(
-                _lib.ptr(d_gy), _lib.ptr(d_x), _lib.ptr(d_smap), 2 * inner, _lib.ptr(G_gx), _lib.ptr(G_gmap), 2 * inner,
-                _lib.ptr(G_gb), _lib.ptr(G_gnw), _lib.ptr(gy), _lib.ptr(out), _lib.ptr(x), _lib.ptr(smap2),
-                smap2.stride(0), _lib.ptr(noise), float(slope), float(scale), n, c, inner, bstride, _lib.ptr(scratch),
-                stream_of(out))
-        _lib.check(rc, "sr_noise_bias_act_affine_bwd2")
+        native(out).sr_noise_bias_act_affine_bwd2(d_gy, d_x, d_smap, 2 * inner, G_gx, G_gmap, 2 * inner, G_gb, G_gnw, gy,
+                                                  out, x, smap2, smap2.stride(0), noise, float(slope), float(scale), n, c,
+                                                  inner, noise_stride(noise, inner), scratch)
         needs = ctx.needs_input_grad
         return (d_gy if needs[0] else None, None, d_x if needs[2] else None, d_smap if needs[3] else None, None,
                 None, None, None)
@@ -192,13 +181,9 @@ class _NBAAffine(Function):
         mark_inputs(ctx, x, smap2, noise, noise_w, bias, slope, scale)
         n, c, inner = _geometry(x)
         y = torch.empty_like(x)
-        bstride = 0 if noise is None or noise.numel() == inner else inner
-        with on_device_of(x):
-            rc = _lib.lib().sr_noise_bias_act_affine(
-                _lib.ptr(y), _lib.ptr(x), smap2.data_ptr(), smap2.data_ptr() + 4 * inner, smap2.stride(0),
-                _lib.ptr(noise), _lib.ptr(noise_w), _lib.ptr(bias), float(slope), float(scale), n, c, inner, bstride,
-                stream_of(x))
-        _lib.check(rc, "sr_noise_bias_act_affine")
+        native(x).sr_noise_bias_act_affine(y, x, smap2.data_ptr(), smap2.data_ptr() + 4 * inner, smap2.stride(0), noise,
+                                           noise_w, bias, float(slope), float(scale), n, c, inner,
+                                           noise_stride(noise, inner))
         ctx.save_for_backward(x, smap2, noise, noise_w, bias, y)
         ctx.cfg = (slope, scale)
         return y
@@ -251,12 +236,8 @@ class _BlurNBA(Function):
             x = x.contiguous()
             k = kernel.contiguous()
             y = torch.empty((n, c, oh, ow), dtype=x.dtype, device=x.device)
-            bstride = 0 if noise is None or noise.numel() == oh * ow else oh * ow
-            with on_device_of(x):
-                rc = _lib.lib().sr_blur_noise_bias_act(_lib.ptr(y), _lib.ptr(x), _lib.ptr(k), _lib.ptr(noise),
-                                                       _lib.ptr(noise_w), _lib.ptr(bias), float(slope), float(scale), n,
-                                                       c, ih, iw, oh, ow, p0, p1, bstride, stream_of(x))
-            _lib.check(rc, "sr_blur_noise_bias_act")
+            native(x).sr_blur_noise_bias_act(y, x, k, noise, noise_w, bias, float(slope), float(scale), n, c, ih, iw, oh,
+                                             ow, p0, p1, noise_stride(noise, oh * ow))
         ctx.save_for_backward(y, noise, kernel)
         ctx.cfg = (slope, scale, p0, p1, tuple(x.shape), (oh, ow))
         return y
@@ -297,12 +278,8 @@ def _rowdot_launch(a, b, scale):
     inner = a.numel() // max(rows, 1)
     dots = torch.empty(a.shape[:2], dtype=a.dtype, device=a.device)
     out = torch.empty_like(b) if scale is not None else None
-    L = _lib.lib()
-    scratch = torch.empty(L.sr_rowdot_scratch_floats(rows, inner), dtype=a.dtype, device=a.device)
-    with on_device_of(a):
-        rc = L.sr_rowdot(_lib.ptr(dots), _lib.ptr(out), _lib.ptr(a), _lib.ptr(b), _lib.ptr(scale), rows,
-                         inner, _lib.ptr(scratch), stream_of(a))
-    _lib.check(rc, "sr_rowdot")
+    scratch = torch.empty(_lib.lib().sr_rowdot_scratch_floats(rows, inner), dtype=a.dtype, device=a.device)
+    native(a).sr_rowdot(dots, out, a, b, scale, rows, inner, scratch)
     return dots, out
 
 
@@ -330,14 +307,9 @@ class _RowDot(Function):
             ga = torch.empty_like(a) if need_a else None
             gb = torch.empty_like(b) if need_b else None
             gs = torch.empty(a.shape[:2], dtype=a.dtype, device=a.device) if (need_s and go_c is not None) else None
-            L = _lib.lib()
-            scratch = (torch.empty(L.sr_rowdot_scratch_floats(rows, inner), dtype=a.dtype, device=a.device)
+            scratch = (torch.empty(_lib.lib().sr_rowdot_scratch_floats(rows, inner), dtype=a.dtype, device=a.device)
                        if gs is not None else None)
-            with on_device_of(a):
-                rc = L.sr_rowdot_bwd(_lib.ptr(ga), _lib.ptr(gb), _lib.ptr(gs), _lib.ptr(a), _lib.ptr(b), _lib.ptr(gd_c),
-                                     _lib.ptr(go_c), _lib.ptr(scale) if go_c is not None else None, rows, inner,
-                                     _lib.ptr(scratch), stream_of(a))
-            _lib.check(rc, "sr_rowdot_bwd")
+            native(a).sr_rowdot_bwd(ga, gb, gs, a, b, gd_c, go_c, scale if go_c is not None else None, rows, inner, scratch)
             return ga, gb, gs
         ga = gd[:, :, None, None] * b
         gb = gd[:, :, None, None] * a
@@ -369,10 +341,6 @@ def rowdot_div(a, b, div):
     rows = a.size(0) * a.size(1)
     inner = a.numel() // max(rows, 1)
     dots = torch.empty(a.shape[:2], dtype=a.dtype, device=a.device)
-    L = _lib.lib()
-    scratch = torch.empty(L.sr_rowdot_scratch_floats(rows, inner), dtype=a.dtype, device=a.device)
-    with on_device_of(a):
-        rc = L.sr_rowdot_div(_lib.ptr(dots), _lib.ptr(a), _lib.ptr(b), _lib.ptr(div), rows, inner, _lib.ptr(scratch),
-                             stream_of(a))
-    _lib.check(rc, "sr_rowdot_div")
+    scratch = torch.empty(_lib.lib().sr_rowdot_scratch_floats(rows, inner), dtype=a.dtype, device=a.device)
+    native(a).sr_rowdot_div(dots, a, b, div, rows, inner, scratch)
     return dots

@@ -14,9 +14,8 @@ import ctypes
 
 import torch
 
-from .. import _lib
 from . import ppl as _ppl
-from ._dispatch import on_device_of, require_f32, stream_of
+from ._dispatch import native, require_f32
 
 POOL = {"max3s2": 0, "avg3s1": 1, "max3s1": 2}
 
@@ -58,10 +57,7 @@ def conv(x, f, segs=None):
     m0 = (ctypes.c_int64 * n)(*[s[1] for s in segs])
     coff = (ctypes.c_int64 * n)(*[s[2] for s in segs])
     ctot = (ctypes.c_int64 * n)(*[s[0].shape[1] for s in segs])
-    with on_device_of(x):
-        rc = _lib.lib().sr_incep_conv(_lib.ptr(x), _lib.ptr(f.wt), _lib.ptr(f.bias), b, c, h, w, f.m, f.kh, f.kw,
-                                      f.stride, f.ph, f.pw, n, outs, m0, coff, ctot, stream_of(x))
-    _lib.check(rc, "sr_incep_conv")
+    native(x).sr_incep_conv(x, f.wt, f.bias, b, c, h, w, f.m, f.kh, f.kw, f.stride, f.ph, f.pw, n, outs, m0, coff, ctot)
     return ret
 
 
@@ -76,10 +72,7 @@ def pool(x, mode, out=None, coff=0):
     if (not out.is_contiguous() or out.device != x.device or out.dim() != 4 or out.shape[0] != b
             or tuple(out.shape[2:]) != (oh, ow) or out.dtype != torch.float32):
         raise ValueError("inception pool: destination must be contiguous float32 [%d, *, %d, %d]" % (b, oh, ow))
-    with on_device_of(x):
-        rc = _lib.lib().sr_incep_pool(_lib.ptr(out), _lib.ptr(x), b, c, h, w, POOL[mode], coff, out.shape[1],
-                                      stream_of(x))
-    _lib.check(rc, "sr_incep_pool")
+    native(x).sr_incep_pool(out, x, b, c, h, w, POOL[mode], coff, out.shape[1])
     return ret
 
 
@@ -88,9 +81,7 @@ def gap(x):
     x = x.contiguous()
     b, c, h, w = x.shape
     out = torch.empty(b, c, dtype=x.dtype, device=x.device)
-    with on_device_of(x):
-        rc = _lib.lib().sr_incep_gap(_lib.ptr(out), _lib.ptr(x), b * c, h * w, stream_of(x))
-    _lib.check(rc, "sr_incep_gap")
+    native(x).sr_incep_gap(out, x, b * c, h * w)
     return out
 
 
@@ -105,18 +96,12 @@ def stats_update(total, gram, shift, feat, first):
     require_f32(feat, "feature stats")
     feat = feat.contiguous()
     n, d = feat.shape
-    with on_device_of(feat):
-        rc = _lib.lib().sr_fstats_update(_lib.ptr(total), _lib.ptr(gram), _lib.ptr(shift), _lib.ptr(feat), n, d,
-                                         1 if first else 0, stream_of(feat))
-    _lib.check(rc, "sr_fstats_update")
+    native(feat).sr_fstats_update(total, gram, shift, feat, n, d, 1 if first else 0)
 
 
 def stats_finalize(total, gram, shift, count):
     d = total.numel()
     mean = torch.empty(d, dtype=torch.float64, device=total.device)
     cov = torch.empty(d, d, dtype=torch.float64, device=total.device)
-    with on_device_of(total):
-        rc = _lib.lib().sr_fstats_finalize(_lib.ptr(mean), _lib.ptr(cov), _lib.ptr(total), _lib.ptr(gram),
-                                           _lib.ptr(shift), count, d, stream_of(total))
-    _lib.check(rc, "sr_fstats_finalize")
+    native(total).sr_fstats_finalize(mean, cov, total, gram, shift, count, d)
     return mean, cov

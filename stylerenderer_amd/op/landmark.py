@@ -37,8 +37,7 @@ import numpy as np
 import torch
 from torch.autograd import Function
 
-from .. import _lib
-from ._dispatch import DerivedCache, host_array, is_device_tensor, on_device_of, stream_of
+from ._dispatch import DerivedCache, host_array, is_device_tensor, native
 
 TINY = 1e-12
 
@@ -118,10 +117,8 @@ def landmark_backward(g, g_rows, lists, nv, size, out=None):
     gv = torch.empty((b, nv, 3), dtype=g.dtype, device=g.device) if out is None else out
     if out is not None and (tuple(out.shape) != (b, nv, 3) or not out.is_contiguous() or out.dtype != g.dtype):
         raise ValueError("landmark_backward: out must be a contiguous float32 [B, nv, 3]")
-    with on_device_of(g):
-        _lib.check(_lib.lib().sr_landmark_loss_bwd(_lib.ptr(gv), _lib.ptr(g), _lib.ptr(gr), gr.stride(0) if b > 1 else 0,
-                                                   _lib.ptr(off), _lib.ptr(cl), _lib.ptr(cw), b, n_l, nv, h, w,
-                                                   int(out is not None), stream_of(g)), "sr_landmark_loss_bwd")
+    native(g).sr_landmark_loss_bwd(gv, g, gr, gr.stride(0) if b > 1 else 0, off, cl, cw, b, n_l, nv, h, w,
+                                   int(out is not None))
     return gv
 
 
@@ -136,11 +133,8 @@ def landmark_forward(v, idx, bary, target, conf, size, beta=1.0, weight=1.0):
     rows = torch.empty((b,), dtype=vc.dtype, device=vc.device)
     p = torch.empty((b, n_l, 2), dtype=vc.dtype, device=vc.device)
     g = torch.empty_like(p)
-    ptr = _lib.ptr
-    with on_device_of(vc):
-        _lib.check(_lib.lib().sr_landmark_loss_fwd(ptr(rows), ptr(p), ptr(g), ptr(vc), ptr(lists[3]), ptr(lists[4]),
-                                                   ptr(q), ptr(c), b, n_l, nv, h, w, float(beta), float(weight),
-                                                   stream_of(vc)), "sr_landmark_loss_fwd")
+    native(vc).sr_landmark_loss_fwd(rows, p, g, vc, lists[3], lists[4], q, c, b, n_l, nv, h, w, float(beta),
+                                    float(weight))
     return rows, p, g, lists
 
 
@@ -393,13 +387,10 @@ def landmark_dynamic_forward(v, idx, bary, target, conf, size, beta=1.0, weight=
     new = lambda shape, dt=vc.dtype: torch.empty(shape, dtype=dt, device=vc.device)              # noqa: E731
     rows, p, g, sel, gate = new((b,)), new((b, n_l, 2)), new((b, n_l, 2)), new((b, n_c), torch.int32), new((b, n_l))
     lo, hi = vis if vis is not None else (0.0, 0.0)
-    ptr = _lib.ptr
-    with on_device_of(vc):
-        _lib.check(_lib.lib().sr_landmark_dyn_fwd(
-            ptr(rows), ptr(p), ptr(g), ptr(sel), ptr(gate), ptr(vc), None if nc is None else ptr(nc), ptr(t["idx"]),
-            ptr(t["bary"]), ptr(q), ptr(c), ptr(t["lmk_line"]), ptr(t["side"]), ptr(t["cand_off"]), ptr(t["cand"]), b,
-            n_l, n_c, nv, t["axis"][0], t["axis"][1], int(vis is not None), float(lo), float(hi), h, w, float(beta),
-            float(weight), stream_of(vc)), "sr_landmark_dyn_fwd")
+    native(vc).sr_landmark_dyn_fwd(rows, p, g, sel, gate, vc, nc, t["idx"], t["bary"], q, c,
+                                   t["lmk_line"], t["side"], t["cand_off"], t["cand"], b, n_l, n_c, nv, t["axis"][0],
+                                   t["axis"][1], int(vis is not None), float(lo), float(hi), h, w, float(beta),
+                                   float(weight))
     return rows, p, g, sel, gate, t
 
 
@@ -412,12 +403,9 @@ def landmark_dynamic_backward(g, g_rows, sel, lists, nv, size, out=None):
     gv = torch.empty((b, nv, 3), dtype=g.dtype, device=g.device) if out is None else out
     if out is not None and (tuple(out.shape) != (b, nv, 3) or not out.is_contiguous() or out.dtype != g.dtype):
         raise ValueError("landmark_dynamic_backward: out must be a contiguous float32 [B, nv, 3]")
-    t, ptr = lists, _lib.ptr
-    with on_device_of(g):
-        _lib.check(_lib.lib().sr_landmark_dyn_bwd(
-            ptr(gv), ptr(g), ptr(gr), gr.stride(0) if b > 1 else 0, ptr(sel), ptr(t["off"]), ptr(t["l"]), ptr(t["w"]),
-            ptr(t["line_off"]), ptr(t["line_c"]), ptr(t["line_l"]), b, n_l, t["n_lines"], nv, h, w, int(out is not None),
-            stream_of(g)), "sr_landmark_dyn_bwd")
+    t = lists
+    native(g).sr_landmark_dyn_bwd(gv, g, gr, gr.stride(0) if b > 1 else 0, sel, t["off"], t["l"], t["w"], t["line_off"],
+                                  t["line_c"], t["line_l"], b, n_l, t["n_lines"], nv, h, w, int(out is not None))
     return gv
 
 

@@ -11,7 +11,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
-from ._dispatch import on_device_of, require_f32, stream_of
+from ._dispatch import native, require_f32
 
 EPS = 1e-10
 
@@ -57,13 +57,9 @@ class _LpipsLayer(Function):
         b, c, h, w = f0.shape
         hw = h * w
         d = torch.empty(b, dtype=f0.dtype, device=f0.device)
-        L = _lib.lib()
-        scratch = torch.empty(L.sr_lpips_layer_scratch_floats(b, hw), dtype=f0.dtype, device=f0.device)
+        scratch = torch.empty(_lib.lib().sr_lpips_layer_scratch_floats(b, hw), dtype=f0.dtype, device=f0.device)
         ctx.bstride = c * hw if t.shape[0] == b else 0            # (one target for the whole batch: stride 0)
-        with on_device_of(f0):
-            rc = L.sr_lpips_layer_fwd(_lib.ptr(d), _lib.ptr(f0), _lib.ptr(t), _lib.ptr(lin), b, c, hw, ctx.bstride,
-                                      EPS, _lib.ptr(scratch), stream_of(f0))
-        _lib.check(rc, "sr_lpips_layer_fwd")
+        native(f0).sr_lpips_layer_fwd(d, f0, t, lin, b, c, hw, ctx.bstride, EPS, scratch)
         ctx.save_for_backward(f0, t, lin)
         return d.view(b, 1, 1, 1)
 
@@ -74,10 +70,7 @@ class _LpipsLayer(Function):
         b, c, h, w = f0.shape
         gd = gd.reshape(b).contiguous()
         gf = torch.empty_like(f0)
-        with on_device_of(f0):
-            rc = _lib.lib().sr_lpips_layer_bwd(_lib.ptr(gf), _lib.ptr(gd), _lib.ptr(f0), _lib.ptr(t), _lib.ptr(lin), b, c,
-                                               h * w, ctx.bstride, EPS, stream_of(f0))
-        _lib.check(rc, "sr_lpips_layer_bwd")
+        native(f0).sr_lpips_layer_bwd(gf, gd, f0, t, lin, b, c, h * w, ctx.bstride, EPS)
         return gf, None, None
 
 
@@ -92,9 +85,7 @@ class _MSE(Function):
     def forward(ctx, a, b):
         a, b = a.contiguous(), b.contiguous()
         out = torch.empty((), dtype=a.dtype, device=a.device)
-        with on_device_of(a):
-            rc = _lib.lib().sr_mse_fwd(_lib.ptr(out), _lib.ptr(a), _lib.ptr(b), a.numel(), stream_of(a))
-        _lib.check(rc, "sr_mse_fwd")
+        native(a).sr_mse_fwd(out, a, b, a.numel())
         ctx.save_for_backward(a, b)
         return out
 
@@ -103,9 +94,7 @@ class _MSE(Function):
     def backward(ctx, g):
         a, b = ctx.saved_tensors
         ga = torch.empty_like(a)
-        with on_device_of(a):
-            rc = _lib.lib().sr_mse_bwd(_lib.ptr(ga), _lib.ptr(g.contiguous()), _lib.ptr(a), _lib.ptr(b), a.numel(), stream_of(a))
-        _lib.check(rc, "sr_mse_bwd")
+        native(a).sr_mse_bwd(ga, g.contiguous(), a, b, a.numel())
         return ga, None
 
 
@@ -126,9 +115,7 @@ class _MaxPool2(Function):
         x = x.contiguous()
         b, c, h, w = x.shape
         out = torch.empty((b, c, h // 2, w // 2), dtype=x.dtype, device=x.device)
-        with on_device_of(x):
-            rc = _lib.lib().sr_maxpool2_fwd(_lib.ptr(out), _lib.ptr(x), b * c, h, w, stream_of(x))
-        _lib.check(rc, "sr_maxpool2_fwd")
+        native(x).sr_maxpool2_fwd(out, x, b * c, h, w)
         ctx.save_for_backward(x)
         return out
 
@@ -138,9 +125,7 @@ class _MaxPool2(Function):
         (x,) = ctx.saved_tensors
         b, c, h, w = x.shape
         gx = torch.empty_like(x)
-        with on_device_of(x):
-            rc = _lib.lib().sr_maxpool2_bwd(_lib.ptr(gx), _lib.ptr(g.contiguous()), _lib.ptr(x), b * c, h, w, stream_of(x))
-        _lib.check(rc, "sr_maxpool2_bwd")
+        native(x).sr_maxpool2_bwd(gx, g.contiguous(), x, b * c, h, w)
         return gx
 
 
@@ -163,11 +148,8 @@ class _MSERows(Function):
         b = a.shape[0]
         n = a.numel() // b
         out = torch.empty(b, dtype=a.dtype, device=a.device)
-        L = _lib.lib()
-        scratch = torch.empty(L.sr_mse_rows_scratch_floats(b, n), dtype=a.dtype, device=a.device)
-        with on_device_of(a):
-            rc = L.sr_mse_rows_fwd(_lib.ptr(out), _lib.ptr(a), _lib.ptr(t), b, n, _lib.ptr(scratch), stream_of(a))
-        _lib.check(rc, "sr_mse_rows_fwd")
+        scratch = torch.empty(_lib.lib().sr_mse_rows_scratch_floats(b, n), dtype=a.dtype, device=a.device)
+        native(a).sr_mse_rows_fwd(out, a, t, b, n, scratch)
         ctx.save_for_backward(a, t)
         return out
 
@@ -177,10 +159,7 @@ class _MSERows(Function):
         a, t = ctx.saved_tensors
         b = a.shape[0]
         ga = torch.empty_like(a)
-        with on_device_of(a):
-            rc = _lib.lib().sr_mse_rows_bwd(_lib.ptr(ga), _lib.ptr(g.contiguous()), _lib.ptr(a), _lib.ptr(t), b,
-                                            a.numel() // b, stream_of(a))
-        _lib.check(rc, "sr_mse_rows_bwd")
+        native(a).sr_mse_rows_bwd(ga, g.contiguous(), a, t, b, a.numel() // b)
         return ga, None
 
 
@@ -207,11 +186,8 @@ class _FitLossRows(Function):
         m = mse.contiguous()
         c = coeff.detach().contiguous() if coeff is not None else None
         s = sigma.detach().contiguous() if sigma is not None else None
-        with on_device_of(m):
-            rc = _lib.lib().sr_fit_loss_rows(_lib.ptr(rows), _lib.ptr(total), *[_lib.ptr(t) for t in d], _lib.ptr(m),
-                                             float(pixel_weight), _lib.ptr(c), _lib.ptr(s), float(shape_reg), b,
-                                             c.shape[1] if c is not None else 0, stream_of(m))
-        _lib.check(rc, "sr_fit_loss_rows")
+        native(m).sr_fit_loss_rows(rows, total, *d, m, float(pixel_weight), c, s, float(shape_reg), b,
+                                   c.shape[1] if c is not None else 0)
         ctx.mark_non_differentiable(rows)
         ctx.pixel_weight = float(pixel_weight)
         ctx.layer_shapes = [t.shape for t in layers]
@@ -227,10 +203,7 @@ class _FitLossRows(Function):
         b = ctx.layer_shapes[0][0]
         gd = torch.empty(b, dtype=g_total.dtype, device=g_total.device)
         gm = torch.empty_like(gd)
-        with on_device_of(gd):
-            rc = _lib.lib().sr_fit_loss_rows_bwd(_lib.ptr(gd), _lib.ptr(gm), _lib.ptr(g_total.contiguous()),
-                                                 ctx.pixel_weight, b, stream_of(gd))
-        _lib.check(rc, "sr_fit_loss_rows_bwd")
+        native(gd).sr_fit_loss_rows_bwd(gd, gm, g_total.contiguous(), ctx.pixel_weight, b)
         greg = g_total if ctx.has_reg else None
         return (None, None, None, None, gm, greg) + tuple(gd.view(s) for s in ctx.layer_shapes)
 

@@ -20,7 +20,7 @@ from torch.autograd import Function
 
 from .. import _lib, utils_3d
 from . import _mesh_node
-from ._dispatch import on_device_of, stream_of
+from ._dispatch import native
 from ._mesh_node import EPS
 
 
@@ -43,11 +43,9 @@ class _Morph(Function):
         w, bs, sg = weight.contiguous(), bias.contiguous(), sigma.contiguous()
         b, d = c.shape
         nv = bs.numel() // 3
-        ptr = _lib.ptr
 
-        def model_fwd(L, st, v, vs, reg, lin):
-            _lib.check(L.sr_morph_fwd(ptr(v), ptr(vs), ptr(reg), ptr(w), ptr(bs), ptr(c), ptr(lin), ptr(p), ptr(sg),
-                                      float(reg_weight), b, nv, d, st), "sr_morph_fwd")
+        def model_fwd(run, v, vs, reg, lin):
+            run.sr_morph_fwd(v, vs, reg, w, bs, c, lin, p, sg, float(reg_weight), b, nv, d)
 
         v, n, reg, mesh, _ = _mesh_node.forward(c, p, tri, nv, model_fwd)
         ctx.save_for_backward(c, w, sg, *mesh)
@@ -59,14 +57,12 @@ class _Morph(Function):
         c, w, sg, *mesh = ctx.saved_tensors
         (b, d), rows = c.shape, ctx.rows
         greg = greg.contiguous()
-        ptr = _lib.ptr
 
-        def model_bwd(L, st, gvs):
-            scratch = torch.empty(max(1, int(L.sr_morph_gcoeff_scratch_floats(rows, b, d))), dtype=c.dtype,
+        def model_bwd(run, gvs):
+            scratch = torch.empty(max(1, int(_lib.lib().sr_morph_gcoeff_scratch_floats(rows, b, d))), dtype=c.dtype,
                                   device=c.device)
             gcoeff = torch.empty_like(c)
-            _lib.check(L.sr_morph_gcoeff(ptr(gcoeff), ptr(scratch), ptr(w), ptr(gvs), ptr(c), ptr(sg), ctx.reg_weight,
-                                         ptr(greg), b, rows, d, st), "sr_morph_gcoeff")
+            run.sr_morph_gcoeff(gcoeff, scratch, w, gvs, c, sg, ctx.reg_weight, greg, b, rows, d)
             return gcoeff
 
         return _mesh_node.backward(ctx.needs_input_grad, mesh, gv, gn, model_bwd) + (None,) * 5
@@ -94,13 +90,7 @@ def vertex_normals_backward(v, tri, g):
     ns = torch.empty_like(vc)
     normc = torch.empty((b, nv), dtype=vc.dtype, device=vc.device)
     out = torch.empty_like(vc)
-    L = _lib.lib()
-    st = stream_of(vc)
-    ptr = _lib.ptr
-    with on_device_of(vc):
-        _lib.check(L.sr_vertex_normals_f32(ptr(ns), ptr(normc), ptr(vc), ptr(tric), ptr(off), ptr(adj), b, nv,
-                                           tric.size(0), EPS, st), "sr_vertex_normals_f32")
-        _lib.check(L.sr_vertex_normals_bwd_f32(ptr(out), None, ptr(gc), None, None, ptr(vc), ptr(ns), ptr(normc),
-                                               ptr(tric), ptr(off), ptr(adj), b, nv, tric.size(0), EPS, st),
-                   "sr_vertex_normals_bwd_f32")
+    run = native(vc)
+    run.sr_vertex_normals_f32(ns, normc, vc, tric, off, adj, b, nv, tric.size(0), EPS)
+    run.sr_vertex_normals_bwd_f32(out, None, gc, None, None, vc, ns, normc, tric, off, adj, b, nv, tric.size(0), EPS)
     return out

@@ -12,7 +12,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from ._dispatch import on_device_of, require_f32, stream_of
+from ._dispatch import native, require_f32
 
 MODES = {"w": 0, "z": 1}
 
@@ -26,10 +26,7 @@ def endpoints(a, b, t, mode, eps=0.0, n_ends=2, in_stride=None):
     in_stride = d if in_stride is None else in_stride
     t = t.reshape(-1).contiguous()
     out = torch.empty(npairs * n_ends, d, dtype=a.dtype, device=a.device)
-    with on_device_of(a):
-        rc = _lib.lib().sr_ppl_endpoints(_lib.ptr(out), _lib.ptr(a), _lib.ptr(b), in_stride, _lib.ptr(t), npairs, d,
-                                         MODES[mode], n_ends, float(eps), stream_of(a))
-    _lib.check(rc, "sr_ppl_endpoints")
+    native(a).sr_ppl_endpoints(out, a, b, in_stride, t, npairs, d, MODES[mode], n_ends, float(eps))
     return out
 
 
@@ -62,10 +59,7 @@ def prep(img, shift, scale, window, size):
     out = torch.empty(n, 3, oh, ow, dtype=img.dtype, device=img.device)
     shift = shift.reshape(-1).to(img.device, torch.float32).contiguous()
     scale = scale.reshape(-1).to(img.device, torch.float32).contiguous()
-    with on_device_of(img):
-        rc = _lib.lib().sr_ppl_prep(_lib.ptr(out), _lib.ptr(img), _lib.ptr(shift), _lib.ptr(scale), n, h, w, y0, x0, ch,
-                                    cw, oh, ow, stream_of(img))
-    _lib.check(rc, "sr_ppl_prep")
+    native(img).sr_ppl_prep(out, img, shift, scale, n, h, w, y0, x0, ch, cw, oh, ow)
     return out
 
 
@@ -86,10 +80,7 @@ def lpips_pair(feats, lins, div):
     fp = (ctypes.c_void_p * nl)(*[f.data_ptr() for f in feats])
     lp = (ctypes.c_void_p * nl)(*[l.data_ptr() for l in lins])
     dev = feats[0].device
-    L = _lib.lib()
-    scratch = torch.empty(L.sr_lpips_pair_scratch_floats(npairs, nl, hw), dtype=torch.float32, device=dev)
+    scratch = torch.empty(_lib.lib().sr_lpips_pair_scratch_floats(npairs, nl, hw), dtype=torch.float32, device=dev)
     d = torch.empty(npairs, dtype=torch.float32, device=dev)
-    with on_device_of(feats[0]):
-        rc = L.sr_lpips_pair(_lib.ptr(d), fp, lp, c, hw, nl, npairs, float(div), _lib.ptr(scratch), stream_of(feats[0]))
-    _lib.check(rc, "sr_lpips_pair")
+    native(feats[0]).sr_lpips_pair(d, fp, lp, c, hw, nl, npairs, float(div), scratch)
     return d

@@ -26,7 +26,7 @@ import torch
 from torch.autograd import Function
 
 from .. import _lib
-from ._dispatch import DerivedCache, is_device_tensor, on_device_of, stream_of
+from ._dispatch import DerivedCache, is_device_tensor, native
 
 
 def _geometry(vertices, triangles):
@@ -111,13 +111,9 @@ def _forward_impl(vertices, triangles, height, width, perspective, eps, tex=None
         attr = torch.empty((b, tex_c, h, w) if chw else (b, h, w, tex_c), dtype=dt, device=dev)
     work = torch.empty(L.sr_rasterize_scratch_bytes(b, nf, h, w, int(suf == "f64")), dtype=torch.uint8,
                        device=dev)
-    with on_device_of(vertices):
-        rc = getattr(L, "sr_rasterize_forward_" + suf)(
-            b, nv, nf, h, w, int(rv), int(rf), int(bool(perspective)) | (SR_RASTER_CHW if chw else 0), _lib.ptr(vertices),
-            _lib.ptr(triangles), _lib.ptr(index), _lib.ptr(coeff), _lib.ptr(zbuf), abs(float(eps)),
-            _lib.ptr(tex_flat), tex_c, _lib.ptr(attr), _lib.ptr(win), _lib.ptr(big), _lib.ptr(work),
-            stream_of(vertices))
-    _lib.check(rc, "sr_rasterize_forward")
+    getattr(native(vertices), "sr_rasterize_forward_" + suf)(
+        b, nv, nf, h, w, int(rv), int(rf), int(bool(perspective)) | (SR_RASTER_CHW if chw else 0), vertices, triangles,
+        index, coeff, zbuf, abs(float(eps)), tex_flat, tex_c, attr, win, big, work)
     if rv and rf:
         index = index[0] if index is not None else None
         coeff = coeff[0] if coeff is not None else None
@@ -161,11 +157,8 @@ def backward(vertices, index, perspective=False, eps=1e-9):
             abs(float(eps)))
         _lib.check(rc, "sr_rasterize_backward_cpu")
         return dcoeff
-    with on_device_of(vertices):
-        rc = getattr(_lib.lib(), "sr_rasterize_backward_" + suf)(
-            b, n, h, w, int(rv), int(bool(perspective)), _lib.ptr(vertices), _lib.ptr(index),
-            _lib.ptr(dcoeff), abs(float(eps)), stream_of(vertices))
-    _lib.check(rc, "sr_rasterize_backward")
+    getattr(native(vertices), "sr_rasterize_backward_" + suf)(b, n, h, w, int(rv), int(bool(perspective)), vertices, index,
+                                                              dcoeff, abs(float(eps)))
     return dcoeff
 
 
@@ -236,15 +229,12 @@ def _device_grad(v, tex, tri, win, big, grad_out, chw, perspective, eps, no_chan
         grad_v = torch.empty_like(v) if need_v else None
         grad_t = torch.empty_like(tex_c) if need_t else None
     off, adj, off_bs, adj_bs, slot = incidence(tri, nv)
-    L = _lib.lib()
-    work = torch.empty(L.sr_rasterize_grad_scratch_bytes(b, nf, c, int(suf == "f64")), dtype=torch.uint8, device=v.device)
+    work = torch.empty(_lib.lib().sr_rasterize_grad_scratch_bytes(b, nf, c, int(suf == "f64")), dtype=torch.uint8,
+                       device=v.device)
     flags = int(bool(perspective)) | (SR_RASTER_CHW if chw else 0) | (SR_RASTER_GRAD_ACC if into is not None else 0)
-    with on_device_of(v):
-        rc = getattr(L, "sr_rasterize_grad_" + suf)(
-            b, nv, nf, h, w, int(tri.dim() == 2), flags, _lib.ptr(v), _lib.ptr(tex_c), c,
-            _lib.ptr(tri), _lib.ptr(win), _lib.ptr(big), _lib.ptr(go), _lib.ptr(off), _lib.ptr(adj), off_bs, adj_bs,
-            _lib.ptr(slot), _lib.ptr(grad_v), _lib.ptr(grad_t), abs(float(eps)), _lib.ptr(work), stream_of(v))
-    _lib.check(rc, "sr_rasterize_grad")
+    getattr(native(v), "sr_rasterize_grad_" + suf)(b, nv, nf, h, w, int(tri.dim() == 2), flags, v, tex_c, c, tri, win, big,
+                                                   go, off, adj, off_bs, adj_bs, slot, grad_v, grad_t, abs(float(eps)),
+                                                   work)
     return grad_v, grad_t
 
 
@@ -345,12 +335,11 @@ def _forward_levels(v, tex, tri, sizes, perspective, eps, want_win, chw):
         total += (sz + 255) // 256 * 256
     work = torch.empty(total, dtype=torch.uint8, device=dev)
     pa = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in ts])      # noqa: E731
-    with on_device_of(v):
-        rc = L.sr_rasterize_forward_levels_f32(
-            n, b, nv, nf, hs, ws, int(rv), int(rf), int(bool(perspective)) | (SR_RASTER_CHW if chw else 0), _lib.ptr(v),
-            _lib.ptr(tri), abs(float(eps)), _lib.ptr(tex_flat), tex_c, pa(attrs), pa(wins) if want_win else None,
-            pa(bigs) if want_win else None, (ctypes.c_void_p * n)(*[work.data_ptr() + o for o in offs]), stream_of(v))
-    _lib.check(rc, "sr_rasterize_forward_levels_f32")
+    native(v).sr_rasterize_forward_levels_f32(n, b, nv, nf, hs, ws, int(rv), int(rf),
+                                              int(bool(perspective)) | (SR_RASTER_CHW if chw else 0), v, tri,
+                                              abs(float(eps)), tex_flat, tex_c, pa(attrs),
+                                              pa(wins) if want_win else None, pa(bigs) if want_win else None,
+                                              (ctypes.c_void_p * n)(*[work.data_ptr() + o for o in offs]))
     states = []
     for wn, bg in zip(wins, bigs):
         states += [wn, bg]
@@ -381,13 +370,11 @@ def _grad_levels(v, tex, tri, wins, bigs, grads, chw, perspective, eps, need_v, 
     pa = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])                                   # noqa: E731
     hs = (ctypes.c_int64 * n)(*[int(w.shape[-2]) for w in wins])
     ws = (ctypes.c_int64 * n)(*[int(w.shape[-1]) for w in wins])
-    with on_device_of(v):
-        rc = L.sr_rasterize_grad_levels_f32(
-            n, b, nv, nf, hs, ws, int(tri.dim() == 2), int(bool(perspective)) | (SR_RASTER_CHW if chw else 0), _lib.ptr(v),
-            _lib.ptr(tex_c), c, _lib.ptr(tri), pa(wins), pa(bigs), pa(gos), _lib.ptr(off), _lib.ptr(adj), off_bs, adj_bs,
-            _lib.ptr(slot), _lib.ptr(grad_v), _lib.ptr(grad_t), abs(float(eps)),
-            (ctypes.c_void_p * n)(*[work.data_ptr() + per * k for k in range(n)]), stream_of(v))
-    _lib.check(rc, "sr_rasterize_grad_levels_f32")
+    native(v).sr_rasterize_grad_levels_f32(n, b, nv, nf, hs, ws, int(tri.dim() == 2),
+                                           int(bool(perspective)) | (SR_RASTER_CHW if chw else 0), v, tex_c, c, tri,
+                                           pa(wins), pa(bigs), pa(gos), off, adj, off_bs, adj_bs, slot, grad_v, grad_t,
+                                           abs(float(eps)),
+                                           (ctypes.c_void_p * n)(*[work.data_ptr() + per * k for k in range(n)]))
     return grad_v, grad_t
 
 

@@ -33,8 +33,7 @@ import numpy as np
 import torch
 from torch.autograd import Function
 
-from .. import _lib
-from ._dispatch import host_array, is_device_tensor, on_device_of, stream_of
+from ._dispatch import host_array, is_device_tensor, native
 
 LIMIT = 1 << 20                 # |coordinate| of a point, and H, W
 MAX_GROW = 32
@@ -144,9 +143,7 @@ def fill_triangles(points, tris, size_hw):
     ti = ti.to(pi.device)
     n_t = int(ti.shape[-2])
     out = torch.empty((b, 1, h, w), dtype=torch.uint8, device=pi.device)
-    with on_device_of(pi):
-        _lib.check(_lib.lib().sr_region_fill(_lib.ptr(out), _lib.ptr(pi), _lib.ptr(ti), 3 * n_t if ti.dim() == 3 else 0,
-                                             b, n_p, n_t, h, w, stream_of(pi)), "sr_region_fill")
+    native(pi).sr_region_fill(out, pi, ti, 3 * n_t if ti.dim() == 3 else 0, b, n_p, n_t, h, w)
     return out
 
 
@@ -186,9 +183,7 @@ def grow(mask_u8, r):
     m = (m != 0).to(torch.uint8).contiguous()
     h, w = int(m.shape[-2]), int(m.shape[-1])
     out = torch.empty_like(m)
-    with on_device_of(m):
-        _lib.check(_lib.lib().sr_region_grow(_lib.ptr(out), _lib.ptr(m), m.numel() // (h * w), h, w, r, stream_of(m)),
-                   "sr_region_grow")
+    native(m).sr_region_grow(out, m, m.numel() // (h * w), h, w, r)
     return out
 
 
@@ -280,11 +275,8 @@ def blend_forward(img, target, mask, normal_map=None, thresh=1e-3):
     y = torch.empty_like(x)
     m_eff = torch.empty_like(m)
     ns = (0, 0, 0, 0) if normal_map is None else tuple(int(s) for s in normal_map.stride())
-    with on_device_of(x):
-        _lib.check(_lib.lib().sr_region_blend_fwd(_lib.ptr(y), _lib.ptr(m_eff), _lib.ptr(x), _lib.ptr(t), _lib.ptr(m),
-                                                  None if normal_map is None else _lib.ptr(normal_map), ns[0], ns[1],
-                                                  ns[2], ns[3], float(thresh), b, c, h, w, stream_of(x)),
-                   "sr_region_blend_fwd")
+    native(x).sr_region_blend_fwd(y, m_eff, x, t, m, normal_map, ns[0], ns[1], ns[2],
+                                  ns[3], float(thresh), b, c, h, w)
     return y, m_eff
 
 
@@ -293,9 +285,7 @@ def blend_backward(g_y, m_eff):
     g = g_y.contiguous()
     b, c, h, w = g.shape
     out = torch.empty_like(g)
-    with on_device_of(g):
-        _lib.check(_lib.lib().sr_region_blend_bwd(_lib.ptr(out), _lib.ptr(g), _lib.ptr(m_eff), b, c, h, w, stream_of(g)),
-                   "sr_region_blend_bwd")
+    native(g).sr_region_blend_bwd(out, g, m_eff, b, c, h, w)
     return out
 
 

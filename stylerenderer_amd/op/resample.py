@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ._dispatch import DerivedCache, on_device_of, stream_of
+from ._dispatch import DerivedCache, native
 
 PRECISION_BITS = 32 - 8 - 2
 ROUND = 1 << (PRECISION_BITS - 1)
@@ -203,7 +203,6 @@ def _resize_host(a, oh, ow, name, window):
 def _resize_device(x, oh, ow, name, window, form, force_mul32=False):
     n, h, w, c = x.shape
     oy0, ox0, wh, ww = window
-    L = _lib.lib()
     kh = bh = kv = bv = None
     bh_host = bv_host = None
     ksh = ksv = 0
@@ -216,7 +215,7 @@ def _resize_device(x, oh, ow, name, window, form, force_mul32=False):
         ck, cb, f24 = _tables(h, oh, name)
         kv, bv = _device_tables(h, oh, name, x.device, False)
         bv_host, ksv, fits = cb.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ck.shape[1], fits and f24
-    need = L.sr_resample_u8_scratch_bytes(n, h, w, c, oh, ow, bv_host, oy0, ox0, wh, ww)
+    need = _lib.lib().sr_resample_u8_scratch_bytes(n, h, w, c, oh, ow, bv_host, oy0, ox0, wh, ww)
     if need < 0:
         raise ValueError("resample: unsupported sizes %s -> %s" % ((n, h, w, c), (oh, ow)))
     scratch = torch.empty(need, dtype=torch.uint8, device=x.device) if need else None
@@ -224,11 +223,8 @@ def _resize_device(x, oh, ow, name, window, form, force_mul32=False):
         out = torch.empty((n, wh, ww, c), dtype=torch.uint8, device=x.device)
     else:
         out = torch.empty((n, c, wh, ww), dtype=torch.float32, device=x.device)
-    with on_device_of(x):
-        rc = L.sr_resample_u8(_lib.ptr(out), _lib.ptr(x), n, h, w, c, oh, ow, _lib.ptr(kh), _lib.ptr(bh), bh_host, ksh,
-                              _lib.ptr(kv), _lib.ptr(bv), bv_host, ksv, oy0, ox0, wh, ww, form,
-                              1 if fits and not force_mul32 else 0, _lib.ptr(scratch), stream_of(x))
-    _lib.check(rc, "sr_resample_u8")
+    native(x).sr_resample_u8(out, x, n, h, w, c, oh, ow, kh, bh, bh_host, ksh, kv, bv, bv_host, ksv, oy0, ox0, wh, ww,
+                             form, 1 if fits and not force_mul32 else 0, scratch)
     return out
 
 

@@ -15,8 +15,7 @@ does not take (float64) raises.
 """
 import torch
 
-from .. import _lib
-from ._dispatch import is_device_tensor, on_device_of, stream_of, strict_native
+from ._dispatch import is_device_tensor, native, strict_native
 
 
 def share_rows_host_(g, k):
@@ -44,6 +43,5 @@ def share_rows_(g, k):
         if is_device_tensor(g) and strict_native():
             raise RuntimeError("share_rows_: SR_STRICT_NATIVE=1 and the kernel takes float32 device tensors only")
         return share_rows_host_(g, k)
-    with on_device_of(g):
-        _lib.check(_lib.lib().sr_share_rows(_lib.ptr(g), b, d, k, stream_of(g)), "sr_share_rows")
+    native(g).sr_share_rows(g, b, d, k)
     return g

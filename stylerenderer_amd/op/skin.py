@@ -25,7 +25,7 @@ from torch.autograd import Function
 
 from .. import _lib, utils_3d
 from . import _mesh_node
-from ._dispatch import DerivedCache, on_device_of, stream_of
+from ._dispatch import DerivedCache, native
 from ._mesh_node import EPS
 _PREP_CACHE = DerivedCache(4)
 
@@ -105,24 +105,18 @@ class _Skin(Function):
         reg = torch.empty((), dtype=f32, device=dev)
         vp = torch.empty((b, nv, 3), dtype=f32, device=dev)
         v = torch.empty_like(vp)
-        L = _lib.lib()
-        s = stream_of(c)
-        ptr = _lib.ptr
-        with on_device_of(c):
-            _lib.check(L.sr_skin_joints_fwd(ptr(cx), ptr(tg), ptr(chain), ptr(reg), ptr(c), ptr(p), ptr(j0), ptr(js),
-                                            ptr(parent), ptr(sigma), ptr(pose_inv), float(reg_weight), b, nj,
-                                            nj - npose, ds, s), "sr_skin_joints_fwd")
-            _lib.check(L.sr_skin_fwd(ptr(v), ptr(vp), ptr(st), ptr(template), ptr(cx), ptr(weights), ptr(tg), b, nv,
-                                     dfull, nj, s), "sr_skin_fwd")
-            if tri is not None:
-                off, adj, _ = utils_3d.incidence_lists(tri, nv)
-                tric = tri.contiguous()
-                n = torch.empty_like(v)
-                normc = torch.empty((b, nv), dtype=f32, device=dev)
-                _lib.check(L.sr_vertex_normals_f32(ptr(n), ptr(normc), ptr(v), ptr(tric), ptr(off), ptr(adj), b, nv,
-                                                   tric.size(0), EPS, s), "sr_vertex_normals_f32")
-            else:
-                tric = off = adj = n = normc = None
+        run = native(c)
+        run.sr_skin_joints_fwd(cx, tg, chain, reg, c, p, j0, js, parent, sigma, pose_inv, float(reg_weight), b, nj,
+                               nj - npose, ds)
+        run.sr_skin_fwd(v, vp, st, template, cx, weights, tg, b, nv, dfull, nj)
+        if tri is not None:
+            off, adj, _ = utils_3d.incidence_lists(tri, nv)
+            tric = tri.contiguous()
+            n = torch.empty_like(v)
+            normc = torch.empty((b, nv), dtype=f32, device=dev)
+            run.sr_vertex_normals_f32(n, normc, v, tric, off, adj, b, nv, tric.size(0), EPS)
+        else:
+            tric = off = adj = n = normc = None
         ctx.with_normals = tri is not None
         ctx.with_pose = p is not None
         ctx.reg_weight = float(reg_weight)
@@ -149,34 +143,27 @@ class _Skin(Function):
             k += 1
         b, nv, nj, npose, ds, dfull = ctx.sizes
         L = _lib.lib()
-        s = stream_of(c)
-        ptr = _lib.ptr
+        run = native(c)
         gv = gv.contiguous()
         greg = None
-        with on_device_of(c):
-            gvn = None
-            if ctx.with_normals:
-                tric, off, adj, v, n, normc = saved[k:k + 6]
-                gn, greg = rest[0].contiguous(), rest[1].contiguous()
-                gvn = torch.empty_like(vp)
-                _lib.check(L.sr_vertex_normals_bwd_f32(ptr(gvn), None, ptr(gn), None, None, ptr(v), ptr(n), ptr(normc),
-                                                       ptr(tric), ptr(off), ptr(adj), b, nv, tric.size(0), EPS, s),
-                           "sr_vertex_normals_bwd_f32")
-            gvp = torch.empty_like(vp)
-            nblk = (nv + 255) // 256
-            part = torch.empty(max(1, int(L.sr_skin_bwd_scratch_floats(nv, b, nj))), dtype=c.dtype, device=c.device)
-            _lib.check(L.sr_skin_bwd(ptr(gvp), ptr(part), ptr(gv), ptr(gvn), ptr(vp), ptr(weights), ptr(tg), b, nv, nj,
-                                     s), "sr_skin_bwd")
-            scratch = torch.empty(max(1, int(L.sr_morph_gcoeff_scratch_floats(3 * nv, b, dfull))), dtype=c.dtype,
-                                  device=c.device)
-            gcx = torch.empty_like(cx)
-            _lib.check(L.sr_morph_gcoeff(ptr(gcx), ptr(scratch), ptr(st), ptr(gvp), ptr(cx), None, 0.0, None, b,
-                                         3 * nv, dfull, s), "sr_morph_gcoeff")
-            gcoeff = torch.empty_like(c)
-            gpose = torch.empty_like(p) if (p is not None and ctx.needs_input_grad[1]) else None
-            _lib.check(L.sr_skin_joints_bwd(ptr(gcoeff), ptr(gpose), ptr(gcx), ptr(part), ptr(c), ptr(p), ptr(chain),
-                                            ptr(js), ptr(parent), ptr(sigma), ptr(pose_inv), ctx.reg_weight,
-                                            ptr(greg), b, nblk, nj, nj - npose, ds, s), "sr_skin_joints_bwd")
+        gvn = None
+        if ctx.with_normals:
+            tric, off, adj, v, n, normc = saved[k:k + 6]
+            gn, greg = rest[0].contiguous(), rest[1].contiguous()
+            gvn = torch.empty_like(vp)
+            run.sr_vertex_normals_bwd_f32(gvn, None, gn, None, None, v, n, normc, tric, off, adj, b, nv, tric.size(0), EPS)
+        gvp = torch.empty_like(vp)
+        nblk = (nv + 255) // 256
+        part = torch.empty(max(1, int(L.sr_skin_bwd_scratch_floats(nv, b, nj))), dtype=c.dtype, device=c.device)
+        run.sr_skin_bwd(gvp, part, gv, gvn, vp, weights, tg, b, nv, nj)
+        scratch = torch.empty(max(1, int(L.sr_morph_gcoeff_scratch_floats(3 * nv, b, dfull))), dtype=c.dtype,
+                              device=c.device)
+        gcx = torch.empty_like(cx)
+        run.sr_morph_gcoeff(gcx, scratch, st, gvp, cx, None, 0.0, None, b, 3 * nv, dfull)
+        gcoeff = torch.empty_like(c)
+        gpose = torch.empty_like(p) if (p is not None and ctx.needs_input_grad[1]) else None
+        run.sr_skin_joints_bwd(gcoeff, gpose, gcx, part, c, p, chain, js, parent, sigma, pose_inv, ctx.reg_weight, greg, b,
+                               nblk, nj, nj - npose, ds)
         return (gcoeff, gpose) + (None,) * 10
 
 

@@ -10,7 +10,7 @@ import torch
 from torch.autograd import Function
 
 from .. import _lib
-from ._dispatch import mark_inputs, on_device_of, stream_of, wanted
+from ._dispatch import mark_inputs, native, wanted
 
 
 def supported(x, n_out):
@@ -30,11 +30,7 @@ def _fwd(x, ws, bias=None):
     b, c, h, w = x.shape
     n = ws.size(1)
     out = torch.empty((b, n, h, w), dtype=x.dtype, device=x.device)
-    with on_device_of(x):
-        rc = _lib.lib().sr_smallconv_fwd(_lib.ptr(out), _lib.ptr(x), _lib.ptr(ws),
-                                         _lib.ptr(bias.contiguous()) if bias is not None else None, b, c, n, h * w,
-                                         stream_of(x))
-    _lib.check(rc, "sr_smallconv_fwd")
+    native(x).sr_smallconv_fwd(out, x, ws, bias.contiguous() if bias is not None else None, b, c, n, h * w)
     return out
 
 
@@ -44,10 +40,7 @@ def _dx(g, ws, addend=None):
     b, n, h, w = g.shape
     c = ws.size(2)
     dx = torch.empty((b, c, h, w), dtype=g.dtype, device=g.device)
-    with on_device_of(g):
-        rc = _lib.lib().sr_smallconv_dx_add(_lib.ptr(dx), _lib.ptr(g), _lib.ptr(ws), _lib.ptr(addend), b, c, n, h * w,
-                                            stream_of(g))
-    _lib.check(rc, "sr_smallconv_dx_add")
+    native(g).sr_smallconv_dx_add(dx, g, ws, addend, b, c, n, h * w)
     return dx
 
 
@@ -56,14 +49,10 @@ def _dw(g, x, want_bias=False):
     g, x = _aligned(g), _aligned(x)
     b, n, h, w = g.shape
     c = x.size(1)
-    L = _lib.lib()
     dws = torch.empty((b, n, c), dtype=g.dtype, device=g.device)
     gb = torch.empty(n, dtype=g.dtype, device=g.device) if want_bias else None
-    scratch = torch.empty(L.sr_smallconv_dw_scratch_floats(b, c, n, h * w), dtype=g.dtype, device=g.device)
-    with on_device_of(g):
-        rc = L.sr_smallconv_dw_bias(_lib.ptr(dws), _lib.ptr(gb), _lib.ptr(g), _lib.ptr(x), b, c, n, h * w,
-                                    _lib.ptr(scratch), stream_of(g))
-    _lib.check(rc, "sr_smallconv_dw_bias")
+    scratch = torch.empty(_lib.lib().sr_smallconv_dw_scratch_floats(b, c, n, h * w), dtype=g.dtype, device=g.device)
+    native(g).sr_smallconv_dw_bias(dws, gb, g, x, b, c, n, h * w, scratch)
     return (dws, gb) if want_bias else dws
 
 
@@ -193,9 +182,7 @@ class _ModRows(Function):
         n, c = w_.shape
         b = s_.shape[0]
         ws = torch.empty((b, n, c), dtype=s.dtype, device=s.device)
-        with on_device_of(s):
-            rc = _lib.lib().sr_modrows_fwd(_lib.ptr(ws), _lib.ptr(w_), _lib.ptr(s_), float(scale), b, n, c, stream_of(s))
-        _lib.check(rc, "sr_modrows_fwd")
+        native(s).sr_modrows_fwd(ws, w_, s_, float(scale), b, n, c)
         ctx.save_for_backward(w, s)
         ctx.scale = float(scale)
         return ws
@@ -217,10 +204,7 @@ class _ModRows(Function):
         gw = torch.empty_like(w_) if need_w else None
         gs = torch.empty_like(s_) if need_s else None
         if gw is not None or gs is not None:
-            with on_device_of(s):
-                rc = _lib.lib().sr_modrows_bwd(_lib.ptr(gs), _lib.ptr(gw), _lib.ptr(g_), _lib.ptr(w_), _lib.ptr(s_),
-                                               ctx.scale, b, n, c, stream_of(s))
-            _lib.check(rc, "sr_modrows_bwd")
+            native(s).sr_modrows_bwd(gs, gw, g_, w_, s_, ctx.scale, b, n, c)
         return gw, gs, None
 
 

@@ -13,8 +13,7 @@ fall to torch.matmul — or raise under SR_STRICT_NATIVE=1 (tests -m gpu, bench.
 import torch
 from torch.autograd import Function
 
-from .. import _lib
-from ._dispatch import mark_inputs, on_device_of, stream_of, strict_native, wanted
+from ._dispatch import mark_inputs, native, strict_native, wanted
 
 _SLOPE, _GAIN = 0.2, 2 ** 0.5
 
@@ -46,10 +45,7 @@ class _NT(Function):
         b, k = a_.shape
         n = w_.size(0)
         y = torch.empty((b, n), dtype=a.dtype, device=a.device)
-        with on_device_of(a):
-            rc = _lib.lib().sr_linear_fwd(_lib.ptr(y), _lib.ptr(a_), _lib.ptr(w_), None, b, k, n, a_.stride(0), 1.0, 1.0,
-                                          0, _SLOPE, _GAIN, stream_of(a))
-        _lib.check(rc, "sr_linear_fwd")
+        native(a).sr_linear_fwd(y, a_, w_, None, b, k, n, a_.stride(0), 1.0, 1.0, 0, _SLOPE, _GAIN)
         ctx.save_for_backward(a, w)
         return y
 
@@ -68,10 +64,7 @@ class _NN(Function):
         b, n = g_.shape
         k = w_.size(1)
         out = torch.empty((b, k), dtype=g.dtype, device=g.device)
-        with on_device_of(g):
-            rc = _lib.lib().sr_linear_bwd_x(_lib.ptr(out), _lib.ptr(g_), None, _lib.ptr(w_), b, k, n, 1.0, 0, _SLOPE,
-                                            _GAIN, stream_of(g))
-        _lib.check(rc, "sr_linear_bwd_x")
+        native(g).sr_linear_bwd_x(out, g_, None, w_, b, k, n, 1.0, 0, _SLOPE, _GAIN)
         ctx.save_for_backward(g, w)
         return out
 
@@ -90,10 +83,7 @@ class _TN(Function):
         b, n = g_.shape
         k = a_.size(1)
         out = torch.empty((n, k), dtype=g.dtype, device=g.device)
-        with on_device_of(g):
-            rc = _lib.lib().sr_linear_bwd_w(_lib.ptr(out), None, _lib.ptr(g_), None, _lib.ptr(a_), b, k, n, a_.stride(0),
-                                            1.0, 1.0, 0, _SLOPE, _GAIN, stream_of(g))
-        _lib.check(rc, "sr_linear_bwd_w")
+        native(g).sr_linear_bwd_w(out, None, g_, None, a_, b, k, n, a_.stride(0), 1.0, 1.0, 0, _SLOPE, _GAIN)
         ctx.save_for_backward(g, a)
         return out
 

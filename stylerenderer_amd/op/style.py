@@ -12,9 +12,8 @@ import torch
 from torch.autograd import Function
 from torch.nn import functional as F
 
-from .. import _lib
 from . import smallmm as _mm
-from ._dispatch import mark_inputs, on_device_of, stream_of, wanted
+from ._dispatch import mark_inputs, native, wanted
 
 LRELU_SLOPE = 0.2
 LRELU_GAIN = 2 ** 0.5
@@ -51,11 +50,7 @@ class _Linear(Function):
         b, k = x.shape
         n = w.size(0)
         y = torch.empty((b, n), dtype=x.dtype, device=x.device)
-        with on_device_of(x):
-            rc = _lib.lib().sr_linear_fwd(_lib.ptr(y), _lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), b, k, n,
-                                          x.stride(0), wscale, bscale, int(act), LRELU_SLOPE, LRELU_GAIN,
-                                          stream_of(x))
-        _lib.check(rc, "sr_linear_fwd")
+        native(x).sr_linear_fwd(y, x, w, bias, b, k, n, x.stride(0), wscale, bscale, int(act), LRELU_SLOPE, LRELU_GAIN)
         ctx.save_for_backward(x, weight, bias, y)
         ctx.cfg = (float(wscale), float(bscale), bool(act))
         return y
@@ -76,21 +71,17 @@ class _Linear(Function):
         w = weight.contiguous()
         b, k = x.shape
         n = w.size(0)
-        L = _lib.lib()
+        run = native(x)
         gx = gw = gb = None
-        with on_device_of(x):
-            if needs[0]:
-                gx = torch.empty((b, k), dtype=x.dtype, device=x.device)
-                _lib.check(L.sr_linear_bwd_x(_lib.ptr(gx), _lib.ptr(gy), _lib.ptr(y), _lib.ptr(w), b, k, n, wscale,
-                                             int(act), LRELU_SLOPE, LRELU_GAIN, stream_of(x)), "sr_linear_bwd_x")
-            if needs[1] or (bias is not None and needs[2]):
-                gw = torch.empty_like(w)
-                gb = torch.empty_like(bias) if bias is not None and needs[2] else None
-                _lib.check(L.sr_linear_bwd_w(_lib.ptr(gw), _lib.ptr(gb), _lib.ptr(gy), _lib.ptr(y), _lib.ptr(x), b,
-                                             k, n, x.stride(0), wscale, bscale, int(act), LRELU_SLOPE, LRELU_GAIN,
-                                             stream_of(x)), "sr_linear_bwd_w")
-                if not needs[1]:
-                    gw = None
+        if needs[0]:
+            gx = torch.empty((b, k), dtype=x.dtype, device=x.device)
+            run.sr_linear_bwd_x(gx, gy, y, w, b, k, n, wscale, int(act), LRELU_SLOPE, LRELU_GAIN)
+        if needs[1] or (bias is not None and needs[2]):
+            gw = torch.empty_like(w)
+            gb = torch.empty_like(bias) if bias is not None and needs[2] else None
+            run.sr_linear_bwd_w(gw, gb, gy, y, x, b, k, n, x.stride(0), wscale, bscale, int(act), LRELU_SLOPE, LRELU_GAIN)
+            if not needs[1]:
+                gw = None
         return gx, gw, gb, None, None, None
 
 
@@ -118,9 +109,7 @@ class _Demod(Function):
         b, ci = s_.shape
         co = w_.size(1)
         d = torch.empty((b, co), dtype=s.dtype, device=s.device)
-        with on_device_of(s):
-            rc = _lib.lib().sr_demod_fwd(_lib.ptr(d), _lib.ptr(s_), _lib.ptr(w_), b, ci, co, eps, stream_of(s))
-        _lib.check(rc, "sr_demod_fwd")
+        native(s).sr_demod_fwd(d, s_, w_, b, ci, co, eps)
         ctx.save_for_backward(s, wsq, d)
         ctx.eps = float(eps)
         return d
@@ -142,10 +131,7 @@ class _Demod(Function):
         gs = torch.empty_like(s_) if needs[0] else None
         gw = torch.empty_like(w_) if needs[1] else None
         if gs is not None or gw is not None:
-            with on_device_of(s):
-                rc = _lib.lib().sr_demod_bwd(_lib.ptr(gs), _lib.ptr(gw), _lib.ptr(gd), None, _lib.ptr(s_),
-                                             _lib.ptr(d), _lib.ptr(w_), b, ci, co, stream_of(s))
-            _lib.check(rc, "sr_demod_bwd")
+            native(s).sr_demod_bwd(gs, gw, gd, None, s_, d, w_, b, ci, co)
         return gs, gw, None
 
 

@@ -54,8 +54,7 @@ trained checkpoint.
 import numpy as np
 import torch
 
-from .. import _lib
-from ._dispatch import DerivedCache, is_device_tensor, on_device_of, stream_of, strict_native
+from ._dispatch import DerivedCache, is_device_tensor, native, strict_native
 from .landmark import _hw, project
 from .rasterize import forward as _raster_forward, forward_with_depth as _raster_depth
 
@@ -291,11 +290,8 @@ def bake(v, n, tri, face, coeff, image, zbuf, facing=(0.1, 0.4), z_bias=None):
     th, tw = (int(x) for x in fc.shape)
     tex = torch.empty((b, c_n, th, tw), dtype=vc.dtype, device=vc.device)
     weight = torch.empty((b, 1, th, tw), dtype=vc.dtype, device=vc.device)
-    ptr = _lib.ptr
-    with on_device_of(vc):
-        _lib.check(_lib.lib().sr_texture_bake(ptr(tex), ptr(weight), ptr(vc), ptr(nc), ptr(tc), ptr(fc), ptr(cc), ptr(ic),
-                                              ptr(zc), b, c_n, nv, int(tc.shape[0]), th, tw, hs, ws, hz, wz, lo, hi,
-                                              z_bias, stream_of(vc)), "sr_texture_bake")
+    native(vc).sr_texture_bake(tex, weight, vc, nc, tc, fc, cc, ic, zc, b, c_n, nv, int(tc.shape[0]), th, tw, hs, ws,
+                               hz, wz, lo, hi, z_bias)
     return tex, weight
 
 
@@ -351,13 +347,10 @@ def pad(tex, weight, passes=8):
     if passes == 0:
         return cur.clone(), cur_f
     bufs = [(torch.empty_like(cur), torch.empty_like(cur_f)) for _ in range(min(passes, 2))]
-    ptr = _lib.ptr
-    with on_device_of(cur):
-        for k in range(passes):
-            nxt, nxt_f = bufs[k % 2]
-            _lib.check(_lib.lib().sr_texture_pad(ptr(nxt), ptr(nxt_f), ptr(cur), ptr(cur_f), b, c_n, th, tw,
-                                                 stream_of(cur)), "sr_texture_pad")
-            cur, cur_f = nxt, nxt_f
+    for k in range(passes):
+        nxt, nxt_f = bufs[k % 2]
+        native(cur).sr_texture_pad(nxt, nxt_f, cur, cur_f, b, c_n, th, tw)
+        cur, cur_f = nxt, nxt_f
     return cur, cur_f
 
 
@@ -436,10 +429,7 @@ def merge(tex, weight, sharpness=2):
     out = torch.empty((1, c_n, th, tw), dtype=tc.dtype, device=tc.device)
     wout = torch.empty((1, 1, th, tw), dtype=tc.dtype, device=tc.device)
     best = torch.empty((th, tw), dtype=torch.uint8, device=tc.device)
-    ptr = _lib.ptr
-    with on_device_of(tc):
-        _lib.check(_lib.lib().sr_texture_merge(ptr(out), ptr(wout), ptr(best), ptr(tc), ptr(wc), n_v, c_n, th, tw,
-                                               sharpness, stream_of(tc)), "sr_texture_merge")
+    native(tc).sr_texture_merge(out, wout, best, tc, wc, n_v, c_n, th, tw, sharpness)
     return out, wout, best
 
 

@@ -15,8 +15,7 @@ import torch
 from torch.autograd import Function
 from torch.nn import functional as F
 
-from .. import _lib
-from ._dispatch import DerivedCache, is_device_tensor, on_device_of, require_f32, stream_of
+from ._dispatch import DerivedCache, is_device_tensor, native, require_f32
 
 
 def _out_size(n, up, down, p0, p1, k):
@@ -40,11 +39,8 @@ def upfirdn2d_op(input, kernel, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_
     if out_h <= 0 or out_w <= 0:
         raise RuntimeError("upfirdn2d: empty output (%d x %d)" % (out_h, out_w))
     out = torch.empty((major, out_h, out_w, 1), dtype=x.dtype, device=x.device)
-    with on_device_of(x):
-        rc = _lib.lib().sr_upfirdn2d(_lib.ptr(out), _lib.ptr(x), _lib.ptr(k), major, in_h, in_w, out_h,
-                                     out_w, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1,
-                                     pad_y0, pad_y1, stream_of(x))
-    _lib.check(rc, "sr_upfirdn2d")
+    native(x).sr_upfirdn2d(out, x, k, major, in_h, in_w, out_h, out_w, kh, kw, up_x, up_y, down_x, down_y, pad_x0, pad_x1,
+                           pad_y0, pad_y1)
     return out
 
 
@@ -147,10 +143,7 @@ class UpsampleAdd(Function):
         oh, ow = 2 * ih + p0 + p1 - 3, 2 * iw + p0 + p1 - 3
         x, a, k = skip.contiguous(), addend.contiguous(), kernel.contiguous()
         out = torch.empty((b, c, oh, ow), dtype=x.dtype, device=x.device)
-        with on_device_of(x):
-            rc = _lib.lib().sr_upsample2_add(_lib.ptr(out), _lib.ptr(x), _lib.ptr(k), _lib.ptr(a), b * c, ih, iw, oh,
-                                             ow, p0, p1, stream_of(x))
-        _lib.check(rc, "sr_upsample2_add")
+        native(x).sr_upsample2_add(out, x, k, a, b * c, ih, iw, oh, ow, p0, p1)
         ctx.save_for_backward(kernel)
         ctx.cfg = (p0, p1, tuple(skip.shape), (oh, ow))
         return out

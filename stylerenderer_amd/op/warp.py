@@ -31,8 +31,7 @@ no fallback between the two paths.
 import numpy as np
 import torch
 
-from .. import _lib
-from ._dispatch import on_device_of, stream_of
+from ._dispatch import native
 from .resample import OUT_FORMS, _size2, to_unit_chw
 
 BORDERS = {"replicate": 0, "reflect": 1, "constant": 2}
@@ -97,10 +96,7 @@ def _warp_device(x, mats, oh, ow, border, fill, form):
         out = torch.empty((n, oh, ow, c), dtype=torch.uint8, device=x.device)
     else:
         out = torch.empty((n, c, oh, ow), dtype=torch.float32, device=x.device)
-    with on_device_of(x):
-        rc = _lib.lib().sr_warp_affine_u8(_lib.ptr(out), _lib.ptr(x), _lib.ptr(mats), 6 if mats.shape[0] > 1 else 0, n, h,
-                                          w, c, oh, ow, border, fill, form, stream_of(x))
-    _lib.check(rc, "sr_warp_affine_u8")
+    native(x).sr_warp_affine_u8(out, x, mats, 6 if mats.shape[0] > 1 else 0, n, h, w, c, oh, ow, border, fill, form)
     return out
 
 

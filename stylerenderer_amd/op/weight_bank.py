@@ -33,8 +33,7 @@ import os
 import torch
 from torch.autograd import Function
 
-from .. import _lib
-from ._dispatch import on_device_of, stream_of
+from ._dispatch import native
 from . import weight_prep as _wp
 
 _REC = None            # recording list of the scope that is open on a network without a plan
@@ -71,12 +70,10 @@ def prep_batch(weights, scales, want_sqs):
         wts.append(wt)
         wsqs.append(wsq)
         outs.append((wt if ld == co else wt[:, :, :co], wsq))
-    with on_device_of(store):
-        rc = _lib.lib().sr_weight_prep_batch(
-            len(ws), _ptrs(wts), _ptrs(wsqs), _ptrs(ws), _arr(ctypes.c_float, [float(s) for s in scales]),
-            _arr(ctypes.c_int64, [d[0] for d in dims]), _arr(ctypes.c_int64, [d[1] for d in dims]),
-            _arr(ctypes.c_int, [d[2] for d in dims]), _arr(ctypes.c_int64, lds), stream_of(store))
-    _lib.check(rc, "sr_weight_prep_batch")
+    native(store).sr_weight_prep_batch(
+        len(ws), _ptrs(wts), _ptrs(wsqs), _ptrs(ws), _arr(ctypes.c_float, [float(s) for s in scales]),
+        _arr(ctypes.c_int64, [d[0] for d in dims]), _arr(ctypes.c_int64, [d[1] for d in dims]),
+        _arr(ctypes.c_int, [d[2] for d in dims]), _arr(ctypes.c_int64, lds))
     return outs
 
 
@@ -97,13 +94,11 @@ def adjoint_batch(wts, flips):
         off += m
         full.append(a)
         outs.append(a if ldc == c else a[:, :, :c])
-    with on_device_of(store):
-        rc = _lib.lib().sr_weight_adjoint_batch(
-            len(srcs), _ptrs(full), _ptrs(srcs), _arr(ctypes.c_int64, [s[0] for s in shapes]),
-            _arr(ctypes.c_int64, [s[1] for s in shapes]), _arr(ctypes.c_int64, [s[2] for s in shapes]),
-            _arr(ctypes.c_int64, [s.stride(1) for s in srcs]), _arr(ctypes.c_int64, ldcs),
-            _arr(ctypes.c_int, [int(bool(f)) for f in flips]), stream_of(store))
-    _lib.check(rc, "sr_weight_adjoint_batch")
+    native(store).sr_weight_adjoint_batch(
+        len(srcs), _ptrs(full), _ptrs(srcs), _arr(ctypes.c_int64, [s[0] for s in shapes]),
+        _arr(ctypes.c_int64, [s[1] for s in shapes]), _arr(ctypes.c_int64, [s[2] for s in shapes]),
+        _arr(ctypes.c_int64, [s.stride(1) for s in srcs]), _arr(ctypes.c_int64, ldcs),
+        _arr(ctypes.c_int, [int(bool(f)) for f in flips]))
     return outs
 
 

@@ -14,8 +14,7 @@ import weakref
 import torch
 from torch.autograd import Function
 
-from .. import _lib
-from ._dispatch import hold_for_capture, on_device_of, require_f32, stream_of
+from ._dispatch import hold_for_capture, native, require_f32
 
 
 def _pitch(n):
@@ -38,10 +37,7 @@ class _WPrep(Function):
         ld = _pitch(co)
         store = torch.empty((k * k, ci, ld), dtype=w.dtype, device=w.device)
         wsq = torch.empty((ci, co) if want_sq else (0,), dtype=w.dtype, device=w.device)
-        with on_device_of(w):
-            rc = _lib.lib().sr_weight_prep(_lib.ptr(store), _lib.ptr(wsq), _lib.ptr(w), float(scale), co, ci, k,
-                                           ld, stream_of(w))
-        _lib.check(rc, "sr_weight_prep")
+        native(w).sr_weight_prep(store, wsq, w, float(scale), co, ci, k, ld)
         ctx.save_for_backward(weight)
         ctx.set_materialize_grads(False)
         ctx.scale, ctx.want_sq = float(scale), bool(want_sq)
@@ -80,10 +76,7 @@ class _WPrepBwd(Function):
                 gw = None
         if gw is None:
             gw = torch.empty_like(w)
-        with on_device_of(w):
-            rc = _lib.lib().sr_weight_prep_bwd(_lib.ptr(gw), _lib.ptr(gwt), _lib.ptr(gwsq), _lib.ptr(w),
-                                               float(scale), co, ci, k, co, stream_of(w))
-        _lib.check(rc, "sr_weight_prep_bwd")
+        native(w).sr_weight_prep_bwd(gw, gwt, gwsq, w, float(scale), co, ci, k, co)
         ctx.save_for_backward(gwsq, weight)
         ctx.scale = float(scale)
         ctx.has = (gwt is not None, gwsq is not None)
@@ -201,10 +194,7 @@ def _adjoint_launch(wt, flip):
         wt = wt.contiguous()
     ldn, ldc = wt.stride(1), _pitch(c)
     store = torch.empty((taps, n, ldc), dtype=wt.dtype, device=wt.device)
-    with on_device_of(wt):
-        rc = _lib.lib().sr_weight_adjoint(_lib.ptr(store), _lib.ptr(wt), taps, c, n, ldn, ldc, int(bool(flip)),
-                                          stream_of(wt))
-    _lib.check(rc, "sr_weight_adjoint")
+    native(wt).sr_weight_adjoint(store, wt, taps, c, n, ldn, ldc, int(bool(flip)))
     return store if ldc == c else store[:, :, :c]
 
 

@@ -9,7 +9,7 @@ moments in buffers of the same layout; a step is one launch of `sr_adam_flat` (2
 """
 import torch
 
-from . import _lib
+from .op._dispatch import native
 
 ALIGN = 64          # floats: 256-byte aligned views
 
@@ -91,16 +91,12 @@ class FlatAdam:
         if self.own_step:
             self.step_t.add_(1.0)
         if self.guards is not None:
-            rc = _lib.lib().sr_adam_flat_guarded(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.m.data_ptr(),
-                                                 self.v.data_ptr(), self.total, g["lr"], g["betas"][0], g["betas"][1],
-                                                 g["eps"], self.step_t.data_ptr(), self.guards, len(self.guards),
-                                                 self.skipped.data_ptr(), _lib.current_stream(self.flat_p.device))
-            _lib.check(rc, "sr_adam_flat_guarded")
+            native(self.flat_p).sr_adam_flat_guarded(self.flat_p, self.flat_g, self.m, self.v, self.total, g["lr"],
+                                                     g["betas"][0], g["betas"][1], g["eps"], self.step_t, self.guards,
+                                                     len(self.guards), self.skipped)
             return
-        rc = _lib.lib().sr_adam_flat(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.m.data_ptr(),
-                                     self.v.data_ptr(), self.total, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
-                                     self.step_t.data_ptr(), _lib.current_stream(self.flat_p.device))
-        _lib.check(rc, "sr_adam_flat")
+        native(self.flat_p).sr_adam_flat(self.flat_p, self.flat_g, self.m, self.v, self.total, g["lr"], g["betas"][0],
+                                         g["betas"][1], g["eps"], self.step_t)
 
     @torch.no_grad()
     def _step_host(self, g):

@@ -17,8 +17,7 @@ differentiable (first and higher order through the defining tensor algebra).
 import torch
 from torch.autograd import Function
 
-from . import _lib
-from .op._dispatch import DerivedCache, on_device_of, stream_of
+from .op._dispatch import DerivedCache, native
 
 
 def normalize(vec, axis=-1, _type="L2", eps=1e-8):
@@ -93,9 +92,7 @@ def _pose_batch(pc, with_rot=True):
     """(lin, rot or None), each [B, 3, 3], of contiguous device poses pc [B, 7]: one launch."""
     lin = torch.empty((pc.shape[0], 3, 3), dtype=pc.dtype, device=pc.device)
     rot = torch.empty_like(lin) if with_rot else None
-    with on_device_of(pc):
-        _lib.check(_lib.lib().sr_pose_batch_fwd(_lib.ptr(lin), _lib.ptr(rot), _lib.ptr(pc), pc.shape[0], stream_of(pc)),
-                   "sr_pose_batch_fwd")
+    native(pc).sr_pose_batch_fwd(lin, rot, pc, pc.shape[0])
     return lin, rot
 
 
@@ -111,10 +108,7 @@ class _Affine3(Function):
         b, nv = mc.shape[0], vc.shape[-2]
         out = torch.empty((b, nv, 3), dtype=vc.dtype, device=vc.device)
         share = vc.dim() == 2 or vc.shape[0] == 1
-        with on_device_of(vc):
-            rc = _lib.lib().sr_affine3_fwd(_lib.ptr(out), _lib.ptr(vc), _lib.ptr(mc), _lib.ptr(tc), b, nv,
-                                           0 if share else nv * 3, stream_of(vc))
-        _lib.check(rc, "sr_affine3_fwd")
+        native(vc).sr_affine3_fwd(out, vc, mc, tc, b, nv, 0 if share else nv * 3)
         ctx.save_for_backward(vc, mc)
         ctx.share, ctx.has_t, ctx.v_shape = share, t is not None, tuple(v.shape)
         return out
@@ -128,19 +122,15 @@ class _Affine3(Function):
         gm = torch.empty_like(mc) if need_m else None
         gt = torch.empty((b, 3), dtype=g.dtype, device=g.device) if need_t else None
         gv = None
-        L = _lib.lib()
-        with on_device_of(g):
-            if need_m or need_t:
-                _lib.check(L.sr_affine3_bwd(_lib.ptr(gm), _lib.ptr(gt), _lib.ptr(vc), _lib.ptr(g), b, nv,
-                                            0 if ctx.share else nv * 3, stream_of(g)), "sr_affine3_bwd")
-            if need_v:
-                gv = torch.empty_like(g)
-                mt = mc.transpose(1, 2).contiguous()
-                _lib.check(L.sr_affine3_fwd(_lib.ptr(gv), _lib.ptr(g), _lib.ptr(mt), None, b, nv, nv * 3,
-                                            stream_of(g)), "sr_affine3_fwd")
-                if ctx.share:
-                    gv = gv.sum(0, keepdim=True)
-                gv = gv.reshape(ctx.v_shape)
+        if need_m or need_t:
+            native(g).sr_affine3_bwd(gm, gt, vc, g, b, nv, 0 if ctx.share else nv * 3)
+        if need_v:
+            gv = torch.empty_like(g)
+            mt = mc.transpose(1, 2).contiguous()
+            native(g).sr_affine3_fwd(gv, g, mt, None, b, nv, nv * 3)
+            if ctx.share:
+                gv = gv.sum(0, keepdim=True)
+            gv = gv.reshape(ctx.v_shape)
         return gv, gm, gt
 
 
@@ -152,8 +142,7 @@ class _PoseMatrices(Function):
         pc = pose.contiguous()
         lin = torch.empty((1, 3, 3), dtype=pc.dtype, device=pc.device)
         rot = torch.empty_like(lin)
-        with on_device_of(pc):
-            _lib.check(_lib.lib().sr_pose_fwd(_lib.ptr(lin), _lib.ptr(rot), _lib.ptr(pc), stream_of(pc)), "sr_pose_fwd")
+        native(pc).sr_pose_fwd(lin, rot, pc)
         ctx.save_for_backward(pc)
         return lin, rot
 
@@ -163,9 +152,7 @@ class _PoseMatrices(Function):
         gp = torch.empty_like(pc)
         gl = glin.contiguous() if glin is not None else None
         gr = grot.contiguous() if grot is not None else None
-        with on_device_of(pc):
-            _lib.check(_lib.lib().sr_pose_bwd(_lib.ptr(gp), _lib.ptr(gl), _lib.ptr(gr), _lib.ptr(pc), stream_of(pc)),
-                       "sr_pose_bwd")
+        native(pc).sr_pose_bwd(gp, gl, gr, pc)
         return gp
 
 
@@ -185,9 +172,7 @@ class _PoseBatchMatrices(Function):
         gp = torch.empty_like(pc)
         gl = glin.contiguous() if glin is not None else None
         gr = grot.contiguous() if grot is not None else None
-        with on_device_of(pc):
-            _lib.check(_lib.lib().sr_morph_pose_bwd(_lib.ptr(gp), _lib.ptr(gl), _lib.ptr(gr), None, _lib.ptr(pc),
-                                                    pc.shape[0], stream_of(pc)), "sr_morph_pose_bwd")
+        native(pc).sr_morph_pose_bwd(gp, gl, gr, None, pc, pc.shape[0])
         return gp
 
 
@@ -255,10 +240,7 @@ class _VertexNormals(Function):
         off, adj, _ = incidence_lists(tri, nv)
         tric = tri.contiguous()
         out = torch.empty_like(vc)
-        with on_device_of(vc):
-            rc = _lib.lib().sr_vertex_normals_f32(_lib.ptr(out), None, _lib.ptr(vc), _lib.ptr(tric), _lib.ptr(off),
-                                                  _lib.ptr(adj), b, nv, tric.size(0), 1e-8, stream_of(vc))
-        _lib.check(rc, "sr_vertex_normals_f32")
+        native(vc).sr_vertex_normals_f32(out, None, vc, tric, off, adj, b, nv, tric.size(0), 1e-8)
         ctx.save_for_backward(v, tri)
         return out
 

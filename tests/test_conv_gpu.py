@@ -240,6 +240,46 @@ def test_wgrad_vs_float64(case, scaled):
     assert float((got.cpu().double() - want).abs().max()) < 3e-5 * scale * max(1.0, np.sqrt(b * h * w) / 30)
 
 
+@pytest.mark.parametrize("geom", ["c3", "c3s2", "t3s2", "c1s2"])
+@pytest.mark.parametrize("scaled", [True, False])
+def test_input_side_gradients_vs_float64(geom, scaled):
+    """gx and the style gradient gis of the differentiable convolution, with and without an input scale, through
+    float64 autograd on the CPU: 9 x 9 is odd, so c3s2 and t3s2 are each other's adjoint, and c1s2 scatters into the
+    even positions.  dxu is a convolution with the adjoint weights: fp32 round-off of a K-term dot product, the
+    2e-6 * sum|a*b| of this file.  gx = iscale * dxu rounds once more (within the bound's slack); gis = sum_p x * dxu
+    carries the error of dxu through |x| and adds the round-off of its own P-term sum: 2e-6 + 2e-6 of
+    sum_p |x| * sum|a*b|."""
+    from stylerenderer_amd.op.conv import _GEOM, conv2d
+
+    b, c, n, h, w = 2, 8, 8, 9, 9
+    k, stride, pad, tr = _GEOM[geom]
+    g = torch.Generator().manual_seed(31 + k + stride + int(tr))
+    x = torch.randn(b, c, h, w, generator=g)
+    wgt = torch.randn((c, n, k, k) if tr else (n, c, k, k), generator=g)
+    isc = torch.randn(b, c, generator=g) if scaled else None
+    osc = torch.randn(b, n, generator=g)
+    xr = x.double().requires_grad_()
+    ir = isc.double().requires_grad_() if scaled else None
+    y = ref_conv(xr, wgt, ir, osc, None, stride, pad, tr)
+    gy = torch.randn(y.shape, generator=g)
+    want = torch.autograd.grad(y, [xr, ir] if scaled else [xr], gy.double())
+    xa = torch.zeros_like(xr).requires_grad_()
+    (mag,) = torch.autograd.grad(ref_conv(xa, wgt.abs(), None, osc.abs(), None, stride, pad, tr), xa, gy.abs().double())
+
+    xd = x.to(DEV).requires_grad_()
+    idv = isc.to(DEV).requires_grad_() if scaled else None
+    out = conv2d(xd, to_taps(wgt, tr).to(DEV), idv, osc.to(DEV), None, geom)
+    assert out.shape == y.shape
+    got = torch.autograd.grad(out, [xd, idv] if scaled else [xd], gy.to(DEV))
+    mag_x = mag * isc.abs().double()[:, :, None, None] if scaled else mag
+    err = (got[0].cpu().double() - want[0]).abs()
+    assert float((err / (mag_x + 1e-30)).max()) < 2e-6
+    if scaled:
+        mag_s = (x.abs().double() * mag).sum((2, 3))
+        err = (got[1].cpu().double() - want[1]).abs()
+        assert float((err / (mag_s + 1e-30)).max()) < 4e-6
+
+
 def test_stride2_wgrad_dma_staging_equals_dword_staging(monkeypatch):
     """k_wgrad_s2_dma stages the same operands as the dword kernel and runs the same MFMA chain in the same k
     order: the weight gradients are bit-identical (SR_WGRAD_DMA=0 selects the dword kernel)."""
