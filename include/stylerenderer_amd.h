@@ -591,6 +591,7 @@ int sr_conv2d_uses_winograd(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t
 #define SR_CONV_PATH_CONVT_BF16 6     /* transposed: interior by split-bf16 (SR_CONV_SPLIT_BF16) */
 #define SR_CONV_PATH_CONVT_FUSED_KS 7 /* transposed: interior by k_convt_fused in K slices + k_convt_fused_reduce */
 #define SR_CONV_PATH_CONVT_FUSED 8    /* transposed: interior by k_convt_fused */
+#define SR_CONV_PATH_CONVT_WINO 9     /* transposed: interior by the 25-product form, k_convt_wino */
 #define SR_CONV_PATH_STRIPS 0x100
 int sr_conv2d_path(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW, int ksize, int stride,
                    int pad, int transposed, const float* in, const float* out, const float* wt, int64_t wt_ld,

@@ -173,7 +173,7 @@ SIGNATURES = {
 
 # sr_conv2d_path / sr_conv2d_wgrad_path values (SR_CONV_PATH_* / SR_WGRAD_PATH_* of the header)
 (CONV_PATH_DIRECT, CONV_PATH_WINO, CONV_PATH_S2_BF16, CONV_PATH_S2_WINO, CONV_PATH_GEMM1X1, CONV_PATH_CONVT_TAPS,
- CONV_PATH_CONVT_BF16, CONV_PATH_CONVT_FUSED_KS, CONV_PATH_CONVT_FUSED) = range(9)
+ CONV_PATH_CONVT_BF16, CONV_PATH_CONVT_FUSED_KS, CONV_PATH_CONVT_FUSED, CONV_PATH_CONVT_WINO) = range(10)
 CONV_PATH_STRIPS = 0x100
 (WGRAD_PATH_DIRECT, WGRAD_PATH_SMALL3, WGRAD_PATH_WINO, WGRAD_PATH_BF16_1X1, WGRAD_PATH_BF16_S2,
  WGRAD_PATH_S2_DMA, WGRAD_PATH_S2_WINO) = range(7)

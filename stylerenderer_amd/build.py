@@ -56,6 +56,7 @@ SOURCES = [
     ("conv_wgrad_s2_wino.hip", []),
     ("conv_s2_bf16x3.hip", []),
     ("conv_s2_wino.hip", []),
+    ("convt_wino.hip", []),
     ("conv_generic.hip", []),
     ("conv1x1_gemm.hip", []),
     ("inception.hip", []),

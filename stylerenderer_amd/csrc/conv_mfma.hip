@@ -40,6 +40,7 @@
 #include "conv_s2_wino.h"
 #include "conv_wgrad_bf16x3.h"
 #include "conv_wino.h"
+#include "convt_wino.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -1100,8 +1101,18 @@ int64_t direct_floats(const ConvCall& c) {
 }
 
 bool convt_interior(int path) {
-    return path == SR_CONV_PATH_CONVT_BF16 || path == SR_CONV_PATH_CONVT_FUSED_KS || path == SR_CONV_PATH_CONVT_FUSED;
+    return path == SR_CONV_PATH_CONVT_BF16 || path == SR_CONV_PATH_CONVT_WINO || path == SR_CONV_PATH_CONVT_FUSED_KS ||
+           path == SR_CONV_PATH_CONVT_FUSED;
 }
+
+// 25-product form of the transposed stride-2 3x3 convolution's interior (csrc/convt_wino.hip).  The kernel has no K
+// slices, so the bar is on the direct flops 18 B C N IH IW of the launch: smaller launches keep k_convt_fused, its K
+// slices and the tap-split form.  Floor: the row ("t3s2", (8, 512, 512, 32, 32)) of tests/conv_plan_cases.py (3.87e10) is
+// launched by the GPU suite as a k_convt_fused shape and stays there.  Measured, the new kernel is ahead on every row from
+// 1.93e10 up (0.67 .. 0.86 of k_convt_fused's time), so the bar sits just above its floor; the generator's
+// launches at batch 16 start at 7.73e10.
+constexpr double CONVT_WINO_MIN_FLOPS = 4.0e10;
+static_assert(CONVT_WINO_MIN_FLOPS > 18.0 * 8 * 512 * 512 * 32 * 32, "the t3s2 row of tests/conv_plan_cases.py stays on k_convt_fused");
 
 struct ConvPlan {
     int path = SR_CONV_PATH_DIRECT; // the direct kernel (per-phase launches when transposed) takes what nobody else does
@@ -1115,7 +1126,7 @@ struct ConvPlan {
 
 // THE path list: every path of a call's geometry goes through candidate(), in priority order.
 //   reach   the SHAPE can get here: with some buffer alignment, below or above a launch-size bar, and with the on / off
-//           switches (SR_CONV_S2_WINO, SR_CONVT_FUSED, SR_CONVT_FUSED_KS, SR_CONVT_STRIPS, SR_CONV1X1_GEMM) in either
+//           switches (SR_CONV_S2_WINO, SR_CONVT_WINO, SR_CONVT_FUSED, SR_CONVT_FUSED_KS, SR_CONVT_STRIPS, SR_CONV1X1_GEMM) in either
 //           position — they are read per call, the scratch may be sized before one flips.  SR_WINOGRAD, SR_CONVT_TAPS and
 //           SR_CONV_SPLIT_BF16 count as they stand.  `sized` is the largest `floats` within reach,
 //   take    THIS call takes it (its buffers, the switches now) unless an earlier candidate did
@@ -1154,16 +1165,24 @@ ConvPlan make_conv_plan(const ConvCall& c, bool have_scratch) {
         // opt-in spike (SR_CONV_SPLIT_BF16=1): the interior of the map on the bf16 matrix cores (three-way operand
         // split); it keeps the tap-split form out, the border stays on the exact-fp32 kernels
         const bool bf = sr_wgrad_bf16x3_enabled('t') && sr_convt_bf16x3_eligible(B, C, N, IH, IW);
+        // SR_CONVT_WINO: =0 never takes k_convt_wino, =force takes it for any eligible size (tests), unset applies the
+        // flop bar; SR_CONVT_FUSED=0 ("per-phase launches") keeps it out too
+        const int sw = sr_env_char("SR_CONVT_FUSED"), wsw = sr_env_char("SR_CONVT_WINO");
+        const bool wino_ok = sw != '0' && wsw != '0' && sr_convt_wino_eligible(B, C, N, IH, IW, c.ldw, c.in);
+        const bool wino_forced = wino_ok && wsw == 'f' && !bf;
         // small problems: nine shifted 1x1 convolutions in one launch + one reduction (k_conv_mfma<..., TAP9>)
         if (convt_taps_wanted(B, C, N, IH, IW)) {
             int ks;
             convt_taps_plan((int)IH, (int)IW, (int)B, (int)N, (int)C, ks, plan.c_per_slice);
-            candidate(SR_CONV_PATH_CONVT_TAPS, true, !bf, (int64_t)ks * 9 * B * N * (IH + 1) * (IW + 1), ks);
+            candidate(SR_CONV_PATH_CONVT_TAPS, true, !bf && !wino_forced, (int64_t)ks * 9 * B * N * (IH + 1) * (IW + 1), ks);
         }
         candidate(SR_CONV_PATH_CONVT_BF16, bf, true, sr_convt_bf16x3_scratch_floats(C, N));
+        // interior of the map in 25 of 36 products (k_convt_wino) for the large launches
+        candidate(SR_CONV_PATH_CONVT_WINO, sr_convt_wino_eligible(B, C, N, IH, IW, c.ldw, nullptr),
+                  wino_ok && (wsw == 'f' || 18.0 * (double)B * (double)C * (double)N * (double)IH * (double)IW >=
+                                                CONVT_WINO_MIN_FLOPS), 0);
         // interior of the map: all four phases in one workgroup (k_convt_fused); SR_CONVT_FUSED=0 keeps the per-phase
         // launches, =1 takes it whatever the size
-        const int sw = sr_env_char("SR_CONVT_FUSED");
         const bool fused_ok = sw != '0' && IW >= 16 && convt_fused_eligible(c);
         // the fused kernel has no split-K: when its workgroups cover less than ~3/4 of the CUs AND the channel loop is
         // long (C > 256: 64 chunks, ~0.38 ms whatever the batch), each one walks the whole loop alone and the per-phase
@@ -1313,6 +1332,9 @@ extern "C" int sr_conv2d_mfma_ex(float* out, const float* in, const float* wt, c
         return launch_convt_taps(p, plan.ks, plan.c_per_slice, plan.taps_gemm, st);
     case SR_CONV_PATH_CONVT_BF16:
         rc = sr_convt_bf16x3_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, scratch, st);
+        break;
+    case SR_CONV_PATH_CONVT_WINO:
+        rc = sr_convt_wino_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, st);
         break;
     case SR_CONV_PATH_CONVT_FUSED_KS:
     case SR_CONV_PATH_CONVT_FUSED:
