@@ -12,6 +12,16 @@ and compared per kernel symbol: the set of kernels, each kernel's disassembly (l
 encodings and the pc-relative offsets of globals stripped: they move with a kernel's place in the code object) and its
 resource numbers from the code object's metadata (llvm-readelf --notes: registers, LDS, scratch, kernarg size, ...).
 Needs no GPU.  Exit status 0 iff everything is identical.
+
+  python scripts/compare_device_code.py --union TREE_A TREE_B [-j N]
+
+compares the UNION of the kernels over all sources of each tree instead of file against file, so a kernel that moved to
+another translation unit still meets its parent: every kernel of TREE_A must exist in TREE_B with the same instructions
+and resource numbers, and TREE_B may add none.  Kernels are matched by their demangled symbol (llvm-cxxfilt, or
+binutils' c++filt where ROCm ships none) with every "(anonymous namespace)::" taken out: a kernel with internal linkage
+carries that decoration in its own name and in the names of its argument types, so it changes when, say, a parameter
+struct moves from a file's anonymous namespace into a shared header although the kernel is the same.  A kernel compiled in several files of a tree (a template in a header)
+must be the same in all of them.
 """
 import argparse
 import importlib.util
@@ -92,29 +102,69 @@ def kernels_of(co, objdump, readelf):
     return {k: ("\n".join(code.get(k, ())), {r: v.get(r) for r in RESOURCES}) for k, v in meta.items()}
 
 
+def diff_kernels(ka, kb):
+    diffs = ["kernel set: -%s +%s" % (sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka)))] if set(ka) != set(kb) else []
+    for k in sorted(set(ka) & set(kb)):
+        if ka[k][0] != kb[k][0]:
+            diffs.append("instructions differ: " + k)
+        if ka[k][1] != kb[k][1]:
+            diffs.append("resources differ: %s %s -> %s" % (k, ka[k][1], kb[k][1]))
+    return diffs
+
+
+def union_of(tree_files, cxxfilt):
+    """{file: kernels_of()} of one tree -> ({undecorated kernel name: (file, instructions, resources)}, [clashes])"""
+    symbols = sorted({k for ks in tree_files.values() for k in ks})
+    plain = subprocess.run([cxxfilt], input="\n".join(symbols), check=True, stdout=subprocess.PIPE, text=True).stdout.splitlines()
+    plain = {s: p.replace("(anonymous namespace)::", "") for s, p in zip(symbols, plain)}
+    union, clashes = {}, []
+    for name in sorted(tree_files):
+        for sym, (text, res) in tree_files[name].items():
+            text = text.replace(sym, "<kernel>")              # the kernel's own symbol in its branch-target labels
+            first = union.setdefault(plain[sym], (name, text, res))
+            if first[1:] != (text, res):
+                clashes.append("%s differs between %s and %s of one tree" % (plain[sym], first[0], name))
+    return union, clashes
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("tree_a")
     ap.add_argument("tree_b")
     ap.add_argument("files", nargs="*")
     ap.add_argument("-j", type=int, default=8)
+    ap.add_argument("--union", action="store_true", help="match kernels over all files of each tree, not file by file")
     a = ap.parse_args()
     builds = [load_build(os.path.abspath(t)) for t in (a.tree_a, a.tree_b)]
     flags = [dict(b.SOURCES) for b in builds]
     names = a.files or sorted(set(flags[0]) | set(flags[1]))
-    objdump, readelf = (llvm_tool(builds[0]._hipcc(), t) for t in ("llvm-objdump", "llvm-readelf"))
+    objdump, readelf, cxxfilt = (llvm_tool(builds[0]._hipcc(), t) for t in ("llvm-objdump", "llvm-readelf", "llvm-cxxfilt"))
+    if not shutil.which(cxxfilt):
+        cxxfilt = "c++filt"                                   # binutils' demangler: not every ROCm ships llvm-cxxfilt
     tmp = tempfile.mkdtemp(prefix="devcode_")
     try:
         jobs = []
         with ThreadPoolExecutor(a.j) as pool:
             for name in names:
-                if name not in flags[0] or name not in flags[1]:
-                    continue
                 for side in (0, 1):
-                    out = os.path.join(tmp, "%d_%s.co" % (side, name))
-                    jobs.append(pool.submit(compile_device, builds[side], name, flags[side][name], out))
+                    if name in flags[side] and (a.union or name in flags[1 - side]):
+                        out = os.path.join(tmp, "%d_%s.co" % (side, name))
+                        jobs.append(pool.submit(compile_device, builds[side], name, flags[side][name], out))
             for j in jobs:
                 j.result()
+        if a.union:
+            trees = [{n: kernels_of(os.path.join(tmp, "%d_%s.co" % (s, n)), objdump, readelf) for n in names if n in flags[s]}
+                     for s in (0, 1)]
+            (ua, clash_a), (ub, clash_b) = (union_of(t, cxxfilt) for t in trees)
+            diffs = clash_a + clash_b + diff_kernels({k: v[1:] for k, v in ua.items()}, {k: v[1:] for k, v in ub.items()})
+            for k in sorted(set(ua) & set(ub)):
+                if ua[k][0] != ub[k][0]:
+                    print("moved: %s  %s -> %s" % (k, ua[k][0], ub[k][0]))
+            for d in diffs:
+                print("    " + d)
+            print("%d + %d files, %d kernels compared by symbol: %s" %
+                  (len(trees[0]), len(trees[1]), len(ua), "identical" if not diffs else "%d differences" % len(diffs)))
+            return 1 if diffs else 0
         bad = kernels = 0
         for name in names:
             if name not in flags[0] or name not in flags[1]:
@@ -122,12 +172,7 @@ def main():
                 bad += 1
                 continue
             ka, kb = (kernels_of(os.path.join(tmp, "%d_%s.co" % (s, name)), objdump, readelf) for s in (0, 1))
-            diffs = ["kernel set: -%s +%s" % (sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka)))] if set(ka) != set(kb) else []
-            for k in sorted(set(ka) & set(kb)):
-                if ka[k][0] != kb[k][0]:
-                    diffs.append("instructions differ: " + k)
-                if ka[k][1] != kb[k][1]:
-                    diffs.append("resources differ: %s %s -> %s" % (k, ka[k][1], kb[k][1]))
+            diffs = diff_kernels(ka, kb)
             kernels += len(ka)
             print("%-28s %3d kernels  %s" % (name, len(ka), "identical" if not diffs else "DIFFERENT"))
             for d in diffs:

@@ -8,7 +8,9 @@
 #include <cstdlib>
 #include <vector>
 
+#include "../stylerenderer_amd/csrc/conv_dispatch.hip"
 #include "../stylerenderer_amd/csrc/conv_mfma.hip"
+#include "../stylerenderer_amd/csrc/convt_fused.hip"
 #ifndef SR_NO_WGRAD
 #include "../stylerenderer_amd/csrc/conv_wgrad_mfma.hip"
 #endif

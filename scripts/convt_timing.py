@@ -1,4 +1,4 @@
-"""Per-workgroup phase timing of k_convt_fused (debug build: scripts/build_variant.sh ct conv_mfma.hip -DCONVT_TIMING).
+"""Per-workgroup phase timing of k_convt_fused (debug build: scripts/build_variant.sh ct convt_fused.hip -DCONVT_TIMING).
 Run:  STYLERENDERER_AMD_LIB=build/mb/libsr_ct.so python scripts/convt_timing.py"""
 import ctypes, os, sys
 import numpy as np

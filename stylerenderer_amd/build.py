@@ -48,7 +48,9 @@ SOURCES = [
     ("augment.hip", EXACT),
     ("resample.hip", EXACT),
     ("warp.hip", EXACT),
+    ("conv_dispatch.hip", []),
     ("conv_mfma.hip", []),
+    ("convt_fused.hip", []),
     ("conv_wino.hip", []),
     ("conv_wgrad_wino.hip", []),
     ("conv_wgrad_mfma.hip", []),

@@ -1,8 +1,8 @@
 // Shared device helpers of the split-bf16 kernels (conv_s2_bf16x3.hip, conv_wgrad_bf16x3.hip): an fp32 operand as the
-// exact sum of three bf16 pieces, multiplied on the bf16 matrix cores.  Included inside each file's anonymous namespace.
+// exact sum of three bf16 pieces, multiplied on the bf16 matrix cores.  Included inside each file's anonymous namespace, so it includes nothing itself:
+// the file includes mfma_tile.h (f32x16) at file scope first.
 #pragma once
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));

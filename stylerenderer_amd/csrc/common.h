@@ -60,6 +60,9 @@ __device__ __forceinline__ float sr_wave_sum(float x) {
     return x;
 }
 
+// Last word of a raw buffer resource (gfx9 DATA_FORMAT = 32-bit): out-of-range offsets are checked against the size in bytes
+constexpr int SR_BUF_RSRC_WORD3 = 0x00020000;
+
 #if __HIP_DEVICE_COMPILE__
 // Buffer resource over [base, base + bytes) for raw buffer loads / LDS-DMA.  Every input goes through readfirstlane
 // so that the descriptor provably lives in SGPRs: a descriptor the compiler believes divergent turns each buffer
@@ -69,6 +72,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const float* base
     const unsigned long long a = reinterpret_cast<unsigned long long>(base);
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+                                             __builtin_amdgcn_readfirstlane(bytes), SR_BUF_RSRC_WORD3);
 }
 #endif

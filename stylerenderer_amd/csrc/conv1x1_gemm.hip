@@ -13,14 +13,12 @@
 //
 // Eligible: C % 16 == 0, N % 128 == 0, pixels % 128 == 0, 16-byte aligned operands, enough tiles to fill the chip
 // (anything else stays on k_conv_mfma).  SR_CONV1X1_GEMM=0 disables.
-#include "common.h"
+#include "mfma_tile.h"
 #include "conv1x1_gemm.h"
 
 #include <cstdlib>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int TN = 128, TP = 128, KC = 16;
 
@@ -110,7 +108,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1x1_gemm(const GemmParams q) {
         __syncthreads();
     }
 
-    // epilogue: rows = output channels (register r -> row (r & 3) + 8 * (r >> 2) + 4 * half), lanes = pixels
+    // epilogue: rows = output channels (register r -> row sr_mfma32_row(r, half)), lanes = pixels
     float* dst = q.out + ((int64_t)b * q.N + n0 + wn) * q.P + p0 + wp + l31;
     const float* osc = q.oscale ? q.oscale + (int64_t)b * q.N + n0 + wn : nullptr;
     const float* bia = q.obias ? q.obias + n0 + wn : nullptr;
@@ -118,7 +116,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1x1_gemm(const GemmParams q) {
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int row = sr_mfma32_row(r, half, i * 32);
             const float s = osc ? osc[row] : 1.0f;
             const float t = bia ? bia[row] : 0.0f;
             float* d = dst + (int64_t)row * q.P;
@@ -252,7 +250,7 @@ __global__ __launch_bounds__(256, 2) void k_convt_taps_gemm(const TapParams q) {
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int row = sr_mfma32_row(r, half, i * 32);
                 d[(int64_t)row * q.region] = acc[i][j][r];
             }
     }

@@ -34,22 +34,16 @@
 // border strips) — and the patch shape for 4x4 ... 256x256 feature maps; small maps split K.
 // The stride-1 3x3 case of maps >= 32 wide is normally taken by the Winograd kernel (conv_wino.hip);
 // this file then serves the strided / transposed / 1x1 / small-map launches and SR_WINOGRAD=0.
-#include "common.h"
+// Which call comes here is decided in csrc/conv_dispatch.hip; conv_mfma.h is this file's interface.
+#include "conv_mfma.h"
+
 #include "conv1x1_gemm.h"
-#include "conv_s2_bf16x3.h"
-#include "conv_s2_wino.h"
-#include "conv_wgrad_bf16x3.h"
-#include "conv_wino.h"
-#include "convt_wino.h"
+#include "mfma_tile.h"
 
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef const void __attribute__((address_space(1)))* gptr_t;
-typedef void __attribute__((address_space(3)))* lptr_t;
 
 constexpr int BN = 128;    // output channels per workgroup
 constexpr int BM = 128;    // pixels per workgroup
@@ -57,33 +51,6 @@ constexpr int BM = 128;    // pixels per workgroup
 // DMA sources for masked lanes
 __device__ __attribute__((aligned(16))) const float g_zero_line[4] = {0.f, 0.f, 0.f, 0.f};
 __device__ __attribute__((aligned(16))) const float g_ones_line[4] = {1.f, 1.f, 1.f, 1.f};
-
-struct ConvParams {
-    const float* in;
-    const float* wt;
-    const float* iscale;
-    const float* oscale;
-    const float* obias;
-    float* out;
-    int B, C, N, ldw;    // ldw: row pitch of wt in floats (multiple of 4, >= N)
-    int IH, IW;          // input extent
-    int GH, GW;          // output grid (phase space): rows [gy_base, GH), columns [gx_base, GW)
-    int gy_base, gx_base;
-    int OH, OW;          // full output extent
-    int osy, osx, ooy, oox;   // output coordinate = grid * os + oo
-    int dy0, dx0;        // input coordinate = grid * IS + d0 + tap
-    int wmap[9];         // weight slab of window position (ty, tx)
-    int tiles_x, tiles_y, tiles_b, tiles_n;
-    // split-K for small feature maps (few tiles, long serial K loop): slice s handles channels
-    // [s * c_per_slice, (s+1) * c_per_slice) and writes raw sums to partial[s] (layout of `out`);
-    // k_conv_reduce adds the slices in order and applies oscale / bias.  ks == 1: direct epilogue.
-    float* partial;
-    int64_t partial_floats;
-    int ks, c_per_slice;
-    // TAP9 launches: the taps this launch walks are tap_first + i * tap_step, i < tap_count (all nine: 0, 1, 9; the
-    // border strips behind the fused kernel: row 2*IH = taps 6, 7, 8; column 2*IW = taps 2, 5, 8)
-    int tap_first, tap_step, tap_count;
-};
 
 // V4: the halo window starts at a 16-byte aligned column (LEAD extra columns on the left), rows
 // are padded to a multiple of 4 floats, and the whole image moves with 16-byte DMAs (a 4-byte DMA
@@ -146,12 +113,7 @@ __global__ __launch_bounds__(256) void k_conv_mfma(const ConvParams p) {
 
     // ---- tile decode; workgroups that share an input patch (different n tiles) and neighbouring
     // patches are numbered consecutively and kept on one XCD (bid % 8 is the XCD): chunked remap.
-    const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / SR_NUM_XCD, r = nwg % SR_NUM_XCD, xcd = bid % SR_NUM_XCD;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / SR_NUM_XCD;
-    }
+    int bid = sr_xcd_chunk(blockIdx.x, gridDim.x);
     // geometry of this workgroup: the launch's, or (TAP9) its tap's
     int tap = 0, g_dy0 = p.dy0, g_dx0 = p.dx0, g_gh = p.GH, g_gw = p.GW, g_ooy = p.ooy, g_oox = p.oox, g_slab = p.wmap[0];
     int tap_local = 0;
@@ -166,17 +128,12 @@ __global__ __launch_bounds__(256) void k_conv_mfma(const ConvParams p) {
         g_gh = min(g_ooy ? p.IH : p.IH + 1, p.GH); g_gw = min(g_oox ? p.IW : p.IW + 1, p.GW);
         g_slab = tap;
     }
-    const int n_t = bid % p.tiles_n;
-    bid /= p.tiles_n;
-    const int tx_i = bid % p.tiles_x;
-    bid /= p.tiles_x;
-    const int ty_i = bid % p.tiles_y;
-    bid /= p.tiles_y;
-    const int tb_i = bid % p.tiles_b;
-    const int slice = bid / p.tiles_b;
+    const SrTile tile = sr_tile_decode(bid, p.tiles_n, p.tiles_x, p.tiles_y);
+    const int tb_i = tile.rest % p.tiles_b;
+    const int slice = tile.rest / p.tiles_b;
     const int c_beg = slice * p.c_per_slice;
     const int c_end = min(p.C, c_beg + p.c_per_slice);
-    const int n0 = n_t * BN, gy0 = p.gy_base + ty_i * PH, gx0 = p.gx_base + tx_i * PW, b0 = tb_i * PB;
+    const int n0 = tile.n_t * BN, gy0 = p.gy_base + tile.ty * PH, gx0 = p.gx_base + tile.tx * PW, b0 = tb_i * PB;
     const int iy0 = gy0 * IS + g_dy0, ix0 = gx0 * IS + g_dx0;
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -401,8 +358,7 @@ __global__ __launch_bounds__(256) void k_conv_mfma(const ConvParams p) {
         buf ^= 1;
     }
 
-    // ---- epilogue: C/D layout of the 32x32 MFMA: column (pixel) = lane & 31,
-    // row (channel) = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+    // ---- epilogue: C/D layout of the 32x32 MFMA: column (pixel) = lane & 31, row (channel) = sr_mfma32_row
     const int64_t plane_out = (int64_t)p.OH * p.OW;
 #pragma unroll
     for (int pt = 0; pt < 2; ++pt) {
@@ -415,7 +371,7 @@ __global__ __launch_bounds__(256) void k_conv_mfma(const ConvParams p) {
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int n = n0 + wco * 64 + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int n = sr_mfma32_row(r, half, n0 + wco * 64 + ct * 32);
                 if (n < p.N) {
                     float v = acc[ct][pt][r];
                     if (TAP9) {
@@ -441,13 +397,8 @@ __global__ __launch_bounds__(256) void k_conv_mfma(const ConvParams p) {
 template <int IS, int TY, int TX, int PW, int PH, int PB, bool V4, bool FAST, bool TAP9 = false>
 int launch_fast(const ConvParams& p, dim3 grid, hipStream_t st) {
     using G = Geo<IS, TY, TX, PW, PH, PB, V4, TAP9>;
-    auto kern = k_conv_mfma<IS, TY, TX, PW, PH, PB, V4, FAST, TAP9>;
-    static bool configured = false;     // opt in to > 64 KiB of dynamic LDS once per variant
-    if (!configured) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        configured = true;
-    }
+    constexpr auto kern = k_conv_mfma<IS, TY, TX, PW, PH, PB, V4, FAST, TAP9>;
+    if (!sr_allow_dynamic_lds<kern>(G::LDS_BYTES)) return SR_EINVAL;
     hipLaunchKernelGGL(kern, grid, dim3(256), G::LDS_BYTES, st, p);
     return sr_launch_status();
 }
@@ -459,329 +410,6 @@ int launch_one(const ConvParams& p, dim3 grid, hipStream_t st) {
     if (p.C % G::KC == 0 && p.c_per_slice % G::KC == 0)
         return launch_fast<IS, TY, TX, PW, PH, PB, V4, true, TAP9>(p, grid, st);
     return launch_fast<IS, TY, TX, PW, PH, PB, V4, false, TAP9>(p, grid, st);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Stride-2 transposed 3x3 convolution, all four output phases in ONE workgroup (interior of the map).
-//
-// out[2j + py, 2i + px] = sum over the taps (ky, kx) with ky = py (mod 2), kx = px (mod 2) of
-// in[j - (ky >> 1), i - (kx >> 1)] * W[ky][kx]: nine (tap -> phase, input shift) pairs over only four
-// distinct input shifts.  Run as four launches (above) every phase re-stages the same halo patch and
-// the 1- and 2-tap phases are operand-fetch bound (80 TFLOP/s).  Here a wave keeps the 2x2 MFMA tiles
-// of ALL four phases (16 accumulator tiles = 256 registers, one wave per SIMD), so per k-step the 36
-// MFMAs share 8 input operands and 18 weight operands, and the halo patch is staged once.
-// Workgroup = 32x4 input positions (-> 64x8 output pixels) x 128 output channels, K chunks of 4 input
-// channels, double-buffered LDS-DMA as in k_conv_mfma.  The last output row / column (grid row H,
-// column W) are left to the strip launches of the per-phase kernel.
-struct TFused {
-    static constexpr int KC = 8;
-    static constexpr int PW = 32, PH = 4;
-    static constexpr int LEAD = 3;                          // halo columns start at i0 - 4 (aligned); i0 - 1 is column 3
-    static constexpr int EWP = 36;                          // LEAD + 33 columns
-    static constexpr int EH = PH + 1;
-    static constexpr int PLANE = EH * EWP;                  // 180
-    static constexpr int W_FLOATS = 9 * KC * BN;            // [tap][c][128] = 9216
-    static constexpr int W_INSTR = W_FLOATS / 256;          // 36 = 9 per wave
-    static constexpr int I_INSTR = (KC * PLANE / 4 + 63) / 64;   // 6
-    static constexpr int I_FLOATS = I_INSTR * 256;          // 1536
-    static constexpr int BUF = W_FLOATS + I_FLOATS;         // 10752 floats = 42 KB
-    static constexpr int W_PER_WAVE = 9, I_PER_WAVE = 2;    // 36 / 8 instruction slots (surplus -> pad zone)
-    static constexpr int PAD = 2 * BUF;
-    static constexpr int STY = PAD + 4 * 256;
-};
-
-#ifdef CONVT_TIMING
-// debug build only (scripts/build_variant.sh): per-workgroup time stamps of wave 0
-__device__ long long g_convt_stamps[8 * 16384];
-#define CONVT_STAMP(i) do { if (threadIdx.x == 0) { g_convt_stamps[(blockIdx.x & 16383) * 8 + (i)] = wall_clock64(); } } while (0)
-#else
-#define CONVT_STAMP(i)
-#endif
-
-// KS: K slices (round 5).  With few tiles and a long channel loop (the 32^2 x 512-channel layer at batch 4: 128
-// workgroups walking 64 chunks each) slice s of p.ks walks the channels [s * c_per_slice, (s + 1) * c_per_slice): the
-// same loop over k = 0 .. n - 1 with the bases of the two buffer resources and of the style row moved, raw sums to
-// partial[s] in the layout of `out`; k_convt_fused_reduce adds the slices in order and applies scale / bias.
-template <bool KS>
-__global__ __launch_bounds__(256) void k_convt_fused(const ConvParams p) {
-#if __HIP_DEVICE_COMPILE__   // buffer-resource builtins: device pass only (the host pass needs just the stub)
-    using G = TFused;
-    CONVT_STAMP(0);
-#ifdef CONVT_TIMING
-    const long long convt_c0 = clock64();
-#endif
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* const sty = smem + G::STY;
-
-    const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / SR_NUM_XCD, r = nwg % SR_NUM_XCD, xcd = bid % SR_NUM_XCD;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / SR_NUM_XCD;
-    }
-    const int n_t = bid % p.tiles_n;
-    bid /= p.tiles_n;
-    const int tx_i = bid % p.tiles_x;
-    bid /= p.tiles_x;
-    const int ty_i = bid % p.tiles_y;
-    bid /= p.tiles_y;
-    const int b = KS ? bid % p.B : bid;
-    const int slice = KS ? bid / p.B : 0;
-    const int c_beg = KS ? slice * p.c_per_slice : 0;          // first channel of this workgroup's K range
-    const int c_cnt = KS ? p.c_per_slice : p.C;
-    const int n0 = n_t * BN, j0 = ty_i * G::PH, i0 = tx_i * G::PW;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = lane >> 5, l31 = lane & 31;
-    const int wco = wave & 1, wpx = wave >> 1;
-
-    // ---- DMA descriptors: byte offsets inside the weight tensor / this sample for chunk 0; lanes with nothing to
-    // fetch (outside the image, surplus instructions) point beyond the buffer and receive zeros.  The chunk part of
-    // every address is the scalar soffset of the buffer load: no vector ALU work per DMA instruction.
-    constexpr int OOB = 0x7FFFFFF0;
-    int w_off[G::W_PER_WAVE];
-#pragma unroll
-    for (int i = 0; i < G::W_PER_WAVE; ++i) {
-        const int j = wave + 4 * i;
-        const int row = 2 * j + half;                       // [tap * KC + c]
-        const int t = row / G::KC, c = row % G::KC;
-        const int col = min(n0 + l31 * 4, p.ldw - 4);
-        w_off[i] = j < G::W_INSTR ? ((t * p.C + c) * p.ldw + col) * 4 : OOB;
-    }
-    int i_off[G::I_PER_WAVE];
-#pragma unroll
-    for (int i = 0; i < G::I_PER_WAVE; ++i) {
-        const int j = wave + 4 * i;
-        const int f = (j * 64 + lane) * 4;
-        int off = OOB;
-        if (j < G::I_INSTR && f < G::KC * G::PLANE) {
-            const int c = f / G::PLANE, q = f % G::PLANE;
-            const int r = q / G::EWP, cola = q % G::EWP;
-            const int gy = j0 - 1 + r, gx = i0 - 4 + cola;
-            if (gy >= 0 && gy < p.IH && gx >= 0 && gx + 3 < p.IW) off = ((c * p.IH + gy) * p.IW + gx) * 4;
-        }
-        i_off[i] = off;
-    }
-    const int plane_in = p.IH * p.IW;
-    const __amdgpu_buffer_rsrc_t r_w = uniform_rsrc(p.wt + (int64_t)c_beg * p.ldw, (9 * p.C - c_beg) * p.ldw * 4);
-    const __amdgpu_buffer_rsrc_t r_in = uniform_rsrc(p.in + ((int64_t)b * p.C + c_beg) * plane_in, c_cnt * plane_in * 4);
-    const int nchunks = c_cnt / G::KC;
-
-    // DMA instruction i (0 .. 10) of chunk k (clamped to the last chunk: a surplus fetch lands in a free buffer)
-    auto dma1 = [&](int k, int i) {
-        const int kc = min(k, nchunks - 1), c0 = kc * G::KC;
-        float* dst = smem + (k & 1) * G::BUF;
-        if (i < G::I_PER_WAVE) {                             // the halo patch first: it may come from HBM
-            const int j = wave + 4 * i;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                r_in, (lptr_t)(j < G::I_INSTR ? dst + G::W_FLOATS + j * 256 : smem + G::PAD + wave * 256), 16, i_off[i],
-                c0 * plane_in * 4, 0, 0);
-        } else {                                             // then the (L2-resident) weights
-            const int ii = i - G::I_PER_WAVE, j = wave + 4 * ii;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(r_w, (lptr_t)(j < G::W_INSTR ? dst + j * 256 : smem + G::PAD + wave * 256),
-                                                     16, w_off[ii], c0 * p.ldw * 4, 0, 0);
-        }
-    };
-    constexpr int N_DMA = G::W_PER_WAVE + G::I_PER_WAVE;    // 11 per wave and chunk
-
-    // accumulators: [phase py*2+px][channel tile][pixel tile]
-    f32x16 acc[4][2][2];
-#pragma unroll
-    for (int ph = 0; ph < 4; ++ph)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[ph][i][j][r] = 0.0f;
-
-    int a_off[2], b_off[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        a_off[t] = half * BN + wco * 64 + t * 32 + l31;
-        const int py = wpx * 2 + t;                          // pixel tile t = input row py of the patch
-        b_off[t] = G::W_FLOATS + half * G::PLANE + (py + 1) * G::EWP + l31 + G::LEAD + 1;
-    }
-
-    // ---- pipeline.  One wave per SIMD: nobody else hides LDS latency or DMA issue, so
-    //  * the 26 operands of k-step g + 1 are fetched (and the 8 input operands style-scaled) under the 36 MFMAs
-    //    of k-step g — across chunk boundaries too: the chunk barrier sits in front of the LAST k-step of a
-    //    chunk, whose operands are already in registers, and the first k-step of the next chunk is fetched
-    //    under it (no MFMA ever waits for an LDS round trip behind a barrier);
-    //  * the 11 DMA instructions of a chunk are spread over three k-steps, one per 8 MFMAs.
-    // Chunk k + 1 is complete at the barrier of chunk k (issued a whole chunk earlier); chunk k + 2 then goes
-    // into the buffer of chunk k, which nobody reads any more.
-#pragma unroll
-    for (int i = 0; i < N_DMA; ++i) dma1(0, i);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma1(1, i);
-    for (int c = tid; c < c_cnt; c += 256) sty[c] = p.iscale ? p.iscale[(int64_t)b * p.C + c_beg + c] : 1.0f;
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    __syncthreads();
-
-    float A[2][9][2], X[2][4][2];                        // [set][tap][channel tile], [set][dy*2+dx][pixel tile]
-    float sc_next;
-    auto load_set = [&](const float* sb, int c0, int cp, int set) {
-#pragma unroll
-        for (int sh = 0; sh < 4; ++sh)
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-                X[set][sh][t] = sb[(2 * cp) * G::PLANE + b_off[t] - (sh >> 1) * G::EWP - (sh & 1)];
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) A[set][tap][t] = sb[(tap * G::KC + 2 * cp) * BN + a_off[t]];
-        sc_next = sty[c0 + 2 * cp + half];
-    };
-    load_set(smem, 0, 0, 0);
-#pragma unroll
-    for (int sh = 0; sh < 4; ++sh) { X[0][sh][0] *= sc_next; X[0][sh][1] *= sc_next; }
-    CONVT_STAMP(1);
-
-    for (int k = 0; k < nchunks; ++k) {
-        const float* sb = smem + (k & 1) * G::BUF;
-        const float* sbn = smem + ((k + 1) & 1) * G::BUF;
-        const int c0 = k * G::KC, c0n = min(k + 1, nchunks - 1) * G::KC;
-#pragma unroll
-        for (int cp = 0; cp < G::KC / 2; ++cp) {
-            const int cur = cp & 1, nxt = cur ^ 1;
-            if (cp == G::KC / 2 - 1) {
-                // chunk k + 1 landed (every wave drained its own DMAs), all reads of chunk k retired
-                __builtin_amdgcn_s_waitcnt(0x0F70);
-                __syncthreads();
-                load_set(sbn, c0n, 0, nxt);
-            } else {
-                load_set(sb, c0, cp + 1, nxt);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const int tap = ky * 3 + kx, ph = (ky & 1) * 2 + (kx & 1), sh = (ky >> 1) * 2 + (kx >> 1);
-                    acc[ph][0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(A[cur][tap][0], X[cur][sh][0], acc[ph][0][0], 0, 0, 0);
-                    acc[ph][0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(A[cur][tap][0], X[cur][sh][1], acc[ph][0][1], 0, 0, 0);
-                    acc[ph][1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(A[cur][tap][1], X[cur][sh][0], acc[ph][1][0], 0, 0, 0);
-                    acc[ph][1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(A[cur][tap][1], X[cur][sh][1], acc[ph][1][1], 0, 0, 0);
-                    // style onto the 8 input operands of the next k-step (not its 18 weights): one multiply per
-                    // tap from the second tap on (eight MFMAs cover the LDS latency of the fetch above)
-                    if (tap >= 1) X[nxt][(tap - 1) >> 1][(tap - 1) & 1] *= sc_next;
-                    // DMA: chunk k + 2 starts behind the barrier (4 instructions), the rest of chunk k + 1 follows in
-                    // the first two k-steps of the next iteration... seen from this iteration: cp 0 / 1 finish
-                    // chunk k + 1, the last k-step starts chunk k + 2
-                    if ((tap & 1) == 1) {
-                        const int u = tap >> 1;                               // 0 .. 3
-                        if (cp == 0) dma1(k + 1, 4 + u);
-                        else if (cp == 1 && 8 + u < N_DMA) dma1(k + 1, 8 + u);
-                        else if (cp == G::KC / 2 - 1) dma1(k + 2, u);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-        }
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    CONVT_STAMP(2);
-
-    // ---- epilogue: lane = input column i, registers = channels; phases (py, 0) and (py, 1) are the
-    // neighbouring output columns 2i, 2i + 1 of output row 2j + py
-    const int64_t plane_out = (int64_t)p.OH * p.OW;
-#pragma unroll
-    for (int pt = 0; pt < 2; ++pt) {
-        const int j = j0 + wpx * 2 + pt, i = i0 + l31;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int n = n0 + wco * 64 + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (n < p.N) {
-                    const float os = (!KS && p.oscale) ? p.oscale[(int64_t)b * p.N + n] : 1.0f;
-                    const float ob = (!KS && p.obias) ? p.obias[n] : 0.0f;
-                    float* o = (KS ? p.partial + (int64_t)slice * p.B * p.N * plane_out : p.out) +
-                               ((int64_t)b * p.N + n) * plane_out + (int64_t)(2 * j) * p.OW + 2 * i;
-                    o[0] = acc[0][ct][pt][r] * os + ob;
-                    o[1] = acc[1][ct][pt][r] * os + ob;
-                    o[p.OW] = acc[2][ct][pt][r] * os + ob;
-                    o[p.OW + 1] = acc[3][ct][pt][r] * os + ob;
-                }
-            }
-    }
-    CONVT_STAMP(3);
-#ifdef CONVT_TIMING
-    if (threadIdx.x == 0) g_convt_stamps[(blockIdx.x & 16383) * 8 + 5] = clock64() - convt_c0;
-#endif
-#endif
-}
-
-#ifdef CONVT_TIMING
-extern "C" int sr_debug_convt_stamps(long long* host, int n) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_convt_stamps), (size_t)n * sizeof(long long));
-}
-#endif
-
-// One dense-convolution call as the dispatch sees it: the shape and, for the alignment rules, the buffers.  A NULL
-// buffer means "alignment unknown, assume aligned" (as the *_eligible functions of the other files treat it).
-struct ConvCall {
-    int64_t B, C, N, IH, IW, OH, OW;
-    int ksize, stride, pad, transposed;
-    const void *in, *out, *wt;
-    int64_t ldw;
-    bool is3x3(int s, int pd) const { return ksize == 3 && stride == s && pad == pd; }
-};
-
-bool convt_fused_eligible(const ConvCall& c) {
-    // buffer addressing: byte offsets inside one sample / the weight tensor below 2^31 - 16
-    if (c.C * c.IH * c.IW >= (1LL << 29) - 4 || 9 * c.C * c.ldw >= (1LL << 29) - 4) return false;
-    return c.IH % TFused::PH == 0 && c.IW % TFused::PW == 0 && c.C % TFused::KC == 0 && c.C <= 2048 && sr_aligned16(c.in);
-}
-
-// interior outputs (rows < 2 IH, columns < 2 IW) = the slices of k_convt_fused<true> added in order, then scale / bias
-__global__ __launch_bounds__(256) void k_convt_fused_reduce(const ConvParams p) {
-    const int iw2 = 2 * p.IW, ih2 = 2 * p.IH;
-    const int64_t plane_out = (int64_t)p.OH * p.OW, planes = (int64_t)p.B * p.N;
-    const int64_t total = planes * ih2 * (iw2 / 4);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t row = i / ((int64_t)ih2 * (iw2 / 4));
-        const int q = (int)(i - row * (int64_t)ih2 * (iw2 / 4));
-        const int Y = q / (iw2 / 4), X = (q - Y * (iw2 / 4)) * 4;
-        const int64_t at = row * plane_out + (int64_t)Y * p.OW + X;
-        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (int s = 0; s < p.ks; ++s) {
-            const float* src = p.partial + (int64_t)s * planes * plane_out + at;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc[k] += src[k];
-        }
-        const float os = p.oscale ? p.oscale[row] : 1.0f, ob = p.obias ? p.obias[row % p.N] : 0.0f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) p.out[at + k] = acc[k] * os + ob;
-    }
-}
-
-// K slices of the fused kernel: the smallest of 2 / 4 that gives >= 192 workgroups with whole chunks and >= 64 channels per slice
-int convt_fused_slices(int64_t fused_blocks, int C) {
-    for (int ks = 2; ks <= 4; ks *= 2)
-        if (C % (ks * TFused::KC) == 0 && C / ks >= 64 && fused_blocks * ks >= 192) return ks;
-    return 1;
-}
-
-// ks > 1: the K slices the plan chose (convt_fused_slices)
-int launch_convt_fused(ConvParams p, int ks, hipStream_t st) {
-    if (ks > 1) { p.ks = ks; p.c_per_slice = p.C / ks; }
-    p.tiles_x = p.IW / TFused::PW;
-    p.tiles_y = p.IH / TFused::PH;
-    p.tiles_n = (p.N + BN - 1) / BN;
-    const int64_t blocks = (int64_t)p.tiles_x * p.tiles_y * p.tiles_n * p.B * p.ks;
-    if (blocks > 0x7FFFFFFFLL) return SR_ERANGE;
-    if (p.ks > 1) {
-        const int lds = (TFused::STY + p.c_per_slice) * 4;
-        hipLaunchKernelGGL(k_convt_fused<true>, dim3((unsigned)blocks), dim3(256), lds, st, p);
-        const int64_t total = (int64_t)p.B * p.N * 2 * p.IH * (2 * p.IW / 4);
-        hipLaunchKernelGGL(k_convt_fused_reduce, dim3(sr_stream_grid(total, 256)), dim3(256), 0, st, p);
-        return sr_launch_status();
-    }
-    const int lds = (TFused::STY + p.C) * 4;
-    hipLaunchKernelGGL(k_convt_fused<false>, dim3((unsigned)blocks), dim3(256), lds, st, p);
-    return sr_launch_status();
 }
 
 void patch_shape(int GW, int& pw, int& ph, int& pb) {
@@ -853,98 +481,13 @@ __global__ __launch_bounds__(256) void k_convt_tap_reduce(const ConvParams p) {
     }
 }
 
-// K slices of the tap-split launch: enough workgroups for ~2 per CU (the nine taps already multiply the tiles by 9),
-// >= 32 channels (a multiple of 16) per slice
-void convt_taps_plan(int IH, int IW, int B, int N, int C, int& ks, int& c_per_slice) {
-    if (sr_convt_taps_gemm_eligible(B, C, N, IW, 4, 16, nullptr)) {
-        // flattened-pixel form (csrc/conv1x1_gemm.hip): 128-point tiles of the (sample, grid point) index; ~2 workgroups
-        // per CU (scripts/taps_wgs_sweep.sh: 16^2 at batch 4 0.148 / 0.104 / 0.126 / 0.127 ms for 1 / 2 / 3 / 4 — more slices
-        // cover a chunk's load latency with other workgroups' MFMAs but multiply the partial sums the reduction reads)
-        const int64_t tiles = sr_ceil_div((int64_t)B * (IH + 1) * (IW + 1), 128) * (N / 128) * 9;
-        static const int per_cu = [] {
-            const char* e = std::getenv("SR_TAPS_WGS");       // workgroups per CU the K slices aim at (measurements)
-            const int v = e ? std::atoi(e) : 0;
-            return v >= 1 && v <= 8 ? v : 2;
-        }();
-        int want = (int)sr_ceil_div((int64_t)per_cu * SR_NUM_CU, tiles);
-        if (want > 8) want = 8;
-        if (want < 1) want = 1;
-        int per = (C + want - 1) / want;
-        per = (per + 15) / 16 * 16;
-        if (per < 64) per = 64;
-        if (per > C) per = C;
-        c_per_slice = per;
-        ks = (C + per - 1) / per;
-        return;
-    }
-    int pw, ph, pb;
-    patch_shape(IW + 1, pw, ph, pb);
-    const int64_t blocks = (int64_t)((IW + pw) / pw) * ((IH + ph) / ph) * ((B + pb - 1) / pb) * ((N + BN - 1) / BN) * 9;
-    ks = 1;
-    c_per_slice = (C + 15) / 16 * 16;
-    if (blocks >= 2 * SR_NUM_CU || C < 64) return;
-    int want = (int)((2 * SR_NUM_CU + blocks - 1) / blocks);
-    if (want > 8) want = 8;
-    int per = (C + want - 1) / want;
-    per = (per + 15) / 16 * 16;
-    if (per < 32) per = 32;
-    c_per_slice = per;
-    ks = (C + per - 1) / per;
-}
-
-// Small problems only: measured inside captured graphs (scripts/bench_convt_small.py, profiles/r05_notes.md) the
-// tap-split form wins up to ~10 GFLOP per call (4^2 .. 16^2 maps at batch 4, 32^2 .. 128^2 at batch 1: 0.042 / 0.069 /
-// 0.128 / 0.135 / 0.168 / 0.172 ms against 0.071 / 0.095 / 0.218 / 0.226 / 0.258 / 0.231; 32^2 at batch 2 and 16^2 at
-// batch 8, 9.7 GFLOP: 0.241 against 0.259 / 0.270) and loses above (its 1x1 workgroups top out at 45-60 TFLOP/s; 32^2
-// at batch 4: 0.429 against 0.352 per-phase).
-// SR_CONVT_TAPS=0 keeps the per-phase launches for small maps (A/B measurements); =1 forces the tap-split form for any size
-bool convt_taps_wanted(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW) {
-    const int sw = sr_env_char("SR_CONVT_TAPS");
-    if (sw >= 0) return sw != '0';
-    return 18.0 * (double)B * (double)C * (double)N * (double)IH * (double)IW < 1.05e10;
-}
-
 // 16-byte halo DMAs for a tap-split launch: aligned rows and an aligned tile origin (one sample per patch is checked
 // by the caller's choice of the patch shape); SR_CONVT_TAPS_V4=0 keeps the 4-byte form (A/B, tests)
 bool taps_v4(const ConvParams& p) {
     return !sr_env_off("SR_CONVT_TAPS_V4") && p.IW % 4 == 0 && p.gx_base % 4 == 0 && sr_aligned16(p.in);
 }
 
-// ks / c_per_slice: convt_taps_plan's; gemm: the flattened-pixel form (sr_convt_taps_gemm_eligible for this call's weights)
-int launch_convt_taps(ConvParams p, int ks, int c_per_slice, bool gemm, hipStream_t st) {
-    p.GH = p.IH + 1; p.GW = p.IW + 1;                // common grid of the four phases
-    p.gy_base = p.gx_base = 0;
-    p.osy = p.osx = 2; p.ooy = p.oox = 0;
-    p.dy0 = p.dx0 = 0;
-    p.tap_first = 0; p.tap_step = 1; p.tap_count = 9;
-    p.ks = ks; p.c_per_slice = c_per_slice;
-    int pw, ph, pb;
-    patch_shape(p.GW, pw, ph, pb);
-    p.tiles_x = (p.GW + pw - 1) / pw;
-    p.tiles_y = (p.GH + ph - 1) / ph;
-    p.tiles_b = (p.B + pb - 1) / pb;
-    p.tiles_n = (p.N + BN - 1) / BN;
-    const int64_t blocks = (int64_t)p.tiles_x * p.tiles_y * p.tiles_b * p.tiles_n * p.ks * 9;
-    if (blocks > 0x7FFFFFFFLL) return SR_ERANGE;
-    const dim3 grid((unsigned)blocks);
-    const bool v4 = taps_v4(p);
-    int rc;
-    if (gemm)
-        // pixels = the flattened (sample, grid point) index instead of 32 x 4 patches of a (2^k + 1)-wide grid
-        rc = sr_convt_taps_gemm_launch(p.partial, p.in, p.wt, p.ldw, p.iscale, p.B, p.C, p.N, p.IH, p.IW, p.ks, p.c_per_slice, st);
-    else if (pw == 32) rc = v4 ? launch_one<1, 1, 1, 32, 4, 1, true, true>(p, grid, st)
-                          : launch_one<1, 1, 1, 32, 4, 1, false, true>(p, grid, st);
-    else if (pw == 16) rc = v4 ? launch_one<1, 1, 1, 16, 8, 1, true, true>(p, grid, st)
-                               : launch_one<1, 1, 1, 16, 8, 1, false, true>(p, grid, st);
-    else if (pw == 8) rc = launch_one<1, 1, 1, 8, 8, 2, false, true>(p, grid, st);
-    else rc = launch_one<1, 1, 1, 4, 4, 8, false, true>(p, grid, st);
-    if (rc != SR_OK) return rc;
-    const int64_t total = (int64_t)p.B * p.N * p.OH * p.OW;
-    hipLaunchKernelGGL(k_convt_tap_reduce, dim3(sr_stream_grid(total, 256)), dim3(256), 0, st, p);
-    return sr_launch_status();
-}
-
-// Border strips behind the fused kernel (output row 2*IH, column 2*IW) through the same tap machinery: only the taps
+// Border strips behind an interior kernel (output row 2*IH, column 2*IW) through the same tap machinery: only the taps
 // ky = 2 reach the last row, only kx = 2 the last column — two TAP9 launches of three taps each (32-wide patches along
 // the row, 4 x 4 x 8-sample patches down the column) and one reduction, instead of four thin per-phase launches with a
 // split-K reduction behind each.  partial = [row: 3 x B x N x (IW + 1)] [column: 3 x B x N x IH].
@@ -981,7 +524,6 @@ __global__ __launch_bounds__(256) void k_convt_strip_reduce(const ConvParams p, 
 
 // (up to STRIP_KS K slices per strip)
 constexpr int STRIP_KS = 4;
-int64_t convt_strip_floats(int64_t B, int64_t N, int64_t IH, int64_t IW) { return STRIP_KS * 3 * B * N * (IW + 1 + IH); }
 
 template <int PW, int PH, int PB>
 int launch_strip_part(ConvParams& p, hipStream_t st) {
@@ -1004,37 +546,6 @@ int launch_strip_part(ConvParams& p, hipStream_t st) {
     if (PB == 1 && taps_v4(p)) return launch_one<1, 1, 1, PW, PH, PB, PB == 1, true>(p, dim3((unsigned)blocks), st);
     return launch_one<1, 1, 1, PW, PH, PB, false, true>(p, dim3((unsigned)blocks), st);
 }
-
-int launch_convt_strips(ConvParams p, hipStream_t st) {
-    float* prow = p.partial;
-    float* pcol = p.partial + STRIP_KS * 3 * (int64_t)p.B * p.N * (p.IW + 1);
-    p.osy = p.osx = 2; p.ooy = p.oox = 0;
-    p.dy0 = p.dx0 = 0;
-    p.ks = 1; p.c_per_slice = (p.C + 15) / 16 * 16;
-    // row 2*IH: grid row IH, all IW + 1 grid columns, taps (2, 0) (2, 1) (2, 2)
-    p.gy_base = p.IH; p.GH = p.IH + 1; p.gx_base = 0; p.GW = p.IW + 1;
-    p.tap_first = 6; p.tap_step = 1; p.tap_count = 3;
-    p.partial = prow;
-    int rc = launch_strip_part<32, 4, 1>(p, st);
-    if (rc != SR_OK) return rc;
-    const int ks_row = p.ks;
-    // column 2*IW: grid column IW, grid rows 0 .. IH - 1 (the corner is the row's), taps (0, 2) (1, 2) (2, 2)
-    p.gy_base = 0; p.GH = p.IH; p.gx_base = p.IW; p.GW = p.IW + 1;
-    p.tap_first = 2; p.tap_step = 3; p.tap_count = 3;
-    p.partial = pcol;
-    rc = launch_strip_part<4, 4, 8>(p, st);
-    if (rc != SR_OK) return rc;
-    const int ks_col = p.ks;
-    const int64_t total = (int64_t)p.B * p.N * (p.OW + p.OH - 1);
-    hipLaunchKernelGGL(k_convt_strip_reduce, dim3(sr_stream_grid(total, 256)), dim3(256), 0, st, p, prow, pcol, ks_row,
-                       ks_col);
-    return sr_launch_status();
-}
-
-// Polyphase 25-product form of the non-transposed stride-2 3x3 convolution (csrc/conv_s2_wino.hip).
-// The kernel has no K slices: launches with fewer workgroups stay on k_conv_mfma, whose split-K serves them (the
-// threshold k_convt_fused uses for the same reason; measurements in DESIGN.md 4.1y).
-constexpr int64_t S2_WINO_MIN_BLOCKS = 192;
 
 template <int IS, int TY, int TX>
 int launch_by_patch(ConvParams& p, hipStream_t st) {
@@ -1082,148 +593,152 @@ int launch_by_patch(ConvParams& p, hipStream_t st) {
     return sr_launch_status();
 }
 
-// ---- dispatch plan: which kernel serves a call is decided ONCE, by make_conv_plan (DESIGN.md 4.0 has the table) ------------
+}  // namespace
 
-// Scratch the direct kernel's split-K would use: ks * B * N * region for the largest region a launch may split — the
-// whole output grid or, transposed, the phase grids and their border strips.  A wish, not a need: launch_by_patch drops
-// to one slice when the slab does not fit.
-int64_t direct_floats(const ConvCall& c) {
+// ---- what the dispatch plan uses (conv_mfma.h) -------------------------------------------------------------------------------
+
+int64_t sr_conv_direct_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW,
+                              int transposed) {
     int ks, per;
     int64_t need = 0;
     auto consider = [&](int64_t gh, int64_t gw) {
         if (gh <= 0 || gw <= 0) return;
-        choose_split((int)gh, (int)gw, (int)c.B, (int)c.N, (int)c.C, ks, per);
-        if (ks > 1) need = std::max(need, ks * c.B * c.N * gh * gw);
+        choose_split((int)gh, (int)gw, (int)B, (int)N, (int)C, ks, per);
+        if (ks > 1) need = std::max(need, ks * B * N * gh * gw);
     };
-    if (!c.transposed) consider(c.OH, c.OW);
-    else consider(c.IH + 1, c.IW + 1), consider(c.IH, c.IW), consider(1, c.IW + 1), consider(c.IH, 1);
+    if (!transposed) consider(OH, OW);
+    else consider(IH + 1, IW + 1), consider(IH, IW), consider(1, IW + 1), consider(IH, 1);
     return need;
 }
 
-bool convt_interior(int path) {
-    return path == SR_CONV_PATH_CONVT_BF16 || path == SR_CONV_PATH_CONVT_WINO || path == SR_CONV_PATH_CONVT_FUSED_KS ||
-           path == SR_CONV_PATH_CONVT_FUSED;
+int sr_conv_direct_launch(ConvParams p, int ksize, int stride, int pad, hipStream_t st) {
+    p.GH = p.OH; p.GW = p.OW;
+    p.gy_base = p.gx_base = 0;
+    p.osy = p.osx = 1; p.ooy = p.oox = 0;
+    p.dy0 = p.dx0 = -pad;
+    for (int i = 0; i < ksize * ksize; ++i) p.wmap[i] = i;
+    if (ksize == 3) return stride == 1 ? launch_by_patch<1, 3, 3>(p, st) : launch_by_patch<2, 3, 3>(p, st);
+    return stride == 1 ? launch_by_patch<1, 1, 1>(p, st) : launch_by_patch<2, 1, 1>(p, st);
 }
 
-// 25-product form of the transposed stride-2 3x3 convolution's interior (csrc/convt_wino.hip).  The kernel has no K
-// slices, so the bar is on the direct flops 18 B C N IH IW of the launch: smaller launches keep k_convt_fused, its K
-// slices and the tap-split form.  Floor: the row ("t3s2", (8, 512, 512, 32, 32)) of tests/conv_plan_cases.py (3.87e10) is
-// launched by the GPU suite as a k_convt_fused shape and stays there.  Measured, the new kernel is ahead on every row from
-// 1.93e10 up (0.67 .. 0.86 of k_convt_fused's time), so the bar sits just above its floor; the generator's
-// launches at batch 16 start at 7.73e10.
-constexpr double CONVT_WINO_MIN_FLOPS = 4.0e10;
-static_assert(CONVT_WINO_MIN_FLOPS > 18.0 * 8 * 512 * 512 * 32 * 32, "the t3s2 row of tests/conv_plan_cases.py stays on k_convt_fused");
-
-struct ConvPlan {
-    int path = SR_CONV_PATH_DIRECT; // the direct kernel (per-phase launches when transposed) takes what nobody else does
-    bool strips = false;            // transposed: launch_convt_strips follows the interior kernel
-    int ks = 1, c_per_slice = 0;    // K slices of the fused / tap-split launch (c_per_slice: tap-split only)
-    bool taps_gemm = false;         // tap-split in its flattened-pixel GEMM form
-    int64_t floats = 0;             // scratch of the chosen path (direct: what its split-K would use)
-    int64_t sized = 0;              // sr_conv2d_scratch_floats of the call
-    int code() const { return path | (strips ? SR_CONV_PATH_STRIPS : 0); }
-};
-
-// THE path list: every path of a call's geometry goes through candidate(), in priority order.
-//   reach   the SHAPE can get here: with some buffer alignment, below or above a launch-size bar, and with the on / off
-//           switches (SR_CONV_S2_WINO, SR_CONVT_WINO, SR_CONVT_FUSED, SR_CONVT_FUSED_KS, SR_CONVT_STRIPS, SR_CONV1X1_GEMM) in either
-//           position — they are read per call, the scratch may be sized before one flips.  SR_WINOGRAD, SR_CONVT_TAPS and
-//           SR_CONV_SPLIT_BF16 count as they stand.  `sized` is the largest `floats` within reach,
-//   take    THIS call takes it (its buffers, the switches now) unless an earlier candidate did
-//   floats  scratch the path cannot run without — so with a scratch (of `sized` floats: the interface has no other
-//           size) whatever is taken fits, and without one only paths that need none are taken
-ConvPlan make_conv_plan(const ConvCall& c, bool have_scratch) {
-    ConvPlan plan;
-    const int64_t B = c.B, C = c.C, N = c.N, IH = c.IH, IW = c.IW, OH = c.OH, OW = c.OW;
-    if (B <= 0 || C <= 0 || N <= 0 || OH <= 0 || OW <= 0) return plan;
-    plan.sized = plan.floats = direct_floats(c);
-    auto candidate = [&](int path, bool reach, bool take, int64_t floats, int ks = 1) {
-        if (!reach) return;
-        plan.sized = std::max(plan.sized, floats);
-        if (plan.path != SR_CONV_PATH_DIRECT || !take || (floats > 0 && !have_scratch)) return;
-        plan.path = path; plan.floats = floats; plan.ks = ks;
-    };
-    if (!c.transposed && c.is3x3(1, 1)) {
-        if (sr_winograd_enabled() && sr_wino_eligible(B, C, N, IH, IW, nullptr, nullptr))
-            candidate(SR_CONV_PATH_WINO, true, sr_wino_eligible(B, C, N, IH, IW, c.in, c.out),
-                      sr_wino_scratch_floats(C, N) + sr_wino_partial_floats(B, C, N, IH, IW));
-    } else if (!c.transposed && c.is3x3(2, 0)) {
-        // opt-in spike (SR_CONV_SPLIT_BF16=1): split-bf16 matrix path for the down-sampling convolution and the data
-        // gradient of the up-sampling one
-        candidate(SR_CONV_PATH_S2_BF16, sr_wgrad_bf16x3_enabled('c') && sr_conv_s2_bf16x3_eligible(B, C, N, IH, IW, OH, OW),
-                  true, sr_conv_s2_bf16x3_scratch_floats(C, N));
-        const int sw = sr_env_char("SR_CONV_S2_WINO");      // =0 keeps k_conv_mfma, =force ignores the workgroup bar (tests)
-        candidate(SR_CONV_PATH_S2_WINO, sr_conv_s2_wino_eligible(B, C, N, IH, IW, OH, OW, nullptr, nullptr),
-                  sw != '0' && sr_conv_s2_wino_eligible(B, C, N, IH, IW, OH, OW, c.in, c.out) &&
-                      (sw == 'f' || sr_conv_s2_wino_blocks(B, N, OH, OW) >= S2_WINO_MIN_BLOCKS),
-                  sr_conv_s2_wino_scratch_floats(C, N));
-    } else if (!c.transposed && c.ksize == 1 && c.stride == 1) {
-        // no window: a plain GEMM with both operands K-major (csrc/conv1x1_gemm.hip) where its tiles fill the chip
-        candidate(SR_CONV_PATH_GEMM1X1, true,
-                  c.pad == 0 && sr_conv1x1_gemm_eligible(B, C, N, c.ldw, IH * IW, c.in, c.wt, c.out), 0);
-    } else if (c.transposed && c.is3x3(2, 0)) {
-        // opt-in spike (SR_CONV_SPLIT_BF16=1): the interior of the map on the bf16 matrix cores (three-way operand
-        // split); it keeps the tap-split form out, the border stays on the exact-fp32 kernels
-        const bool bf = sr_wgrad_bf16x3_enabled('t') && sr_convt_bf16x3_eligible(B, C, N, IH, IW);
-        // SR_CONVT_WINO: =0 never takes k_convt_wino, =force takes it for any eligible size (tests), unset applies the
-        // flop bar; SR_CONVT_FUSED=0 ("per-phase launches") keeps it out too
-        const int sw = sr_env_char("SR_CONVT_FUSED"), wsw = sr_env_char("SR_CONVT_WINO");
-        const bool wino_ok = sw != '0' && wsw != '0' && sr_convt_wino_eligible(B, C, N, IH, IW, c.ldw, c.in);
-        const bool wino_forced = wino_ok && wsw == 'f' && !bf;
-        // small problems: nine shifted 1x1 convolutions in one launch + one reduction (k_conv_mfma<..., TAP9>)
-        if (convt_taps_wanted(B, C, N, IH, IW)) {
-            int ks;
-            convt_taps_plan((int)IH, (int)IW, (int)B, (int)N, (int)C, ks, plan.c_per_slice);
-            candidate(SR_CONV_PATH_CONVT_TAPS, true, !bf && !wino_forced, (int64_t)ks * 9 * B * N * (IH + 1) * (IW + 1), ks);
-        }
-        candidate(SR_CONV_PATH_CONVT_BF16, bf, true, sr_convt_bf16x3_scratch_floats(C, N));
-        // interior of the map in 25 of 36 products (k_convt_wino) for the large launches
-        candidate(SR_CONV_PATH_CONVT_WINO, sr_convt_wino_eligible(B, C, N, IH, IW, c.ldw, nullptr),
-                  wino_ok && (wsw == 'f' || 18.0 * (double)B * (double)C * (double)N * (double)IH * (double)IW >=
-                                                CONVT_WINO_MIN_FLOPS), 0);
-        // interior of the map: all four phases in one workgroup (k_convt_fused); SR_CONVT_FUSED=0 keeps the per-phase
-        // launches, =1 takes it whatever the size
-        const bool fused_ok = sw != '0' && IW >= 16 && convt_fused_eligible(c);
-        // the fused kernel has no split-K: when its workgroups cover less than ~3/4 of the CUs AND the channel loop is
-        // long (C > 256: 64 chunks, ~0.38 ms whatever the batch), each one walks the whole loop alone and the per-phase
-        // launches, which split K, are faster — in-graph, scripts/bench_convt_small.py: 32^2 512->512 at batch 1 / 2 / 4
-        // 0.23 / 0.26 / 0.35 ms against 0.38 / 0.39 / 0.40 fused (batch 8: 0.56 against 0.43, fused stays);
-        // 64^2 512->256 at batch 1 / 2 0.26 / 0.33 against 0.39; 128^2 256->128 (32 chunks) is fused from batch 1 on
-        const int64_t blocks = (IW / TFused::PW) * (IH / TFused::PH) * ((N + BN - 1) / BN) * B;
-        const bool pays = blocks >= 192 || C <= 256;
-        // few tiles, long channel loop: K slices inside the fused kernel (SR_CONVT_FUSED_KS=0: the per-phase launches)
-        const int ks = (IW % TFused::PW || IH % TFused::PH || pays) ? 1 : convt_fused_slices(blocks, (int)C);
-        candidate(SR_CONV_PATH_CONVT_FUSED_KS, ks > 1, fused_ok && !sr_env_off("SR_CONVT_FUSED_KS"),
-                  ks * B * N * (2 * IH + 1) * (2 * IW + 1), ks);
-        candidate(SR_CONV_PATH_CONVT_FUSED, true, fused_ok && (pays || sw == '1'), 0);
-        // behind an interior kernel the output row 2*IH and column 2*IW run as two three-tap launches + one reduction
-        // (SR_CONVT_STRIPS=0: the four thin per-phase launches and their split-K reductions)
-        const int64_t strip = convt_strip_floats(B, N, IH, IW);
-        plan.sized = std::max(plan.sized, strip);
-        if (convt_interior(plan.path) && have_scratch && !sr_env_off("SR_CONVT_STRIPS")) {
-            plan.strips = true;
-            plan.floats = std::max(plan.floats, strip);
-        }
+// K slices of the tap-split launch: enough workgroups for ~2 per CU (the nine taps already multiply the tiles by 9),
+// >= 32 channels (a multiple of 16) per slice
+void sr_convt_taps_plan(int IH, int IW, int B, int N, int C, int& ks, int& c_per_slice) {
+    if (sr_convt_taps_gemm_eligible(B, C, N, IW, 4, 16, nullptr)) {
+        // flattened-pixel form (csrc/conv1x1_gemm.hip): 128-point tiles of the (sample, grid point) index; ~2 workgroups
+        // per CU (scripts/taps_wgs_sweep.sh: 16^2 at batch 4 0.148 / 0.104 / 0.126 / 0.127 ms for 1 / 2 / 3 / 4 — more slices
+        // cover a chunk's load latency with other workgroups' MFMAs but multiply the partial sums the reduction reads)
+        const int64_t tiles = sr_ceil_div((int64_t)B * (IH + 1) * (IW + 1), 128) * (N / 128) * 9;
+        static const int per_cu = [] {
+            const char* e = std::getenv("SR_TAPS_WGS");       // workgroups per CU the K slices aim at (measurements)
+            const int v = e ? std::atoi(e) : 0;
+            return v >= 1 && v <= 8 ? v : 2;
+        }();
+        int want = (int)sr_ceil_div((int64_t)per_cu * SR_NUM_CU, tiles);
+        if (want > 8) want = 8;
+        if (want < 1) want = 1;
+        int per = (C + want - 1) / want;
+        per = (per + 15) / 16 * 16;
+        if (per < 64) per = 64;
+        if (per > C) per = C;
+        c_per_slice = per;
+        ks = (C + per - 1) / per;
+        return;
     }
-    if (plan.path == SR_CONV_PATH_CONVT_TAPS)
-        plan.taps_gemm = sr_convt_taps_gemm_eligible(B, C, N, IW, c.ldw, plan.c_per_slice, c.wt);
-    return plan;
+    int pw, ph, pb;
+    patch_shape(IW + 1, pw, ph, pb);
+    const int64_t blocks = (int64_t)((IW + pw) / pw) * ((IH + ph) / ph) * ((B + pb - 1) / pb) * ((N + BN - 1) / BN) * 9;
+    ks = 1;
+    c_per_slice = (C + 15) / 16 * 16;
+    if (blocks >= 2 * SR_NUM_CU || C < 64) return;
+    int want = (int)((2 * SR_NUM_CU + blocks - 1) / blocks);
+    if (want > 8) want = 8;
+    int per = (C + want - 1) / want;
+    per = (per + 15) / 16 * 16;
+    if (per < 32) per = 32;
+    c_per_slice = per;
+    ks = (C + per - 1) / per;
 }
 
-// The geometries the matrix-core kernels serve (SR_EINVAL otherwise).
-bool conv_call_valid(const ConvCall& c) {
-    if (c.B < 0 || c.C <= 0 || c.N <= 0 || c.IH <= 0 || c.IW <= 0 || c.OH <= 0 || c.OW <= 0) return false;
-    if (c.transposed) return c.is3x3(2, 0) && c.OH == 2 * c.IH + 1 && c.OW == 2 * c.IW + 1;
-    return (c.ksize == 3 || c.ksize == 1) && (c.stride == 1 || c.stride == 2) &&
-           c.OH == (c.IH + 2 * c.pad - c.ksize) / c.stride + 1 && c.OW == (c.IW + 2 * c.pad - c.ksize) / c.stride + 1;
+// Small problems only: measured inside captured graphs (scripts/bench_convt_small.py, profiles/r05_notes.md) the
+// tap-split form wins up to ~10 GFLOP per call (4^2 .. 16^2 maps at batch 4, 32^2 .. 128^2 at batch 1: 0.042 / 0.069 /
+// 0.128 / 0.135 / 0.168 / 0.172 ms against 0.071 / 0.095 / 0.218 / 0.226 / 0.258 / 0.231; 32^2 at batch 2 and 16^2 at
+// batch 8, 9.7 GFLOP: 0.241 against 0.259 / 0.270) and loses above (its 1x1 workgroups top out at 45-60 TFLOP/s; 32^2
+// at batch 4: 0.429 against 0.352 per-phase).
+// SR_CONVT_TAPS=0 keeps the per-phase launches for small maps (A/B measurements); =1 forces the tap-split form for any size
+bool sr_convt_taps_wanted(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW) {
+    const int sw = sr_env_char("SR_CONVT_TAPS");
+    if (sw >= 0) return sw != '0';
+    return 18.0 * (double)B * (double)C * (double)N * (double)IH * (double)IW < 1.05e10;
+}
+
+int sr_convt_taps_launch(ConvParams p, int ks, int c_per_slice, bool gemm, hipStream_t st) {
+    p.GH = p.IH + 1; p.GW = p.IW + 1;                // common grid of the four phases
+    p.gy_base = p.gx_base = 0;
+    p.osy = p.osx = 2; p.ooy = p.oox = 0;
+    p.dy0 = p.dx0 = 0;
+    p.tap_first = 0; p.tap_step = 1; p.tap_count = 9;
+    p.ks = ks; p.c_per_slice = c_per_slice;
+    int pw, ph, pb;
+    patch_shape(p.GW, pw, ph, pb);
+    p.tiles_x = (p.GW + pw - 1) / pw;
+    p.tiles_y = (p.GH + ph - 1) / ph;
+    p.tiles_b = (p.B + pb - 1) / pb;
+    p.tiles_n = (p.N + BN - 1) / BN;
+    const int64_t blocks = (int64_t)p.tiles_x * p.tiles_y * p.tiles_b * p.tiles_n * p.ks * 9;
+    if (blocks > 0x7FFFFFFFLL) return SR_ERANGE;
+    const dim3 grid((unsigned)blocks);
+    const bool v4 = taps_v4(p);
+    int rc;
+    if (gemm)
+        // pixels = the flattened (sample, grid point) index instead of 32 x 4 patches of a (2^k + 1)-wide grid
+        rc = sr_convt_taps_gemm_launch(p.partial, p.in, p.wt, p.ldw, p.iscale, p.B, p.C, p.N, p.IH, p.IW, p.ks, p.c_per_slice, st);
+    else if (pw == 32) rc = v4 ? launch_one<1, 1, 1, 32, 4, 1, true, true>(p, grid, st)
+                          : launch_one<1, 1, 1, 32, 4, 1, false, true>(p, grid, st);
+    else if (pw == 16) rc = v4 ? launch_one<1, 1, 1, 16, 8, 1, true, true>(p, grid, st)
+                               : launch_one<1, 1, 1, 16, 8, 1, false, true>(p, grid, st);
+    else if (pw == 8) rc = launch_one<1, 1, 1, 8, 8, 2, false, true>(p, grid, st);
+    else rc = launch_one<1, 1, 1, 4, 4, 8, false, true>(p, grid, st);
+    if (rc != SR_OK) return rc;
+    const int64_t total = (int64_t)p.B * p.N * p.OH * p.OW;
+    hipLaunchKernelGGL(k_convt_tap_reduce, dim3(sr_stream_grid(total, 256)), dim3(256), 0, st, p);
+    return sr_launch_status();
+}
+
+int64_t sr_convt_strip_floats(int64_t B, int64_t N, int64_t IH, int64_t IW) { return STRIP_KS * 3 * B * N * (IW + 1 + IH); }
+
+int sr_convt_strips_launch(ConvParams p, hipStream_t st) {
+    float* prow = p.partial;
+    float* pcol = p.partial + STRIP_KS * 3 * (int64_t)p.B * p.N * (p.IW + 1);
+    p.osy = p.osx = 2; p.ooy = p.oox = 0;
+    p.dy0 = p.dx0 = 0;
+    p.ks = 1; p.c_per_slice = (p.C + 15) / 16 * 16;
+    // row 2*IH: grid row IH, all IW + 1 grid columns, taps (2, 0) (2, 1) (2, 2)
+    p.gy_base = p.IH; p.GH = p.IH + 1; p.gx_base = 0; p.GW = p.IW + 1;
+    p.tap_first = 6; p.tap_step = 1; p.tap_count = 3;
+    p.partial = prow;
+    int rc = launch_strip_part<32, 4, 1>(p, st);
+    if (rc != SR_OK) return rc;
+    const int ks_row = p.ks;
+    // column 2*IW: grid column IW, grid rows 0 .. IH - 1 (the corner is the row's), taps (0, 2) (1, 2) (2, 2)
+    p.gy_base = 0; p.GH = p.IH; p.gx_base = p.IW; p.GW = p.IW + 1;
+    p.tap_first = 2; p.tap_step = 3; p.tap_count = 3;
+    p.partial = pcol;
+    rc = launch_strip_part<4, 4, 8>(p, st);
+    if (rc != SR_OK) return rc;
+    const int ks_col = p.ks;
+    const int64_t total = (int64_t)p.B * p.N * (p.OW + p.OH - 1);
+    hipLaunchKernelGGL(k_convt_strip_reduce, dim3(sr_stream_grid(total, 256)), dim3(256), 0, st, p, prow, pcol, ks_row,
+                       ks_col);
+    return sr_launch_status();
 }
 
 // The transposed convolution as its four output phases.  Output phase (py, px) of grid point (j, i) = output
 // (2j + py, 2i + px); window position ty reads input row j + ty - (TY - 1) and pairs with ky = py + 2 * (TY - 1 - ty).
 // The phase grids have 2^k + 1 points per side: the 2^k x 2^k interior tiles the 32-wide patches exactly, the last grid
 // row / column (output row 2*IH, column 2*IW: even phases only) runs as thin strip launches instead of padding every
-// tile row by up to 50 %.  interior_done: an interior kernel has written the interior already.
-int launch_convt_phases(ConvParams p, bool interior_done, hipStream_t st) {
+// tile row by up to 50 %.
+int sr_convt_phases_launch(ConvParams p, bool interior_done, hipStream_t st) {
     for (int py = 0; py < 2; ++py)
         for (int px = 0; px < 2; ++px) {
             const int TYp = py == 0 ? 2 : 1, TXp = px == 0 ? 2 : 1;
@@ -1259,135 +774,4 @@ int launch_convt_phases(ConvParams p, bool interior_done, hipStream_t st) {
             }
         }
     return SR_OK;
-}
-
-}  // namespace
-
-extern "C" int64_t sr_conv2d_scratch_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW,
-                                            int64_t OH, int64_t OW, int ksize, int stride, int pad,
-                                            int transposed) {
-    const ConvCall c{B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, nullptr, nullptr, nullptr, 0};
-    return make_conv_plan(c, true).sized;
-}
-
-extern "C" int sr_conv2d_path(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW, int ksize,
-                              int stride, int pad, int transposed, const float* in, const float* out, const float* wt,
-                              int64_t wt_ld, int have_scratch) {
-    const ConvCall c{B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, in, out, wt, wt_ld};
-    return conv_call_valid(c) ? make_conv_plan(c, have_scratch != 0).code() : SR_CONV_PATH_INVALID;
-}
-
-extern "C" int64_t sr_conv2d_path_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW,
-                                         int ksize, int stride, int pad, int transposed, const float* in, const float* out,
-                                         const float* wt, int64_t wt_ld, int have_scratch) {
-    const ConvCall c{B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, in, out, wt, wt_ld};
-    return conv_call_valid(c) ? make_conv_plan(c, have_scratch != 0).floats : -1;
-}
-
-// 1 when a stride-1 3x3 convolution call with these sizes AND these buffers runs the Winograd kernel (and therefore
-// writes / reads the Winograd-domain weights at the head of its scratch), 0 when it takes the direct kernel.
-extern "C" int sr_conv2d_uses_winograd(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, const float* in,
-                                       const float* out) {
-    return make_conv_plan(ConvCall{B, C, N, IH, IW, IH, IW, 3, 1, 1, 0, in, out, nullptr, 0}, true).path == SR_CONV_PATH_WINO;
-}
-
-extern "C" int sr_conv2d_mfma_ex(float* out, const float* in, const float* wt, const float* iscale,
-                              const float* oscale, const float* obias, int64_t B, int64_t C,
-                              int64_t N, int64_t wt_ld, int64_t IH, int64_t IW, int64_t OH, int64_t OW,
-                              int ksize, int stride, int pad, int transposed, int flags, float* scratch,
-                              sr_stream_t stream) {
-    const ConvCall c{B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, in, out, wt, wt_ld};
-    if (B < 0 || C <= 0 || N <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0) return SR_EINVAL;
-    if (wt_ld < N || wt_ld % 4 != 0 || !sr_aligned16(wt)) return SR_EINVAL;
-    if (B == 0) return SR_OK;
-    if (!out || !in || !wt) return SR_EINVAL;
-    // 32-bit element offsets inside the kernel
-    if (B * C * IH * IW >= (1LL << 31) || B * N * OH * OW >= (1LL << 40) ||
-        (int64_t)ksize * ksize * C * wt_ld >= (1LL << 31))
-        return SR_ERANGE;
-    if (!conv_call_valid(c)) return SR_EINVAL;
-    const ConvPlan plan = make_conv_plan(c, scratch != nullptr);
-    hipStream_t st = sr_stream(stream);
-    ConvParams p;
-    p.in = in; p.wt = wt; p.iscale = iscale; p.oscale = oscale; p.obias = obias; p.out = out;
-    p.B = (int)B; p.C = (int)C; p.N = (int)N; p.ldw = (int)wt_ld;
-    p.IH = (int)IH; p.IW = (int)IW; p.OH = (int)OH; p.OW = (int)OW;
-    p.partial = scratch;
-    p.partial_floats = scratch ? plan.sized : 0;
-    for (int i = 0; i < 9; ++i) p.wmap[i] = 0;
-    p.ks = 1; p.c_per_slice = (p.C + 15) / 16 * 16;
-    p.tap_first = 0; p.tap_step = 1; p.tap_count = 9;
-    int rc = SR_OK;
-    switch (plan.path) {
-    case SR_CONV_PATH_WINO:
-        return sr_wino_conv3x3(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, scratch, st, nullptr,
-                               (flags & SR_CONV_U_READY) != 0);
-    case SR_CONV_PATH_S2_BF16:
-        return sr_conv_s2_bf16x3_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, OH, OW, scratch, st);
-    case SR_CONV_PATH_S2_WINO:
-        return sr_conv_s2_wino_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, OH, OW, scratch, st);
-    case SR_CONV_PATH_GEMM1X1:
-        return sr_conv1x1_gemm_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH * IW, st);
-    case SR_CONV_PATH_CONVT_TAPS:
-        return launch_convt_taps(p, plan.ks, plan.c_per_slice, plan.taps_gemm, st);
-    case SR_CONV_PATH_CONVT_BF16:
-        rc = sr_convt_bf16x3_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, scratch, st);
-        break;
-    case SR_CONV_PATH_CONVT_WINO:
-        rc = sr_convt_wino_launch(out, in, wt, wt_ld, iscale, oscale, obias, B, C, N, IH, IW, st);
-        break;
-    case SR_CONV_PATH_CONVT_FUSED_KS:
-    case SR_CONV_PATH_CONVT_FUSED:
-        for (int i = 0; i < 9; ++i) p.wmap[i] = i;
-        rc = launch_convt_fused(p, plan.ks, st);
-        break;
-    default:    // SR_CONV_PATH_DIRECT
-        if (transposed) break;
-        p.GH = p.OH; p.GW = p.OW;
-        p.gy_base = p.gx_base = 0;
-        p.osy = p.osx = 1; p.ooy = p.oox = 0;
-        p.dy0 = p.dx0 = -pad;
-        for (int i = 0; i < ksize * ksize; ++i) p.wmap[i] = i;
-        if (ksize == 3) return stride == 1 ? launch_by_patch<1, 3, 3>(p, st) : launch_by_patch<2, 3, 3>(p, st);
-        return stride == 1 ? launch_by_patch<1, 1, 1>(p, st) : launch_by_patch<2, 1, 1>(p, st);
-    }
-    // transposed 3x3 stride 2, no padding: out[2y + ky, 2x + kx] += in[y, x] * W[ky][kx]; the interior is done or left to
-    // the per-phase launches, the border follows
-    if (rc != SR_OK) return rc;
-    if (plan.strips) return launch_convt_strips(p, st);
-    return launch_convt_phases(p, convt_interior(plan.path), st);
-}
-
-extern "C" int sr_conv2d_mfma(float* out, const float* in, const float* wt, const float* iscale,
-                              const float* oscale, const float* obias, int64_t B, int64_t C,
-                              int64_t N, int64_t wt_ld, int64_t IH, int64_t IW, int64_t OH, int64_t OW,
-                              int ksize, int stride, int pad, int transposed, float* scratch,
-                              sr_stream_t stream) {
-    return sr_conv2d_mfma_ex(out, in, wt, iscale, oscale, obias, B, C, N, wt_ld, IH, IW, OH, OW, ksize, stride, pad,
-                             transposed, 0, scratch, stream);
-}
-
-// Modulated 3x3 stride-1 convolution with the StyledConv tail fused into the store (Winograd kernel only).
-// SR_EINVAL when the shape is not taken by the Winograd path: the caller then runs sr_conv2d_mfma followed
-// by sr_noise_bias_act.
-extern "C" int sr_conv2d_nba_ex(float* out, const float* in, const float* wt, const float* iscale, const float* oscale,
-                                const float* noise, const float* noise_w, const float* abias, float alpha, float gain,
-                                int64_t B, int64_t C, int64_t N, int64_t wt_ld, int64_t H, int64_t W,
-                                int64_t noise_bstride, int flags, float* scratch, sr_stream_t stream) {
-    if (B < 0 || C <= 0 || N <= 0 || H <= 0 || W <= 0) return SR_EINVAL;
-    if (wt_ld < N || wt_ld % 4 != 0 || !sr_aligned16(wt)) return SR_EINVAL;
-    if (B == 0) return SR_OK;
-    if (!out || !in || !wt || !scratch || (noise && !noise_w)) return SR_EINVAL;
-    if (!sr_conv2d_uses_winograd(B, C, N, H, W, in, out)) return SR_EINVAL;
-    const WinoNba nba{noise, noise_w, abias, noise_bstride, alpha, gain};
-    return sr_wino_conv3x3(out, in, wt, wt_ld, iscale, oscale, nullptr, B, C, N, H, W, scratch, sr_stream(stream), &nba,
-                           (flags & SR_CONV_U_READY) != 0);
-}
-
-extern "C" int sr_conv2d_nba(float* out, const float* in, const float* wt, const float* iscale, const float* oscale,
-                             const float* noise, const float* noise_w, const float* abias, float alpha, float gain,
-                             int64_t B, int64_t C, int64_t N, int64_t wt_ld, int64_t H, int64_t W,
-                             int64_t noise_bstride, float* scratch, sr_stream_t stream) {
-    return sr_conv2d_nba_ex(out, in, wt, iscale, oscale, noise, noise_w, abias, alpha, gain, B, C, N, wt_ld, H, W,
-                            noise_bstride, 0, scratch, stream);
 }

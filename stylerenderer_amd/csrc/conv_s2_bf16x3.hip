@@ -19,15 +19,12 @@
 // block.  (v1 double-buffered 156 KB in one workgroup per CU: with a single wave per SIMD its ~650 non-MFMA
 // instructions and 14 DMA issues per chunk ran beside, not under, its 120 MFMAs — 0.41 of the matrix pipe, and the
 // ablation without any MFMA still took 65 % of the time.)
-#include "common.h"
+#include "mfma_tile.h"
 #include "conv_s2_bf16x3.h"
 
 namespace {
 
 #include "bf16x3.h"
-
-typedef const void __attribute__((address_space(1)))* gptr_t;
-typedef void __attribute__((address_space(3)))* lptr_t;
 
 constexpr int NT = 128, KC = 8, THREADS = 256;
 #ifndef SR_FLIP_LOG2
@@ -266,7 +263,6 @@ __global__ __launch_bounds__(THREADS, 2) void k_conv_s2_bf16x3(const PS2 p) {
             p.out[(((int64_t)b * p.N + n) * p.OH + oy) * p.OW + ox] = v;
         }
 }
-
 
 // ---- stride-2 TRANSPOSED 3x3 convolution (the up-sampling layers' forward), interior of the map ----------------------
 //   out[b,n,2j+ky,2i+kx] += oscale[b,n] * W[ky][kx][c][n] * (iscale[b,c] * in[b,c,j,i])
@@ -523,12 +519,7 @@ int sr_conv_s2_bf16x3_launch(float* out, const float* in, const float* wt, int64
     p.in = in; p.wb = wb; p.iscale = iscale; p.oscale = oscale; p.obias = obias; p.out = out;
     p.B = (int)B; p.C = (int)C; p.N = (int)N; p.IH = (int)IH; p.IW = (int)IW; p.OH = (int)OH; p.OW = (int)OW;
     p.tiles_x = (int)(OW / 32); p.tiles_y = (int)(OH / 4); p.tiles_n = tiles_n;
-    static bool configured = false;
-    if (!configured) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_s2_bf16x3), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  LDS_BYTES);
-        configured = true;
-    }
+    if (!sr_allow_dynamic_lds<k_conv_s2_bf16x3>(LDS_BYTES)) return SR_EINVAL;
     hipLaunchKernelGGL(k_conv_s2_bf16x3, dim3((unsigned)(B * p.tiles_y * p.tiles_x * tiles_n)), dim3(THREADS), LDS_BYTES, st,
                        p);
     return sr_launch_status();
@@ -558,12 +549,7 @@ int sr_convt_bf16x3_launch(float* out, const float* in, const float* wt, int64_t
     p.B = (int)B; p.C = (int)C; p.N = (int)N; p.IH = (int)IH; p.IW = (int)IW; p.OH = (int)(2 * IH + 1);
     p.OW = (int)(2 * IW + 1);
     p.tiles_x = (int)(IW / 32); p.tiles_y = (int)(IH / 4); p.tiles_n = tiles_n;
-    static bool configured = false;
-    if (!configured) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_convt_bf16x3), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  tc::LDS_BYTES);
-        configured = true;
-    }
+    if (!sr_allow_dynamic_lds<k_convt_bf16x3>(tc::LDS_BYTES)) return SR_EINVAL;
     hipLaunchKernelGGL(k_convt_bf16x3, dim3((unsigned)(B * p.tiles_y * p.tiles_x * tiles_n)), dim3(tc::THREADS),
                        tc::LDS_BYTES, st, p);
     return sr_launch_status();

@@ -33,14 +33,13 @@
 // Deterministic: no atomics, one fixed channel order.
 // LDS: 2 x (U 25.6 KB + V 25.6 KB + halo 19.5 KB) + 3 KB landing zone + the scale row = 144.4 KB + 4 C bytes.
 #include <type_traits>
-#include "common.h"
 #include "conv_s2_wino.h"
+
+#include "mfma_tile.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f2 __attribute__((ext_vector_type(2)));
-typedef void __attribute__((address_space(3)))* lptr_t;
 
 constexpr int TW = 16, TH = 4;            // tiles per workgroup: 32 x 8 output pixels
 constexpr int NB = 64;                    // output channels per workgroup
@@ -89,19 +88,9 @@ __global__ __launch_bounds__(256) void k_conv_s2_wino(const S2WinoParams p) {
     float* const sty = smem + STY;
 
     // ---- tile decode (XCD-chunked: consecutive ids = the output-channel tiles of one input patch on one L2)
-    const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / SR_NUM_XCD, r = nwg % SR_NUM_XCD, xcd = bid % SR_NUM_XCD;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / SR_NUM_XCD;
-    }
-    const int n_t = bid % p.tiles_n;
-    bid /= p.tiles_n;
-    const int tx_i = bid % p.tiles_x;
-    bid /= p.tiles_x;
-    const int ty_i = bid % p.tiles_y;
-    const int b = bid / p.tiles_y;
-    const int oy0 = ty_i * (2 * TH), ox0 = tx_i * (2 * TW), n0 = n_t * NB;
+    const SrTile wg = sr_tile_decode(sr_xcd_chunk(blockIdx.x, gridDim.x), p.tiles_n, p.tiles_x, p.tiles_y);
+    const int n_t = wg.n_t, b = wg.rest;
+    const int oy0 = wg.ty * (2 * TH), ox0 = wg.tx * (2 * TW), n0 = n_t * NB;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -118,7 +107,7 @@ __global__ __launch_bounds__(256) void k_conv_s2_wino(const S2WinoParams p) {
     for (int i = 0; i < D_PER_WAVE; ++i) {
         const int j = wave + 4 * i;
         const int L = j * 64 + lane;
-        int off = 0x7FFFFFF0;
+        int off = SR_BUF_OOB;
         if (j < D_INSTR && L < D_LINES) {
             const int c = L / (PR * LPR), q = L % (PR * LPR);
             const int r = q / LPR, l = q % LPR;
@@ -128,10 +117,11 @@ __global__ __launch_bounds__(256) void k_conv_s2_wino(const S2WinoParams p) {
         d_off[i] = off;
     }
     const int chunk_in_bytes = KC * p.IH * p.IW * 4;
+    // (not uniform_rsrc: its readfirstlanes change this kernel's device code; every input here is uniform already)
     const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.in + (int64_t)b * p.C * p.IH * p.IW), 0, nchunks * chunk_in_bytes, 0x00020000);
+        const_cast<float*>(p.in + (int64_t)b * p.C * p.IH * p.IW), 0, nchunks * chunk_in_bytes, SR_BUF_RSRC_WORD3);
     const __amdgpu_buffer_rsrc_t r_u = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.u + (int64_t)n_t * nchunks * UV), 0, nchunks * UV * 4, 0x00020000);
+        const_cast<float*>(p.u + (int64_t)n_t * nchunks * UV), 0, nchunks * UV * 4, SR_BUF_RSRC_WORD3);
 
     // one DMA instruction each (all waves issue the same number; surplus ones land in the pad zone)
     auto dma_d1 = [&](int k, int buf, int i) {
@@ -143,7 +133,7 @@ __global__ __launch_bounds__(256) void k_conv_s2_wino(const S2WinoParams p) {
         const int j = wave + 4 * i;
         const bool real = j < U_INSTR;
         float* dst = real ? ubuf + buf * UV + j * 256 : smem + PAD + (wave - 1) * 256;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(r_u, (lptr_t)dst, 16, real ? lane * 16 : 0x7FFFFFF0,
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(r_u, (lptr_t)dst, 16, real ? lane * 16 : SR_BUF_OOB,
                                                  real ? (k * UV + j * 256) * 4 : 0, 0, 0);
     };
     auto dma_d = [&](int k, int buf) {
@@ -297,13 +287,13 @@ __global__ __launch_bounds__(256) void k_conv_s2_wino(const S2WinoParams p) {
     __builtin_amdgcn_s_waitcnt(0x0070);
 
     // ---- epilogue: y[r][s] = (A[r][s] + A[2][s]) + (A[r][2] + A[2][2]) per (tile, channel); C/D layout: column
-    // (tile) = lane & 31, row (channel) = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+    // (tile) = lane & 31, row (channel) = sr_mfma32_row
     const int tile = wt * 32 + l31;
     const int oy = oy0 + 2 * (tile >> 4), ox = ox0 + 2 * (tile & 15);
     const int64_t plane = (int64_t)p.OH * p.OW;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int n = n0 + wn * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int n = sr_mfma32_row(r, half, n0 + wn * 32);
         const float os = p.oscale ? p.oscale[(int64_t)b * p.N + n] : 1.0f;
         const float ob = p.obias ? p.obias[n] : 0.0f;
         float* o = p.out + ((int64_t)b * p.N + n) * plane + (int64_t)oy * p.OW + ox;
@@ -385,15 +375,7 @@ int sr_conv_s2_wino_launch(float* out, const float* in, const float* wt, int64_t
     p.B = (int)B; p.C = (int)C; p.N = (int)N; p.IH = (int)IH; p.IW = (int)IW; p.OH = (int)OH; p.OW = (int)OW;
     p.tiles_x = (int)(OW / (2 * TW)); p.tiles_y = (int)(OH / (2 * TH)); p.tiles_n = (int)(N / NB);
     const int lds = (STY + (int)C) * 4;
-    static bool configured = false;
-    if (!configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_s2_wino),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return SR_EINVAL;
-        }
-        configured = true;
-    }
+    if (!sr_allow_dynamic_lds<k_conv_s2_wino>(160 * 1024)) return SR_EINVAL;
     hipLaunchKernelGGL(k_s2_wino_weights, dim3((unsigned)(N / NB), (unsigned)(C / 2)), dim3(64), 0, st, scratch, wt,
                        (int)C, (int)N, (int)ldw);
     const int64_t blocks = sr_conv_s2_wino_blocks(B, N, OH, OW);

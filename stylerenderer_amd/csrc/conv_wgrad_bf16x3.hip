@@ -22,7 +22,7 @@
 // sample, staged through registers into double-buffered LDS (row pitch 36 floats: the eight lanes of a ds_read_b128
 // phase hit 32 distinct banks), scales multiplied at staging.  72 KB of LDS: two workgroups per CU.  K slices write
 // partial slabs in k_wgrad_mfma's layout; k_wgrad_reduce (conv_wgrad_mfma.hip) sums them in a fixed order.
-#include "common.h"
+#include "mfma_tile.h"
 #include "conv_wgrad_bf16x3.h"
 
 namespace {
@@ -177,12 +177,11 @@ __global__ __launch_bounds__(s1::THREADS, 2) void k_wgrad1_bf16x3(const P3 p) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int u = u0 + wu * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int u = sr_mfma32_row(r, half, u0 + wu * 64 + i * 32);
                 const int v = v0 + wv * 64 + j * 32 + l31;
                 dst[(int64_t)u * p.VP + v] = acc[i][j][r];
             }
 }
-
 
 // ---- stride-2 3x3 weight gradient (the up- / down-sampling convolutions), split-bf16 ---------------------------------
 //   D[tap][u][v] = sum_{b, j, i} (us[b,u] U[b,u,2j+ky,2i+kx]) * (vs[b,v] V[b,v,j,i])       tap = 3 ky + kx
@@ -382,7 +381,7 @@ __global__ __launch_bounds__(512) void k_wgrad_s2_bf16x3(const P9 p) {
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int u = u0 + wu * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int u = sr_mfma32_row(r, half, u0 + wu * 32);
             const int v = v0 + wv * 32 + l31;
             dst[((int64_t)t * p.UP + u) * p.VP + v] = acc[t][r];
         }
@@ -442,12 +441,7 @@ int sr_wgrad_bf16x3_launch(const float* U, const float* V, const float* uscale, 
     *ks = (p.nchunk + p.per_slice - 1) / p.per_slice;
     *UP = p.UP;
     *VP = p.VP;
-    static bool configured = false;
-    if (!configured) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad1_bf16x3), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  s1::LDS_BYTES);
-        configured = true;
-    }
+    if (!sr_allow_dynamic_lds<k_wgrad1_bf16x3>(s1::LDS_BYTES)) return SR_EINVAL;
     hipLaunchKernelGGL(k_wgrad1_bf16x3, dim3((unsigned)(p.tiles_u * p.tiles_v * *ks)), dim3(s1::THREADS), s1::LDS_BYTES, st, p);
     return sr_launch_status();
 }
@@ -491,12 +485,7 @@ int sr_wgrad_s2_bf16x3_launch(const float* U, const float* V, const float* uscal
     *ks = (p.nchunk + p.per_slice - 1) / p.per_slice;
     *UP = p.UP;
     *VP = p.VP;
-    static bool configured = false;
-    if (!configured) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_s2_bf16x3),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, s2::LDS_BYTES);
-        configured = true;
-    }
+    if (!sr_allow_dynamic_lds<k_wgrad_s2_bf16x3>(s2::LDS_BYTES)) return SR_EINVAL;
     hipLaunchKernelGGL(k_wgrad_s2_bf16x3, dim3((unsigned)(p.tiles_u * p.tiles_v * *ks)), dim3(s2::THREADS), s2::LDS_BYTES,
                        st, p);
     return sr_launch_status();

@@ -27,7 +27,7 @@
 // different banks.
 // The modulation scales are fetched per patch as two small LDS rows and multiplied onto the
 // operands after the ds_read (never onto freshly loaded registers: no wait on memory in the loop).
-#include "common.h"
+#include "mfma_tile.h"
 #include "conv_wgrad_bf16x3.h"
 #include "conv_wgrad_s2_wino.h"
 #include "conv_wino.h"
@@ -36,10 +36,6 @@
 #include <cstdlib>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef const void __attribute__((address_space(1)))* gptr_t;
-typedef void __attribute__((address_space(3)))* lptr_t;
 
 __device__ __attribute__((aligned(16))) const float g_wzero_line[4] = {0.f, 0.f, 0.f, 0.f};
 __device__ __attribute__((aligned(16))) const float g_wones_line[4] = {1.f, 1.f, 1.f, 1.f};
@@ -289,7 +285,7 @@ __global__ __launch_bounds__(256 * NG) void k_wgrad_mfma(const WgradParams p) {
     for (int t = 0; t < G::NT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int u = u0 + wu * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int u = sr_mfma32_row(r, half, u0 + wu * 32);
             const int v = v0 + wv * 32 + l31;
             dst[((int64_t)t * p.UP + u) * p.VP + v] = acc[t][r];
         }
@@ -437,7 +433,7 @@ __global__ __launch_bounds__(512) void k_wgrad_s2_dma(const WgradParams p) {
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int u = u0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int u = sr_mfma32_row(r, half, u0);
             const int v = v0 + wv * 32 + l31;
             dst[((int64_t)t * p.UP + u) * p.VP + v] = acc[t][r];
         }
@@ -555,13 +551,8 @@ int launch_wgrad_one(const WgradParams& p, dim3 grid, hipStream_t st) {
     constexpr int NG = NG_OF(PB);
     using G = WG<IS, TY, TX, PW, PH, PB, UT, VT, NG>;
     static_assert(G::LDS_BYTES <= 160 * 1024, "LDS budget");
-    auto kern = k_wgrad_mfma<IS, TY, TX, PW, PH, PB, UT, VT, NG>;
-    static bool configured = false;
-    if (!configured) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        configured = true;
-    }
+    constexpr auto kern = k_wgrad_mfma<IS, TY, TX, PW, PH, PB, UT, VT, NG>;
+    if (!sr_allow_dynamic_lds<kern>(G::LDS_BYTES)) return SR_EINVAL;
     hipLaunchKernelGGL(kern, grid, dim3(G::THREADS), G::LDS_BYTES, st, p);
     return sr_launch_status();
 }
@@ -588,12 +579,7 @@ template <int TY, int TX>
 int launch_wgrad_s2(const WgradParams& p, const Plan& pl, bool dma, hipStream_t st) {
     const dim3 grid((unsigned)(pl.tiles_u * pl.tiles_v * pl.ks));
     if (TY == 3 && TX == 3 && dma) {
-        static bool configured = false;
-        if (!configured) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_s2_dma),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, s2d::LDS_BYTES);
-            configured = true;
-        }
+        if (!sr_allow_dynamic_lds<k_wgrad_s2_dma>(s2d::LDS_BYTES)) return SR_EINVAL;
         hipLaunchKernelGGL(k_wgrad_s2_dma, grid, dim3(512), s2d::LDS_BYTES, st, p);
         return sr_launch_status();
     }

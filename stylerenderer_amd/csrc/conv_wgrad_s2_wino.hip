@@ -21,13 +21,10 @@
 // The non-MFMA work is pinned one or two instructions behind each MFMA; nothing in the loop waits on memory except
 // the stage barrier.  One 16-position slab per K slice: ks * 16 <= the ks * 2 * 9 the direct plan reserves.
 // k_wgrad_s2p_finish adds the slices in slice order, combines 16 -> 9 in a fixed order and applies the output layout.
-#include "common.h"
+#include "mfma_tile.h"
 #include "conv_wgrad_s2_wino.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef void __attribute__((address_space(3)))* lptr_t;
 
 __device__ const float g_s2p_one[1] = {1.f};
 
@@ -256,7 +253,7 @@ __global__ __launch_bounds__(256) void k_wgrad_s2p(const S2pParams p) {
     for (int t = 0; t < 16; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int u = u0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int u = sr_mfma32_row(r, half, u0);
             const int v = v0 + wave * 32 + l31;
             dst[((int64_t)t * p.CU + u) * p.CV + v] = acc[t][r];
         }
@@ -312,12 +309,7 @@ int sr_wgrad_s2_wino_launch(const float* U, const float* V, const float* uscale,
     p.B = (int)B; p.CU = (int)CU; p.CV = (int)CV; p.UH = (int)UH; p.UW = (int)UW; p.GH = (int)GH; p.GW = (int)GW;
     p.tiles_x = (int)(GW / 16); p.tiles_y = (int)(GH / 4); p.tiles_u = (int)(CU / 32); p.tiles_v = (int)(CV / 128);
     p.pps = pps;
-    static bool configured = false;
-    if (!configured) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_s2p), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  s2p::LDS_BYTES);
-        configured = true;
-    }
+    if (!sr_allow_dynamic_lds<k_wgrad_s2p>(s2p::LDS_BYTES)) return SR_EINVAL;
     hipLaunchKernelGGL(k_wgrad_s2p, dim3((unsigned)(p.tiles_u * p.tiles_v * ks)), dim3(256), s2p::LDS_BYTES, st, p);
     return sr_launch_status();
 }

@@ -28,13 +28,10 @@
 //     | (odd j) DMA of strip (j+1)/2 + 1.
 #include <cstdlib>
 #include <type_traits>
-#include "common.h"
+#include "mfma_tile.h"
 #include "conv_wino.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef void __attribute__((address_space(3)))* lptr_t;
 
 constexpr int XS = 25;                      // float4 slots per channel of the x strip (4 rows x 6 + hole)
 constexpr int GS = 9;                       // float4 slots per channel of the gy strip (2 rows x 4 + hole)
@@ -46,7 +43,7 @@ constexpr int RAW = X_FLOATS + G_FLOATS;    // 8708 floats = 34 KB per strip
 constexpr int OB = 4096;                    // floats of one operand (V or Z) of a sub-chunk: [4][2][2][64][4]
 constexpr int OBUF = 2 * OB;                // V then Z
 constexpr int MAX_B = 32;                   // scale tables [B][64] x 2 in LDS
-constexpr int OOB = 0x7FFFFFF0;             // buffer offset beyond every tensor: the load returns zeros
+constexpr int OOB = SR_BUF_OOB;
 // NW waves per workgroup (4: one per SIMD, 8: two per SIMD, see k_wgrad_wino): DMA instructions per wave and strip,
 // landing zone of the surplus ones (never read)
 template <int NW>
@@ -102,12 +99,7 @@ __global__ __launch_bounds__(64 * NW) void k_wgrad_wino(const WgWinoParams p) {
     float* const tabx = pad + K::PAD;                 // [B][64] style of this channel block
     float* const tabg = tabx + MAX_B * 64;            // [B][64] demodulation of this output block
 
-    const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / SR_NUM_XCD, r = nwg % SR_NUM_XCD, xcd = bid % SR_NUM_XCD;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / SR_NUM_XCD;
-    }
+    int bid = sr_xcd_chunk(blockIdx.x, gridDim.x);
     const int n_t = bid % p.tiles_n;
     bid /= p.tiles_n;
     const int c_t = bid % p.tiles_c;
@@ -501,7 +493,7 @@ __global__ __launch_bounds__(64 * NW) void k_wgrad_wino(const WgWinoParams p) {
     for (int pos = 0; pos < NPOS; ++pos)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int c = c0 + wc * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int c = sr_mfma32_row(r, half, c0 + wc * 32);
             out[((int64_t)(ph * 8 + pos) * p.C + c) * p.N + n0 + wn * 32 + l31] = acc[pos][r];
         }
     WGW_STAMP(3);
@@ -592,17 +584,7 @@ int sr_wgrad_wino_3x3(float* dwt, const float* x, const float* gy, const float* 
     plan(B, C, N, H, W, p.slices, p.chunks_per_slice, p.chunks_total);
     // SR_WGW_WAVES=4: one wave per SIMD (round 2's form); default 8: two per SIMD (same bits)
     const bool two = sr_env_char("SR_WGW_WAVES") != '4';
-    static bool configured = false;
-    if (!configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_wino<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_wino<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return SR_EINVAL;
-        }
-        configured = true;
-    }
+    if (!sr_allow_dynamic_lds<k_wgrad_wino<4>>(160 * 1024) || !sr_allow_dynamic_lds<k_wgrad_wino<8>>(160 * 1024)) return SR_EINVAL;
     const int64_t blocks = (int64_t)p.tiles_c * p.tiles_n * p.slices;
     if (two) hipLaunchKernelGGL(k_wgrad_wino<8>, dim3((unsigned)blocks), dim3(512), WgW<8>::LDS_FLOATS * 4, st, p);
     else hipLaunchKernelGGL(k_wgrad_wino<4>, dim3((unsigned)blocks), dim3(256), WgW<4>::LDS_FLOATS * 4, st, p);

@@ -26,15 +26,11 @@
 // LDS: 2 x (U 32 KB + V 32 KB + d 13 KB) + style = 156 KB of the CU's 160 KB; one workgroup per CU
 // (the 256 accumulators allow one wave per SIMD anyway).
 #include <type_traits>
-#include "common.h"
+#include "mfma_tile.h"
 #include "conv_wino.h"
 #include <cstdlib>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef const void __attribute__((address_space(1)))* gptr_t;
-typedef void __attribute__((address_space(3)))* lptr_t;
 
 __device__ __attribute__((aligned(16))) const float g_wino_zero[4] = {0.f, 0.f, 0.f, 0.f};
 
@@ -78,12 +74,7 @@ __global__ __launch_bounds__(256) void k_conv_wino(const WinoParams p) {
     float* const sty = smem + G::STY;
 
     // ---- tile decode (XCD-chunked: consecutive ids = same input patch / neighbouring patches on one L2)
-    const int nwg = gridDim.x;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg / SR_NUM_XCD, r = nwg % SR_NUM_XCD, xcd = bid % SR_NUM_XCD;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / SR_NUM_XCD;
-    }
+    int bid = sr_xcd_chunk(blockIdx.x, gridDim.x);
     const int slice = bid % p.ks;           // K slices of one tile are neighbours: same halo patch on one L2
     bid /= p.ks;
     const int n_t = bid % p.tiles_n;
@@ -120,7 +111,7 @@ __global__ __launch_bounds__(256) void k_conv_wino(const WinoParams p) {
     for (int i = 0; i < G::D_PER_WAVE; ++i) {
         const int j = wave + 4 * i;
         const int f = (j * 64 + lane) * 4;
-        int off = 0x7FFFFFF0;
+        int off = SR_BUF_OOB;
         if (j < G::D_INSTR && f < G::D_FLOATS) {
             const int c = f / PLANE, q = f % PLANE;
             const int r = q / EWP, cola = q % EWP;
@@ -132,9 +123,9 @@ __global__ __launch_bounds__(256) void k_conv_wino(const WinoParams p) {
     const int chunk_in_bytes = KC * p.H * p.W * 4;
     const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(p.in + ((int64_t)b * p.C + (int64_t)k_lo * KC) * p.H * p.W), 0, nchunks * chunk_in_bytes,
-        0x00020000);
+        SR_BUF_RSRC_WORD3);
     const __amdgpu_buffer_rsrc_t r_u = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.u + ((int64_t)n_t * all_chunks + k_lo) * G::UV), 0, nchunks * G::UV * 4, 0x00020000);
+        const_cast<float*>(p.u + ((int64_t)n_t * all_chunks + k_lo) * G::UV), 0, nchunks * G::UV * 4, SR_BUF_RSRC_WORD3);
     const int u_voff = lane * 16;
 
     // one DMA instruction each (all waves issue the same number; surplus ones land in the pad zone)
@@ -409,7 +400,7 @@ __global__ __launch_bounds__(256) void k_conv_wino(const WinoParams p) {
     WINO_STAMP(3);
 
     // ---- epilogue: Y = A^T M A per (tile, channel); C/D layout: column (tile) = lane & 31,
-    // row (channel) = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+    // row (channel) = sr_mfma32_row
     const int tile = wt * 32 + l31;
     const int oy = oy0 + 2 * (tile >> 4), ox = ox0 + 2 * (tile & 15);
     const int64_t plane = (int64_t)p.H * p.W;
@@ -427,7 +418,7 @@ __global__ __launch_bounds__(256) void k_conv_wino(const WinoParams p) {
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int n = n0 + wn * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int n = sr_mfma32_row(r, half, n0 + wn * 32);
         float s[2][4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -545,16 +536,8 @@ template <int KC>
 int launch(const WinoParams& p, float* u, const float* wt, int ldw, hipStream_t st, bool u_ready) {
     using G = WG<KC>;
     const int lds = (G::STY + p.kchunks * KC) * 4;
-    auto kern = k_conv_wino<KC>;
-    static bool configured = false;
-    if (!configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return SR_EINVAL;
-        }
-        configured = true;
-    }
+    constexpr auto kern = k_conv_wino<KC>;
+    if (!sr_allow_dynamic_lds<kern>(160 * 1024)) return SR_EINVAL;
     // (u_ready: the caller kept the scratch of an earlier call with the same weights — a frozen network)
     if (!u_ready) hipLaunchKernelGGL(k_wino_weights<KC>, dim3(p.N / 64, p.C), dim3(64), 0, st, u, wt, p.C, p.N, ldw);
     const int64_t blocks = (int64_t)p.tiles_n * p.tiles_x * p.tiles_y * p.B * p.ks;

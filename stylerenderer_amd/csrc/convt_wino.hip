@@ -16,23 +16,20 @@
 // Workgroup = 32 x 8 input positions (4 x 16 tiles -> 64 x 16 output pixels, every second row) x 64 output channels; four
 // waves, one per SIMD, as 2 (tile halves) x 2 (channel halves): a wave owns 32 tiles x 32 channels for all of its
 // products.  K chunks of 8 input channels: the raw halo patch [8][9][36] and the raw taps [9 or 3][8][64] are staged by
-// 16-byte buffer-addressed LDS-DMA, double buffered, one barrier per chunk, exactly as in k_convt_fused.  Both transforms
+// 16-byte buffer-addressed LDS-DMA, double buffered, one barrier per chunk, by the code k_convt_fused uses (convt_stage.h).  Both transforms
 // run in the MFMA wave on the fetched operands (as k_convt_fused scales its inputs): per k-step 18 / 9 operand fetches and
 // 21 / 11 VALU instructions, pinned between the 15 / 10 MFMAs of the step before.  The style row is folded into the first
 // stage of the input transform.  No scratch, no atomics, a fixed K order: the result is bit-repeatable.
-#include "common.h"
 #include "convt_wino.h"
+
+#include "convt_stage.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef void __attribute__((address_space(3)))* lptr_t;
-
-constexpr int KC = 8;                                     // input channels per chunk = 4 k-steps
+constexpr int KC = CONVT_KC;                              // input channels per chunk = 4 k-steps
 constexpr int NB = 64;                                    // output channels per workgroup
-constexpr int PW = 32, PH = 8;                            // input positions per workgroup
-constexpr int LEAD = 3;                                   // halo columns start at i0 - 4 (aligned); i0 - 1 is column 3
-constexpr int EWP = LEAD + 1 + PW;                        // 36
+constexpr int PW = CONVT_PW, PH = 8;                      // input positions per workgroup
+constexpr int LEAD = CONVT_LEAD, EWP = CONVT_EWP;         // halo columns i0 - 4 .. i0 + 31: i0 - 1 is column 3 of 36
 constexpr int EH = PH + 1;                                // rows j0 - 1 .. j0 + 7
 constexpr int PLANE = EH * EWP;                           // 324
 constexpr int I_INSTR = (KC * PLANE / 4 + 63) / 64;       // 11 wave instructions of 1 KiB
@@ -41,7 +38,6 @@ constexpr int I_PER_WAVE = (I_INSTR + 3) / 4;             // 3 slots (12: one su
 constexpr int BUF = I_FLOATS + 9 * KC * NB;               // halo patch, then the taps: 7424 floats = 29 KB
 constexpr int PAD = 2 * BUF;
 constexpr int STY = PAD + 4 * 256;
-static_assert(PLANE % 4 == 0 && EWP % 4 == 0, "16-byte DMA pieces must not straddle a row");
 
 struct ConvtWinoParams {
     const float* in;
@@ -69,18 +65,9 @@ __device__ __forceinline__ void convt_wino_body(const ConvtWinoParams& p, float*
     static_assert(N_DMA > 4 && N_DMA <= 8, "DMA slots: four behind the barrier, the rest in the first k-step");
     float* const sty = smem + STY;
 
-    {
-        const int nwg = p.half_blocks;
-        const int q = nwg / SR_NUM_XCD, r = nwg % SR_NUM_XCD, xcd = bid % SR_NUM_XCD;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / SR_NUM_XCD;
-    }
-    const int n_t = bid % p.tiles_n;
-    bid /= p.tiles_n;
-    const int tx_i = bid % p.tiles_x;
-    bid /= p.tiles_x;
-    const int ty_i = bid % p.tiles_y;
-    const int b = bid / p.tiles_y;
-    const int n0 = n_t * NB, j0 = ty_i * PH, i0 = tx_i * PW;
+    const SrTile tile = sr_tile_decode(sr_xcd_chunk(bid, p.half_blocks), p.tiles_n, p.tiles_x, p.tiles_y);
+    const int b = tile.rest;
+    const int n0 = tile.n_t * NB, j0 = tile.ty * PH, i0 = tile.tx * PW;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -88,29 +75,16 @@ __device__ __forceinline__ void convt_wino_body(const ConvtWinoParams& p, float*
     const int wn = wave & 1, wt = wave >> 1;
     const int ty_l = wt * 2 + (l31 >> 4), tx_l = l31 & 15;    // this lane's tile inside the patch
 
-    // ---- DMA descriptors: byte offsets for chunk 0; lanes with nothing to fetch (outside the image: the in[-1] halo,
-    // surplus instructions) point beyond the buffer and receive zeros.  The chunk part of an address is the scalar soffset.
-    constexpr int OOB = 0x7FFFFFF0;
+    // ---- DMA descriptors: byte offsets for chunk 0 (csrc/convt_stage.h)
     int i_off[I_PER_WAVE], w_off[W_PER_WAVE];
 #pragma unroll
-    for (int i = 0; i < I_PER_WAVE; ++i) {
-        const int j = wave + 4 * i;
-        const int f = (j * 64 + lane) * 4;
-        int off = OOB;
-        if (j < I_INSTR && f < KC * PLANE) {
-            const int c = f / PLANE, q = f % PLANE;
-            const int r = q / EWP, cola = q % EWP;
-            const int gy = j0 - 1 + r, gx = i0 - 4 + cola;
-            if (gy >= 0 && gy < p.IH && gx >= 0 && gx + 3 < p.IW) off = ((c * p.IH + gy) * p.IW + gx) * 4;
-        }
-        i_off[i] = off;
-    }
+    for (int i = 0; i < I_PER_WAVE; ++i) i_off[i] = convt_patch_offset<PLANE, I_INSTR>(p, wave + 4 * i, lane, j0, i0);
 #pragma unroll
     for (int i = 0; i < W_PER_WAVE; ++i) {
         const int j = wave + 4 * i;
         const int row = 4 * j + (lane >> 4);                 // [tap slot * KC + c], 64 channels = 16 lanes per row
         const int t = TAP0 + row / KC, c = row % KC;
-        w_off[i] = j < W_INSTR ? ((t * p.C + c) * p.ldw + n0 + (lane & 15) * 4) * 4 : OOB;
+        w_off[i] = j < W_INSTR ? ((t * p.C + c) * p.ldw + n0 + (lane & 15) * 4) * 4 : SR_BUF_OOB;
     }
     const int plane_in = p.IH * p.IW;
     const __amdgpu_buffer_rsrc_t r_w = uniform_rsrc(p.wt, 9 * p.C * p.ldw * 4);
@@ -262,7 +236,7 @@ __device__ __forceinline__ void convt_wino_body(const ConvtWinoParams& p, float*
     const int Y0 = 2 * j0 + 4 * ty_l, X0 = 2 * i0 + 4 * tx_l;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int n = n0 + wn * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int n = sr_mfma32_row(r, half, n0 + wn * 32);
         const float os = p.oscale ? p.oscale[(int64_t)b * p.N + n] : 1.0f;
         const float ob = p.obias ? p.obias[n] : 0.0f;
         float* o = p.out + ((int64_t)b * p.N + n) * plane_out + (int64_t)Y0 * p.OW + X0;
@@ -312,15 +286,7 @@ int sr_convt_wino_launch(float* out, const float* in, const float* wt, int64_t l
     p.tiles_x = (int)(IW / PW); p.tiles_y = (int)(IH / PH); p.tiles_n = (int)(N / NB);
     p.half_blocks = p.tiles_x * p.tiles_y * p.tiles_n * p.B;
     const int lds = (STY + (int)C) * 4;
-    static bool configured = false;
-    if (!configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_convt_wino), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess) {
-            (void)hipGetLastError();
-            return SR_EINVAL;
-        }
-        configured = true;
-    }
+    if (!sr_allow_dynamic_lds<k_convt_wino>(160 * 1024)) return SR_EINVAL;
     hipLaunchKernelGGL(k_convt_wino, dim3(2u * (unsigned)p.half_blocks), dim3(256), lds, st, p);
     return sr_launch_status();
 }

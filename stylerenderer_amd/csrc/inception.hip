@@ -19,11 +19,9 @@
 //                     the same features give the same bits), then mean and covariance (np.mean / np.cov)
 //
 // The bilinear resize to 299^2 is k_ppl_prep (csrc/ppl.hip) with shift 0 and scale 1.
-#include "common.h"
+#include "mfma_tile.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int MAXSEG = 3;
 constexpr int BK = 16;   // K depth of one LDS stage
@@ -141,6 +139,7 @@ __global__ __launch_bounds__(256) void k_incep_conv(const ConvArgs a) {
         for (int i = 0; i < TM; ++i) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
+                // (sr_mfma32_row written out: through the helper all 32 instantiations compile differently)
                 const int m = m_blk + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 if (m >= a.M) continue;
                 // segment by selects (a dynamic index into the kernel-argument struct would go through scratch)

@@ -1,4 +1,4 @@
-"""Dense convolution on the matrix cores — host side of csrc/conv_mfma.hip (C ABI sr_conv2d_mfma).
+"""Dense convolution on the matrix cores — host side of csrc/conv_dispatch.hip (C ABI sr_conv2d_mfma; the kernels: csrc/conv_mfma.hip and its siblings).
 
 Low-level operator used by layers.ModulatedConv2d / EqualConv2d for device tensors:
 

@@ -1,4 +1,4 @@
-"""CPU: the dispatch plan of the dense convolutions (csrc/conv_mfma.hip, csrc/conv_wgrad_mfma.hip) through its host-only
+"""CPU: the dispatch plan of the dense convolutions (csrc/conv_dispatch.hip, csrc/conv_wgrad_mfma.hip) through its host-only
 queries — no GPU is touched.
 
   * scratch sizes and the Winograd query equal, row for row and under every switch, what the selection code they

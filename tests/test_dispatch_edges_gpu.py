@@ -598,7 +598,7 @@ def test_from_rgb_weight_gradient_at_256_vs_float64():
     _check(got, want, mag, 2e-6, "dwt")
 
 
-# ---- the dispatch queries and the launches agree (csrc/conv_mfma.hip make_conv_plan, csrc/conv_wgrad_mfma.hip) ---------
+# ---- the dispatch queries and the launches agree (csrc/conv_dispatch.hip make_conv_plan, csrc/conv_wgrad_mfma.hip) ---------
 # kernels that tell the paths apart: a path's launch runs exactly its own of these (no numeric assertions here: the
 # float64 comparisons of the same shapes are in test_conv_gpu, test_conv_s2_wino_gpu and above).  k_conv_mfma is judged
 # apart: it is the direct path's only kernel and no other non-transposed path runs it, but the transposed paths use its
