@@ -12,7 +12,11 @@
 #include "../stylerenderer_amd/csrc/conv_mfma.hip"
 #include "../stylerenderer_amd/csrc/convt_fused.hip"
 #ifndef SR_NO_WGRAD
+#include "../stylerenderer_amd/csrc/conv_wgrad_dispatch.hip"
 #include "../stylerenderer_amd/csrc/conv_wgrad_mfma.hip"
+#include "../stylerenderer_amd/csrc/conv_wgrad_reduce.hip"
+#include "../stylerenderer_amd/csrc/conv_wgrad_s2_dma.hip"
+#include "../stylerenderer_amd/csrc/conv_wgrad_small3.hip"
 #endif
 
 static float* dev_random(size_t n, unsigned seed) {

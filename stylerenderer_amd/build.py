@@ -53,7 +53,11 @@ SOURCES = [
     ("convt_fused.hip", []),
     ("conv_wino.hip", []),
     ("conv_wgrad_wino.hip", []),
+    ("conv_wgrad_dispatch.hip", []),
     ("conv_wgrad_mfma.hip", []),
+    ("conv_wgrad_s2_dma.hip", []),
+    ("conv_wgrad_small3.hip", []),
+    ("conv_wgrad_reduce.hip", []),
     ("conv_wgrad_bf16x3.hip", []),
     ("conv_wgrad_s2_wino.hip", []),
     ("conv_s2_bf16x3.hip", []),

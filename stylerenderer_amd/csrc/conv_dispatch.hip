@@ -7,7 +7,7 @@
 #include "conv_mfma.h"
 #include "conv_s2_bf16x3.h"
 #include "conv_s2_wino.h"
-#include "conv_wgrad_bf16x3.h"
+#include "conv_split_bf16.h"
 #include "conv_wino.h"
 #include "convt_fused.h"
 #include "convt_wino.h"

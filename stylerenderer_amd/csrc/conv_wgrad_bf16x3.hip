@@ -21,9 +21,12 @@
 // Tiling: workgroup = 128 (u) x 128 (v) channels, 4 waves of 64 x 64 (2 x 2 MFMA tiles), K chunks of 32 pixels of one
 // sample, staged through registers into double-buffered LDS (row pitch 36 floats: the eight lanes of a ds_read_b128
 // phase hit 32 distinct banks), scales multiplied at staging.  72 KB of LDS: two workgroups per CU.  K slices write
-// partial slabs in k_wgrad_mfma's layout; k_wgrad_reduce (conv_wgrad_mfma.hip) sums them in a fixed order.
-#include "mfma_tile.h"
+// partial slabs in k_wgrad_mfma's layout; k_wgrad_reduce (conv_wgrad_reduce.hip) sums them in a fixed order.
+#include "wgrad_tile.h"
+#include "conv_split_bf16.h"
 #include "conv_wgrad_bf16x3.h"
+
+#include <cstdlib>
 
 namespace {
 
@@ -69,10 +72,8 @@ __device__ __forceinline__ Split3 split8(const float4 lo, const float4 hi) {
 __global__ __launch_bounds__(s1::THREADS, 2) void k_wgrad1_bf16x3(const P3 p) {
     using namespace s1;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int bid = blockIdx.x;
-    const int tile_uv = bid % (p.tiles_u * p.tiles_v);
-    const int slice = bid / (p.tiles_u * p.tiles_v);
-    const int u0 = (tile_uv / p.tiles_v) * UT, v0 = (tile_uv % p.tiles_v) * VT;
+    const SrWgradTile wt = sr_wgrad_tile(blockIdx.x, p.tiles_u, p.tiles_v, UT, VT);
+    const int slice = wt.slice, u0 = wt.u0, v0 = wt.v0;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
@@ -233,10 +234,8 @@ __device__ __forceinline__ u32x4 shift1(const u32x4 d, unsigned d4) {
 __global__ __launch_bounds__(512) void k_wgrad_s2_bf16x3(const P9 p) {
     using namespace s2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int bid = blockIdx.x;
-    const int tile_uv = bid % (p.tiles_u * p.tiles_v);
-    const int slice = bid / (p.tiles_u * p.tiles_v);
-    const int u0 = (tile_uv / p.tiles_v) * UT, v0 = (tile_uv % p.tiles_v) * VT;
+    const SrWgradTile wt = sr_wgrad_tile(blockIdx.x, p.tiles_u, p.tiles_v, UT, VT);
+    const int slice = wt.slice, u0 = wt.u0, v0 = wt.v0;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;

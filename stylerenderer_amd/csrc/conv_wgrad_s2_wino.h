@@ -1,9 +1,13 @@
 // Internal interface of the polyphase stride-2 3x3 weight gradient (csrc/conv_wgrad_s2_wino.hip): 25 instead of 36
-// matrix products per 2x2 tile of the base grid, used by sr_conv2d_wgrad_mfma for the shapes k_wgrad_s2_dma serves.
-// U is the windowed (2G + 1)-wide operand, V the G-wide one (conv_wgrad_mfma.hip).
+// matrix products per 2x2 tile of the base grid, used by sr_conv2d_wgrad_mfma for the shapes k_wgrad_s2_dma serves: the
+// same U window (sr_s2_window of wgrad_tile.h), the same patch order (sr_wgrad_patch) and the K slices of
+// sr_wgrad_tiles (conv_wgrad_mfma.h), which the dispatch passes in as ks / pps.
+// U is the windowed (2G + 1)-wide operand, V the G-wide one (conv_wgrad_mfma.hip has the formula).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "wgrad_params.h"
 
 // 3x3 stride 2 pad 0: GW % 16 == 0, GH % 4 == 0, CU % 32 == 0, CV % 128 == 0, windows inside U, byte offsets < 2^31
 bool sr_wgrad_s2_wino_eligible(int64_t B, int64_t CU, int64_t CV, int64_t UH, int64_t UW, int64_t GH, int64_t GW, int d0);
@@ -13,6 +17,5 @@ int64_t sr_wgrad_s2_wino_scratch_floats(int64_t ks, int64_t CU, int64_t CV);
 int sr_wgrad_s2_wino_launch(const float* U, const float* V, const float* uscale, const float* vscale, float* partial,
                             int64_t B, int64_t CU, int64_t CV, int64_t UH, int64_t UW, int64_t GH, int64_t GW, int ks,
                             int pps, hipStream_t st);
-// finish: slices summed in slice order, 16 -> 9 positions, element (t, u, v) to dwt[t * slab + u * su + v * sv]
-int sr_wgrad_s2_wino_finish(float* dwt, const float* partial, int ks, int64_t CU, int64_t CV, int64_t slab, int64_t su,
-                            int64_t sv, hipStream_t st);
+// finish: slices summed in slice order, 16 -> 9 positions, written in the layout of `out`
+int sr_wgrad_s2_wino_finish(const WgradOut& out, const float* partial, int ks, int64_t CU, int64_t CV, hipStream_t st);

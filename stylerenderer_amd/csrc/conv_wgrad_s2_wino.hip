@@ -21,7 +21,7 @@
 // The non-MFMA work is pinned one or two instructions behind each MFMA; nothing in the loop waits on memory except
 // the stage barrier.  One 16-position slab per K slice: ks * 16 <= the ks * 2 * 9 the direct plan reserves.
 // k_wgrad_s2p_finish adds the slices in slice order, combines 16 -> 9 in a fixed order and applies the output layout.
-#include "mfma_tile.h"
+#include "wgrad_tile.h"
 #include "conv_wgrad_s2_wino.h"
 
 namespace {
@@ -40,14 +40,14 @@ struct S2pParams {
 };
 
 namespace s2p {
-constexpr int RP = 36;                    // floats per staged window row (33 used)
-constexpr int UPL = 5 * RP + 1;           // 181: odd channel pitch of the raw window
-constexpr int URAW = 32 * UPL;            // 5792 floats, one raw buffer
+constexpr int RP = sr_s2_window::RP;      // 36 floats per staged window row (33 used)
+constexpr int UPL = sr_s2_window::UPL;    // 181: odd channel pitch of the raw window
+constexpr int URAW = sr_s2_window::BLOCK; // 5792 floats, one raw buffer
 constexpr int VPL = 8 * 32 + 1;           // 257: row l holds the 32 pixels of channels l, l + 16, ..., l + 112
 constexpr int VBUF = 16 * VPL;            // 4112
 constexpr int TP = 25 * 32;               // 800: tile pitch of u^ [tile][product][channel]
 constexpr int UHAT = 8 * TP;              // 6400
-constexpr int OFF_V = 2 * URAW;           // 11584
+constexpr int OFF_V = sr_s2_window::OFF_V; // 11584
 constexpr int OFF_UH = OFF_V + 2 * VBUF;  // 19808
 constexpr int LDS_FLOATS = OFF_UH + 2 * UHAT;     // 32608
 constexpr int LDS_BYTES = LDS_FLOATS * 4;         // 130432
@@ -61,10 +61,8 @@ __global__ __launch_bounds__(256) void k_wgrad_s2p(const S2pParams p) {
 #if __HIP_DEVICE_COMPILE__
     using namespace s2p;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int bid = blockIdx.x;
-    const int tile_uv = bid % (p.tiles_u * p.tiles_v);
-    const int slice = bid / (p.tiles_u * p.tiles_v);
-    const int u0 = (tile_uv / p.tiles_v) * 32, v0 = (tile_uv % p.tiles_v) * 128;
+    const SrWgradTile wt = sr_wgrad_tile(blockIdx.x, p.tiles_u, p.tiles_v, 32, 128);
+    const int slice = wt.slice, u0 = wt.u0, v0 = wt.v0;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
@@ -80,9 +78,9 @@ __global__ __launch_bounds__(256) void k_wgrad_s2p(const S2pParams p) {
     const __amdgpu_buffer_rsrc_t r_u = uniform_rsrc(p.U, p.B * p.CU * plane_u * 4);
     const __amdgpu_buffer_rsrc_t r_v = uniform_rsrc(p.V, p.B * p.CV * plane_v * 4);
     // U: 45 lanes = 5 rows x 9 float4.  V: lane = (channel l + 16 k: k = lane >> 3, row = (lane >> 2) & 1, float4 = lane & 3)
-    const int u_lane_off = ((lane / 9) * p.UW + 4 * (lane % 9)) * 4;
+    const int u_lane_off = sr_s2_window::lane_off(lane, p.UW);
     const int v_lane_off = ((lane >> 3) * 16 * plane_v + ((lane >> 2) & 1) * p.GW + 4 * (lane & 3)) * 4;
-    const bool u_lane = lane < 45;
+    const bool u_lane = lane < sr_s2_window::LANES;
     const float* usc = p.uscale ? p.uscale : g_s2p_one;
     const float* vsc = p.vscale ? p.vscale : g_s2p_one;
     const int us_on = p.uscale ? 1 : 0, vs_on = p.vscale ? 1 : 0;
@@ -91,14 +89,14 @@ __global__ __launch_bounds__(256) void k_wgrad_s2p(const S2pParams p) {
     auto clamp_hp = [&](int hp) { return hp < last ? hp : last - 1; };
     auto sample_of = [&](int hp) { return (hp >> 1) / tiles_xy; };
     auto origin_u = [&](int hp) {       // byte offset of the window's first float at channel u0
-        const int patch = hp >> 1, g = hp & 1;
-        const int tx_i = patch % p.tiles_x, ty_i = (patch / p.tiles_x) % p.tiles_y, b = patch / tiles_xy;
-        return ((b * p.CU + u0) * plane_u + (ty_i * 8 + g * 4) * p.UW + tx_i * 32) * 4;
+        const int g = hp & 1;
+        const SrWgradPatch pt = sr_wgrad_patch(hp >> 1, p.tiles_x, p.tiles_y);
+        return ((pt.b * p.CU + u0) * plane_u + (pt.ty * 8 + g * 4) * p.UW + pt.tx * 32) * 4;
     };
     auto origin_v = [&](int hp) {
-        const int patch = hp >> 1, g = hp & 1;
-        const int tx_i = patch % p.tiles_x, ty_i = (patch / p.tiles_x) % p.tiles_y, b = patch / tiles_xy;
-        return ((b * p.CV + v0) * plane_v + (ty_i * 4 + g * 2) * p.GW + tx_i * 16) * 4;
+        const int g = hp & 1;
+        const SrWgradPatch pt = sr_wgrad_patch(hp >> 1, p.tiles_x, p.tiles_y);
+        return ((pt.b * p.CV + v0) * plane_v + (pt.ty * 4 + g * 2) * p.GW + pt.tx * 16) * 4;
     };
     // (readfirstlane: a soffset the compiler keeps in a VGPR turns the DMA into a waterfall loop)
     // DMA item i of this wave (compile-time i): 0..7 = U channel wave + 4 i; 8..11 = V row wave + 4 (i - 8)
@@ -314,10 +312,10 @@ int sr_wgrad_s2_wino_launch(const float* U, const float* V, const float* uscale,
     return sr_launch_status();
 }
 
-int sr_wgrad_s2_wino_finish(float* dwt, const float* partial, int ks, int64_t CU, int64_t CV, int64_t slab, int64_t su,
-                            int64_t sv, hipStream_t st) {
+int sr_wgrad_s2_wino_finish(const WgradOut& out, const float* partial, int ks, int64_t CU, int64_t CV, hipStream_t st) {
     S2pFinish r;
-    r.partial = partial; r.out = dwt; r.ks = ks; r.CU = (int)CU; r.CV = (int)CV; r.slab = slab; r.su = su; r.sv = sv;
+    r.partial = partial; r.out = out.dwt; r.ks = ks; r.CU = (int)CU; r.CV = (int)CV;
+    r.slab = out.slab; r.su = out.su; r.sv = out.sv;
     hipLaunchKernelGGL(k_wgrad_s2p_finish, dim3(sr_stream_grid(9 * CU * CV, 256)), dim3(256), 0, st, r);
     return sr_launch_status();
 }

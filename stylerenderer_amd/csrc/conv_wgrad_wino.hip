@@ -5,7 +5,7 @@
 // d = 4x4 input tile of channel c (style-scaled), dY = 2x2 output-gradient tile of channel n
 // (demodulation-scaled): 16 independent GEMMs  dU[pos][c][n] = sum_k V[pos][k][c] * Z[pos][k][n]  over
 // k = (sample, tile) — 16 multiply-adds per tile instead of the 36 of the direct correlation
-// (csrc/conv_wgrad_mfma.hip), the same 2.25x as the forward Winograd kernel (csrc/conv_wino.hip).
+// (csrc/conv_wgrad_mfma.hip: k_wgrad_mfma), the same 2.25x as the forward Winograd kernel (csrc/conv_wino.hip).
 //
 // One 256-thread workgroup = 64 input channels x 64 output channels x all 16 positions; wave (i, j)
 // owns channel block i and output block j (16 accumulator tiles of 32x32 = 256 registers).  The K
@@ -29,7 +29,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "mfma_tile.h"
-#include "conv_wino.h"
+#include "conv_wgrad_wino.h"
 
 namespace {
 
@@ -574,8 +574,8 @@ int64_t sr_wgrad_wino_scratch_floats(int64_t B, int64_t C, int64_t N, int64_t H,
     return (int64_t)slices * 16 * C * N;
 }
 
-int sr_wgrad_wino_3x3(float* dwt, const float* x, const float* gy, const float* xscale, const float* gscale,
-                      int64_t B, int64_t C, int64_t N, int64_t H, int64_t W, float* scratch, hipStream_t st) {
+int sr_wgrad_wino_launch(float* dwt, const float* x, const float* gy, const float* xscale, const float* gscale,
+                         int64_t B, int64_t C, int64_t N, int64_t H, int64_t W, float* scratch, hipStream_t st) {
     WgWinoParams p;
     p.x = x; p.gy = gy; p.xscale = xscale; p.gscale = gscale; p.partial = scratch;
     p.B = (int)B; p.C = (int)C; p.N = (int)N; p.H = (int)H; p.W = (int)W;

@@ -1,8 +1,11 @@
-"""CPU: the dispatch plan of the dense convolutions (csrc/conv_dispatch.hip, csrc/conv_wgrad_mfma.hip) through its host-only
-queries — no GPU is touched.
+"""CPU: the dispatch plan of the dense convolutions (csrc/conv_dispatch.hip, csrc/conv_wgrad_dispatch.hip) through its
+host-only queries — no GPU is touched.
 
   * scratch sizes and the Winograd query equal, row for row and under every switch, what the selection code they
     replaced answered (tests/golden/conv_plan_parent.json, recorded by tests/make_golden_conv_plan.py);
+  * the weight-gradient path and what it needs equal, row for row, under every switch and with either buffer
+    misaligned, what the parent's selection answered (tests/golden/wgrad_plan_parent.json, recorded by
+    tests/make_golden_wgrad_plan.py);
   * sr_conv2d_path / sr_conv2d_wgrad_path say what the written rules say, one shape on each side of every threshold;
   * the scratch a chosen path needs never exceeds the size the caller was told to allocate.
 """
@@ -11,6 +14,7 @@ import json
 import pytest
 
 import make_golden_conv_plan as G
+import make_golden_wgrad_plan as W
 from conv_plan_cases import FORWARD, MISALIGNED, SWITCHES, WGRAD, case_id, conv_args
 from stylerenderer_amd import _lib
 
@@ -24,9 +28,18 @@ def golden():
     return doc
 
 
+@pytest.fixture(scope="module")
+def wgrad_golden():
+    with open(W.OUT) as f:
+        doc = json.load(f)
+    assert doc["rows"] == len(G.shapes()) == len(doc["unset"])
+    assert sorted(doc["settings"]) == sorted(G.setting_key(n, v) for n, v in W.SETTINGS)
+    return doc
+
+
 @pytest.fixture
 def clean_env(monkeypatch):
-    for name in SWITCHES:
+    for name in sorted(set(SWITCHES) | {name for name, _ in W.SETTINGS}):
         monkeypatch.delenv(name, raising=False)
     return monkeypatch
 
@@ -49,6 +62,20 @@ def test_sizes_and_winograd_query_match_parent_under_switch(golden, clean_env, s
         want[int(j)] = v
     clean_env.setenv(*setting)
     bad = _mismatches(G.query(_lib.lib(), rows), want, rows)
+    assert not bad, "%d rows differ, first: %s" % (len(bad), bad[:3])
+
+
+@pytest.mark.parametrize("setting", (None,) + W.SETTINGS, ids=lambda s: "unset" if s is None else G.setting_key(*s))
+def test_wgrad_path_and_floats_match_parent(wgrad_golden, clean_env, setting):
+    """Every row of the sweep, asked with (x, gy) = (NULL, NULL), (misaligned, NULL), (NULL, misaligned): the path
+    taken and the floats it needs are the parent's."""
+    rows = G.shapes()
+    want = list(wgrad_golden["unset"])
+    if setting is not None:
+        for j, v in wgrad_golden["settings"][G.setting_key(*setting)].items():
+            want[int(j)] = v
+        clean_env.setenv(*setting)
+    bad = _mismatches(W.query(_lib.lib(), rows), want, rows)
     assert not bad, "%d rows differ, first: %s" % (len(bad), bad[:3])
 
 

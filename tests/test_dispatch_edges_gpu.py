@@ -250,7 +250,7 @@ def test_styled_map_tail_vs_float64(case):
     _check(d_m, dm_want, dm_mag, 3e-6, "second order: d map")
 
 
-# ---- weight gradients (csrc/conv_wgrad_mfma.hip) ----------------------------------------------------------------------
+# ---- weight gradients (csrc/conv_wgrad_dispatch.hip and the conv_wgrad_*.hip it launches) -----------------------------
 def _wgrad_reference(x, gy, xs, gs, k):
     def f(xx, gg, a, bsc):
         xx = xx * a[:, :, None, None] if a is not None else xx
@@ -598,7 +598,7 @@ def test_from_rgb_weight_gradient_at_256_vs_float64():
     _check(got, want, mag, 2e-6, "dwt")
 
 
-# ---- the dispatch queries and the launches agree (csrc/conv_dispatch.hip make_conv_plan, csrc/conv_wgrad_mfma.hip) ---------
+# ---- the dispatch queries and the launches agree (csrc/conv_dispatch.hip make_conv_plan, csrc/conv_wgrad_dispatch.hip) -----
 # kernels that tell the paths apart: a path's launch runs exactly its own of these (no numeric assertions here: the
 # float64 comparisons of the same shapes are in test_conv_gpu, test_conv_s2_wino_gpu and above).  k_conv_mfma is judged
 # apart: it is the direct path's only kernel and no other non-transposed path runs it, but the transposed paths use its

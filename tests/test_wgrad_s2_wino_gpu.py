@@ -14,7 +14,7 @@ DEV = "cuda"
 BAR = 2e-6
 NEW, NEW_FINISH, OLD, DIRECT = "k_wgrad_s2p", "k_wgrad_s2p_finish", "k_wgrad_s2_dma", "k_wgrad_mfma"
 SWITCH = "SR_WGRAD_S2_WINO"
-T_WORK = 6.0e9                # SR_WGRAD_S2_WINO_MIN_WORK of csrc/conv_wgrad_mfma.hip: 18 B CU CV GH GW >= T takes the new path
+T_WORK = 6.0e9                # SR_WGRAD_S2_WINO_MIN_WORK of csrc/conv_wgrad_dispatch.hip: 18 B CU CV GH GW >= T takes the new path
 
 
 def _out_size(ih, iw, pad, tr):
