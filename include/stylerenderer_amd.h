@@ -438,6 +438,8 @@ int sr_blur_nba_bwd(float* gx, float* gbias, float* gnoise_w, float* rowdot, con
 #define SR_RASTER_CHW 2
 #define SR_RASTER_GRAD_ACC 4
 int64_t sr_rasterize_scratch_bytes(int64_t b, int64_t nf, int64_t h, int64_t w, int is_double);
+/* int32 entries of the gradient state `big` above (2 + 2*b*nf): what the caller of a forward pass allocates. */
+int64_t sr_rasterize_grad_state_ints(int64_t b, int64_t nf);
 int sr_rasterize_forward_f32(int64_t b, int64_t nv, int64_t nf, int64_t h, int64_t w, int repeat_v,
                              int repeat_f, int perspective, const float* v, const int64_t* tri,
                              int64_t* index, float* coeff, float* zbuf, float eps,

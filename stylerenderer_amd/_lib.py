@@ -97,6 +97,7 @@ SIGNATURES = {
     "sr_blur_nba_bwd_scratch_floats": (_l, [_l, _l, _i, _i]),
     "sr_blur_nba_bwd": (_i, [_p] * 10 + [_f, _f, _l, _l] + [_i] * 5 + [_l, _p, _p]),
     "sr_rasterize_scratch_bytes": (_l, [_l, _l, _l, _l, _i]),
+    "sr_rasterize_grad_state_ints": (_l, [_l, _l]),
     "sr_rasterize_forward_f32": (_i, [_l] * 5 + [_i] * 3 + [_p] * 5 + [_f, _p, _l, _p, _p, _p, _p, _p]),
     "sr_rasterize_levels_supported": (_i, [_i, _l, _l, _p, _p]),
     "sr_rasterize_forward_levels_f32": (_i, [_i, _l, _l, _l, _p, _p, _i, _i, _i, _p, _p, _f, _p, _l, _p, _p, _p, _p, _p]),

@@ -30,6 +30,9 @@ SOURCES = [
     ("fused_bias_act.hip", EXACT),
     ("upfirdn2d.hip", EXACT + NOSLP),
     ("rasterize.hip", EXACT),
+    ("rasterize_keys.hip", EXACT),
+    ("rasterize_tiled.hip", EXACT),
+    ("rasterize_grad.hip", EXACT),
     ("fused_elem.hip", EXACT),
     ("weight_prep.hip", EXACT),
     ("style_linear.hip", EXACT),

@@ -1,4 +1,5 @@
-"""3DMM triangle rasterizer — host side of csrc/rasterize.hip.
+"""3DMM triangle rasterizer — host side of csrc/rasterize.hip (the entries; the kernels are csrc/rasterize_keys.hip,
+rasterize_tiled.hip and rasterize_grad.hip, the buffer layouts csrc/raster_layout.h).
 
 Interface parity with the reference:
   rasterize(v, tex, tri, h=256, w=0, perspective=False, eps=1e-6) -> [b,h,w,c] (or [b,h,w])
@@ -62,6 +63,12 @@ SR_RASTER_GRAD_ACC = 4     # sr_rasterize_grad_*: add to what grad_v / grad_tex 
 SR_RASTER_CHW = 2          # include/stylerenderer_amd.h: attribute maps / their gradient channel-major [b, c, h, w]
 
 
+def grad_state_ints(b, nf):
+    """int32 entries of the gradient state `big` of a forward call: [count | big-triangle ids b*nf | leader table b*nf |
+    state word] — GradState in csrc/raster_layout.h; tests/test_raster_layout_cpu.py holds the two together."""
+    return 2 + 2 * b * nf
+
+
 def _forward_impl(vertices, triangles, height, width, perspective, eps, tex=None, want_z=False,
                   want_index=True, want_win=False, chw=False):
     if vertices.device != triangles.device:
@@ -100,8 +107,7 @@ def _forward_impl(vertices, triangles, height, width, perspective, eps, tex=None
     coeff = torch.empty((b, h, w, 3), dtype=dt, device=dev) if want_index else None
     zbuf = torch.empty((b, h, w), dtype=dt, device=dev) if want_z else None
     win = torch.empty((b, h, w), dtype=torch.int32, device=dev) if want_win else None
-    # gradient state: [count | big-triangle ids b*nf | leader table b*nf | state word] (include/stylerenderer_amd.h)
-    big = torch.empty(2 + 2 * b * nf, dtype=torch.int32, device=dev) if want_win else None
+    big = torch.empty(grad_state_ints(b, nf), dtype=torch.int32, device=dev) if want_win else None
     attr, tex_c, tex_flat = None, 0, None
     if tex is not None:
         tex_c = 1 if tex.dim() == vertices.dim() - 1 else int(tex.shape[-1])
@@ -327,7 +333,7 @@ def _forward_levels(v, tex, tri, sizes, perspective, eps, want_win, chw):
     tex_flat = tex.contiguous().view(-1, tex_c)
     attrs = [torch.empty((b, tex_c, h, w) if chw else (b, h, w, tex_c), dtype=v.dtype, device=dev) for h, w in sizes]
     wins = [torch.empty((b, h, w), dtype=torch.int32, device=dev) if want_win else None for h, w in sizes]
-    bigs = [torch.empty(2 + 2 * b * nf, dtype=torch.int32, device=dev) if want_win else None for _ in sizes]
+    bigs = [torch.empty(grad_state_ints(b, nf), dtype=torch.int32, device=dev) if want_win else None for _ in sizes]
     sizes_b = [int(L.sr_rasterize_scratch_bytes(b, nf, h, w, 0)) for h, w in sizes]
     offs, total = [], 0
     for sz in sizes_b:

@@ -158,7 +158,7 @@ RASTER_CASES = ["raster_ellipsoid_32", "raster_ellipsoid_64", "raster_perspectiv
 
 @pytest.fixture(params=["auto", "tiled"])
 def raster_path(request, monkeypatch):
-    """The forward has two device paths chosen per call (csrc/rasterize.hip tiled_ok): the LDS-tiled one only pays for
+    """The forward has two device paths chosen per call (csrc/rasterize_tiled.hip raster_tiled_ok): the LDS-tiled one only pays for
     thousands of (sample, tile) workgroups, so small test inputs would never reach it — every bit-exactness test runs
     once with the automatic choice and once with the tiled path forced."""
     if request.param == "tiled":
@@ -343,6 +343,119 @@ def test_rasterize_large_triangles_forward_and_gradients(c, raster_path):
     wv, wt = _oracle_grads(vh, tex, tri, go, 256)
     assert np.abs(got[0][0].cpu().numpy() - wv).max() <= 5e-5 * np.abs(wv).max()
     assert np.abs(got[0][1].cpu().numpy() - wt).max() <= 5e-6 * np.abs(wt).max()
+
+
+def _ab_mesh(h, w, persp):
+    """(v [2, nv, 3], tri [nf, 3]): a closed fan of 32 triangles around one vertex (valence 32 > 24: the wave-summed
+    branch of the vertex gather), a 6 x 6 grid of cells of two small triangles each, and one screen-filling triangle
+    (bounding box > 64 pixels: k_grad_big) whose depth crosses the other two parts.  Every z is negative (perspective
+    accepts it); the second sample is the first one shrunk, shifted and tilted in depth.
+
+    The screen of an h x w image with h > w: the rasterizer keeps the reference's call convention, which scales x by h
+    and y by w, so x = -1 .. 1 spans h columns of which the image has w; what lies right of column w is not
+    on the image (the reference lets it run into the next row; op/texture.py draws non-square pictures inside the
+    leading block for that reason).  The mesh is laid out on x = -1 .. 1 and then mapped onto the w columns there are,
+    x -> (x + 1) w / h - 1, so that "screen-filling" means the image and not the columns beyond it.  For the perspective
+    projection x and y are then multiplied by -z: the division brings the same layout to the screen."""
+    ang = 2.0 * np.pi * np.arange(32) / 32
+    fan = [(-0.45, 0.40, -0.70)] + [(-0.45 + 0.25 * np.cos(a), 0.40 + 0.25 * np.sin(a), -0.72 + 0.05 * np.sin(3 * a))
+                                    for a in ang]
+    tri = [(0, 1 + k, 1 + (k + 1) % 32) for k in range(32)]
+    g0 = len(fan)
+    grid = [(0.10 + 0.1 * i, -0.70 + 0.1 * j, -0.70 + 0.02 * ((3 * i + 5 * j) % 7)) for j in range(7) for i in range(7)]
+    for j in range(6):
+        for i in range(6):
+            a = g0 + 7 * j + i
+            tri += [(a, a + 1, a + 8), (a, a + 8, a + 7)]
+    b0 = g0 + len(grid)
+    big = [(-0.95, -0.90, -0.90), (0.95, -0.90, -0.55), (0.0, 0.95, -0.75)]
+    tri.append((b0, b0 + 1, b0 + 2))
+    v0 = np.array(fan + grid + big, np.float32)
+    v1 = v0 * np.array([0.9, 0.85, 1.0], np.float32) + np.array([0.06, -0.04, 0.0], np.float32)
+    v1[:, 2] += 0.1 * v0[:, 0]
+    v = np.stack([v0, v1])
+    if h > w:
+        v[..., 0] = (v[..., 0] + 1) * np.float32(w / h) - 1
+    if persp:
+        v[..., :2] *= -v[..., 2:]
+    return v, np.array(tri, np.int64)
+
+
+RASTER_AB_SWITCHES = [("SR_RASTER_BIN_LDS", "0"), ("SR_RASTER_GRAD_SLOTS", "0"), ("SR_RASTER_GRAD_EAGER", "0"),
+                      ("SR_RASTER_GRAD_EAGER", "1")]
+
+
+@pytest.mark.parametrize("c", [3, 6])
+@pytest.mark.parametrize("persp", [False, True], ids=["ortho", "persp"])
+@pytest.mark.parametrize("h,w,tiled", [(64, 64, True), (40, 24, False)], ids=["tiled64", "keys40x24"])
+def test_rasterize_ab_switches_change_no_bit(h, w, tiled, persp, c, monkeypatch):
+    """The A/B switches of the rasterizer's host code select between kernels that must compute the same thing:
+    SR_RASTER_BIN_LDS=0 (k_tile_bin, the wave-vote binning, instead of k_tile_bin_lds), SR_RASTER_GRAD_SLOTS=0 (one
+    record per triangle instead of vertex-major corner slots) and SR_RASTER_GRAD_EAGER=0 / 1 (the two slot modes of
+    k_grad_vert).  With each of them set, ids, weights, depth, attributes and both gradients equal the run with the
+    switch unset bit for bit; the unset run is checked against the library's sequential host loops and the C oracle
+    (forward bitwise, gradients with test_rasterize_large_triangles_forward_and_gradients' tolerance).  64 x 64 with the
+    tiled path forced has 4 tiles; 40 x 24 is non-square, so the global-key path — the binning switch has no effect
+    there and is not run.  Six channels = two channel chunks, the first with tail planes.
+
+    (Geometry right of column w on such an image is a known defect of the global-key kernels; _ab_mesh
+    keeps the mesh on the image.)"""
+    import stylerenderer_amd.op as op
+    from stylerenderer_amd import synth
+    R = importlib.import_module("stylerenderer_amd.op.rasterize")
+
+    vh, tri = _ab_mesh(h, w, persp)
+    tex = synth.det_normal((2, vh.shape[1], c), 91)
+    go = synth.det_normal((2, h, w, c), 92)
+    names = sorted({name for name, _ in RASTER_AB_SWITCHES})
+
+    def run(setting):
+        for name in names:
+            monkeypatch.delenv(name, raising=False)
+        if tiled:
+            monkeypatch.setenv("SR_RASTER_TILED", "1")
+        else:
+            monkeypatch.delenv("SR_RASTER_TILED", raising=False)
+        if setting is not None:
+            monkeypatch.setenv(*setting)
+        idx, coeff, zbuf = R.forward_with_depth(T(vh), T(tri), h, w, persp, 1e-6)
+        v, tx = T(vh).requires_grad_(), T(tex).requires_grad_()
+        out = op.rasterize(v, tx, T(tri), h, w, persp)
+        gv, gt = torch.autograd.grad(out, [v, tx], T(go))
+        return idx, coeff, zbuf, out.detach(), gv, gt
+
+    base = run(None)
+    changed = []
+    for setting in RASTER_AB_SWITCHES:
+        if setting[0] == "SR_RASTER_BIN_LDS" and not tiled:
+            continue
+        got = run(setting)
+        changed += ["%s=%s changes %s" % (setting + (what,))
+                    for what, a, b in zip(("ids", "weights", "depth", "attributes", "grad_v", "grad_tex"), got, base)
+                    if not torch.equal(a, b)]
+    print("switches:", changed or "no bit changed")
+    idx, coeff, zbuf, out, gv, gt = (t.cpu().numpy() for t in base)
+    wi, wc, wz = raster.forward_buffers(vh, tri, h, w, persp, 1e-6)
+    hi, hc, hz = R.forward_with_depth(torch.from_numpy(vh), torch.from_numpy(tri), h, w, persp, 1e-6)   # host loops
+    wo = raster.rasterize(vh, tex, tri, h, w, persp)
+    wv, wt = raster.rasterize_grads(vh, tex, tri, go, h, w, persp)
+    differ = lambda a, b: int((a.view(np.uint32) != b.view(np.uint32)).reshape(2 * h * w, -1).any(1).sum())   # noqa: E731
+    err_v = np.abs(gv - wv).max() / np.abs(wv).max()
+    err_t = np.abs(gt - wt).max() / np.abs(wt).max()
+    print("pixels of %d that differ from the oracle: ids %d, weights %d, depth %d, attributes %d; host loops vs oracle: "
+          "weights %d, depth %d; grad_v rel. err %.3g, grad_tex %.3g"
+          % (2 * h * w, int((idx != wi).reshape(2 * h * w, 3).any(1).sum()), differ(coeff, wc), differ(zbuf, wz),
+             differ(out, wo), differ(hc.numpy(), wc), differ(hz.numpy(), wz), err_v, err_t))
+    # every part of the mesh is on screen: the fan's hub, the grid and the large triangle each won pixels
+    rows = wi[0].reshape(-1, 3)
+    lead = rows[rows.any(1)][:, 0]
+    hub, grid0, big0 = 0, 33, int(tri[-1, 0])
+    assert (lead == hub).any() and ((lead >= grid0) & (lead < big0)).any() and (lead == big0).any()
+    assert not changed
+    assert np.array_equal(hi.numpy(), wi) and bits_equal(hc.numpy(), wc) and bits_equal(hz.numpy(), wz)
+    assert np.array_equal(idx, wi) and bits_equal(coeff, wc) and bits_equal(zbuf, wz)
+    assert bits_equal(out, wo)
+    assert err_v <= 5e-5 and err_t <= 5e-6
 
 
 @pytest.mark.parametrize("fwd,bwd", [("1", "0"), ("0", "1")])
