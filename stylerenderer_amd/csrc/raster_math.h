@@ -295,6 +295,35 @@ SR_HD bool shade(const Tri<R>& t, int x, int y, bool perspective, R eps, R& c0, 
     return pixel_depth<R>(t, c0, c1, c2, perspective, eps, z);
 }
 
+// An h x w image with h > w.  The call convention lets x span h columns and y span w rows, and sample
+// (x, y) lands on buffer entry x + y w: the samples (px + k w, py - k), k = 0, 1, ..., of a triangle's box all land on
+// pixel (px, py).  Among one triangle's samples on a pixel the sequential sweep keeps the largest depth and, of equal
+// depths, the sample it meets first in box order — the smaller sample row, i.e. the larger k (`zB < z` is strict).
+// This finds that sample of triangle `t` (set up) for pixel (px, py): where it is, and its weights and depth, from the
+// same shade() every pass uses.  false (outputs untouched) = no sample of the box covers the pixel.  With w >= h no two
+// samples share a pixel and nobody calls this.
+template <typename R>
+SR_HD bool alias_winner(const Tri<R>& t, int px, int py, long long w, bool perspective, R eps, int& sx, int& sy, R& c0,
+                        R& c1, R& c2, R& z) {
+    long long k = t.x1 >= px ? (t.x1 - px) / w : -1;          // the largest k with px + k w inside the box's columns
+    if (k > (long long)py - t.y0) k = (long long)py - t.y0;   // ... and py - k inside its rows
+    const long long k_end = py > t.y1 ? (long long)py - t.y1 : 0;
+    bool found = false;
+    for (; k >= k_end; --k) {                                 // descending k = box order
+        const int qx = (int)(px + k * w), qy = (int)(py - k);
+        if (qx < t.x0) continue;
+        R a0, a1, a2, az;
+        if (!shade<R>(t, qx, qy, perspective, eps, a0, a1, a2, az)) continue;
+        if (!(az == az)) continue;                            // NaN never passes `zB < z`
+        if (!found || az > z) {
+            found = true;
+            sx = qx; sy = qy;
+            c0 = a0; c1 = a1; c2 = a2; z = az;
+        }
+    }
+    return found;
+}
+
 // d(3 weights)/d(3 vertices x xyz) at one pixel (reference op/rasterize.h:169-228).  `g` = 27 values
 // [weight][vertex][component]; returns false (g untouched) for a degenerate triangle.
 template <typename R>

@@ -7,6 +7,7 @@
 //                compacted through LDS, then each sums, in box order, d/d(3 vertices) and d/d(3 attribute rows) over
 //                the triangle's pixels (winner map written by k_resolve) into the triangle's three corner records;
 //   k_grad_big   the large triangles k_depth_keys listed: one workgroup each, fixed-order tree over the lanes;
+//   k_grad_pix_alias / k_grad_big_alias  the same two on an image with h > w, where samples alias onto pixels;
 //   k_grad_vert  one lane per (sample, vertex): sums the corner blocks of its incident triangles in the fixed
 //                order of a per-topology incidence list (corner-major, ascending triangle id).
 // (The reference builds a COO matrix per call and runs sparse.mm, op/rasterize.py:46-77; round 1 of this repo
@@ -571,6 +572,140 @@ __global__ __launch_bounds__(256) void k_grad_pix(long long b, long long nv, lon
                                 eps, chw, slot_of, slot_bs, tail, plane);
 }
 
+// ---- phase 1 on an image with h > w -------------------------------------------------------------------------
+// There several samples of a triangle's box may land on one pixel (alias_winner, raster_math.h), so a box walk meets
+// a pixel the triangle won more than once, and the pixel's position is not the sample's.  The pixel counts ONCE, at
+// the sample that won it: weights from that sample (what the resolve pass interpolated with), the Jacobian at the
+// pixel's own position (pix % w, pix / w) like k_dcoeff.  Kernels of their own, chosen by the launch: the ones above
+// stay the code they were.  Same records, same validity bits, summation in box order of the winning samples.
+template <typename R, int CT, bool PERSP>
+__device__ __forceinline__ void grad_sample_alias(TriAcc<R, CT, PERSP>& acc, const Tri<R>& t, const JacTri<R, PERSP>& jt,
+                                                  bool want_v, int x, int y, long long w, long long hw, long long h_arg,
+                                                  R eps, const int* __restrict__ wins, int ti,
+                                                  const R* __restrict__ gos, const R* __restrict__ tex0,
+                                                  const R* __restrict__ tex1, const R* __restrict__ tex2,
+                                                  int tex_c, int ch0, long long gcs) {
+    const long long pix = x + (long long)y * w;
+    if (pix >= hw || wins[pix] != ti) return;
+    const int py = (int)(pix / w), px = (int)(pix - (long long)py * w);
+    int sx, sy;
+    R c0, c1, c2, z;
+    if (!alias_winner<R>(t, px, py, w, PERSP, eps, sx, sy, c0, c1, c2, z)) return;
+    if (sx != x || sy != y) return;                       // another sample of the box won this pixel: counted there
+    const R* go = gos + pix * (gcs == 1 ? tex_c : 1);
+    acc.n += 1;
+#pragma unroll
+    for (int j = 0; j < CT; ++j) {
+        if (ch0 + j < tex_c) {
+            const R gch = go[(ch0 + j) * gcs];
+            acc.gt[j] += gch * c0;
+            acc.gt[CT + j] += gch * c1;
+            acc.gt[2 * CT + j] += gch * c2;
+        }
+    }
+    if (want_v) {
+        R d0 = 0, d1 = 0, d2 = 0;
+        for (int ch = 0; ch < tex_c; ++ch) {
+            const R gch = go[ch * gcs];
+            d0 += gch * tex0[ch];
+            d1 += gch * tex1[ch];
+            d2 += gch * tex2[ch];
+        }
+        jt.add(acc.gv, d0, d1, d2, (R)px, (R)py, (R)h_arg, (R)w, eps);
+    }
+}
+
+// k_grad_big for h > w: the same workgroup walk and fixed-order tree
+template <typename R, int CT, bool PERSP>
+__global__ __launch_bounds__(256) void k_grad_big_alias(long long nv, long long nf, long long h, long long w,
+                                                        bool repeat_f, const R* __restrict__ v,
+                                                        const R* __restrict__ tex, int tex_c, int ch0,
+                                                        const long long* __restrict__ f, const int* __restrict__ win,
+                                                        const int* __restrict__ big, const R* __restrict__ grad_out,
+                                                        bool want_v, R* __restrict__ tg, R eps, bool chw,
+                                                        const int* __restrict__ slot_of, long long slot_bs,
+                                                        R* __restrict__ tail, long long plane) {
+    __shared__ R s_part[4];
+    const long long hw = h * w;
+    const int count = big[0];
+    for (int q = blockIdx.x; q < count; q += gridDim.x) {
+        const long long g = big[1 + q];
+        const long long s = g / nf, ti = g - s * nf;
+        const long long* fs = repeat_f ? f : f + s * nf * 3;
+        Tri<R> t;
+        long long i0, i1, i2;
+        load_tri<R>(t, v + s * nv * 3, fs, ti, nv, i0, i1, i2);
+        const R praw[9] = {t.p0, t.p1, t.p2, t.p3, t.p4, t.p5, t.p6, t.p7, t.p8};
+        JacTri<R, PERSP> jt;
+        jt.init(praw, eps);
+        tri_setup<R>(t, h, w, PERSP, eps);
+        TriAcc<R, CT, PERSP> acc;
+        acc.clear();
+        const bool distinct = want_v && jt.ok && i0 != i1 && i0 != i2 && i1 != i2;
+        const R* tb = tex + s * nv * tex_c;
+        const int bw = t.x1 - t.x0 + 1;
+        const long long npx = (long long)bw * (t.y1 - t.y0 + 1);
+        for (long long p = threadIdx.x; p < npx; p += 256) {
+            const int yy = (int)(p / bw);
+            grad_sample_alias<R, CT, PERSP>(acc, t, jt, distinct, t.x0 + (int)(p - (long long)yy * bw), t.y0 + yy, w, hw, h,
+                                            eps, win + s * hw, (int)ti, grad_out + s * hw * tex_c, tb + i0 * tex_c,
+                                            tb + i1 * tex_c, tb + i2 * tex_c, tex_c, ch0, chw ? hw : 1);
+        }
+        const R cnt = block_sum_256<R>((R)acc.n, s_part);
+#pragma unroll
+        for (int j = 0; j < JacTri<R, PERSP>::NV; ++j) acc.gv[j] = block_sum_256<R>(acc.gv[j], s_part);
+#pragma unroll
+        for (int j = 0; j < 3 * CT; ++j) acc.gt[j] = block_sum_256<R>(acc.gt[j], s_part);
+        if (threadIdx.x == 0 && cnt > 0) {
+            if (slot_of) store_slots<R, CT, PERSP>(acc, tg, tail, plane, s * 3 * nf, slot_of + s * slot_bs, nf, ti);
+            else store_row<R, CT, PERSP>(acc, tg, g);
+        }
+    }
+}
+
+// k_grad_pix for h > w: one lane per (sample, triangle), no compaction.  The leader table only says whether the
+// triangle won a pixel; every row whose validity bit is set gets its record, here or from k_grad_big_alias.
+template <typename R, int CT, bool PERSP>
+__global__ __launch_bounds__(256) void k_grad_pix_alias(long long b, long long nv, long long nf, long long h,
+                                                        long long w, bool repeat_f, const R* __restrict__ v,
+                                                        const R* __restrict__ tex, int tex_c, int ch0,
+                                                        const long long* __restrict__ f, const int* __restrict__ win,
+                                                        const int* __restrict__ first,
+                                                        unsigned long long* __restrict__ valid,
+                                                        const R* __restrict__ grad_out, bool want_v,
+                                                        R* __restrict__ tg, R eps, bool chw,
+                                                        const int* __restrict__ slot_of, long long slot_bs,
+                                                        R* __restrict__ tail, long long plane) {
+    const long long hw = h * w;
+    const long long row = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool has = row < b * nf && first[row] != 0x7FFFFFFF;
+    const unsigned long long won = __ballot(has);
+    if ((threadIdx.x & 63) == 0 && row < b * nf) valid[row >> 6] = won;
+    if (!has) return;
+    const long long s = row / nf;
+    const int ti = (int)(row - s * nf);
+    const long long* fs = repeat_f ? f : f + s * nf * 3;
+    Tri<R> t;
+    long long i0, i1, i2;
+    load_tri<R>(t, v + s * nv * 3, fs, ti, nv, i0, i1, i2);
+    const R praw[9] = {t.p0, t.p1, t.p2, t.p3, t.p4, t.p5, t.p6, t.p7, t.p8};
+    tri_setup<R>(t, h, w, PERSP, eps);
+    if ((long long)(t.x1 - t.x0 + 1) * (t.y1 - t.y0 + 1) > BIG_BOX) return;      // k_grad_big_alias owns it
+    JacTri<R, PERSP> jt;
+    jt.init(praw, eps);
+    TriAcc<R, CT, PERSP> acc;
+    acc.clear();
+    const bool distinct = want_v && jt.ok && i0 != i1 && i0 != i2 && i1 != i2;
+    const R* tb = tex + s * nv * tex_c;
+    for (int y = t.y0; y <= t.y1; ++y)
+        for (int x = t.x0; x <= t.x1; ++x)
+            grad_sample_alias<R, CT, PERSP>(acc, t, jt, distinct, x, y, w, hw, h, eps, win + s * hw, ti,
+                                            grad_out + s * hw * tex_c, tb + i0 * tex_c, tb + i1 * tex_c, tb + i2 * tex_c,
+                                            tex_c, ch0, chw ? hw : 1);
+    if (slot_of) store_slots<R, CT, PERSP>(acc, tg, tail, plane, s * 3 * nf, slot_of + s * slot_bs, nf, ti);
+    else store_row<R, CT, PERSP>(acc, tg, row);
+}
+
 // ---- fused gradient, phase 2: per-vertex sum over its incident corners, in incidence-list order ---------------
 // One step of the gather: U list entries (already in registers; -1 = none) -> validity words -> records, every level's
 // loads in flight together (unconditional loads from clamped addresses, masked afterwards); the sums keep list order.
@@ -866,13 +1001,23 @@ void grad_chunk_launch(const RasterGrad<R>& c, int ch0, const GradScratch<R>& s,
                        long long slot_bs, hipStream_t st) {
     const bool want_v = c.grad_v != nullptr && ch0 == 0;
     const bool eager = grad_eager(c.b, c.nv);
-    hipLaunchKernelGGL((k_grad_big<R, CT, PERSP>), dim3(SR_NUM_CU * 2), dim3(256), 0, st, c.nv, c.nf, c.h, c.w, c.repeat_f,
-                       c.v, c.tex, (int)c.tex_c, ch0, c.tri, c.win, c.big, c.grad_out, want_v, s.quad, c.eps, c.chw, slot_of,
-                       slot_bs, s.tail, s.plane);
-    if (c.b * c.nf > 0)
-        hipLaunchKernelGGL((k_grad_pix<R, CT, PERSP>), dim3((unsigned)sr_ceil_div(c.b * c.nf, 256)), dim3(256), 0, st, c.b,
-                           c.nv, c.nf, c.h, c.w, c.repeat_f, c.v, c.tex, (int)c.tex_c, ch0, c.tri, c.win, first, s.valid,
-                           c.grad_out, want_v, s.quad, c.eps, c.chw, slot_of, slot_bs, s.tail, s.plane);
+    if (c.h > c.w) {                                      // samples alias onto pixels: the kernels that count a pixel once
+        hipLaunchKernelGGL((k_grad_big_alias<R, CT, PERSP>), dim3(SR_NUM_CU * 2), dim3(256), 0, st, c.nv, c.nf, c.h, c.w,
+                           c.repeat_f, c.v, c.tex, (int)c.tex_c, ch0, c.tri, c.win, c.big, c.grad_out, want_v, s.quad,
+                           c.eps, c.chw, slot_of, slot_bs, s.tail, s.plane);
+        if (c.b * c.nf > 0)
+            hipLaunchKernelGGL((k_grad_pix_alias<R, CT, PERSP>), dim3((unsigned)sr_ceil_div(c.b * c.nf, 256)), dim3(256), 0,
+                               st, c.b, c.nv, c.nf, c.h, c.w, c.repeat_f, c.v, c.tex, (int)c.tex_c, ch0, c.tri, c.win, first,
+                               s.valid, c.grad_out, want_v, s.quad, c.eps, c.chw, slot_of, slot_bs, s.tail, s.plane);
+    } else {
+        hipLaunchKernelGGL((k_grad_big<R, CT, PERSP>), dim3(SR_NUM_CU * 2), dim3(256), 0, st, c.nv, c.nf, c.h, c.w,
+                           c.repeat_f, c.v, c.tex, (int)c.tex_c, ch0, c.tri, c.win, c.big, c.grad_out, want_v, s.quad,
+                           c.eps, c.chw, slot_of, slot_bs, s.tail, s.plane);
+        if (c.b * c.nf > 0)
+            hipLaunchKernelGGL((k_grad_pix<R, CT, PERSP>), dim3((unsigned)sr_ceil_div(c.b * c.nf, 256)), dim3(256), 0, st,
+                               c.b, c.nv, c.nf, c.h, c.w, c.repeat_f, c.v, c.tex, (int)c.tex_c, ch0, c.tri, c.win, first,
+                               s.valid, c.grad_out, want_v, s.quad, c.eps, c.chw, slot_of, slot_bs, s.tail, s.plane);
+    }
     hipLaunchKernelGGL((k_grad_vert<R, CT, PERSP>), dim3((unsigned)sr_ceil_div(c.nv, 256), (unsigned)c.b), dim3(256), 0, st,
                        c.nv, c.nf, c.adj_off, c.adj, c.off_bs, c.adj_bs, s.quad, s.valid, (int)c.tex_c, ch0, c.grad_v,
                        c.grad_tex, slot_of == nullptr ? 0 : (eager ? 2 : 1), s.tail, s.plane, c.accumulate);
@@ -885,10 +1030,37 @@ void grad_levels_launch(const GradLevels& t, const RasterGrad<float>& c, long lo
     const unsigned n = (unsigned)t.n;
     hipLaunchKernelGGL(k_first_pix_levels, dim3((unsigned)std::min<long long>(sr_ceil_div(max_pix, 256), 1024), n), dim3(256),
                        0, st, t, c.b, c.nf);
-    hipLaunchKernelGGL((k_grad_big_levels<CT, PERSP>), dim3(SR_NUM_CU * 2, n), dim3(256), 0, st, t, c.b, c.nv, c.nf,
-                       c.repeat_f, c.v, c.tex, (int)c.tex_c, c.tri, want_v, c.eps, c.chw, c.adj_slot, c.adj_bs);
-    hipLaunchKernelGGL((k_grad_pix_levels<CT, PERSP>), dim3((unsigned)sr_ceil_div(c.b * c.nf, 256), n), dim3(256), 0, st, t,
-                       c.b, c.nv, c.nf, c.repeat_f, c.v, c.tex, (int)c.tex_c, c.tri, want_v, c.eps, c.chw, c.adj_slot, c.adj_bs);
+    // Phase 1 of a level with h > w is k_grad_big_alias + k_grad_pix_alias, a pair of launches per such level (the choice
+    // stays uniform per launch, the *_levels kernels the code they were); the other levels go, in their order, through
+    // the *_levels pair as a table of their own.  Leaders before and vertex sums after run over all levels of `t`.
+    GradLevels own = t;
+    own.n = 0;
+    for (int l = 0; l < t.n; ++l) {
+        if (t.res_h[l] > t.res_w[l]) continue;
+        const int k = own.n++;
+        own.res_h[k] = t.res_h[l]; own.res_w[k] = t.res_w[l];
+        own.win[k] = t.win[l]; own.big[k] = t.big[l]; own.grad_out[k] = t.grad_out[l];
+        own.tg[k] = t.tg[l]; own.valid[k] = t.valid[l];
+    }
+    if (own.n > 0) {
+        const unsigned m = (unsigned)own.n;
+        hipLaunchKernelGGL((k_grad_big_levels<CT, PERSP>), dim3(SR_NUM_CU * 2, m), dim3(256), 0, st, own, c.b, c.nv, c.nf,
+                           c.repeat_f, c.v, c.tex, (int)c.tex_c, c.tri, want_v, c.eps, c.chw, c.adj_slot, c.adj_bs);
+        hipLaunchKernelGGL((k_grad_pix_levels<CT, PERSP>), dim3((unsigned)sr_ceil_div(c.b * c.nf, 256), m), dim3(256), 0, st,
+                           own, c.b, c.nv, c.nf, c.repeat_f, c.v, c.tex, (int)c.tex_c, c.tri, want_v, c.eps, c.chw, c.adj_slot,
+                           c.adj_bs);
+    }
+    for (int l = 0; l < t.n; ++l) {
+        if (t.res_h[l] <= t.res_w[l]) continue;
+        const long long h = t.res_h[l], w = t.res_w[l];
+        hipLaunchKernelGGL((k_grad_big_alias<float, CT, PERSP>), dim3(SR_NUM_CU * 2), dim3(256), 0, st, c.nv, c.nf, h, w,
+                           c.repeat_f, c.v, c.tex, (int)c.tex_c, 0, c.tri, t.win[l], t.big[l], t.grad_out[l], want_v, t.tg[l],
+                           c.eps, c.chw, c.adj_slot, c.adj_bs, grad_tail(t.tg[l], c.b, c.nf), grad_plane(c.b, c.nf));
+        hipLaunchKernelGGL((k_grad_pix_alias<float, CT, PERSP>), dim3((unsigned)sr_ceil_div(c.b * c.nf, 256)), dim3(256), 0,
+                           st, c.b, c.nv, c.nf, h, w, c.repeat_f, c.v, c.tex, (int)c.tex_c, 0, c.tri, t.win[l],
+                           grad_leaders(t.big[l], c.b, c.nf), t.valid[l], t.grad_out[l], want_v, t.tg[l], c.eps, c.chw,
+                           c.adj_slot, c.adj_bs, grad_tail(t.tg[l], c.b, c.nf), grad_plane(c.b, c.nf));
+    }
     hipLaunchKernelGGL((k_grad_vert_levels<CT, PERSP>), dim3((unsigned)sr_ceil_div(c.nv, 256), (unsigned)c.b), dim3(256), 0,
                        st, t, c.b, c.nv, c.nf, c.adj_off, c.adj, c.off_bs, c.adj_bs, (int)c.tex_c, c.grad_v, c.grad_tex,
                        eager ? 2 : 1);

@@ -11,6 +11,7 @@
 //           device functions (IEEE ops, no contraction => same bits as pass 1 and as x86), write
 //           ids (+ nv*batch), weights, depth and, optionally, interpolated attributes.  Every
 //           pixel is written, so no pre-initialised outputs and no float atomics are needed.
+//           h > w: several samples of the winner may land on the pixel; k_resolve_alias finds the one that won it.
 //   fp64    a 64-bit depth cannot share a word with the id: pass 1a atomicMax(orderable(z)),
 //           pass 1b atomicMin(t) among lanes whose depth equals the maximum, then pass 2.
 //
@@ -135,7 +136,9 @@ __global__ __launch_bounds__(256) void k_depth_keys(long long b, long long nv, l
     depth_keys_body<R, MODE>(b, nv, nf, h, w, repeat_v, repeat_f, perspective, v, f, keys, tmin, big, eps);
 }
 
-template <typename R>
+// ALIAS: an image with h > w, where several samples of the winning triangle may land on the pixel and the one that won
+// it — the one whose depth is in the key — has to be found first (alias_winner, raster_math.h).  Uniform per launch.
+template <typename R, bool ALIAS>
 __device__ __forceinline__ void resolve_body(long long b, long long nv, long long nf, long long h, long long w,
                                              bool repeat_v, bool repeat_f, bool perspective, const R* __restrict__ v,
                                              const long long* __restrict__ f,
@@ -166,7 +169,12 @@ __device__ __forceinline__ void resolve_body(long long b, long long nv, long lon
         load_tri<R>(t, vs, fs, ti, nv, i0, i1, i2);
         tri_setup<R>(t, h, w, perspective, eps);
         const int y = (int)(pix / w), x = (int)(pix - (long long)y * w);
-        shade<R>(t, x, y, perspective, eps, c0, c1, c2, z);
+        if constexpr (ALIAS) {
+            int sx, sy;
+            alias_winner<R>(t, x, y, w, perspective, eps, sx, sy, c0, c1, c2, z);
+        } else {
+            shade<R>(t, x, y, perspective, eps, c0, c1, c2, z);
+        }
         const long long shift = repeat_v ? 0 : nv * s;
         i0 += shift; i1 += shift; i2 += shift;
     }
@@ -204,8 +212,24 @@ __global__ __launch_bounds__(256) void k_resolve(long long b, long long nv, long
                                                  R* __restrict__ zbuf, const R* __restrict__ tex,
                                                  long long tex_c, R* __restrict__ attr,
                                                  int* __restrict__ win, R eps, bool chw) {
-    resolve_body<R>(b, nv, nf, h, w, repeat_v, repeat_f, perspective, v, f, keys, tmin, index, coeff, zbuf, tex, tex_c,
-                    attr, win, eps, chw);
+    resolve_body<R, false>(b, nv, nf, h, w, repeat_v, repeat_f, perspective, v, f, keys, tmin, index, coeff, zbuf, tex,
+                           tex_c, attr, win, eps, chw);
+}
+
+// k_resolve for h > w (a kernel of its own: the launch knows, and k_resolve stays the code it was)
+template <typename R>
+__global__ __launch_bounds__(256) void k_resolve_alias(long long b, long long nv, long long nf, long long h,
+                                                       long long w, bool repeat_v, bool repeat_f,
+                                                       bool perspective, const R* __restrict__ v,
+                                                       const long long* __restrict__ f,
+                                                       const unsigned long long* __restrict__ keys,
+                                                       const unsigned* __restrict__ tmin,
+                                                       long long* __restrict__ index, R* __restrict__ coeff,
+                                                       R* __restrict__ zbuf, const R* __restrict__ tex,
+                                                       long long tex_c, R* __restrict__ attr,
+                                                       int* __restrict__ win, R eps, bool chw) {
+    resolve_body<R, true>(b, nv, nf, h, w, repeat_v, repeat_f, perspective, v, f, keys, tmin, index, coeff, zbuf, tex,
+                          tex_c, attr, win, eps, chw);
 }
 
 __global__ __launch_bounds__(256) void k_fill_levels(const RasterLevels t, long long b, long long nf) {
@@ -241,7 +265,7 @@ __global__ __launch_bounds__(256) void k_resolve_levels(const RasterLevels t, lo
                                                         const float* __restrict__ tex, long long tex_c, float eps,
                                                         bool chw) {
     const int l = blockIdx.y;
-    resolve_body<float>(b, nv, nf, t.res_h[l], t.res_w[l], repeat_v, repeat_f, perspective, v, f, t.keys[l], nullptr, nullptr,
+    resolve_body<float, false>(b, nv, nf, t.res_h[l], t.res_w[l], repeat_v, repeat_f, perspective, v, f, t.keys[l], nullptr, nullptr,
                         nullptr, nullptr, tex, tex_c, t.attr[l], t.win[l], eps, chw);
 }
 
@@ -270,9 +294,14 @@ int raster_keys_launch(const RasterForward<R>& c, void* work, hipStream_t st) {
                                c.repeat_f, c.perspective, c.v, c.tri, s.keys, s.tmin, c.big, c.eps);
         }
     }
-    hipLaunchKernelGGL((k_resolve<R>), dim3((unsigned)sr_ceil_div(npix, 256)), dim3(256), 0, st, c.b, c.nv, c.nf, c.h, c.w,
-                       c.repeat_v, c.repeat_f, c.perspective, c.v, c.tri, s.keys, s.tmin, c.index, c.coeff, c.zbuf, c.tex,
-                       c.tex_c, c.attr, c.win, c.eps, c.chw);
+    if (c.h > c.w)
+        hipLaunchKernelGGL((k_resolve_alias<R>), dim3((unsigned)sr_ceil_div(npix, 256)), dim3(256), 0, st, c.b, c.nv, c.nf,
+                           c.h, c.w, c.repeat_v, c.repeat_f, c.perspective, c.v, c.tri, s.keys, s.tmin, c.index, c.coeff,
+                           c.zbuf, c.tex, c.tex_c, c.attr, c.win, c.eps, c.chw);
+    else
+        hipLaunchKernelGGL((k_resolve<R>), dim3((unsigned)sr_ceil_div(npix, 256)), dim3(256), 0, st, c.b, c.nv, c.nf, c.h,
+                           c.w, c.repeat_v, c.repeat_f, c.perspective, c.v, c.tri, s.keys, s.tmin, c.index, c.coeff, c.zbuf,
+                           c.tex, c.tex_c, c.attr, c.win, c.eps, c.chw);
     return sr_launch_status();
 }
 template int raster_keys_launch<float>(const RasterForward<float>&, void*, hipStream_t);
@@ -285,7 +314,20 @@ int raster_keys_levels_launch(const RasterLevels& t, const RasterForward<float>&
     if (c.b * c.nf > 0)
         hipLaunchKernelGGL(k_depth_keys_levels, dim3((unsigned)sr_ceil_div(c.b * c.nf, 256), n), dim3(256), 0, st, t, c.b,
                            c.nv, c.nf, c.repeat_v, c.repeat_f, c.perspective, c.v, c.tri, c.eps);
-    hipLaunchKernelGGL(k_resolve_levels, dim3((unsigned)sr_ceil_div(max_pix, 256), n), dim3(256), 0, st, t, c.b, c.nv, c.nf,
+    // A level with h > w is resolved by k_resolve_alias, in a launch of its own (the choice stays uniform per launch and
+    // k_resolve_levels the code it was): in the table k_resolve_levels gets, such a level has no rows, so its lanes
+    // leave at the bounds test.  Fill and depth keys are the same for every shape.
+    RasterLevels own = t;
+    for (int l = 0; l < t.n; ++l)
+        if (t.res_h[l] > t.res_w[l]) own.res_h[l] = 0;
+    hipLaunchKernelGGL(k_resolve_levels, dim3((unsigned)sr_ceil_div(max_pix, 256), n), dim3(256), 0, st, own, c.b, c.nv, c.nf,
                        c.repeat_v, c.repeat_f, c.perspective, c.v, c.tri, c.tex, c.tex_c, c.eps, c.chw);
+    for (int l = 0; l < t.n; ++l) {
+        if (t.res_h[l] <= t.res_w[l]) continue;
+        const long long h = t.res_h[l], w = t.res_w[l];
+        hipLaunchKernelGGL((k_resolve_alias<float>), dim3((unsigned)sr_ceil_div(c.b * h * w, 256)), dim3(256), 0, st, c.b,
+                           c.nv, c.nf, h, w, c.repeat_v, c.repeat_f, c.perspective, c.v, c.tri, t.keys[l], nullptr, nullptr,
+                           nullptr, nullptr, c.tex, c.tex_c, t.attr[l], t.win[l], c.eps, c.chw);
+    }
     return sr_launch_status();
 }

@@ -869,6 +869,39 @@ add("raster-flat-f32-tiled-raster_ellipsoid_64", raster_flat_case("raster_ellips
 add("raster-flat-f64-raster_ellipsoid_32", raster_flat_case("raster_ellipsoid_32", torch.float64))
 
 
+def raster_nonsquare_case(h, w, persp, dtype):
+    """raster_nonsquare_cases.ab_mesh over the whole x = -1 .. 1 span of an h x w image: with h > w samples alias into
+    later rows (k_resolve_alias, k_grad_pix_alias, k_grad_big_alias), with w > h rows are dropped."""
+    def build():
+        import importlib
+
+        import stylerenderer_amd.op as op
+        from raster_nonsquare_cases import ab_mesh
+
+        R = importlib.import_module("stylerenderer_amd.op.rasterize")
+        vh, trih = ab_mesh(h, w, persp, on_image=False)
+        r = Rand(_seed(h, w, persp))
+        v = torch.from_numpy(vh).to(DEV, dtype).requires_grad_()
+        tex = r(2, vh.shape[1], 6).to(dtype).requires_grad_()
+        tri = torch.from_numpy(trih).to(DEV)
+        go = r(2, h, w, 6).to(dtype)
+
+        def run(v, tex, tri, go):
+            out = op.rasterize(v, tex, tri, h, w, persp)
+            gv, gt = torch.autograd.grad(out, [v, tex], go)
+            chw = op.rasterize(v.detach(), tex.detach(), tri, h, w, persp, channel_major=True)
+            idx, coeff, zbuf = R.forward_with_depth(v.detach(), tri, h, w, persp, 1e-6)
+            return out, gv, gt, chw, idx, coeff, zbuf, R.backward(v.detach(), idx, persp, 1e-6)
+        return run, [v, tex, tri, go], ()
+    return build
+
+
+for _h, _w in ((20, 12), (12, 20)):
+    add("raster-nonsquare-f32-orthographic-%dx%d" % (_h, _w), raster_nonsquare_case(_h, _w, False, torch.float32))
+    add("raster-nonsquare-f32-perspective-%dx%d" % (_h, _w), raster_nonsquare_case(_h, _w, True, torch.float32))
+    add("raster-nonsquare-f64-orthographic-%dx%d" % (_h, _w), raster_nonsquare_case(_h, _w, False, torch.float64))
+
+
 @case("raster-levels-f32-raster_ellipsoid_64")
 def _raster_levels():
     from stylerenderer_amd.op.rasterize import rasterize_pyramid

@@ -345,40 +345,14 @@ def test_rasterize_large_triangles_forward_and_gradients(c, raster_path):
     assert np.abs(got[0][1].cpu().numpy() - wt).max() <= 5e-6 * np.abs(wt).max()
 
 
-def _ab_mesh(h, w, persp):
-    """(v [2, nv, 3], tri [nf, 3]): a closed fan of 32 triangles around one vertex (valence 32 > 24: the wave-summed
-    branch of the vertex gather), a 6 x 6 grid of cells of two small triangles each, and one screen-filling triangle
-    (bounding box > 64 pixels: k_grad_big) whose depth crosses the other two parts.  Every z is negative (perspective
-    accepts it); the second sample is the first one shrunk, shifted and tilted in depth.
+def _ab_mesh(h, w, persp, on_image=True):
+    """raster_nonsquare_cases.ab_mesh: a 32-triangle fan, a 6 x 6 grid of small triangles and one screen-filling
+    triangle, two samples.  on_image=True (what this module always used) maps the mesh, on an image with h > w, onto the
+    w columns the image has; on_image=False leaves it on x = -1 .. 1, i.e. on h columns, and what lies right of column w
+    aliases into the next row — test_rasterize_nonsquare_gpu.py is about that."""
+    from raster_nonsquare_cases import ab_mesh
 
-    The screen of an h x w image with h > w: the rasterizer keeps the reference's call convention, which scales x by h
-    and y by w, so x = -1 .. 1 spans h columns of which the image has w; what lies right of column w is not
-    on the image (the reference lets it run into the next row; op/texture.py draws non-square pictures inside the
-    leading block for that reason).  The mesh is laid out on x = -1 .. 1 and then mapped onto the w columns there are,
-    x -> (x + 1) w / h - 1, so that "screen-filling" means the image and not the columns beyond it.  For the perspective
-    projection x and y are then multiplied by -z: the division brings the same layout to the screen."""
-    ang = 2.0 * np.pi * np.arange(32) / 32
-    fan = [(-0.45, 0.40, -0.70)] + [(-0.45 + 0.25 * np.cos(a), 0.40 + 0.25 * np.sin(a), -0.72 + 0.05 * np.sin(3 * a))
-                                    for a in ang]
-    tri = [(0, 1 + k, 1 + (k + 1) % 32) for k in range(32)]
-    g0 = len(fan)
-    grid = [(0.10 + 0.1 * i, -0.70 + 0.1 * j, -0.70 + 0.02 * ((3 * i + 5 * j) % 7)) for j in range(7) for i in range(7)]
-    for j in range(6):
-        for i in range(6):
-            a = g0 + 7 * j + i
-            tri += [(a, a + 1, a + 8), (a, a + 8, a + 7)]
-    b0 = g0 + len(grid)
-    big = [(-0.95, -0.90, -0.90), (0.95, -0.90, -0.55), (0.0, 0.95, -0.75)]
-    tri.append((b0, b0 + 1, b0 + 2))
-    v0 = np.array(fan + grid + big, np.float32)
-    v1 = v0 * np.array([0.9, 0.85, 1.0], np.float32) + np.array([0.06, -0.04, 0.0], np.float32)
-    v1[:, 2] += 0.1 * v0[:, 0]
-    v = np.stack([v0, v1])
-    if h > w:
-        v[..., 0] = (v[..., 0] + 1) * np.float32(w / h) - 1
-    if persp:
-        v[..., :2] *= -v[..., 2:]
-    return v, np.array(tri, np.int64)
+    return ab_mesh(h, w, persp, on_image)
 
 
 RASTER_AB_SWITCHES = [("SR_RASTER_BIN_LDS", "0"), ("SR_RASTER_GRAD_SLOTS", "0"), ("SR_RASTER_GRAD_EAGER", "0"),
@@ -387,8 +361,9 @@ RASTER_AB_SWITCHES = [("SR_RASTER_BIN_LDS", "0"), ("SR_RASTER_GRAD_SLOTS", "0"),
 
 @pytest.mark.parametrize("c", [3, 6])
 @pytest.mark.parametrize("persp", [False, True], ids=["ortho", "persp"])
-@pytest.mark.parametrize("h,w,tiled", [(64, 64, True), (40, 24, False)], ids=["tiled64", "keys40x24"])
-def test_rasterize_ab_switches_change_no_bit(h, w, tiled, persp, c, monkeypatch):
+@pytest.mark.parametrize("h,w,tiled,on_image", [(64, 64, True, True), (40, 24, False, True), (40, 24, False, False)],
+                         ids=["tiled64", "keys40x24", "keys40x24-aliased"])
+def test_rasterize_ab_switches_change_no_bit(h, w, tiled, on_image, persp, c, monkeypatch):
     """The A/B switches of the rasterizer's host code select between kernels that must compute the same thing:
     SR_RASTER_BIN_LDS=0 (k_tile_bin, the wave-vote binning, instead of k_tile_bin_lds), SR_RASTER_GRAD_SLOTS=0 (one
     record per triangle instead of vertex-major corner slots) and SR_RASTER_GRAD_EAGER=0 / 1 (the two slot modes of
@@ -398,13 +373,14 @@ def test_rasterize_ab_switches_change_no_bit(h, w, tiled, persp, c, monkeypatch)
     tiled path forced has 4 tiles; 40 x 24 is non-square, so the global-key path — the binning switch has no effect
     there and is not run.  Six channels = two channel chunks, the first with tail planes.
 
-    (Geometry right of column w on such an image is a known defect of the global-key kernels; _ab_mesh
-    keeps the mesh on the image.)"""
+    keys40x24 keeps the mesh on the image's 24 columns; keys40x24-aliased leaves it on x = -1 .. 1, where a third of the
+    covered pixels are won by a sample that aliased in from the row above (k_resolve_alias, k_grad_pix_alias and
+    k_grad_big_alias; tests/test_rasterize_nonsquare_gpu.py has the per-element gradient measure)."""
     import stylerenderer_amd.op as op
     from stylerenderer_amd import synth
     R = importlib.import_module("stylerenderer_amd.op.rasterize")
 
-    vh, tri = _ab_mesh(h, w, persp)
+    vh, tri = _ab_mesh(h, w, persp, on_image)
     tex = synth.det_normal((2, vh.shape[1], c), 91)
     go = synth.det_normal((2, h, w, c), 92)
     names = sorted({name for name, _ in RASTER_AB_SWITCHES})
