@@ -159,6 +159,9 @@ SIGNATURES = {
     "sr_texture_bake": (_i, [_p] * 9 + [_l] * 10 + [_f, _f, _f, _p]),
     "sr_texture_pad": (_i, [_p] * 4 + [_l] * 4 + [_p]),
     "sr_texture_merge": (_i, [_p] * 5 + [_l] * 4 + [_i, _p]),
+    "sr_texture_sample_fwd": (_i, [_p] * 4 + [_l] * 7 + [_f, _p]),
+    "sr_texture_sample_bwd_uv": (_i, [_p] * 5 + [_l] * 7 + [_p]),
+    "sr_texture_sample_bwd_tex": (_i, [_p] * 6 + [_l] * 7 + [_p]),
     "sr_share_rows": (_i, [_p] + [_l] * 3 + [_p]),
     "sr_camera_fwd": (_i, [_p] * 5 + [_l, _l, _p]),
     "sr_camera_bwd": (_i, [_p] * 6 + [_l, _l, _p]),

@@ -41,6 +41,7 @@ SOURCES = [
     ("landmark.hip", EXACT),
     ("region.hip", EXACT),
     ("texture.hip", EXACT),
+    ("texture_sample.hip", EXACT),
     ("share.hip", EXACT),
     ("camera.hip", EXACT),
     ("morph.hip", []),

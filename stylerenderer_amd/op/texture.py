@@ -1,4 +1,5 @@
-"""UV texture baking of face reconstruction: the picture's colours carried onto the fitted surface (csrc/texture.hip).
+"""UV texture baking of face reconstruction: the picture's colours carried onto the fitted surface (csrc/texture.hip), and
+the way back: the textured surface drawn into a picture (csrc/texture_sample.hip).
 
 A layout gives the mesh texture coordinates: uv [nt, 2] in [0, 1] with v pointing up and tri_uv [nf, 3], row-parallel to
 the mesh's tri (face_model.uv_layout computes one, face_model.load_uv reads one).  Texel (ty, tx) of a (Th, Tw) texture
@@ -36,8 +37,29 @@ has its centre at u = (tx + 1/2) / Tw, v = 1 - (ty + 1/2) / Th: row 0 is the top
               and a seam between two views narrows; with weights (1, 2^-4) sharpness 4 gives the first view exactly.
               Weights are expected finite and not negative (a negative one counts as 0).
 
-CPU tensors and float64 take the torch composites `bake_composite`, `pad_host` and `merge_composite`, which are the
-definition.  Float32 device tensors take sr_texture_bake / sr_texture_pad / sr_texture_merge through the C ABI: one launch
+  uv_map      (uvmap [B, H, W, 2], cover bool [B, H, W]): the layout's coordinates of the surface point under every pixel
+              of the posed mesh, drawn by the `rasterize` Function over the mesh with its corners exploded (a seam gives a
+              vertex two uvs; a face keeps its own), so the gradient to the mesh is the rasterizer's.
+  sample      out [B, C, H, W]: the bilinear look-up of a texture T [Bt, C, Th, Tw], Bt = B or 1 (one texture under all
+              views), at a uv map.  For a pixel with cover true and finite (u, v), every step one operation of the float
+              type, no fused multiply-add:
+                  sx = u Tw - 1/2;  sy = (1 - v) Th - 1/2
+                  inx = -1 <= sx <= Tw, sxc = clamp(sx, -1, Tw);  likewise iny, syc
+                  x0 = floor(sxc), fx = sxc - x0;  xa = clamp(x0, 0, Tw - 1), xb = clamp(x0 + 1, 0, Tw - 1);  likewise y
+                  top = (1 - fx) T[ya, xa] + fx T[ya, xb];  bot = (1 - fx) T[yb, xa] + fx T[yb, xb]
+                  out_c = top (1 - fy) + bot fy
+              Any other pixel gets `background` and contributes to no gradient.  Backward, g the incoming gradient:
+                  gx = sum over c from 0 in channel order of g_c ((T[ya, xb] - T[ya, xa]) (1 - fy) + (T[yb, xb] - T[yb, xa]) fy)
+                  gy = likewise of g_c (bot - top);  grad_u = inx ? gx Tw : 0;  grad_v = iny ? -(gy Th) : 0
+                  grad_T[bt, c, ty, tx] = the sum from 0, in ascending (b, y, x, k) order, over the taps on that texel, of
+                         w_k g_c;  k = 0..3: (ya, xa), (ya, xb), (yb, xa), (yb, xb);  w = (1 - fx)(1 - fy), fx (1 - fy),
+                         (1 - fx) fy, fx fy, one product each.  Two taps of a pixel that clamp onto one texel are added
+                         separately; a texel no tap reaches gets exactly 0; with Bt = 1 the sum runs over all B views.
+              The texture's gradient is a gather over a tap list (`tap_plan`), not a scatter: no atomics, one order.
+  render      `uv_map` followed by `sample`.
+
+CPU tensors and float64 take the torch composites `bake_composite`, `pad_host`, `merge_composite` and `sample_composite`,
+which are the definition.  Float32 device tensors take sr_texture_bake / sr_texture_pad / sr_texture_merge through the C ABI: one launch
 per bake, per padding pass and per merge, nothing allocated by the launch and nothing read back, so the calls can be
 captured.  The kernels are compiled without contraction and with correctly rounded division and square root: weight, tex,
 the padding and the merge are the host float32 definition's bit for bit.  Under SR_STRICT_NATIVE=1 nothing falls to a
@@ -438,3 +460,263 @@ def coverage(face, weight):
     live = (face >= 0).view(1, 1, *face.shape)
     n = live.sum().clamp_min(1).double()
     return ((weight > 0) & live).sum((1, 2, 3)).double() / n
+
+
+# ---- the uv map of a posed mesh ----------------------------------------------------------------------------------------
+def uv_map(v, tri, uv, tri_uv, size, keep=None):
+    """(uvmap [B, H, W, 2], cover bool [B, H, W]) of the posed mesh v [B, nv, 3], tri [nf, 3] with the layout uv [nt, 2],
+    tri_uv [nf, 3] in the pixels `project(., (H, W))` means: the texture coordinates of the surface point under every
+    pixel and whether there is one.  A layout has seams, so a vertex has no single uv: the mesh is drawn with its corners
+    exploded to 3 nf vertices (v[:, tri.reshape(-1)] with the attributes uv[tri_uv.reshape(-1)], topology
+    arange(3 nf).view(nf, 3)) through the `rasterize` Function, so every face interpolates its own chart's coordinates
+    and the gradient to v comes from the rasterizer's.  cover is the rasterizer's "some coefficient is non-zero", read
+    from a third attribute that is 1 on every corner.  With keep (bool [nf], the faces face_model.uv_layout maps) the
+    other faces still occlude, but their pixels are not covered (their three attributes are 0).  A non-square size is
+    drawn in a square of side max(H, W) and cropped, as `depth_buffer` does.  Host and device results are equal bit for
+    bit (the rasterizer's parity)."""
+    from .rasterize import rasterize
+
+    h, w = _hw(size)
+    if h < 1 or w < 1:
+        raise ValueError("uv_map: size must be positive, got (%d, %d)" % (h, w))
+    if v.dim() != 3 or v.shape[2] != 3 or tri.dim() != 2 or tri.shape[1] != 3 or tri.dtype != torch.int64:
+        raise ValueError("uv_map: v [B, nv, 3] and tri int64 [nf, 3], got %s and %s" % (tuple(v.shape), tuple(tri.shape)))
+    if uv.dim() != 2 or uv.shape[1] != 2 or tuple(tri_uv.shape) != tuple(tri.shape):
+        raise ValueError("uv_map: uv [nt, 2] and tri_uv [nf, 3] row-parallel to tri, got %s and %s"
+                         % (tuple(uv.shape), tuple(tri_uv.shape)))
+    dev, dt = v.device, v.dtype
+    b, nf = int(v.shape[0]), int(tri.shape[0])
+    if keep is not None and int(keep.numel()) != nf:
+        raise ValueError("uv_map: keep must have one entry per face (%d), got %d" % (nf, int(keep.numel())))
+    if h != w:
+        x, y = _square_vertices(v[..., 0], v[..., 1], (h, w))
+        v = torch.stack((x, y, v[..., 2]), -1)
+    corners = v[:, tri.to(dev).reshape(-1)].contiguous()                       # [B, 3 nf, 3]
+    attr = torch.cat((uv.detach().to(device=dev, dtype=dt)[tri_uv.to(dev).reshape(-1)],
+                      torch.ones(3 * nf, 1, dtype=dt, device=dev)), 1)
+    if keep is not None:
+        attr = attr * keep.to(dev).reshape(-1, 1).expand(-1, 3).reshape(-1, 1).to(dt)
+    attr = attr.unsqueeze(0).expand(b, -1, -1).contiguous()
+    topo = torch.arange(3 * nf, dtype=torch.int64, device=dev).view(nf, 3)
+    s = max(h, w)
+    out = rasterize(corners, attr, topo, s, s, False, 1e-9)[:, :h, :w]
+    return out[..., :2].contiguous(), (out[..., 2].detach() != 0).contiguous()
+
+
+# ---- the sampler -------------------------------------------------------------------------------------------------------
+_PLAN_CACHE = DerivedCache(8)
+
+
+def _check_sample(tex, uvmap, cover):
+    if tex.dim() != 4 or not tex.is_floating_point() or min(tex.shape[1:]) < 1:
+        raise ValueError("sample: tex must be a floating-point [Bt, C, Th, Tw], got %s %s" % (tex.dtype, tuple(tex.shape)))
+    if uvmap.dim() != 4 or uvmap.shape[3] != 2 or uvmap.dtype != tex.dtype or uvmap.device != tex.device:
+        raise ValueError("sample: uvmap must be [B, H, W, 2] of tex's float type and device, got %s %s"
+                         % (uvmap.dtype, tuple(uvmap.shape)))
+    if cover.dtype != torch.bool or tuple(cover.shape) != tuple(uvmap.shape[:3]) or cover.device != tex.device:
+        raise ValueError("sample: cover must be bool [B, H, W] on tex's device, got %s %s" % (cover.dtype, tuple(cover.shape)))
+    if tex.shape[0] != uvmap.shape[0] and tex.shape[0] != 1:
+        raise ValueError("sample: %d views need B textures or one, got %d" % (uvmap.shape[0], tex.shape[0]))
+
+
+def _footprint(uvmap, cover, th, tw):
+    """The definition's per-pixel quantities, each [B, H W]: (live, inx, iny, fx, fy, xa, xb, ya, yb)."""
+    b = uvmap.shape[0]
+    u, v = uvmap[..., 0].reshape(b, -1), uvmap[..., 1].reshape(b, -1)
+    live = cover.reshape(b, -1) & torch.isfinite(u) & torch.isfinite(v)
+    zero = torch.zeros_like(u)
+    u, v = torch.where(live, u, zero), torch.where(live, v, zero)
+    sx, sy = u * tw - 0.5, (1.0 - v) * th - 0.5
+    inx, iny = (sx >= -1) & (sx <= tw), (sy >= -1) & (sy <= th)
+    sxc, syc = sx.clamp(-1.0, float(tw)), sy.clamp(-1.0, float(th))
+    x0f, y0f = torch.floor(sxc.detach()), torch.floor(syc.detach())
+    fx, fy = sxc - x0f, syc - y0f
+    x0, y0 = x0f.long(), y0f.long()
+    return (live, inx, iny, fx, fy, x0.clamp(0, tw - 1), (x0 + 1).clamp(0, tw - 1), y0.clamp(0, th - 1),
+            (y0 + 1).clamp(0, th - 1))
+
+
+def _taps(tex, foot, b):
+    """(t00, t01, t10, t11), each [B, C, H W]: the four texels of every pixel."""
+    bt, c_n, th, tw = tex.shape
+    flat = tex.reshape(bt, c_n, th * tw)
+    if bt != b:
+        flat = flat.expand(b, -1, -1)
+    xa, xb, ya, yb = foot[5:]
+
+    def tap(yy, xx):
+        return torch.gather(flat, 2, (yy * tw + xx).unsqueeze(1).expand(-1, c_n, -1))
+
+    return tap(ya, xa), tap(ya, xb), tap(yb, xa), tap(yb, xb)
+
+
+def _sample_forward(tex, uvmap, cover, background):
+    b, h, w = (int(x) for x in uvmap.shape[:3])
+    foot = _footprint(uvmap, cover, int(tex.shape[2]), int(tex.shape[3]))
+    live, fx, fy = foot[0].unsqueeze(1), foot[3].unsqueeze(1), foot[4].unsqueeze(1)
+    t00, t01, t10, t11 = _taps(tex, foot, b)
+    top = (1.0 - fx) * t00 + fx * t01
+    bot = (1.0 - fx) * t10 + fx * t11
+    colour = top * (1.0 - fy) + bot * fy
+    out = torch.where(live, colour, torch.full_like(colour, float(background)))
+    return out.view(b, int(tex.shape[1]), h, w)
+
+
+def tap_plan(uvmap, cover, size, bt):
+    """(off int32 [Bt Th Tw + 2], entries int32 [4 B H W]): the tap list of the uv map on a (Th, Tw) texture, a CSR over
+    the texel keys bt Th Tw + ty Tw + tx (bt = b with Bt = B textures, 0 with one shared texture).  The entries of a key
+    are the taps ((b H + y) W + x) 4 + k that fall on it, ascending; k = 0..3 names (ya, xa), (ya, xb), (yb, xa),
+    (yb, xb).  The bucket after the last key holds the entries of the uncovered pixels, so the sizes do not depend on the
+    data and nothing is read back.  Built with tensor ops on uvmap's device (a stable sort, bincount, cumsum: as
+    op.rasterize.incidence builds its list) and cached per uv map (its address and version, cover's, the texture's size
+    and Bt): with a fixed pose (texture refinement, a turntable frame) it is built once, while a uv map that changes from
+    call to call rebuilds it in every call."""
+    th, tw = _hw(size)
+    b, h, w = (int(x) for x in uvmap.shape[:3])
+    bt = int(bt)
+    if bt not in (1, b):
+        raise ValueError("tap_plan: Bt is B (%d) or 1, got %d" % (b, bt))
+    if 4 * b * h * w >= 2 ** 31 or bt * th * tw >= 2 ** 31 - 1:
+        raise ValueError("tap_plan: 4 B H W and Bt Th Tw must be below 2^31")
+    key = (uvmap.data_ptr(), uvmap._version, tuple(uvmap.shape), uvmap.dtype, str(uvmap.device), cover.data_ptr(),
+           cover._version, th, tw, bt)
+    hit = _PLAN_CACHE.get(key)
+    if hit is not None:
+        return hit[0], hit[1]
+    with torch.no_grad():
+        foot = _footprint(uvmap.detach(), cover, th, tw)
+        live, (xa, xb, ya, yb) = foot[0], foot[5:]
+        n_keys = bt * th * tw
+        base = torch.arange(b, device=uvmap.device).view(b, 1) * (th * tw) if bt == b else torch.zeros_like(xa)
+        keys = torch.stack((ya * tw + xa, ya * tw + xb, yb * tw + xa, yb * tw + xb), -1) + base.unsqueeze(-1)
+        keys = torch.where(live.unsqueeze(-1), keys, torch.full_like(keys, n_keys)).reshape(-1)
+        entries = torch.sort(keys, stable=True)[1].to(torch.int32).contiguous()
+        off = torch.zeros(n_keys + 2, dtype=torch.int32, device=uvmap.device)
+        off[1:] = torch.cumsum(torch.bincount(keys, minlength=n_keys + 1), 0).to(torch.int32)
+    _PLAN_CACHE.put(key, (off, entries, uvmap, cover))                       # (holds both: the key is their addresses)
+    return off, entries
+
+
+def _ordered_sum(terms, off, entries, n_keys):
+    """[C, n_keys]: per key the sum from 0, in list order, of terms [C, 4 B H W] at the key's entries.  Pass r adds every
+    list's r-th entry, one addition per texel, so the order inside a list is the list's."""
+    acc = terms.new_zeros((terms.shape[0], n_keys))
+    start = off[:n_keys].long()
+    counts = off[1:n_keys + 1].long() - start
+    longest = int(counts.max()) if n_keys else 0
+    if longest == 0:
+        return acc
+    by = torch.sort(counts, descending=True, stable=True)[1]
+    more = (n_keys - torch.cumsum(torch.bincount(counts, minlength=longest + 1), 0)).tolist()      # lists longer than r
+    for r in range(longest):
+        ks = by[:more[r]]
+        acc.index_add_(1, ks, terms[:, entries[start[ks] + r].long()])
+    return acc
+
+
+def _sample_backward(tex, uvmap, cover, g, need_uv=True, need_tex=True):
+    """(grad_uv [B, H, W, 2], grad_tex [Bt, C, Th, Tw]) of the gradient g [B, C, H, W] of `sample`'s output: the
+    definition, the ordered sum of grad_tex included.  Torch operations throughout, so a recorded backward
+    (create_graph=True) differentiates again."""
+    bt, c_n, th, tw = (int(x) for x in tex.shape)
+    b, h, w = (int(x) for x in uvmap.shape[:3])
+    foot = _footprint(uvmap, cover, th, tw)
+    live, inx, iny, fx, fy = foot[:5]
+    gf = g.reshape(b, c_n, h * w)
+    guv = gtex = None
+    if need_uv:
+        t00, t01, t10, t11 = _taps(tex, foot, b)
+        fxe, fye = fx.unsqueeze(1), fy.unsqueeze(1)
+        top = (1.0 - fxe) * t00 + fxe * t01
+        bot = (1.0 - fxe) * t10 + fxe * t11
+        dx = (t01 - t00) * (1.0 - fye) + (t11 - t10) * fye
+        dy = bot - top
+        gx, gy = torch.zeros_like(fx), torch.zeros_like(fy)
+        for c in range(c_n):
+            gx = gx + gf[:, c] * dx[:, c]
+            gy = gy + gf[:, c] * dy[:, c]
+        zero = torch.zeros_like(gx)
+        guv = torch.stack((torch.where(live & inx, gx * tw, zero), torch.where(live & iny, -(gy * th), zero)), -1)
+        guv = guv.view(b, h, w, 2)
+    if need_tex:
+        off, entries = tap_plan(uvmap, cover, (th, tw), bt)
+        wgt = torch.stack(((1.0 - fx) * (1.0 - fy), fx * (1.0 - fy), (1.0 - fx) * fy, fx * fy), -1)      # [B, H W, 4]
+        safe = torch.where(live.unsqueeze(1), gf, torch.zeros_like(gf))        # (what stands under no tap cannot leak)
+        terms = wgt.unsqueeze(1) * safe.unsqueeze(-1)                          # [B, C, H W, 4]
+        terms = terms.permute(1, 0, 2, 3).reshape(c_n, -1)
+        acc = _ordered_sum(terms, off, entries, bt * th * tw)
+        gtex = acc.view(c_n, bt, th, tw).permute(1, 0, 2, 3).contiguous()
+    return guv, gtex
+
+
+class _Sample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tex, uvmap, cover, background, kernels):
+        ctx.kernels, ctx.background = kernels, background
+        tc, uc, cc = tex.contiguous(), uvmap.contiguous(), cover.contiguous()
+        ctx.save_for_backward(tc, uc, cc)
+        if not kernels:
+            return _sample_forward(tc, uc, cc, background)
+        bt, c_n, th, tw = (int(x) for x in tc.shape)
+        b, h, w = (int(x) for x in uc.shape[:3])
+        out = torch.empty((b, c_n, h, w), dtype=tc.dtype, device=tc.device)
+        native(tc).sr_texture_sample_fwd(out, tc, uc, cc, b, bt, c_n, h, w, th, tw, background)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        tc, uc, cc = ctx.saved_tensors
+        need_tex, need_uv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_tex or need_uv):
+            return None, None, None, None, None
+        if torch.is_grad_enabled() or not ctx.kernels:
+            # the definition in torch operations; under create_graph=True it is recorded and differentiates again
+            guv, gtex = _sample_backward(tc, uc, cc, g, need_uv, need_tex)
+            return gtex, guv, None, None, None
+        g = g.contiguous()
+        bt, c_n, th, tw = (int(x) for x in tc.shape)
+        b, h, w = (int(x) for x in uc.shape[:3])
+        guv = gtex = None
+        if need_uv:
+            guv = torch.empty_like(uc)
+            native(tc).sr_texture_sample_bwd_uv(guv, g, tc, uc, cc, b, bt, c_n, h, w, th, tw)
+        if need_tex:
+            off, entries = tap_plan(uc, cc, (th, tw), bt)
+            gtex = torch.empty_like(tc)
+            native(tc).sr_texture_sample_bwd_tex(gtex, g, uc, cc, off, entries, b, bt, c_n, h, w, th, tw)
+        return gtex, guv, None, None, None
+
+
+def _background(background, dtype):
+    return float(np.float32(background)) if dtype == torch.float32 else float(background)
+
+
+def sample_composite(tex, uvmap, cover, background=0.0):
+    """The defining tensor algebra of `sample`, in tex's float type, as an autograd node whose backward is the stated
+    formulas (`_sample_backward`: the ordered sum of the texture's gradient included)."""
+    _check_sample(tex, uvmap, cover)
+    return _Sample.apply(tex.contiguous(), uvmap.contiguous(), cover, _background(background, tex.dtype), False)
+
+
+def sample(tex, uvmap, cover, background=0.0):
+    """out [B, C, H, W]: the texture tex [Bt, C, Th, Tw] (Bt = B, or 1: one texture shared by all views) looked up
+    bilinearly at the uv map [B, H, W, 2] of `uv_map`; a pixel with cover false or a non-finite coordinate gets
+    `background` and contributes to no gradient.  Differentiable in tex and uvmap (the module's note has both gradients).
+    Device float32 runs sr_texture_sample_fwd / _bwd_uv / _bwd_tex, one launch each, nothing allocated by a launch and
+    nothing read back; everything else `sample_composite`.  The texture's gradient walks the tap list of `tap_plan`, which
+    is cached per uv map: with a fixed uv map (refinement, a turntable frame) it is built once and forward and backward can
+    be captured after one call of `tap_plan`; a uv map that changes from call to call rebuilds the list in every
+    backward.  The results are the host float32 composite's bit for bit, and reruns are bit-identical (no atomics)."""
+    _check_sample(tex, uvmap, cover)
+    kernels = native_ok(tex, uvmap) and is_device_tensor(cover)
+    if not kernels and is_device_tensor(tex) and strict_native():
+        raise RuntimeError("sample: SR_STRICT_NATIVE=1 and the kernels take float32 device tensors only")
+    return _Sample.apply(tex.contiguous(), uvmap.contiguous(), cover, _background(background, tex.dtype), kernels)
+
+
+def render(v, tri, uv, tri_uv, tex, size, background=0.0, keep=None):
+    """(image [B, C, H, W], cover bool [B, H, W]): the posed mesh v [B, nv, 3], tri [nf, 3] with the layout uv, tri_uv
+    drawn with the texture tex [B or 1, C, Th, Tw] over `background`: `uv_map` followed by `sample`.  Differentiable in tex
+    and, through the uv map and the rasterizer, in v."""
+    uvmap, cover = uv_map(v, tri, uv, tri_uv, size, keep)
+    return sample(tex, uvmap, cover, background), cover

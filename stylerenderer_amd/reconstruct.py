@@ -8,7 +8,8 @@ for it):
          [--lmk_dynamic | --lmk_lines FILE] [--lmk_axis I,J] [--lmk_vis LO,HI]]
         [--mask_lmk [--mask_tri FILE] [--mask_margin R]] [--mask_dir DIR] [--mask_mesh]
         [--texture [T] [--uv FILE] [--texture_from picture|render] [--texture_facing LO,HI] [--texture_pad N]
-         [--texture_fill mean|none]]
+         [--texture_fill mean|none] [--texture_check] [--turntable N [--turntable_yaw DEG]]
+         [--texture_refine STEPS [--texture_lr LR]]]
         [--camera_distance D | --camera_fov DEG] [--fit_camera] [--camera_lr 0.01] CHECKPOINT IMAGE [IMAGE ...]
 
 For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with inversion.LatentInverter(fit_shape=True)
@@ -74,6 +75,24 @@ checkpoint, like --lmk_weight) and is not hidden (the posed mesh's z-buffer, squ
 them; --texture_fill mean (the default) paints what is left with the mean colour, none leaves it black.  Without --texture
 nothing changes.
 
+The textured head can be drawn (op.texture.uv_map / sample: the layout's coordinates rasterised over the fitted mesh, then a
+bilinear look-up of the texture that is differentiable in the texture; three options, all of which need --texture and
+without which nothing changes).  --texture_check draws the written texture (after padding and fill) on the fitted mesh at
+the fitted pose and camera at the fit's resolution: <stem>_rerender.png, and <stem>.npz `rerender_error`, the mean absolute
+difference to the fit's target over the pixels that are covered and where the look-up of the bake's weight is positive
+(`rerender_covered` and `rerender_counted` are the two counts).  --turntable N writes N renders <stem>_turn_KK.png over
+background -1 of the camera-space mesh turned about the vertical axis through its centroid, the yaws spaced evenly in
+[-DEG, DEG] (--turntable_yaw, default 30; one render: yaw 0), projected by the fitted camera when there is one.
+--texture_refine STEPS runs Adam (optim.FlatAdam) on the texture alone, from the padded bake, on the sum over the covered
+pixels of (render - target)^2; the mesh, the uv map and its tap list are fixed, texels no tap reaches keep their padded
+value, the refined texture is the one written, and <stem>.npz gains `texture_refine_loss` [STEPS] (the loss before every
+step) and, with --texture_check, `rerender_error_before`.  --texture_lr's default 0.02 is a starting value, not tuned on any
+trained checkpoint.  With --multiview the merged texture is refined over all views of the subject at once (one texture
+under V uv maps) and checked on every view: NAME_identity.npz `merged_texture_refine_loss`, `merged_rerender_error` [V]
+(with `merged_rerender_covered`, `merged_rerender_counted` and, after a refinement, `merged_rerender_error_before`): the
+number the merge's sharpness and the facing gate can be tuned against; --turntable also writes NAME_merged_turn_KK.png, the
+identity mesh (pose 0, no camera) with the merged texture.
+
 With --multiview V the IMAGE arguments are taken in consecutive groups of V, each group V pictures of one subject (their
 count must be a multiple of V).  It implies --batch V: a group is fitted as one batched LatentInverter with
 shared_identity=K, so the views share the leading K coefficients (K = the face model's n_identity: shape before
@@ -92,7 +111,7 @@ with NAME_merged.mtl, the identity mesh carrying the merged texture.  NAME_ident
 merge before padding: `merged_texture` [C, T, T], `merged_weight` [T, T] and `merged_best` [T, T]; every view's .npz
 holds its bake before padding, `texture` [C, T, T] and `texture_weight` [T, T] (float32; 4 MB per view at T = 512), so a
 merge can be repeated at another sharpness without a new fit.  Not built: exposure or colour matching between the views,
-mirror fill, a differentiable texture, choosing the views automatically.  Without --multiview nothing changes.
+mirror fill, choosing the views automatically.  Without --multiview nothing changes.
 
 With --camera_distance D (D > 0: the camera's distance from the plane z = 0 of pose space in half-picture-widths, which is
 the focal length in that unit) or --camera_fov DEG (the full field of view across the picture) the fit sees the mesh through
@@ -413,11 +432,60 @@ def landmark_outputs(inv, index, conf, listed, shape):
     return dict(more, landmarks=fit, landmarks_target=np.asarray(listed, np.float64), lmk_error=np.float64(err))
 
 
+def texture_rerender(tex, weight, views):
+    """With views a list of (uvmap [1, S, S, 2], cover [1, S, S], target [1, C, S, S]), per view (image [1, C, S, S] over
+    background -1, error, covered, counted): the texture tex [1, C, T, T] drawn on the view's uv map; error is the mean
+    absolute difference to the view's target over the `counted` pixels, those that are covered and where the look-up of
+    the bake's weight [1, 1, T, T] is positive."""
+    from .op import texture
+
+    out = []
+    with torch.no_grad():
+        for uvmap, cover, target in views:
+            img = texture.sample(tex, uvmap, cover, -1.0)
+            on = cover & (texture.sample(weight, uvmap, cover, 0.0)[:, 0] > 0)
+            n = int(on.sum())
+            err = float(((img - target).abs() * on.unsqueeze(1)).sum()) / max(n * int(img.shape[1]), 1)
+            out.append((img, err, int(cover.sum()), n))
+    return out
+
+
+def texture_refine(tex, views, steps, lr=0.02):
+    """(tex' [1, C, T, T], loss [STEPS]; the loss before every step) with views a list of (uvmap [1, S, S, 2], cover
+    [1, S, S], target [1, C, S, S]): Adam (optim.FlatAdam) on the texture alone from tex, on the sum over the views' covered
+    pixels of (render - target)^2; one texture for all views (Bt = 1).  The uv maps are fixed, so the tap list is built
+    once; a texel no tap reaches has gradient 0 in every step and keeps its value bit for bit.  lr's default is a
+    starting value, not tuned on any trained checkpoint."""
+    from . import optim
+    from .op import texture
+
+    uvmap = torch.cat([u for u, _, _ in views], 0).contiguous()
+    cover = torch.cat([c for _, c, _ in views], 0).contiguous()
+    target = torch.cat([t for _, _, t in views], 0)
+    p = tex.detach().clone().contiguous().requires_grad_(True)
+    offs, total = optim.flat_layout([p])
+    flat_g = torch.zeros(total, dtype=p.dtype, device=p.device)
+    opt = optim.FlatAdam([p], flat_g, lr=float(lr))
+    slot = optim.flat_views(flat_g, [p], offs)[0]
+    texture.tap_plan(uvmap, cover, tuple(p.shape[-2:]), 1)
+    on = cover.unsqueeze(1).to(p.dtype)
+    losses = []
+    for _ in range(int(steps)):
+        diff = (texture.sample(p, uvmap, cover, 0.0) - target) * on
+        loss = (diff * diff).sum()
+        (g,) = torch.autograd.grad(loss, p)
+        slot.copy_(g)
+        opt.step()
+        losses.append(loss.detach())
+    return p.detach().clone(), torch.stack(losses).cpu().numpy().astype(np.float64)
+
+
 class TextureGuide:
     """The texture options of one run: the layout and its texel map (built once), and `outputs`, which bakes one fitted
     sample and writes its files."""
 
-    def __init__(self, face, size, uv_file=None, source="picture", facing="0.1,0.4", passes=8, fill="mean"):
+    def __init__(self, face, size, uv_file=None, source="picture", facing="0.1,0.4", passes=8, fill="mean", check=False,
+                 turntable=0, turntable_yaw=30.0, refine=0, refine_lr=0.02):
         from .face_model import load_uv, uv_layout
         from .op import texture
 
@@ -432,6 +500,12 @@ class TextureGuide:
         if not lo <= hi:
             raise SystemExit("reconstruct: --texture_facing needs LO <= HI")
         self.facing, self.source, self.fill = (lo, hi), source, fill
+        self.check, self.turntable, self.turntable_yaw = bool(check), int(turntable), float(turntable_yaw)
+        self.refine_steps, self.refine_lr = int(refine), float(refine_lr)
+        if self.turntable < 0 or self.refine_steps < 0 or not self.refine_lr > 0:
+            raise SystemExit("reconstruct: --turntable and --texture_refine are not negative, --texture_lr is positive")
+        self.views = []                                                  # (--multiview: what the merged texture is checked on)
+        self.view_size = None                                            # the fit's resolution, known with the first sample
         self.passes = int(passes)
         if not 0 <= self.passes <= texture.MAX_PASSES:
             raise SystemExit("reconstruct: --texture_pad lies in [0, %d]" % texture.MAX_PASSES)
@@ -461,6 +535,62 @@ class TextureGuide:
             out = texture.fill_mean(out, weight, filled)
         return out
 
+    renders = property(lambda self: self.check or self.refine_steps > 0)
+
+    def view(self, inv, index):
+        """(uvmap [1, S, S, 2], cover [1, S, S], target [1, 3, S, S]) of sample `index`: the uv map of the fitted mesh at the
+        fitted pose and camera at the fit's resolution, and the fit's target.  The mesh is fixed from here on, so the tap
+        list of the map is built once."""
+        from .op import texture
+
+        k = slice(index, index + 1)
+        v, _, tri = inv.fitted_mesh()
+        with torch.no_grad():
+            uvmap, cover = texture.uv_map(v[k].contiguous(), tri, self._layout[0], self.tri_uv, int(inv.target.shape[-1]),
+                                          self._layout[2])
+        return uvmap, cover, inv.target[k].to(uvmap.dtype).contiguous()
+
+    def checked(self, tex, weight, views, prefix=""):
+        """(tex as it is written, .npz entries, the re-rendered images): --texture_refine and --texture_check on the padded
+        texture tex over `views`; the entries' names start with `prefix`."""
+        entries, before = {}, None
+        if self.check and self.refine_steps:
+            before = texture_rerender(tex, weight, views)
+        if self.refine_steps:
+            tex, loss = texture_refine(tex, views, self.refine_steps, self.refine_lr)
+            entries[prefix + "texture_refine_loss"] = loss
+        images = []
+        if self.check:
+            after = texture_rerender(tex, weight, views)
+            one = len(views) == 1 and not prefix
+            pick = (lambda col: np.float64(col[0])) if one else (lambda col: np.asarray(col, np.float64))
+            entries[prefix + "rerender_error"] = pick([r[1] for r in after])
+            entries[prefix + "rerender_covered"] = pick([r[2] for r in after])
+            entries[prefix + "rerender_counted"] = pick([r[3] for r in after])
+            if before is not None:
+                entries[prefix + "rerender_error_before"] = pick([r[1] for r in before])
+            images = [r[0] for r in after]
+        return tex, entries, images
+
+    def turn(self, tex, v, tri, size, kappa, out_dir, prefix):
+        """Writes the --turntable renders <prefix>_turn_KK.png: the mesh v [1, nv, 3] turned about the vertical axis through
+        its centroid by yaws spaced evenly in [-DEG, DEG] (one render: 0), projected by the camera kappa [1] when there is
+        one, drawn with tex over background -1."""
+        from .op import camera, texture
+
+        n = self.turntable
+        yaws = np.linspace(-self.turntable_yaw, self.turntable_yaw, n) if n > 1 else np.zeros(1)
+        with torch.no_grad():
+            centre = v.mean(1, keepdim=True)
+            for j, deg in enumerate(yaws):
+                angle = torch.tensor([np.deg2rad(deg), 0.0, 0.0], dtype=v.dtype, device=v.device)
+                turned = torch.matmul(v - centre, utils_3d.euler_mat(angle)) + centre
+                if kappa is not None:
+                    turned = camera.project(turned.contiguous(), kappa)
+                img, _ = texture.render(turned.contiguous(), tri, self._layout[0], self.tri_uv, tex, size, -1.0,
+                                        self._layout[2])
+                generate.save_image(img.clamp(-1, 1).cpu(), os.path.join(out_dir, "%s_turn_%02d.png" % (prefix, j)))
+
     @staticmethod
     def save_grey(grey, path):
         try:
@@ -480,6 +610,7 @@ class TextureGuide:
         k = slice(index, index + 1)
         v, n, tri = inv.fitted_mesh()
         v, n = v[k].contiguous(), n[k].contiguous()
+        self.view_size = int(inv.target.shape[-1])
         # (under a camera the bake reads the projected mesh and the .obj lists the camera-space one)
         vo, no = (t[k] for t in inv.fitted_mesh(projected=False)[:2]) if inv.camera is not None else (v, n)
         if self.source == "render":
@@ -493,6 +624,17 @@ class TextureGuide:
                                        facing=self.facing)
             cover = float(texture.coverage(self.face, weight)[0])
             out = self.finish(tex, weight)
+        more = {}
+        if self.renders:
+            views = [self.view(inv, index)]
+            out, more, images = self.checked(out, weight, views)
+            if images:
+                generate.save_image(images[0].clamp(-1, 1).cpu(), os.path.join(out_dir, stem + "_rerender.png"))
+            if keep is not None:
+                self.views.append(views[0])
+        if self.turntable:
+            self.turn(out, vo.contiguous(), tri, int(inv.target.shape[-1]),
+                      inv.camera.detach()[k].contiguous() if inv.camera is not None else None, out_dir, stem)
         generate.save_image(out.clamp(-1, 1).cpu(), os.path.join(out_dir, stem + "_texture.png"))
         grey = np.round(weight[0, 0].cpu().numpy().astype(np.float64) * 255.0).astype(np.uint8)
         try:
@@ -506,9 +648,9 @@ class TextureGuide:
                                    self.uv.numpy(), self.tri_uv.numpy(), no[0].cpu().numpy(), stem + "_texture.png")
         if keep is not None:
             keep.append((tex, weight))
-            return {"texture_coverage": np.float64(cover), "texture": tex[0].cpu().numpy(),
-                    "texture_weight": weight[0, 0].cpu().numpy()}
-        return {"texture_coverage": np.float64(cover)}
+            return dict(more, texture_coverage=np.float64(cover), texture=tex[0].cpu().numpy(),
+                        texture_weight=weight[0, 0].cpu().numpy())
+        return dict(more, texture_coverage=np.float64(cover))
 
     def merged_outputs(self, bakes, sharpness, out_dir, name, v, n, tri):
         """Merges the views' bakes (`outputs`' keep list), writes the subject's NAME_merged_texture.png, _weight.png,
@@ -520,14 +662,21 @@ class TextureGuide:
                                               sharpness)
             cover = float(texture.coverage(self.face, weight)[0])
             out = self.finish(tex, weight)
+        more = {}
+        if self.renders:
+            # the merged texture on every view's own mesh and target: the number the merge is tuned against
+            views, self.views = self.views[-len(bakes):], []
+            out, more, _ = self.checked(out, weight, views, "merged_")
+        if self.turntable:
+            self.turn(out, v, tri, int(self.view_size), None, out_dir, name + "_merged")
         generate.save_image(out.clamp(-1, 1).cpu(), os.path.join(out_dir, name + "_merged_texture.png"))
         grey = np.round(weight[0, 0].cpu().numpy().astype(np.float64) * 255.0).astype(np.uint8)
         self.save_grey(grey, os.path.join(out_dir, name + "_merged_texture_weight.png"))
         self.save_grey(np.ascontiguousarray(best.cpu().numpy()), os.path.join(out_dir, name + "_merged_texture_views.png"))
         utils_3d.save_textured_obj(os.path.join(out_dir, name + "_merged.obj"), v[0].cpu().numpy(), tri.cpu().numpy(),
                                    self.uv.numpy(), self.tri_uv.numpy(), n[0].cpu().numpy(), name + "_merged_texture.png")
-        return {"merged_coverage": np.float64(cover), "merged_texture": tex[0].cpu().numpy(),
-                "merged_weight": weight[0, 0].cpu().numpy(), "merged_best": best.cpu().numpy()}
+        return dict(more, merged_coverage=np.float64(cover), merged_texture=tex[0].cpu().numpy(),
+                    merged_weight=weight[0, 0].cpu().numpy(), merged_best=best.cpu().numpy())
 
 
 def reconstruct(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, coeff_lr=0.01, shape_reg=0.0,
@@ -699,6 +848,19 @@ def main(argv=None):
                     help="with --texture: grow the charts by N texels (0..64) [8]")
     ap.add_argument("--texture_fill", default=None, choices=("mean", "none"),
                     help="with --texture: paint the texels still unfilled with the mean colour, or leave them black [mean]")
+    ap.add_argument("--texture_check", action="store_true",
+                    help="with --texture: draw the written texture on the fitted mesh at the fit's resolution "
+                         "(<stem>_rerender.png) and report its mean absolute difference to the target (rerender_error)")
+    ap.add_argument("--turntable", type=int, default=None, metavar="N",
+                    help="with --texture: write N renders <stem>_turn_KK.png of the textured mesh turned about its vertical "
+                         "axis")
+    ap.add_argument("--turntable_yaw", type=float, default=None, metavar="DEG",
+                    help="with --turntable: the yaws are spaced evenly in [-DEG, DEG] [30]")
+    ap.add_argument("--texture_refine", type=int, default=None, metavar="STEPS",
+                    help="with --texture: STEPS Adam steps on the texture alone against the target, from the padded bake "
+                         "(or merge); the refined texture is the one written")
+    ap.add_argument("--texture_lr", type=float, default=None, metavar="LR",
+                    help="with --texture_refine: Adam's learning rate; a starting value, not tuned [0.02]")
     cam = ap.add_mutually_exclusive_group()
     cam.add_argument("--camera_distance", type=float, default=None, metavar="D",
                      help="perspective camera at distance D > 0 from the plane z = 0 of pose space, in half-picture-widths "
@@ -749,6 +911,12 @@ def main(argv=None):
     if args.texture is None and (args.uv or args.texture_from or args.texture_facing or args.texture_pad is not None
                                  or args.texture_fill):
         ap.error("--uv, --texture_from, --texture_facing, --texture_pad and --texture_fill need --texture")
+    if args.texture is None and (args.texture_check or args.turntable is not None or args.texture_refine is not None):
+        ap.error("--texture_check, --turntable and --texture_refine need --texture")
+    if args.turntable_yaw is not None and args.turntable is None:
+        ap.error("--turntable_yaw needs --turntable")
+    if args.texture_lr is not None and args.texture_refine is None:
+        ap.error("--texture_lr needs --texture_refine")
     camera_args = {}
     if args.camera_distance is not None or args.camera_fov is not None:
         if args.camera_distance is not None:
@@ -786,7 +954,11 @@ def main(argv=None):
                         guide.count if guide else None)
               if (args.mask_lmk or args.mask_dir or args.mask_mesh) else None)
     painter = (TextureGuide(face, args.texture, args.uv, args.texture_from or "picture", args.texture_facing or "0.1,0.4",
-                            8 if args.texture_pad is None else args.texture_pad, args.texture_fill or "mean")
+                            8 if args.texture_pad is None else args.texture_pad, args.texture_fill or "mean",
+                            check=args.texture_check, turntable=args.turntable or 0,
+                            turntable_yaw=30.0 if args.turntable_yaw is None else args.turntable_yaw,
+                            refine=args.texture_refine or 0,
+                            refine_lr=0.02 if args.texture_lr is None else args.texture_lr)
                if args.texture is not None else None)
     shared = None
     if args.multiview is not None:
