@@ -669,6 +669,21 @@ int sr_conv2d_wgrad_path(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW
  * same shape.  -1 for an invalid geometry. */
 int64_t sr_conv2d_wgrad_path_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW,
                                     int ksize, int stride, int pad, int transposed, const float* x, const float* gy);
+/* Weight gradient AND style gradient of y = gscale * conv(iscale (.) x, wt) from one pass over x and gy:
+ *   dwt as sr_conv2d_wgrad_mfma(xscale = iscale);   gis[b][c] = sum_{t,n} wt[t][c][n] * P_b[t][c][n]  (= sum_p x * dx_unscaled),
+ * P_b the weight gradient of sample b without the style.  Served where the call's path is SR_WGRAD_PATH_WINO, or
+ * SR_WGRAD_PATH_S2_WINO of a transposed convolution, and its K slices do not straddle samples: the finish kernel then
+ * forms both from the per-sample partial slabs in a fixed order (deterministic, no atomics).
+ * sr_conv2d_wgrad_style_floats: floats of `part` for such a call, -1 for every other call (which keeps
+ * sr_conv2d_wgrad_mfma and a row-dot pass; sr_conv2d_wgrad_style returns SR_EINVAL for it).
+ * wt [9][C][ldw] is the forward weight (ldw >= N), iscale [B][C] required, gscale [B][N] or NULL;
+ * `scratch`: sr_conv2d_wgrad_scratch_floats(...) floats. */
+int64_t sr_conv2d_wgrad_style_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW,
+                                     int ksize, int stride, int pad, int transposed, const float* x, const float* gy);
+int sr_conv2d_wgrad_style(float* dwt, float* gis, const float* x, const float* gy, const float* iscale,
+                          const float* gscale, const float* wt, int64_t ldw, int64_t B, int64_t C, int64_t N, int64_t IH,
+                          int64_t IW, int64_t OH, int64_t OW, int ksize, int stride, int pad, int transposed,
+                          float* scratch, float* part, sr_stream_t stream);
 
 /* ---- signalling out of a replayed hipGraph (overlapped gradient all-reduce) -----------------------------------
  * The reference overlaps the gradient all-reduce with the backward through torch DDP's bucket hooks

@@ -120,6 +120,8 @@ SIGNATURES = {
     "sr_conv2d_path_floats": (_l, [_l] * 7 + [_i] * 4 + [_p, _p, _p, _l, _i]),
     "sr_conv2d_wgrad_path": (_i, [_l] * 7 + [_i] * 4 + [_p, _p]),
     "sr_conv2d_wgrad_path_floats": (_l, [_l] * 7 + [_i] * 4 + [_p, _p]),
+    "sr_conv2d_wgrad_style_floats": (_l, [_l] * 7 + [_i] * 4 + [_p, _p]),
+    "sr_conv2d_wgrad_style": (_i, [_p] * 7 + [_l] * 8 + [_i] * 4 + [_p, _p, _p]),
     "sr_conv2d_mfma_ex": (_i, [_p] * 6 + [_l] * 8 + [_i] * 5 + [_p, _p]),
     "sr_conv1x1_add_supported": (_i, [_l] * 5 + [_p] * 4),
     "sr_conv1x1_add": (_i, [_p] * 5 + [_l] * 5 + [_p]),

@@ -12,6 +12,7 @@
 #include "conv_wgrad_small3.h"
 #include "conv_wgrad_wino.h"
 #include "conv_wino.h"
+#include "wgrad_style_finish.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -108,6 +109,31 @@ WgradPlan make_wgrad_plan(const WgradCall& c) {
     return w;
 }
 
+// Style gradient from the per-sample slabs (wgrad_style_finish.h): the two transform-domain paths, where
+// the plan the call takes anyway cuts K into whole slices per sample.  Nothing is re-planned: a call whose slices
+// straddle samples keeps the plain finish and the caller its row-dot pass.
+struct StylePlan {
+    int sps = 0;                 // whole K slices per sample; 0: not on this path
+    int64_t part = -1;           // floats of the style-gradient partials
+};
+StylePlan make_style_plan(const WgradCall& c, const WgradPlan& w) {
+    StylePlan s;
+    if (c.B <= 0 || c.B > SR_STYLE_FINISH_MAX_B) return s;
+    if (w.path == SR_WGRAD_PATH_WINO) {
+        s.sps = sr_wgrad_wino_slices_per_sample(c.B, c.C, c.N, c.IH, c.IW);
+        if (s.sps > 0) s.part = sr_wgrad_style_part_floats(c.B, c.C, c.N, false);
+    } else if (w.path == SR_WGRAD_PATH_S2_WINO && c.transposed) {
+        // one sample per patch row of the plan (pb = 1): sample b owns patches [b * per, (b + 1) * per)
+        const SrWgradTiles& pl = w.tiles;
+        const int per = pl.tiles_x * pl.tiles_y;
+        if (pl.pb == 1 && per % pl.pps == 0 && (int64_t)pl.ks * pl.pps == (int64_t)per * c.B) {
+            s.sps = per / pl.pps;
+            s.part = sr_wgrad_style_part_floats(c.B, c.CU, c.CV, true);
+        }
+    }
+    return s;
+}
+
 WgradCall wgrad_call(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH, int64_t OW, int ksize, int stride,
                      int pad, int transposed, const void* x, const void* gy) {
     WgradCall c{B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, x, gy};
@@ -173,4 +199,30 @@ extern "C" int sr_conv2d_wgrad_mfma(float* dwt, const float* x, const float* gy,
                                       c.CV, st);
     }
     }
+}
+
+extern "C" int64_t sr_conv2d_wgrad_style_floats(int64_t B, int64_t C, int64_t N, int64_t IH, int64_t IW, int64_t OH,
+                                                int64_t OW, int ksize, int stride, int pad, int transposed, const float* x,
+                                                const float* gy) {
+    const WgradCall c = wgrad_call(B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, x, gy);
+    return make_style_plan(c, make_wgrad_plan(c)).part;
+}
+
+extern "C" int sr_conv2d_wgrad_style(float* dwt, float* gis, const float* x, const float* gy, const float* iscale,
+                                     const float* gscale, const float* wt, int64_t ldw, int64_t B, int64_t C, int64_t N,
+                                     int64_t IH, int64_t IW, int64_t OH, int64_t OW, int ksize, int stride, int pad,
+                                     int transposed, float* scratch, float* part, sr_stream_t stream) {
+    const WgradCall c = wgrad_call(B, C, N, IH, IW, OH, OW, ksize, stride, pad, transposed, x, gy);
+    const WgradPlan w = make_wgrad_plan(c);
+    const StylePlan s = make_style_plan(c, w);
+    if (s.sps <= 0) return SR_EINVAL;
+    if (!dwt || !gis || !x || !gy || !iscale || !wt || !scratch || !part || ldw < N) return SR_EINVAL;
+    if (B * C * IH * IW >= (1LL << 31) || B * N * OH * OW >= (1LL << 31)) return SR_ERANGE;
+    hipStream_t st = sr_stream(stream);
+    if (w.path == SR_WGRAD_PATH_WINO)
+        return sr_wgrad_wino_style_launch(dwt, gis, x, gy, iscale, gscale, wt, ldw, B, C, N, IH, IW, scratch, part, st);
+    // SR_WGRAD_PATH_S2_WINO, transposed: U = gy with the demodulation, V = x WITHOUT the style (it enters in the finish)
+    const SrWgradTiles& pl = w.tiles;
+    const int rc = sr_wgrad_s2_wino_launch(gy, x, gscale, nullptr, scratch, B, c.CU, c.CV, c.UH, c.UW, c.GH, c.GW, pl.ks, pl.pps, st);
+    return rc != SR_OK ? rc : sr_wgrad_s2_wino_style_finish(dwt, gis, scratch, iscale, wt, ldw, s.sps, B, c.CU, c.CV, part, st);
 }

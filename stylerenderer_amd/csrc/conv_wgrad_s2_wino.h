@@ -19,3 +19,9 @@ int sr_wgrad_s2_wino_launch(const float* U, const float* V, const float* uscale,
                             int pps, hipStream_t st);
 // finish: slices summed in slice order, 16 -> 9 positions, written in the layout of `out`
 int sr_wgrad_s2_wino_finish(const WgradOut& out, const float* partial, int ks, int64_t CU, int64_t CV, hipStream_t st);
+// Transposed convolution ((u, v) = (n, c)) whose K slices hold `sps` whole slices per sample, main launch with
+// vscale = NULL: the finish of wgrad_style_finish.h — dwt [9][C = CV][N = CU] with the style iscale [B][CV] applied, and
+// gis[b][c] = sum_{t,n} wt[t][c][n] * (weight gradient of sample b without the style).  wt [9][CV][ldw] is the forward
+// weight, `part` sr_wgrad_style_part_floats(B, CU, CV, true) floats.  B <= 32.
+int sr_wgrad_s2_wino_style_finish(float* dwt, float* gis, const float* partial, const float* iscale, const float* wt,
+                                  int64_t ldw, int sps, int64_t B, int64_t CU, int64_t CV, float* part, hipStream_t st);

@@ -23,6 +23,7 @@
 // k_wgrad_s2p_finish adds the slices in slice order, combines 16 -> 9 in a fixed order and applies the output layout.
 #include "wgrad_tile.h"
 #include "conv_wgrad_s2_wino.h"
+#include "wgrad_style_finish.h"
 
 namespace {
 
@@ -318,4 +319,12 @@ int sr_wgrad_s2_wino_finish(const WgradOut& out, const float* partial, int ks, i
     r.slab = out.slab; r.su = out.su; r.sv = out.sv;
     hipLaunchKernelGGL(k_wgrad_s2p_finish, dim3(sr_stream_grid(9 * CU * CV, 256)), dim3(256), 0, st, r);
     return sr_launch_status();
+}
+
+int sr_wgrad_s2_wino_style_finish(float* dwt, float* gis, const float* partial, const float* iscale, const float* wt,
+                                  int64_t ldw, int sps, int64_t B, int64_t CU, int64_t CV, float* part, hipStream_t st) {
+    SrStyleFinish f;
+    f.partial = partial; f.iscale = iscale; f.wt = wt; f.dwt = dwt; f.part = part;
+    f.B = (int)B; f.sps = sps; f.CU = (int)CU; f.CV = (int)CV; f.C = (int)CV; f.N = (int)CU; f.ldw = (int)ldw;
+    return sr_wgrad_style_finish_launch<SrPullS2p, true>(f, gis, st);
 }

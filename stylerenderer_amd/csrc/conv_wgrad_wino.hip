@@ -30,6 +30,7 @@
 #include <type_traits>
 #include "mfma_tile.h"
 #include "conv_wgrad_wino.h"
+#include "wgrad_style_finish.h"
 
 namespace {
 
@@ -574,8 +575,11 @@ int64_t sr_wgrad_wino_scratch_floats(int64_t B, int64_t C, int64_t N, int64_t H,
     return (int64_t)slices * 16 * C * N;
 }
 
-int sr_wgrad_wino_launch(float* dwt, const float* x, const float* gy, const float* xscale, const float* gscale,
-                         int64_t B, int64_t C, int64_t N, int64_t H, int64_t W, float* scratch, hipStream_t st) {
+namespace {
+
+// k_wgrad_wino over the plan's slices: partial slabs into `scratch`; returns the number of slices, < 0 on error
+int launch_slabs(const float* x, const float* gy, const float* xscale, const float* gscale, int64_t B, int64_t C, int64_t N,
+                 int64_t H, int64_t W, float* scratch, hipStream_t st) {
     WgWinoParams p;
     p.x = x; p.gy = gy; p.xscale = xscale; p.gscale = gscale; p.partial = scratch;
     p.B = (int)B; p.C = (int)C; p.N = (int)N; p.H = (int)H; p.W = (int)W;
@@ -584,12 +588,42 @@ int sr_wgrad_wino_launch(float* dwt, const float* x, const float* gy, const floa
     plan(B, C, N, H, W, p.slices, p.chunks_per_slice, p.chunks_total);
     // SR_WGW_WAVES=4: one wave per SIMD (round 2's form); default 8: two per SIMD (same bits)
     const bool two = sr_env_char("SR_WGW_WAVES") != '4';
-    if (!sr_allow_dynamic_lds<k_wgrad_wino<4>>(160 * 1024) || !sr_allow_dynamic_lds<k_wgrad_wino<8>>(160 * 1024)) return SR_EINVAL;
+    if (!sr_allow_dynamic_lds<k_wgrad_wino<4>>(160 * 1024) || !sr_allow_dynamic_lds<k_wgrad_wino<8>>(160 * 1024)) return -1;
     const int64_t blocks = (int64_t)p.tiles_c * p.tiles_n * p.slices;
     if (two) hipLaunchKernelGGL(k_wgrad_wino<8>, dim3((unsigned)blocks), dim3(512), WgW<8>::LDS_FLOATS * 4, st, p);
     else hipLaunchKernelGGL(k_wgrad_wino<4>, dim3((unsigned)blocks), dim3(256), WgW<4>::LDS_FLOATS * 4, st, p);
+    return p.slices;
+}
+
+}  // namespace
+
+int sr_wgrad_wino_launch(float* dwt, const float* x, const float* gy, const float* xscale, const float* gscale,
+                         int64_t B, int64_t C, int64_t N, int64_t H, int64_t W, float* scratch, hipStream_t st) {
+    const int slices = launch_slabs(x, gy, xscale, gscale, B, C, N, H, W, scratch, st);
+    if (slices < 0) return SR_EINVAL;
     const int64_t cn = C * N;
     hipLaunchKernelGGL(k_wgrad_wino_finish, dim3((unsigned)sr_ceil_div(cn, 64)), dim3(256), 0, st, dwt, scratch,
-                       p.slices, (int)C, (int)N);
+                       slices, (int)C, (int)N);
     return sr_launch_status();
+}
+
+int sr_wgrad_wino_slices_per_sample(int64_t B, int64_t C, int64_t N, int64_t H, int64_t W) {
+    if (B > SR_STYLE_FINISH_MAX_B) return 0;
+    int slices, cps, total;
+    plan(B, C, N, H, W, slices, cps, total);
+    const int per_sample = (int)((H / 2) * (W / 16));
+    return per_sample % cps == 0 ? per_sample / cps : 0;
+}
+
+int sr_wgrad_wino_style_launch(float* dwt, float* gis, const float* x, const float* gy, const float* iscale,
+                               const float* gscale, const float* wt, int64_t ldw, int64_t B, int64_t C, int64_t N, int64_t H,
+                               int64_t W, float* scratch, float* part, hipStream_t st) {
+    const int sps = sr_wgrad_wino_slices_per_sample(B, C, N, H, W);
+    if (sps <= 0) return SR_EINVAL;
+    // the slabs of P_b: the style scale stays out of the main kernel (xscale = NULL) and enters in the finish
+    if (launch_slabs(x, gy, nullptr, gscale, B, C, N, H, W, scratch, st) != sps * (int)B) return SR_EINVAL;
+    SrStyleFinish f;
+    f.partial = scratch; f.iscale = iscale; f.wt = wt; f.dwt = dwt; f.part = part;
+    f.B = (int)B; f.sps = sps; f.CU = (int)C; f.CV = (int)N; f.C = (int)C; f.N = (int)N; f.ldw = (int)ldw;
+    return sr_wgrad_style_finish_launch<SrPullWino, false>(f, gis, st);
 }

@@ -9,12 +9,14 @@ Low-level operator used by layers.ModulatedConv2d / EqualConv2d for device tenso
 It replaces the F.conv2d / F.conv_transpose2d(groups=batch) calls of reference layers.py:301-322.
 """
 import os
+import threading
 
 import torch
 
 from .. import _lib
 from ._dispatch import hold_for_capture, mark_inputs, native, require_f32, wanted
 from . import weight_prep as _wp
+from . import wgrad_style as _ws
 from .fused_elem import noise_stride, param_grads, rowdot, rowdot_div
 
 
@@ -116,6 +118,19 @@ def _scratch_written(entry, b, c, n, h, w, x, out):
         entry.ready = True
 
 
+class _StyleRequest:
+    """Set (per thread) by `_conv_grads` around ONE conv2d_wgrad_mfma call that is also to yield the style gradient: the
+    forward weight in, gis [B, C] out (op.wgrad_style).  A request and not an argument: the call keeps the signature
+    and the return value that WgradFn and everything wrapped around the function rely on."""
+    __slots__ = ("wt", "gis")
+
+    def __init__(self, wt):
+        self.wt, self.gis = wt, None
+
+
+_TLS = threading.local()
+
+
 def conv2d_wgrad_mfma(x, gy, xscale=None, gscale=None, ksize=3, stride=1, pad=1, transposed=False):
     """dwt [k*k, C, N] = sum over batch and pixels of (xscale*x)[window] * (gscale*gy)."""
     require_f32(x, "conv2d_wgrad_mfma")
@@ -139,13 +154,20 @@ def conv2d_wgrad_mfma(x, gy, xscale=None, gscale=None, ksize=3, stride=1, pad=1,
         from .smallconv import _dw
 
         return _dw(x, gy).sum(0).view(1, c, n)
+    gh, gw = (ih, iw) if transposed else (oh, ow)
+    flops = 2.0 * b * gh * gw * c * n * ksize * ksize
+    req = getattr(_TLS, "style", None)
+    if req is not None and req.gis is None:
+        wtp, ldw = _wt_pitch(req.wt)
+        dwt, req.gis = _ws.wgrad_style(
+            x, gy, xscale, gscale, wtp, ldw, ksize, stride, pad, transposed,
+            lambda launch: _timed(x, "wgrad", (ksize, stride, int(bool(transposed)), b, c, n, gh, gw), flops, launch))
+        return dwt
     nfl = _lib.lib().sr_conv2d_wgrad_scratch_floats(b, c, n, ih, iw, oh, ow, ksize, stride, pad, int(bool(transposed)))
     if nfl < 0:
         raise RuntimeError("conv2d_wgrad_mfma: unsupported geometry")
     scratch = torch.empty(nfl, dtype=torch.float32, device=x.device)
     dwt = torch.empty((ksize * ksize, c, n), dtype=torch.float32, device=x.device)
-    gh, gw = (ih, iw) if transposed else (oh, ow)
-    flops = 2.0 * b * gh * gw * c * n * ksize * ksize
     _timed(x, "wgrad", (ksize, stride, int(bool(transposed)), b, c, n, gh, gw), flops,
            lambda: native(x).sr_conv2d_wgrad_mfma(dwt, x, gy, xscale, gscale, b, c, n, ih, iw, oh, ow, ksize, stride, pad,
                                                   int(bool(transposed)), scratch))
@@ -153,7 +175,7 @@ def conv2d_wgrad_mfma(x, gy, xscale=None, gscale=None, ksize=3, stride=1, pad=1,
 
 
 # ------------------------------------------------------------------------------------------------
-# Differentiable operators.  Two mutually recursive autograd Functions close the algebra:
+# Differentiable operators. Two mutually recursive autograd Functions close the algebra:
 #   ConvFn   y  = oscale * conv(iscale * x, wt) + bias
 #   WgradFn  dW = sum_b corr(iscale * x, oscale * g)
 # d(ConvFn)/dx is a ConvFn with the adjoint geometry, d(ConvFn)/dwt is a WgradFn, and both
@@ -203,6 +225,36 @@ def _input_grads(x, g, wt, iscale, oscale, geom, need_x, need_is, frozen=False, 
     return gx, gis
 
 
+# How often `_conv_grads` formed a wanted style gradient in the weight gradient's finish / by the row-dot pass (tests)
+STYLE_PATH_COUNTS = {"wgrad": 0, "rowdot": 0}
+
+
+def _conv_grads(x, g, wt, iscale, oscale, geom, need_x, need_w, need_is, frozen=False, banked=None):
+    """(gx, gw, gis) of y = oscale * conv(iscale * x, wt) for the cotangent g: the backward the three convolution nodes
+    share.  Where the weight and the style gradient are both wanted, the pass is not itself recorded and the weight
+    gradient's plan cuts K into whole slices per sample (`op.wgrad_style.part_floats`), the style gradient comes out of
+    the weight gradient's finish kernel and the adjoint convolution applies the style in its store (its `oscale`):
+    no row-dot pass over x and the data gradient.  SR_STYLE_FROM_WGRAD=0, and every other case: `_input_grads` and
+    `WgradFn` as before, bit for bit."""
+    if (need_w and need_is and iscale is not None and geom in ("c3", "t3s2") and not torch.is_grad_enabled()
+            and os.environ.get("SR_STYLE_FROM_WGRAD", "1") != "0" and _ws.part_floats(x, g, *_GEOM[geom]) >= 0):
+        STYLE_PATH_COUNTS["wgrad"] += 1
+        gx = None
+        if need_x:
+            gx = ConvFn.apply(g, adjoint_weight(wt, geom, frozen, banked), oscale, iscale, None, _ADJOINT[geom])
+        req = _TLS.style = _StyleRequest(wt)
+        try:
+            gw = conv2d_wgrad_mfma(x, g, iscale, oscale, *_GEOM[geom])
+        finally:
+            _TLS.style = None
+        return gx, gw, req.gis
+    if need_is:
+        STYLE_PATH_COUNTS["rowdot"] += 1
+    gx, gis = _input_grads(x, g, wt, iscale, oscale, geom, need_x, need_is, frozen, banked)
+    gw = WgradFn.apply(x, g, iscale, oscale, geom) if need_w else None
+    return gx, gw, gis
+
+
 class ConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, wt, iscale, oscale, bias, geom):
@@ -222,10 +274,8 @@ class ConvFn(torch.autograd.Function):
         need_x, need_w, need_is, need_os, need_b = wanted(ctx)[:5]      # minus what this pass would discard
         geom = ctx.geom
         g = g.contiguous()
-        gw = gos = gb = None
-        gx, gis = _input_grads(x, g, wt, iscale, oscale, geom, need_x, need_is, ctx.frozen, ctx.adj)
-        if need_w:
-            gw = WgradFn.apply(x, g, iscale, oscale, geom)
+        gos = gb = None
+        gx, gw, gis = _conv_grads(x, g, wt, iscale, oscale, geom, need_x, need_w, need_is, ctx.frozen, ctx.adj)
         if need_os:
             y0 = out - bias[None, :, None, None] if bias is not None else out
             gos = rowdot_div(g, y0, oscale)
@@ -364,10 +414,8 @@ class ConvNBAFn(torch.autograd.Function):
             rdot = None
         else:
             g, gb, gnw, rdot = _nba_bwd_dot(gy, out, noise, noise_w, abias, slope, gain, want_p)
-        gw = gos = None
-        gx, gis = _input_grads(x, g, wt, iscale, oscale, "c3", needs[0], needs[2], ctx.frozen, ctx.adj)
-        if needs[1]:
-            gw = WgradFn.apply(x, g, iscale, oscale, "c3")
+        gos = None
+        gx, gw, gis = _conv_grads(x, g, wt, iscale, oscale, "c3", needs[0], needs[1], needs[2], ctx.frozen, ctx.adj)
         if needs[3] and oscale is not None:
             gos = rdot / oscale
         return (gx, gw, gis, gos, None, (gnw if noise is not None and want_p and needs[5] else None),
@@ -465,10 +513,8 @@ class UpConvNBAFn(torch.autograd.Function):
             g, gb, gnw, rdot = _nba_bwd_dot(gy, out, noise, noise_w, abias, slope, gain, want_p)
             g257 = upfirdn2d_op(g.reshape(-1, oh, ow, 1), flipped(kernel), 1, 1, 1, 1, 3 - p0,
                                 shape257[3] - ow + p0, 3 - p0, shape257[2] - oh + p0).view(shape257)
-        gw = gos = None
-        gx, gis = _input_grads(x, g257, wt, iscale, oscale, "t3s2", needs[0], needs[2], ctx.frozen, ctx.adj)
-        if needs[1]:
-            gw = WgradFn.apply(x, g257, iscale, oscale, "t3s2")
+        gos = None
+        gx, gw, gis = _conv_grads(x, g257, wt, iscale, oscale, "t3s2", needs[0], needs[1], needs[2], ctx.frozen, ctx.adj)
         if needs[3] and oscale is not None:
             gos = rdot / oscale
         return (gx, gw, gis, gos, None, None, None, (gnw if noise is not None and want_p and needs[7] else None),
