@@ -171,6 +171,19 @@ int sr_smallconv_dw(float* dws, const float* g, const float* x, int64_t B, int64
  * launch (gb may be NULL); same scratch */
 int sr_smallconv_dw_bias(float* dws, float* gb, const float* g, const float* x, int64_t B, int64_t C, int64_t N, int64_t hw,
                          float* scratch, sr_stream_t stream);
+/* Backward of a styled layer's tail whose output y [B, C, hw] feeds both the next layer and ToRGB (reference
+ * model.py:206-219) in ONE pass: what sr_smallconv_dx_add(gy, g_rgb, ws, g_above), sr_smallconv_dw_bias(dws, gb_rgb, g_rgb, y)
+ * and sr_noise_bias_act_bwd_dot(gpre, gbias, gnoise_w, rowdot, gy, y, ...) compute in that order, every output bit for bit
+ * (the same partition and expression order; the same finish kernels), without writing gy and reading y once instead of
+ * twice.  g_above (the next layer's cotangent, [B, C, hw]) may be NULL (the last layer) and must not be gpre; gbias NULL =
+ * frozen bias / noise strength; gb_rgb NULL = no ToRGB bias gradient.  C % 4 == 0, hw % 4 == 0, B * C <= 65535, N <= 4,
+ * alpha != 0, scale != 0; gpre, g_above, y, g_rgb, noise on 16-byte boundaries.  scratch: sr_fork_nba_bwd_scratch_floats
+ * floats, 8-byte aligned. */
+int64_t sr_fork_nba_bwd_scratch_floats(int64_t B, int64_t C, int64_t N, int64_t hw);
+int sr_fork_nba_bwd(float* gpre, float* gbias, float* gnoise_w, float* rowdot, float* dws, float* gb_rgb,
+                    const float* g_above, const float* y, const float* g_rgb, const float* ws, const float* noise,
+                    const float* noise_w, const float* bias, float alpha, float scale, int64_t B, int64_t C, int64_t N,
+                    int64_t hw, int64_t noise_bstride, float* scratch, sr_stream_t stream);
 /* Modulated weight rows of that convolution and their pull-back (reference layers.py:293-297, demodulate=False):
  *   sr_modrows_fwd: ws[b,j,c] = (scale * w[j,c]) * s[b,c]                       w [N, C], s [B, C], ws [B, N, C]
  *   sr_modrows_bwd: gs[b,c] = sum_j dws[b,j,c] * (scale * w[j,c]);  gw[j,c] = scale * sum_b dws[b,j,c] * s[b,c]

@@ -1099,6 +1099,206 @@ extern "C" int sr_smallconv_dw(float* dws, const float* g, const float* x, int64
 }
 
 // ------------------------------------------------------------------------------------------------
+// Backward of a styled layer's tail whose output y feeds both the next layer and ToRGB (reference model.py:206-219), as
+// ONE pass over the cotangent from above and y instead of three launches and six passes:
+//   k_smallconv_dx (addend)   gy   = g_above + Ws^T g_rgb        read g_above, write gy
+//   k_smallconv_dw            dws  = sum_p g_rgb * y             read y
+//   k_nba_bwd<true>           gpre = lrelu'(y) * gy * scale ...  read gy, y, write gpre
+// The partition is the one all three share (256 lanes, one ECHUNK of a (sample, channel) row per sweep, a float4 per
+// lane, CH rows per workgroup as in k_smallconv_dw) and every expression is theirs, term by term and in their order, so
+// each output equals theirs bit for bit; the partials leave in the layouts their finish kernels read.
+namespace {
+
+template <int N, int CH>
+__global__ __launch_bounds__(EB) void k_fork_nba_bwd(float* __restrict__ gpre, float* __restrict__ partial,
+                                                     float* __restrict__ dot_partial, float* __restrict__ dw_partial,
+                                                     float* __restrict__ dws, float* __restrict__ gsum,
+                                                     const float* __restrict__ addend, const float* __restrict__ y,
+                                                     const float* __restrict__ g, const float* __restrict__ ws,
+                                                     const float* __restrict__ noise, const float* __restrict__ noise_w,
+                                                     const float* __restrict__ bias, float alpha, float scale,
+                                                     float inv_pos, float inv_neg, int C, int64_t hw,
+                                                     int64_t noise_bstride, int chunks) {
+    __shared__ float lds_nba[CH][2][8];
+    __shared__ float lds[CH][4 * SC_MAXN];
+    __shared__ float lds_g[4 * SC_MAXN];
+    const int64_t row0 = (int64_t)blockIdx.y * CH;   // b * C + c0, CH consecutive channels of one sample
+    const int64_t b = row0 / C;
+    const int c0 = (int)(row0 - b * C);
+    const int64_t off = (int64_t)blockIdx.x * ECHUNK;
+    const int64_t remain = hw - off;
+    const int n4 = (int)((remain < ECHUNK ? remain : ECHUNK) / 4);
+    const float4* ns = noise ? reinterpret_cast<const float4*>(noise + b * noise_bstride + off) : nullptr;
+    const float nw = noise ? noise_w[0] : 0.0f;
+    float w[CH][N], bb[CH];
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+        bb[k] = bias ? bias[c0 + k] : 0.0f;
+#pragma unroll
+        for (int j = 0; j < N; ++j) w[k][j] = ws[(b * N + j) * C + c0 + k];
+    }
+    float acc[CH][N], sb[CH], sn[CH], sd[CH], ag[N];
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+        sb[k] = sn[k] = sd[k] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < N; ++j) acc[k][j] = 0.0f;
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) ag[j] = 0.0f;
+    const bool sum_g = gsum != nullptr && c0 == 0;       // (the ToRGB bias gradient: see k_smallconv_dw)
+    for (int i = threadIdx.x; i < n4; i += EB) {
+        float4 gg[N], a[CH], o[CH];
+#pragma unroll
+        for (int j = 0; j < N; ++j) gg[j] = reinterpret_cast<const float4*>(g + (b * N + j) * hw + off)[i];
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            o[k] = reinterpret_cast<const float4*>(y + (row0 + k) * hw + off)[i];
+            if (addend) a[k] = reinterpret_cast<const float4*>(addend + (row0 + k) * hw + off)[i];
+        }
+        float4 nz = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (noise) nz = ns[i];
+        if (sum_g) {
+#pragma unroll
+            for (int j = 0; j < N; ++j) ag[j] += (gg[j].x + gg[j].y) + (gg[j].z + gg[j].w);
+        }
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            // k_smallconv_dx: from zero, ascending j, the addend last
+            float4 gy = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                gy.x += w[k][j] * gg[j].x; gy.y += w[k][j] * gg[j].y; gy.z += w[k][j] * gg[j].z; gy.w += w[k][j] * gg[j].w;
+            }
+            if (addend) { gy.x = a[k].x + gy.x; gy.y = a[k].y + gy.y; gy.z = a[k].z + gy.z; gy.w = a[k].w + gy.w; }
+            // k_nba_bwd<true>
+            const float4 v = o[k];
+            float4 r;
+            r.x = ((v.x > 0.0f) ? gy.x : gy.x * alpha) * scale;
+            r.y = ((v.y > 0.0f) ? gy.y : gy.y * alpha) * scale;
+            r.z = ((v.z > 0.0f) ? gy.z : gy.z * alpha) * scale;
+            r.w = ((v.w > 0.0f) ? gy.w : gy.w * alpha) * scale;
+            reinterpret_cast<float4*>(gpre + (row0 + k) * hw + off)[i] = r;
+            sb[k] += (r.x + r.y) + (r.z + r.w);
+            if (noise) sn[k] += (r.x * nz.x + r.y * nz.y) + (r.z * nz.z + r.w * nz.w);
+            const float y0 = ((v.x > 0.0f) ? v.x * inv_pos : v.x * inv_neg) - nw * nz.x - bb[k];
+            const float y1 = ((v.y > 0.0f) ? v.y * inv_pos : v.y * inv_neg) - nw * nz.y - bb[k];
+            const float y2 = ((v.z > 0.0f) ? v.z * inv_pos : v.z * inv_neg) - nw * nz.z - bb[k];
+            const float y3 = ((v.w > 0.0f) ? v.w * inv_pos : v.w * inv_neg) - nw * nz.w - bb[k];
+            sd[k] += (r.x * y0 + r.y * y1) + (r.z * y2 + r.w * y3);
+            // k_smallconv_dw
+#pragma unroll
+            for (int j = 0; j < N; ++j)
+                acc[k][j] += (v.x * gg[j].x + v.y * gg[j].y) + (v.z * gg[j].z + v.w * gg[j].w);
+        }
+    }
+    // k_nba_bwd's reductions, one LDS slot pair per channel (no barrier between them beyond block_sum2's own)
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+        float dummy = 0.0f;
+        block_sum2(sb[k], sn[k], lds_nba[k][0]);
+        block_sum2(sd[k], dummy, lds_nba[k][1]);
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            partial[((row0 + k) * chunks + blockIdx.x) * 2] = sb[k];
+            partial[((row0 + k) * chunks + blockIdx.x) * 2 + 1] = sn[k];
+            dot_partial[(row0 + k) * chunks + blockIdx.x] = sd[k];
+        }
+    }
+    // k_smallconv_dw's reductions
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < CH; ++k)
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const float r = sr_wave_sum(acc[k][j]);
+            if (lane == 0) lds[k][j * 4 + wave] = r;
+        }
+    if (sum_g) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const float r = sr_wave_sum(ag[j]);
+            if (lane == 0) lds_g[j * 4 + wave] = r;
+        }
+    }
+    __syncthreads();
+    if (sum_g && threadIdx.x >= 64 && threadIdx.x < 64 + N) {
+        const int j = threadIdx.x - 64;
+        gsum[(b * chunks + blockIdx.x) * N + j] = (lds_g[j * 4] + lds_g[j * 4 + 1]) + (lds_g[j * 4 + 2] + lds_g[j * 4 + 3]);
+    }
+    if (threadIdx.x < CH * N) {
+        const int k = threadIdx.x / N, j = threadIdx.x % N;
+        const float r = (lds[k][j * 4] + lds[k][j * 4 + 1]) + (lds[k][j * 4 + 2] + lds[k][j * 4 + 3]);
+        if (dws) dws[(b * N + j) * C + (c0 + k)] = r;                          // one chunk per row: the result itself
+        else dw_partial[((row0 + k) * chunks + blockIdx.x) * N + j] = r;
+    }
+}
+
+constexpr int FORK_CH = 4;
+
+inline int64_t fork_nba_floats(int64_t B, int64_t C, int64_t hw) {      // (even: what follows stays 8-byte aligned)
+    const int64_t n = 3 * B * C * sr_ceil_div(hw, ECHUNK) + C + 2;
+    return n + (n & 1);
+}
+
+}  // namespace
+
+extern "C" int64_t sr_fork_nba_bwd_scratch_floats(int64_t B, int64_t C, int64_t N, int64_t hw) {
+    if (B <= 0 || C <= 0 || N <= 0 || hw <= 0) return 4;
+    // the activation backward's partials (sr_noise_bias_act_bwd_dot's layout), then the weight-gradient and ToRGB
+    // bias-gradient partials (sr_smallconv_dw_bias's layout)
+    return fork_nba_floats(B, C, hw) + B * C * sr_ceil_div(hw, ECHUNK) * N + B * sr_ceil_div(hw, ECHUNK) * N + 1;
+}
+
+extern "C" int sr_fork_nba_bwd(float* gpre, float* gbias, float* gnoise_w, float* rowdot, float* dws, float* gb_rgb,
+                               const float* g_above, const float* y, const float* g_rgb, const float* ws,
+                               const float* noise, const float* noise_w, const float* bias, float alpha, float scale,
+                               int64_t B, int64_t C, int64_t N, int64_t hw, int64_t noise_bstride, float* scratch,
+                               sr_stream_t stream) {
+    if (!gpre || !rowdot || !dws || !y || !g_rgb || !ws || !scratch || (noise && !noise_w) || scale == 0.0f ||
+        alpha == 0.0f)
+        return SR_EINVAL;
+    if (!smallconv_ok(B, C, N, hw, g_rgb, y) || hw <= 0 || C % FORK_CH != 0 || B * C > 65535) return SR_EINVAL;
+    if (!vec_ok(hw, gpre, g_above, y, noise) || (noise && noise_bstride % 4 != 0) || gpre == g_above) return SR_EINVAL;
+    const int chunks = (int)sr_ceil_div(hw, ECHUNK);
+    hipStream_t st = sr_stream(stream);
+    const int64_t rows = B * C;
+    float* dot_scratch = scratch + 2 * rows * chunks;
+    float* chan_nw = dot_scratch + rows * chunks;
+    float* dw_scratch = scratch + fork_nba_floats(B, C, hw);
+    float* dot_partial = chunks == 1 ? rowdot : dot_scratch;              // (one chunk: in place, as the three entries do)
+    float* direct = chunks == 1 ? dws : nullptr;
+    float* gsum = gb_rgb ? dw_scratch + rows * chunks * N : nullptr;
+    const dim3 grid((unsigned)chunks, (unsigned)(rows / FORK_CH));
+#define SR_FORK_NBA(NN)                                                                                                    \
+    hipLaunchKernelGGL((k_fork_nba_bwd<NN, FORK_CH>), grid, dim3(EB), 0, st, gpre, scratch, dot_partial, dw_scratch, direct,  \
+                       gsum, g_above, y, g_rgb, ws, noise, noise_w, bias, alpha, scale, 1.0f / scale,                       \
+                       1.0f / (alpha * scale), (int)C, hw, noise_bstride, chunks)
+    switch (N) {
+        case 1: SR_FORK_NBA(1); break;
+        case 2: SR_FORK_NBA(2); break;
+        case 3: SR_FORK_NBA(3); break;
+        default: SR_FORK_NBA(4); break;
+    }
+#undef SR_FORK_NBA
+    if (gbias) {                                            // (NULL: frozen bias / noise strength)
+        hipLaunchKernelGGL(k_nba_finish, dim3((unsigned)C), dim3(64), 0, st, gbias, chan_nw, scratch, B, (int)C, chunks);
+        if (noise && gnoise_w)
+            hipLaunchKernelGGL(k_nba_finish2, dim3(1), dim3(64), 0, st, gnoise_w, chan_nw, (int)C);
+    }
+    if (chunks > 1) {
+        hipLaunchKernelGGL(k_rowdot_finish, dim3((unsigned)rows), dim3(64), 0, st, rowdot, dot_partial, chunks);
+        hipLaunchKernelGGL(k_smallconv_dw_finish, dim3((unsigned)rows), dim3(64), 0, st, dws, dw_scratch, (int)C, (int)N,
+                           chunks, rows);
+    }
+    if (gb_rgb)
+        hipLaunchKernelGGL(k_smallconv_gb_finish, dim3(1), dim3(64), 0, st, gb_rgb, gsum, (int)N, (int)(B * chunks));
+    return sr_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------
 // Modulated weight rows of the small 1x1 convolution (ToRGB, reference layers.py:293-297 without demodulation):
 //   ws[b,j,c] = (scale * w[j,c]) * s[b,c]                                     one launch instead of two tensor products
 // and the pull-back of a gradient dws [B,N,C] (what k_smallconv_dw produces) onto both factors:

@@ -23,6 +23,7 @@ from torch.nn import functional as F
 from .op import FusedLeakyReLU, fused_leaky_relu, upfirdn2d
 from .op import conv as _conv
 from .op import conv_generic as _convg
+from .op import fork_tail as _fork_tail
 from .op import smallconv as _smallconv
 from .op import style as _style
 from .op.style_bank import StylePack
@@ -315,9 +316,11 @@ class ModulatedConv2d(nn.Module):
             out = out * d[:, :, None, None]
         return self.blur(out) if (self.upsample and not skip_blur) else out
 
-    def forward_noise_bias_act(self, input, style, noise, noise_weight, act_bias, negative_slope, act_scale):
+    def forward_noise_bias_act(self, input, style, noise, noise_weight, act_bias, negative_slope, act_scale, fork=None):
         """conv -> noise -> bias -> LeakyReLU of a non-upsampling 3x3 layer as one autograd node (device tensors,
-        Winograd-eligible shapes); None when that path does not apply (the caller runs the separate operators)."""
+        Winograd-eligible shapes); None when that path does not apply (the caller runs the separate operators).
+        fork: an `op.fork_tail.Head` of the ToRGB head that reads this layer's output.  Where the combined node serves the
+        layer, the head's rows are formed, its image is left in `fork.rgb`, and the output is returned as always."""
         if (input.device.type != "cuda" or self.upsample or self.downsample or self.kernel_size != 3
                 or not self.demodulate or act_bias is None or not _fused_tails()):
             return None
@@ -336,6 +339,12 @@ class ModulatedConv2d(nn.Module):
             if not (_conv.conv_nba_supported(input, wt, noise) and _style.demod_supported(s, wsq)):
                 return None
             d = _style.demod_scale(s, wsq, self.eps)
+        if fork is not None and _fork_tail.enabled():
+            if _fork_tail.supported(input, self.out_channel, fork.n_rgb, noise, d):
+                ws, rgb_bias = fork.rows()
+                out, fork.rgb = _fork_tail.conv2d_nba_fork(input, wt, s, d, noise, noise_weight, act_bias, negative_slope,
+                                                           act_scale, ws, rgb_bias)
+                return out
         return _conv.conv2d_nba(input, wt, s, d, noise, noise_weight, act_bias, negative_slope, act_scale)
 
     def forward_up_noise_bias_act(self, input, style, noise, noise_weight, act_bias, negative_slope, act_scale):

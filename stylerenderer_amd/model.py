@@ -18,6 +18,7 @@ from torch import nn
 from .layers import (BiasBank, Blur, ConstantInput, ConvLayer, EqualLinear, ModulatedConv2d, NoiseInjection,  # noqa: F401
                      PixelNorm, ResBlock, Upsample)
 from .op import FusedLeakyReLU, rasterize
+from .op import fork_tail as _fork_tail
 from .op import smallconv as _smallconv
 from .op import style_bank as _style_bank
 from .op import weight_bank as _weight_bank
@@ -44,7 +45,10 @@ class StyledConv(nn.Module):
         self.bias = None
         self.activate = FusedLeakyReLU(out_channel)
 
-    def forward(self, input, style, noise=None):
+    def forward(self, input, style, noise=None, fork=None):
+        """fork: the `op.fork_tail.Head` (`ToRGB.fork_head`) of the head that reads this layer's output.  Where the layer
+        and the head run as one node (the 32^2 .. 256^2 stride-1 layers) the head's image is left in `fork.rgb`.  The
+        result is the layer's output either way: forward hooks on this module see and may rewrite the activation."""
         if noise is not None and noise.requires_grad:
             # optimising the noise maps (projector-style use): the fused nodes do not differentiate with
             # respect to `noise`, the separate operators do (reference layers.py:324-332)
@@ -71,7 +75,7 @@ class StyledConv(nn.Module):
             # 32^2 .. 256^2 layers: the Winograd convolution applies noise + bias + LeakyReLU in its store
             fused = self.conv.forward_noise_bias_act(input, style, noise.contiguous(), self.noise.weight,
                                                      self.activate.bias, self.activate.negative_slope,
-                                                     self.activate.scale)
+                                                     self.activate.scale, fork=fork)
             if fused is not None:
                 return fused
             out = self.conv(input, style)
@@ -145,6 +149,31 @@ class ToRGB(nn.Module):
         if skip is not None:
             out = out + self.upsample(skip)
         return (input, out) if fork else out
+
+    def fork_head(self, style):
+        """This head's side of the node that runs it together with the layer in front (`StyledConv.forward(..., fork=)`);
+        the rows are only formed where that node applies."""
+        conv = self.conv
+        return _fork_tail.Head(conv.out_channel, lambda: (
+            _smallconv.modulated_rows(conv.weight.view(conv.out_channel, conv.in_channel), conv.style_of(style), conv.scale),
+            self.bias.view(-1)))
+
+
+def _conv_to_rgb(conv, to_rgb, out, s_conv, s_rgb, skip, noise, *maps):
+    """(out, skip) of `conv` followed by its ToRGB head with `out` handed on to the next layer: one node for both where
+    op.fork_tail serves the layer (device tensors, the conv-NBA path, SR_TORGB_FORK and SR_FORK_TAIL not 0), else the two
+    nodes `conv` and `ToRGB.forward(fork=True)`."""
+    if not maps and isinstance(conv, StyledConv) and _fork_enabled() and _fork_tail.enabled():
+        head = to_rgb.fork_head(s_rgb)
+        out = conv(out, s_conv, noise=noise, fork=head)
+        if head.rgb is not None:
+            rgb = head.rgb
+            if skip is not None:
+                rgb = upsample2_add(skip, to_rgb.upsample.kernel, to_rgb.upsample.pad, rgb)
+            return out, rgb
+    else:
+        out = conv(out, s_conv, *maps, noise=noise)
+    return to_rgb(out, s_rgb, skip, fork=True)
 
 
 class Generator(nn.Module):
@@ -306,8 +335,7 @@ class Generator(nn.Module):
             for conv_up, conv, n_up, n_conv, to_rgb in zip(self.convs[::2], self.convs[1::2],
                                                            noise[1::2], noise[2::2], self.to_rgbs):
                 out = conv_up(out, st[k], noise=n_up)
-                out = conv(out, st[k + 1], noise=n_conv)
-                out, skip = to_rgb(out, st[k + 2], skip, fork=True)
+                out, skip = _conv_to_rgb(conv, to_rgb, out, st[k + 1], st[k + 2], skip, n_conv)
                 k += 3
         return skip, (latent if return_latents else None)
 
@@ -372,8 +400,7 @@ class GeneratorWithMap(Generator):
             # full-size copies of `maps` — per resolution and per order of differentiation
             maps_up, maps_conv = maps.split([2, maps.shape[1] - 2], 1)
             out = conv_up(out, st[k], maps_up, noise=n_up)
-            out = conv(out, st[k + 1], maps_conv, noise=n_conv)
-            out, skip = to_rgb(out, st[k + 2], skip, fork=True)
+            out, skip = _conv_to_rgb(conv, to_rgb, out, st[k + 1], st[k + 2], skip, n_conv, maps_conv)
             i += 2
             k += 3
         return skip, (latent if return_latents else None), (norm_maps if return_normals else None)

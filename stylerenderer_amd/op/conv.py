@@ -366,22 +366,69 @@ def _wt_pitch(wt):
     return (torch.nn.functional.pad(wt, (0, ldw - n)) if ldw != n else wt.contiguous()), ldw
 
 
+def _nba_forward(x, wt, iscale, oscale, noise, noise_w, abias, slope, gain):
+    """The launch of `ConvNBAFn.forward` (and of op.fork_tail's node): convolution with the tail in its store."""
+    b, c, h, w = x.shape
+    n = wt.shape[2]
+    wtp, ldw = _wt_pitch(wt)
+    out = torch.empty((b, n, h, w), dtype=x.dtype, device=x.device)
+    nscr = _lib.lib().sr_conv2d_scratch_floats(b, c, n, h, w, h, w, 3, 1, 1, 0)
+    scratch, flags, entry = _conv_scratch(wt if wtp is wt else wtp, max(nscr, 1), (b, c, n, h, w, 3, 1, 1, False), x)
+    flops = 2.0 * b * h * w * c * n * 9
+    _timed(x, "conv", (3, 1, 0, b, c, n, h, w), flops,
+           lambda: native(x).sr_conv2d_nba_ex(out, x, wtp, iscale, oscale, noise, noise_w, abias, float(slope),
+                                              float(gain), b, c, n, ldw, h, w, noise_stride(noise, h * w), flags,
+                                              scratch))
+    _scratch_written(entry, b, c, n, h, w, x, out)
+    return out
+
+
+def _nba_backward(saved, cfg, frozen, adj, needs, gy):
+    """The backward of `ConvNBAFn` for the cotangent gy: `saved` = (x, wt, iscale, oscale, noise, noise_w, abias, out),
+    `needs` one flag per forward input.  Nine gradients."""
+    from .fused_elem import _NBA
+
+    x, wt, iscale, oscale, noise, noise_w, abias, out = saved
+    slope, gain = cfg
+    if torch.is_grad_enabled() and oscale is not None:
+        # a recorded backward of the DEMODULATED layer needs the pre-activation as a function of its operands (the
+        # demodulation gradient is sum_p g * y0): re-derived from the separate operators.  Without demodulation (the
+        # discriminator's layers under R1, the LPIPS trunk) nothing below reads y0 — the operators of the plain
+        # branch are differentiable themselves and record the same pass without convolving again
+        return _recorded_backward(
+            (x, wt, iscale, oscale, None, noise_w, abias), needs, gy,
+            lambda xa, wa, sa, da, _, nwa, aba: _NBA.apply(ConvFn.apply(xa, wa, sa, da, None, "c3"), noise, nwa, aba,
+                                                           slope, gain, out.detach()))
+    want_p = bool(needs[6] or (noise is not None and needs[5]))
+    if oscale is None:
+        # no demodulation (the LPIPS trunk's plain convolution + bias + ReLU): nothing to row-dot — and with slope 0
+        # the pre-activation cannot be rebuilt from the output anyway
+        from .fused_elem import _NBABackward
+
+        g, gb, gnw = _NBABackward.apply(gy, out, noise, slope, gain, want_p)
+        rdot = None
+    else:
+        g, gb, gnw, rdot = _nba_bwd_dot(gy, out, noise, noise_w, abias, slope, gain, want_p)
+    return _nba_grads(saved, frozen, adj, needs, want_p, g, gb, gnw, rdot)
+
+
+def _nba_grads(saved, frozen, adj, needs, want_p, g, gb, gnw, rdot):
+    """The nine gradients of `ConvNBAFn` from the activation backward's outputs: g (cotangent of the convolution), gb, gnw
+    (bias / noise-strength gradients, where want_p) and rdot (demodulation row-dots, None without demodulation)."""
+    x, wt, iscale, oscale, noise = saved[:5]
+    gos = None
+    gx, gw, gis = _conv_grads(x, g, wt, iscale, oscale, "c3", needs[0], needs[1], needs[2], frozen, adj)
+    if needs[3] and oscale is not None:
+        gos = rdot / oscale
+    return (gx, gw, gis, gos, None, (gnw if noise is not None and want_p and needs[5] else None),
+            (gb if want_p and needs[6] else None), None, None)
+
+
 class ConvNBAFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, wt, iscale, oscale, noise, noise_w, abias, slope, gain):
         mark_inputs(ctx, x, wt, iscale, oscale, noise, noise_w, abias, slope, gain)
-        b, c, h, w = x.shape
-        n = wt.shape[2]
-        wtp, ldw = _wt_pitch(wt)
-        out = torch.empty((b, n, h, w), dtype=x.dtype, device=x.device)
-        nscr = _lib.lib().sr_conv2d_scratch_floats(b, c, n, h, w, h, w, 3, 1, 1, 0)
-        scratch, flags, entry = _conv_scratch(wt if wtp is wt else wtp, max(nscr, 1), (b, c, n, h, w, 3, 1, 1, False), x)
-        flops = 2.0 * b * h * w * c * n * 9
-        _timed(x, "conv", (3, 1, 0, b, c, n, h, w), flops,
-               lambda: native(x).sr_conv2d_nba_ex(out, x, wtp, iscale, oscale, noise, noise_w, abias, float(slope),
-                                                  float(gain), b, c, n, ldw, h, w, noise_stride(noise, h * w), flags,
-                                                  scratch))
-        _scratch_written(entry, b, c, n, h, w, x, out)
+        out = _nba_forward(x, wt, iscale, oscale, noise, noise_w, abias, slope, gain)
         ctx.save_for_backward(x, wt, iscale, oscale, noise, noise_w, abias, out)
         ctx.cfg = (float(slope), float(gain))
         ctx.frozen = bool(getattr(wt, "_sr_frozen", False))
@@ -390,36 +437,7 @@ class ConvNBAFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from .fused_elem import _NBA
-
-        x, wt, iscale, oscale, noise, noise_w, abias, out = ctx.saved_tensors
-        slope, gain = ctx.cfg
-        needs = wanted(ctx)
-        if torch.is_grad_enabled() and oscale is not None:
-            # a recorded backward of the DEMODULATED layer needs the pre-activation as a function of its operands (the
-            # demodulation gradient is sum_p g * y0): re-derived from the separate operators.  Without demodulation (the
-            # discriminator's layers under R1, the LPIPS trunk) nothing below reads y0 — the operators of the plain
-            # branch are differentiable themselves and record the same pass without convolving again
-            return _recorded_backward(
-                (x, wt, iscale, oscale, None, noise_w, abias), needs, gy,
-                lambda xa, wa, sa, da, _, nwa, aba: _NBA.apply(ConvFn.apply(xa, wa, sa, da, None, "c3"), noise, nwa, aba,
-                                                               slope, gain, out.detach()))
-        want_p = bool(needs[6] or (noise is not None and needs[5]))
-        if oscale is None:
-            # no demodulation (the LPIPS trunk's plain convolution + bias + ReLU): nothing to row-dot — and with slope 0
-            # the pre-activation cannot be rebuilt from the output anyway
-            from .fused_elem import _NBABackward
-
-            g, gb, gnw = _NBABackward.apply(gy, out, noise, slope, gain, want_p)
-            rdot = None
-        else:
-            g, gb, gnw, rdot = _nba_bwd_dot(gy, out, noise, noise_w, abias, slope, gain, want_p)
-        gos = None
-        gx, gw, gis = _conv_grads(x, g, wt, iscale, oscale, "c3", needs[0], needs[1], needs[2], ctx.frozen, ctx.adj)
-        if needs[3] and oscale is not None:
-            gos = rdot / oscale
-        return (gx, gw, gis, gos, None, (gnw if noise is not None and want_p and needs[5] else None),
-                (gb if want_p and needs[6] else None), None, None)
+        return _nba_backward(ctx.saved_tensors, ctx.cfg, ctx.frozen, ctx.adj, wanted(ctx), gy)
 
 
 def _nba_bwd_dot(gy, out, noise, noise_w, abias, slope, gain, want_params=True):

@@ -95,28 +95,33 @@ class SmallConvFork(Function):
     @staticmethod
     def backward(ctx, g_x, g):
         x, ws = ctx.saved_tensors
-        needs = wanted(ctx)
-        if g is None:
-            return (g_x if needs[0] else None), None, None
-        gx = None
-        if needs[0]:
-            fused = (g_x is not None and not torch.is_grad_enabled() and g_x.is_contiguous() and g_x.data_ptr() % 16 == 0
-                     and g_x.dtype == g.dtype and g_x.shape == x.shape)
-            if fused:
-                gx = _dx(g, ws, g_x)
-            else:
-                gx = SmallConvDx.apply(g, ws)
-                if g_x is not None:
-                    gx = gx + g_x
-        want_b = len(needs) > 2 and needs[2]
-        gw = gb = None
-        if needs[1] and want_b:
-            gw, gb = SmallConvDwBias.apply(g, x)
-        elif needs[1]:
-            gw = SmallConvDw.apply(g, x)
-        elif want_b:
-            gb = g.sum((0, 2, 3))
-        return gx, gw, gb
+        return fork_backward(x, ws, wanted(ctx), g_x, g)
+
+
+def fork_backward(x, ws, needs, g_x, g):
+    """The backward of `SmallConvFork` (x, ws saved; `needs` = wanted gradients of (x, ws, bias); g_x, g the cotangents of
+    its two outputs, either may be None): (gx, gws, gbias)."""
+    if g is None:
+        return (g_x if needs[0] else None), None, None
+    gx = None
+    if needs[0]:
+        fused = (g_x is not None and not torch.is_grad_enabled() and g_x.is_contiguous() and g_x.data_ptr() % 16 == 0
+                 and g_x.dtype == g.dtype and g_x.shape == x.shape)
+        if fused:
+            gx = _dx(g, ws, g_x)
+        else:
+            gx = SmallConvDx.apply(g, ws)
+            if g_x is not None:
+                gx = gx + g_x
+    want_b = len(needs) > 2 and needs[2]
+    gw = gb = None
+    if needs[1] and want_b:
+        gw, gb = SmallConvDwBias.apply(g, x)
+    elif needs[1]:
+        gw = SmallConvDw.apply(g, x)
+    elif want_b:
+        gb = g.sum((0, 2, 3))
+    return gx, gw, gb
 
 
 class SmallConvDx(Function):
