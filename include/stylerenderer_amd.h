@@ -398,7 +398,9 @@ int sr_upsample2_add(float* out, const float* x, const float* k, const float* ad
  * stride-2 transposed convolution) with the StyledConv tail fused into its store (reference
  * model.py:26-32): y = lrelu((fir(x) + noise_w[0]*noise[b, p]) + bias[ch], alpha) * gain.
  * x [n, c, in_h, in_w] -> y [n, c, out_h, out_w], out = in + pad0 + pad1 - 3; noise [n or 1, 1, out_h, out_w]
- * with batch stride noise_bstride (0 = shared) or NULL; bias [c] or NULL.  One pass instead of two. */
+ * with batch stride noise_bstride (0 = shared) or NULL; bias [c] or NULL.  One pass instead of two.  This entry and
+ * sr_blur_nba_bwd tile maps whose 2^k side is 64 .. 1024 wide (pad 1, 16-byte aligned pointers) by bands of whole rows,
+ * everything else by 32 x 64 tiles: same values bit for bit (SR_FIR_BAND=0: tiles everywhere). */
 int sr_blur_noise_bias_act(float* y, const float* x, const float* k, const float* noise, const float* noise_w,
                            const float* bias, float alpha, float gain, int64_t n, int64_t c, int in_h, int in_w,
                            int out_h, int out_w, int pad0, int pad1, int64_t noise_bstride, sr_stream_t stream);
@@ -411,7 +413,7 @@ int sr_blur_noise_bias_act(float* y, const float* x, const float* k, const float
  * extent (pad0 = the forward's symmetric padding); k_flipped = the forward taps flipped in both axes (what sr_upfirdn2d
  * takes for the gradient of a blur).  gx is bit-identical to sr_noise_bias_act_bwd followed by sr_upfirdn2d; the three
  * sums are deterministic (per-workgroup partials added in a fixed order) but associate differently from
- * sr_noise_bias_act_bwd_dot.  scratch: sr_blur_nba_bwd_scratch_floats floats. */
+ * sr_noise_bias_act_bwd_dot, and differently by bands than by tiles.  scratch: sr_blur_nba_bwd_scratch_floats floats. */
 int64_t sr_blur_nba_bwd_scratch_floats(int64_t n, int64_t c, int out_h, int out_w);
 int sr_blur_nba_bwd(float* gx, float* gbias, float* gnoise_w, float* rowdot, const float* gy, const float* y,
                     const float* k_flipped, const float* noise, const float* noise_w, const float* bias, float alpha,

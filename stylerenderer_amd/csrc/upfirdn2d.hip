@@ -8,6 +8,9 @@
 //     (9.5 KiB, rows padded to 68 floats so every lane's 8-float window is two aligned
 //     ds_read_b128), each lane producing a 2x4 output micro-tile from a register sliding window and
 //     writing 16-byte stores.  HBM traffic = 4*(N_in + N_out) bytes, the algorithmic minimum.
+//   * k_fir4_band_fwd / k_fir4_band_nba_bwd — the same blur with the up-sampling layers' tail (noise, bias, LeakyReLU) and
+//     its one-pass backward on the large maps, tiled by bands of whole rows: every HBM access but a band's first and
+//     last three floats is an aligned 16-byte one although rows of 2^k + 1 floats are not aligned.
 //   * k_upfirdn_generic — any up/down/kernel/pad (ToRGB skip upsample up=2, its gradient down=2,
 //     odd kernels, crops): one output per lane, consecutive lanes on consecutive columns
 //     (coalesced), polyphase tap skipping instead of multiplying inserted zeros.
@@ -413,6 +416,284 @@ __global__ __launch_bounds__(256) void k_fir4_nba_bwd(float* __restrict__ out, c
     }
 }
 
+// ------------------------------------------------------------------------------ whole-row bands (up-sampling layers)
+// The two kernels above on the maps of the up-sampling layers (2^k + 1 wide on one side, 2^k on the other), tiled by
+// BANDS of whole rows instead of 32 x 64 tiles.  A plane of an NCHW tensor is contiguous, so a band of whole rows of the
+// (2^k + 1)-wide map is ONE contiguous span of memory: it is moved with 16-byte accesses from / to the span's address
+// rounded down to 16 bytes, whatever the residue of its rows, and the at most three floats in front of and behind the
+// aligned part are moved one by one by the band that owns them.  No workgroup owns a one-pixel edge column or row, and
+// the 2^k-wide side (noise, gy, y, the forward's output) is aligned as it stands.
+//   lanes: lanes_x = 2^k / 4 per row (four columns each), 256 / lanes_x lane rows of B_RPL = 4 output rows each
+//          -> rmax = 4 * (256 / lanes_x) rows per band (16 at 256, 32 at 128, 64 at 64);
+//   bands: ceil(rows / rmax) per plane, the rows spread evenly over them (band_rows).
+// The arithmetic is that of fir4_rows and of the tiled kernels' epilogues, tap for tap.
+constexpr int B_RPL = 4;                    // output rows per lane
+constexpr int B_ST = 5;                     // 16-byte groups a lane has in flight per staging trip (one trip up to 257 wide)
+constexpr int B_MIN_W = 64, B_MAX_W = 1024; // 2^k-side widths the band kernels take (profiles/fir_band_notes.md)
+
+__device__ __forceinline__ void band_rows(int rows, int bands, int i, int& r0, int& rb) {
+    const int base = rows / bands, rem = rows - base * bands;
+    r0 = i * base + (i < rem ? i : rem);
+    rb = base + (i < rem ? 1 : 0);
+}
+
+// B_RPL x 4 accumulators from window row t (tap row ky = t - r of output row r): fir4_rows' order for every accumulator
+template <int NW>
+__device__ __forceinline__ void band_taps(const float (&win)[NW], const float (&kf)[16], int t, float (&acc)[B_RPL][4]) {
+#pragma unroll
+    for (int r = 0; r < B_RPL; ++r) {
+        const int ky = t - r;
+        if (ky < 0 || ky > 3) continue;
+#pragma unroll
+        for (int kx = 0; kx < 4; ++kx)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float prod = win[c + kx] * kf[ky * 4 + kx];
+                acc[r][c] = acc[r][c] + prod;
+            }
+    }
+}
+
+// Forward, pad 1: input [planes, in_h, in_w] -> output [planes, in_h - 1, in_w - 1], in_w - 1 = 4 * lanes_x.  The band's
+// input rows r0 - 1 .. r0 + rb + 1 are one span of the tensor; LDS slot 4 + i holds the element i floats behind the
+// span's start rounded down to a multiple of four floats (x is 16-byte aligned), elements of other planes (= rows
+// outside the image) as zeros.  The LDS pitch is the global pitch: columns -1 and in_w have no slots, the first and last lane of a row
+// select them to zero.  `total`: elements of the tensor — no load before its first or past its last element.
+__global__ __launch_bounds__(256, 6) void k_fir4_band_fwd(float* __restrict__ out, const float* __restrict__ x,
+                                                       const float* __restrict__ k, int in_h, int in_w, int lanes_x,
+                                                       int bands, int64_t total, FirNba nba) {
+    extern __shared__ __attribute__((aligned(16))) float s_band[];
+    const int out_h = in_h - 1, out_w = in_w - 1;
+    const int band = blockIdx.x % bands;
+    const int64_t plane = blockIdx.x / bands;
+    int r0, rb;
+    band_rows(out_h, bands, band, r0, rb);
+    const int pe = in_h * in_w;                                     // < 2^30 (sr_blur_noise_bias_act)
+    const int64_t p0 = plane * (int64_t)pe;
+    const int res = (int)((p0 + (int64_t)(r0 - 1) * in_w) & 3);
+    const int e0 = (r0 - 1) * in_w - res;                           // LDS slot 4 + i = plane element e0 + i, e0 + p0 = 0 mod 4
+    const int ng = (res + (rb + 3) * in_w + 3) >> 2;
+    // loads stay inside the tensor: plane elements e_lo .. e_hi + 3 are its first and its last whole 16-byte group
+    const int64_t last_full = (total & ~(int64_t)3) - 4;
+    const int e_lo = (int)(-p0 > -(int64_t)(1 << 30) ? -p0 : -(int64_t)(1 << 30));
+    const int e_hi = (int)(last_full - p0 < (int64_t)(1 << 30) ? last_full - p0 : (int64_t)(1 << 30));
+    const float* xp = x + p0;
+    FIR4_LOAD_TAPS(kf, k)
+
+    // the lane's outputs: rows r0 + ly .. + 3, columns ox .. ox + 3; their noise travels with the staging loads
+    const int gyi = threadIdx.x / lanes_x, gx = threadIdx.x - gyi * lanes_x;
+    const int ly = gyi * B_RPL, ox = gx * 4;
+    const int64_t b = plane / nba.channels;
+    const float* nz = nba.noise ? nba.noise + b * nba.noise_bstride : nullptr;
+    const float nw = nz ? nba.noise_w[0] : 0.0f;
+    const float bb = nba.bias ? nba.bias[plane - b * nba.channels] : 0.0f;
+    float4 nzv[B_RPL];
+    if (nz) {
+#pragma unroll
+        for (int r = 0; r < B_RPL; ++r) {
+            const int oy = min(r0 + ly + r, out_h - 1);
+            nzv[r] = *reinterpret_cast<const float4*>(nz + (int64_t)oy * out_w + ox);
+        }
+    }
+
+    for (int base = 0; base < ng; base += 256 * B_ST) {
+        float4 st[B_ST];
+#pragma unroll
+        for (int j = 0; j < B_ST; ++j) {
+            const int e = e0 + 4 * (base + (int)threadIdx.x + 256 * j);
+            st[j] = *reinterpret_cast<const float4*>(xp + (e < e_lo ? e_lo : (e > e_hi ? e_hi : e)));
+        }
+#pragma unroll
+        for (int j = 0; j < B_ST; ++j) {
+            const int i = base + (int)threadIdx.x + 256 * j;
+            if (i >= ng) continue;
+            const int e = e0 + 4 * i;
+            float4 v = st[j];
+            if (e > e_hi) {                                         // the tensor's last, partial group: element by element
+                const int64_t t = p0 + e;
+                v.x = t < total ? x[t] : 0.0f;
+                v.y = t + 1 < total ? x[t + 1] : 0.0f;
+                v.z = t + 2 < total ? x[t + 2] : 0.0f;
+                v.w = 0.0f;
+            }
+            // outside the plane = a padding row (or another plane's data, or the clamped load's)
+            v.x = (unsigned)e < (unsigned)pe ? v.x : 0.0f;
+            v.y = (unsigned)(e + 1) < (unsigned)pe ? v.y : 0.0f;
+            v.z = (unsigned)(e + 2) < (unsigned)pe ? v.z : 0.0f;
+            v.w = (unsigned)(e + 3) < (unsigned)pe ? v.w : 0.0f;
+            *reinterpret_cast<float4*>(s_band + 4 + 4 * i) = v;
+        }
+    }
+    __syncthreads();
+    if (ly >= rb) return;
+
+    float acc[B_RPL][4];
+#pragma unroll
+    for (int r = 0; r < B_RPL; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = 0.0f;
+    const float* w0 = s_band + 4 + res + ly * in_w + ox - 1;         // window row 0, image column ox - 1
+#pragma unroll
+    for (int t = 0; t < B_RPL + 3; ++t) {
+        float win[7];
+#pragma unroll
+        for (int c = 0; c < 7; ++c) win[c] = w0[t * in_w + c];
+        if (gx == 0) win[0] = 0.0f;                                  // column -1
+        if (gx == lanes_x - 1) win[6] = 0.0f;                        // column in_w
+        band_taps(win, kf, t, acc);
+    }
+
+    float* dst = out + plane * (int64_t)out_h * out_w;
+#pragma unroll
+    for (int r = 0; r < B_RPL; ++r) {
+        if (ly + r >= rb) continue;
+        float nr[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (nz) { nr[0] = nzv[r].x; nr[1] = nzv[r].y; nr[2] = nzv[r].z; nr[3] = nzv[r].w; }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            float v = acc[r][c];
+            if (nz) v = v + nw * nr[c];
+            v += bb;
+            acc[r][c] = ((v > 0.0f) ? v : v * nba.alpha) * nba.gain;
+        }
+        *reinterpret_cast<float4*>(dst + (int64_t)(r0 + ly + r) * out_w + ox) =
+            make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+    }
+}
+
+// Backward (k_fir4_nba_bwd), gradient pad 2: gy, y [planes, in_h, in_w] (in_w = 4 * lanes_x, aligned rows) -> gradient
+// [planes, in_h + 1, in_w + 1].  A band owns rb rows of the gradient; it stages gpre rows r0 - 2 .. r0 + rb at pitch
+// in_w + 8 (four zero columns on either side: aligned 16-byte LDS stores, the window at an 8-byte aligned column - 2) and
+// owns — for the three sums — the gpre rows r0 .. r0 + rb - 1 that exist: every row belongs to exactly one band.  The
+// rb output rows then go through LDS at the global pitch and leave as one flat span (see above): no 16-byte store
+// straddles two bands.  One partial triple per band, in the layout of k_fir4_nba_bwd with chunks = bands.
+__global__ __launch_bounds__(256) void k_fir4_band_nba_bwd(float* __restrict__ out, const float* __restrict__ gy,
+                                                           const float* __restrict__ k, int in_h, int in_w, int lanes_x,
+                                                           int bands, FirNbaBwd q) {
+    extern __shared__ __attribute__((aligned(16))) float s_band[];
+    __shared__ float s_red[12];
+    const int out_h = in_h + 1, out_w = in_w + 1, ld = in_w + 8;
+    const int band = blockIdx.x % bands;
+    const int64_t plane = blockIdx.x / bands;
+    int r0, rb;
+    band_rows(out_h, bands, band, r0, rb);
+    const float* src = gy + plane * (int64_t)in_h * in_w;
+    const float* fws = q.fw + plane * (int64_t)in_h * in_w;
+    const int64_t b = plane / q.channels;
+    const float* nz = q.noise ? q.noise + b * q.noise_bstride : nullptr;
+    const float nw = q.noise ? q.noise_w[0] : 0.0f;
+    const float bb = q.bias ? q.bias[plane - b * q.channels] : 0.0f;
+    FIR4_LOAD_TAPS(kf, k)
+
+    for (int i = threadIdx.x; i < 2 * (rb + 3); i += 256)            // the zero columns left and right of every row
+        *reinterpret_cast<float4*>(s_band + (i >> 1) * ld + ((i & 1) ? 4 + in_w : 0)) = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int ng = (rb + 3) * lanes_x;
+    FirSums sums{0.0f, 0.0f, 0.0f};
+    for (int base = 0; base < ng; base += 256 * B_ST) {
+        float4 sg[B_ST], so[B_ST], sn[B_ST];
+#pragma unroll
+        for (int j = 0; j < B_ST; ++j) {
+            const int i = base + (int)threadIdx.x + 256 * j;
+            const int wr = i / lanes_x, g = i - wr * lanes_x;
+            const int y = r0 - 2 + wr;
+            const bool ok = i < ng && y >= 0 && y < in_h;
+            const int64_t o = ok ? (int64_t)y * in_w + 4 * g : 0;
+            sg[j] = *reinterpret_cast<const float4*>(src + o);
+            so[j] = *reinterpret_cast<const float4*>(fws + o);
+            sn[j] = nz ? *reinterpret_cast<const float4*>(nz + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int j = 0; j < B_ST; ++j) {
+            const int i = base + (int)threadIdx.x + 256 * j;
+            const int wr = i / lanes_x, g = i - wr * lanes_x;
+            const int y = r0 - 2 + wr;
+            const bool ok = i < ng && y >= 0 && y < in_h;
+            const bool own = ok && y >= r0 && y < r0 + rb;
+            float4 v;
+            v.x = fir4_gpre(sg[j].x, so[j].x, sn[j].x, ok, own, q, nw, bb, sums);
+            v.y = fir4_gpre(sg[j].y, so[j].y, sn[j].y, ok, own, q, nw, bb, sums);
+            v.z = fir4_gpre(sg[j].z, so[j].z, sn[j].z, ok, own, q, nw, bb, sums);
+            v.w = fir4_gpre(sg[j].w, so[j].w, sn[j].w, ok, own, q, nw, bb, sums);
+            if (i < ng) *reinterpret_cast<float4*>(s_band + wr * ld + 4 + 4 * g) = v;
+        }
+    }
+    sums.b = sr_wave_sum(sums.b);
+    sums.n = sr_wave_sum(sums.n);
+    sums.d = sr_wave_sum(sums.d);
+    {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 0) { s_red[wave] = sums.b; s_red[4 + wave] = sums.n; s_red[8 + wave] = sums.d; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int64_t slot = plane * (int64_t)bands + band;
+        q.partial[slot * 2] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+        q.partial[slot * 2 + 1] = (s_red[4] + s_red[5]) + (s_red[6] + s_red[7]);
+        q.dot_partial[slot] = (s_red[8] + s_red[9]) + (s_red[10] + s_red[11]);
+    }
+
+    const int gyi = threadIdx.x / lanes_x, gx = threadIdx.x - gyi * lanes_x;
+    const int ly = gyi * B_RPL, ox = gx * 4;
+    const bool active = ly < rb;
+    float acc[B_RPL][4];
+#pragma unroll
+    for (int r = 0; r < B_RPL; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = 0.0f;
+    if (active) {
+        const float* w0 = s_band + ly * ld + 4 + ox - 2;             // window row 0, gpre column ox - 2: 8-byte aligned
+#pragma unroll
+        for (int t = 0; t < B_RPL + 3; ++t) {
+            float win[8];
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                const float2 a = *reinterpret_cast<const float2*>(w0 + t * ld + 2 * h);
+                win[2 * h] = a.x;
+                win[2 * h + 1] = a.y;
+            }
+            band_taps(win, kf, t, acc);
+        }
+    }
+    // the last column (in_w = 4 * lanes_x) has no lane of the 4-column layout: one output per row, by the last rb lanes
+    const int er = (int)threadIdx.x - (256 - rb);
+    float edge = 0.0f;
+    if (er >= 0) {
+#pragma unroll
+        for (int ky = 0; ky < 4; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 4; ++kx) {
+                const float prod = s_band[(er + ky) * ld + 4 + in_w - 2 + kx] * kf[ky * 4 + kx];
+                edge = edge + prod;
+            }
+    }
+    __syncthreads();                                                 // every window is read: the LDS takes the output rows
+    const int64_t a0 = (plane * out_h + r0) * (int64_t)out_w;        // the band's first element in the tensor
+    const int res = (int)(a0 & 3);
+    if (active) {
+#pragma unroll
+        for (int r = 0; r < B_RPL; ++r) {
+            if (ly + r >= rb) continue;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) s_band[res + (ly + r) * out_w + ox + c] = acc[r][c];
+        }
+    }
+    if (er >= 0) s_band[res + er * out_w + in_w] = edge;
+    __syncthreads();
+    const int end = res + rb * out_w;                                // LDS slots res .. end - 1 = tensor a0 .. of this band
+    float* dst = out + (a0 - res);                                   // 16-byte aligned
+    for (int j = 4 * (int)threadIdx.x; j < end; j += 4 * 256) {
+        const float4 v = *reinterpret_cast<const float4*>(s_band + j);
+        if (j >= res && j + 3 < end) {
+            *reinterpret_cast<float4*>(dst + j) = v;
+        } else {                                                     // the span's head and tail: this band's floats only
+            if (j >= res && j < end) dst[j] = v.x;
+            if (j + 1 >= res && j + 1 < end) dst[j + 1] = v.y;
+            if (j + 2 >= res && j + 2 < end) dst[j + 2] = v.z;
+            if (j + 3 >= res && j + 3 < end) dst[j + 3] = v.w;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------ 4x4 taps, up = 2 or down = 2
 // The two resampling shapes of the networks: down = 2 (the blur in front of ResBlock.skip's 1x1 stride-2
 // convolution evaluated only at the pixels that convolution reads, and the gradient of the ToRGB skip
@@ -538,12 +819,42 @@ __global__ __launch_bounds__(256) void k_fir4_resample(float* __restrict__ out, 
 }
 
 // aligned staging of k_fir4_tile / k_fir4_nba_bwd (see A_LD); SR_FIR_ALIGNED=0 keeps the scalar staging (A/B)
-inline bool fir4_aligned(const float* x, int in_w, int pad_x0) {
+inline bool fir4_aligned_enabled() {
     static const bool enabled = [] {
         const char* e = std::getenv("SR_FIR_ALIGNED");
         return !(e && e[0] == '0');
     }();
-    return enabled && pad_x0 == 2 && in_w % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+    return enabled;
+}
+
+inline bool fir4_aligned(const float* x, int in_w, int pad_x0) {
+    return fir4_aligned_enabled() && pad_x0 == 2 && in_w % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+}
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// whole-row bands (k_fir4_band_*) for a map whose 2^k side is w4 wide and whose kernel writes `rows` rows per plane;
+// bands == 0: the shape is not theirs
+struct FirBand {
+    int lanes_x, rmax, bands;
+};
+
+inline FirBand fir4_band_geom(int w4, int rows) {
+    FirBand g{0, 0, 0};
+    if (w4 % 4 != 0 || w4 < B_MIN_W || w4 > B_MAX_W || rows <= 0) return g;
+    g.lanes_x = w4 / 4;
+    g.rmax = B_RPL * (256 / g.lanes_x);
+    g.bands = (rows + g.rmax - 1) / g.rmax;
+    return g;
+}
+
+// SR_FIR_BAND=0 keeps the tiled kernels everywhere (A/B); SR_FIR_ALIGNED=0 does so too (it asks for the scalar staging)
+inline bool fir4_band_enabled() {
+    static const bool enabled = [] {
+        const char* e = std::getenv("SR_FIR_BAND");
+        return !(e && e[0] == '0');
+    }();
+    return enabled && fir4_aligned_enabled();
 }
 
 }  // namespace
@@ -623,6 +934,16 @@ extern "C" int sr_blur_noise_bias_act(float* y, const float* x, const float* k, 
     const int64_t blocks = (int64_t)tiles_x * tiles_y * n * c;
     if (blocks >= 0x7FFFFFFFLL) return SR_ERANGE;
     const FirNba nba{noise, noise_w, bias, noise_bstride, (int)c, alpha, gain};
+    if (fir4_band_enabled() && pad0 == 1 && pad1 == 1 && al16(x) && al16(y) &&
+        (!noise || (al16(noise) && noise_bstride % 4 == 0))) {
+        const FirBand g = fir4_band_geom(out_w, out_h);
+        if (g.bands > 0 && (int64_t)g.bands * n * c < 0x7FFFFFFFLL && (int64_t)in_h * in_w < (1 << 30)) {
+            const size_t lds = ((size_t)(g.rmax + 3) * in_w + 16) * sizeof(float);
+            hipLaunchKernelGGL(k_fir4_band_fwd, dim3((unsigned)(g.bands * n * c)), dim3(256), lds, sr_stream(stream), y, x,
+                               k, in_h, in_w, g.lanes_x, g.bands, n * c * (int64_t)in_h * in_w, nba);
+            return sr_launch_status();
+        }
+    }
     if (fir4_aligned(x, in_w, pad0))
         hipLaunchKernelGGL((k_fir4_tile<true, true>), dim3((unsigned)blocks), dim3(256), 0, sr_stream(stream), y, x, k,
                            in_h, in_w, out_h, out_w, pad0, pad0, tiles_x, tiles_y, nba);
@@ -639,7 +960,8 @@ int sr_nba_finish_launch(float* gbias, float* gnoise_w, float* rowdot, const flo
 extern "C" int64_t sr_blur_nba_bwd_scratch_floats(int64_t n, int64_t c, int out_h, int out_w) {
     if (n <= 0 || c <= 0 || out_h <= 0 || out_w <= 0) return 3;
     const int64_t tiles = (int64_t)((out_w + T_OW - 1) / T_OW) * ((out_h + T_OH - 1) / T_OH);
-    return 3 * n * c * tiles + c + 2;
+    const int64_t bands = fir4_band_geom(out_w - 1, out_h).bands;      // one partial triple per tile or per band
+    return 3 * n * c * (tiles > bands ? tiles : bands) + c + 2;
 }
 
 // gx [n, c, out_h, out_w] = blur^T( lrelu'(y) * gy * gain ) with `k` the FORWARD blur kernel and pad0 / pad1 the
@@ -656,20 +978,27 @@ extern "C" int sr_blur_nba_bwd(float* gx, float* gbias, float* gnoise_w, float* 
     if (!gx || !rowdot || !gy || !y || !k_flipped || !scratch || (noise && !noise_w) || gain == 0.0f || alpha == 0.0f)
         return SR_EINVAL;
     const int tiles_x = (out_w + T_OW - 1) / T_OW, tiles_y = (out_h + T_OH - 1) / T_OH;
-    const int chunks = tiles_x * tiles_y;
+    const int gpad = 3 - pad0;
+    const bool vec = al16(gy) && al16(y) && (!noise || (al16(noise) && noise_bstride % 4 == 0));
+    // whole-row bands on the up-sampling layers' maps, else 32 x 64 tiles
+    FirBand band{0, 0, 0};
+    if (fir4_band_enabled() && pad0 == 1 && vec && al16(gx)) band = fir4_band_geom(in_w, out_h);
+    const int chunks = band.bands > 0 ? band.bands : tiles_x * tiles_y;
     const int64_t blocks = (int64_t)chunks * n * c;
     if (blocks >= 0x7FFFFFFFLL) return SR_ERANGE;
     // every gpre element must lie in some tile's owned corner: the tiles start at -gpad and cover chunks * 32 / 64
-    const int gpad = 3 - pad0;
     if (tiles_y * T_OH - gpad < in_h || tiles_x * T_OW - gpad < in_w) return SR_EINVAL;
     hipStream_t st = sr_stream(stream);
     float* dot_partial = scratch + 2 * n * c * (int64_t)chunks;
     float* chan_nw = dot_partial + n * c * (int64_t)chunks;
     const FirNbaBwd q{y, noise, noise_w, bias, scratch, chunks == 1 ? rowdot : dot_partial, noise_bstride, (int)c, alpha,
                       gain, 1.0f / gain, 1.0f / (alpha * gain)};
-    const bool aln = fir4_aligned(gy, in_w, gpad) && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-                     (!noise || ((reinterpret_cast<uintptr_t>(noise) & 15) == 0 && noise_bstride % 4 == 0));
-    if (aln)
+    const bool aln = fir4_aligned(gy, in_w, gpad) && vec;
+    if (band.bands > 0)
+        hipLaunchKernelGGL(k_fir4_band_nba_bwd, dim3((unsigned)blocks), dim3(256),
+                           (size_t)(band.rmax + 3) * (in_w + 8) * sizeof(float), st, gx, gy, k_flipped, in_h, in_w,
+                           band.lanes_x, band.bands, q);
+    else if (aln)
         hipLaunchKernelGGL(k_fir4_nba_bwd<true>, dim3((unsigned)blocks), dim3(256), 0, st, gx, gy, k_flipped, in_h, in_w,
                            out_h, out_w, gpad, gpad, tiles_x, tiles_y, q);
     else
