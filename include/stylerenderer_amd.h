@@ -1080,6 +1080,46 @@ int sr_camera_fwd(float* vp, float* n_view, const float* v, const float* n, cons
 int sr_camera_bwd(float* gv, float* gkappa, const float* v, const float* vp, const float* gvp, const float* kappa,
                   int64_t B, int64_t nv, sr_stream_t stream);
 
+/* Albedo and lighting: Lambertian shading under second-order spherical harmonics (definition:
+ * stylerenderer_amd/op/light.py), csrc/light.hip.  a, out, g, ga are [B, C, H, W], normals and gn [B, 3, H, W], on uint8
+ * [B, H, W] (non-zero: the pixel counts), gamma [B, Cl, 9] with Cl = 1 (every channel reads light 0) or Cl = C (channel c
+ * reads light c).  Per pixel, every step one float32 operation in this order:
+ *     r = sqrt((nx nx + ny ny) + nz nz);  len = r > 1e-12 ? r : 1e-12;  (x, y, z) = n / len
+ *     Y = [1, x, y, z, x y, x z, y z, x x - y y, 3 (z z) - 1];   s_l = (((g0 + g1 Y1) + g2 Y2) + ...) + g8 Y8
+ * A pixel is live when `on` holds and its normal is finite.
+ * sr_light_shade_fwd: divide == 0: out_c = (a_c - black) (s > 0 ? s : 0) + black on live pixels, `background` elsewhere;
+ *   divide != 0 (floor > 0): out_c = (a_c - black) / (s > floor ? s : floor) + black on live pixels, a_c elsewhere.  A lane
+ *   owns four consecutive pixels of a row; 16-byte accesses where W % 4 == 0 and out, a, normals are 16-byte aligned (on:
+ *   4-byte), scalar ones otherwise.
+ * sr_light_shade_bwd (Cl <= 4): ga_c = g_c (s > 0 ? s : 0) on live pixels, 0 elsewhere; with e_l the sum from 0 in channel
+ *   order of g_c (a_c - black) over the channels that read light l, 0 unless s_l > 0 and the pixel is live:
+ *     gn (when given): gY_k = sum_l e_l gamma[l, k];  gx = ((gY1 + gY4 y) + gY5 z) + (2 gY7) x;
+ *       gy = ((gY2 + gY4 x) + gY6 z) - (2 gY7) y;  gz = ((gY3 + gY5 x) + gY6 y) + (6 gY8) z;  d = (x gx + y gy) + z gz;
+ *       gn = ((gx - x d) / len, (gy - y d) / len, (gz - z d) / len), 0 where r < 1e-12 or the pixel is not live
+ *     partial (when given) [B, P, Cl, 9], P = max(1, ceil(H ceil(W / 4) / 1024)): row p holds the sums of e_l Y_k over the
+ *       pixels of workgroup p (items 1024 p .. 1024 p + 1023 of four pixels each; a lane adds its up to 16 terms in index
+ *       order, then a fixed tree of depth 8).  Every row is written.
+ * sr_light_reduce: out [B, n] = the sum of partial [B, P, n] over P in ascending order; f64 != 0: double, else float.
+ * sr_light_moments (C <= 4): partial double [B, P, 45 + 9 C], reduced as above: the upper triangle (i <= j, row-major) of
+ *   sum w Y Y^T and then sum w Y (a_c - black) for every c, over the pixels with weight [B, 1, H, W] > 0 and a finite
+ *   normal.  Y and a_c - black are float32; the products (w Y_i) Y_j, (w Y_k) (a_c - black) and the sums are double.
+ * sr_light_texel_attr: out [B, A, Th, Tw] (1 <= A <= 4) from attr [B, nv, A] and the texel map (face int32 [Th, Tw], coeff
+ *   [Th, Tw, 3]) of a mesh with the faces tri int64 [nf, 3]: (c0 attr[i0] + c1 attr[i1]) + c2 attr[i2], i_k = tri[face, k];
+ *   0 where face < 0; a face or vertex index outside the mesh counts as empty and is not read.
+ * B <= 65535.  No atomics, no memset, no allocation, no host read: all run under graph capture on `stream`; reruns are
+ * bit-identical. */
+int sr_light_shade_fwd(float* out, const float* a, const float* normals, const uint8_t* on, const float* gamma, int64_t B,
+                       int64_t C, int64_t Cl, int64_t H, int64_t W, float black, float floor, float background, int divide,
+                       sr_stream_t stream);
+int sr_light_shade_bwd(float* ga, float* gn, float* partial, const float* g, const float* a, const float* normals,
+                       const uint8_t* on, const float* gamma, int64_t B, int64_t C, int64_t Cl, int64_t H, int64_t W,
+                       float black, sr_stream_t stream);
+int sr_light_reduce(void* out, const void* partial, int64_t B, int64_t P, int64_t n, int f64, sr_stream_t stream);
+int sr_light_moments(double* partial, const float* a, const float* normals, const float* weight, int64_t B, int64_t C,
+                     int64_t H, int64_t W, float black, sr_stream_t stream);
+int sr_light_texel_attr(float* out, const float* attr, const int64_t* tri, const int32_t* face, const float* coeff,
+                        int64_t B, int64_t A, int64_t nv, int64_t nf, int64_t Th, int64_t Tw, sr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,11 @@ SIGNATURES = {
     "sr_share_rows": (_i, [_p] + [_l] * 3 + [_p]),
     "sr_camera_fwd": (_i, [_p] * 5 + [_l, _l, _p]),
     "sr_camera_bwd": (_i, [_p] * 6 + [_l, _l, _p]),
+    "sr_light_shade_fwd": (_i, [_p] * 5 + [_l] * 5 + [_f, _f, _f, _i, _p]),
+    "sr_light_shade_bwd": (_i, [_p] * 8 + [_l] * 5 + [_f, _p]),
+    "sr_light_reduce": (_i, [_p, _p, _l, _l, _l, _i, _p]),
+    "sr_light_moments": (_i, [_p] * 4 + [_l] * 4 + [_f, _p]),
+    "sr_light_texel_attr": (_i, [_p] * 5 + [_l] * 6 + [_p]),
     "sr_signal_bump": (_i, [_p, _p]),
     "sr_signal_wait": (_i, [_p, ctypes.c_uint32, _p]),
     "sr_signal_set": (_i, [_p, _p, _p]),

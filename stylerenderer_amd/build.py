@@ -44,6 +44,7 @@ SOURCES = [
     ("texture_sample.hip", EXACT),
     ("share.hip", EXACT),
     ("camera.hip", EXACT),
+    ("light.hip", EXACT),
     ("morph.hip", []),
     ("skin.hip", []),
     ("blend.hip", []),

@@ -9,7 +9,8 @@ for it):
         [--mask_lmk [--mask_tri FILE] [--mask_margin R]] [--mask_dir DIR] [--mask_mesh]
         [--texture [T] [--uv FILE] [--texture_from picture|render] [--texture_facing LO,HI] [--texture_pad N]
          [--texture_fill mean|none] [--texture_check] [--turntable N [--turntable_yaw DEG]]
-         [--texture_refine STEPS [--texture_lr LR]]]
+         [--texture_refine STEPS [--texture_lr LR]]
+         [--light [--light_mono] [--light_floor S] [--light_ridge L] [--light_lr LR] [--relight FILE]]]
         [--camera_distance D | --camera_fov DEG] [--fit_camera] [--camera_lr 0.01] CHECKPOINT IMAGE [IMAGE ...]
 
 For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with inversion.LatentInverter(fit_shape=True)
@@ -92,6 +93,26 @@ under V uv maps) and checked on every view: NAME_identity.npz `merged_texture_re
 (with `merged_rerender_covered`, `merged_rerender_counted` and, after a refinement, `merged_rerender_error_before`): the
 number the merge's sharpness and the facing gate can be tuned against; --turntable also writes NAME_merged_turn_KK.png, the
 identity mesh (pose 0, no camera) with the merged texture.
+
+With --light (it needs --texture, as its five companions do) every bake is separated into an albedo and a light (op.light:
+Lambertian shading under second-order spherical harmonics, nine coefficients per colour channel, or one white light with
+--light_mono).  After the bake the posed normals are carried to the texels, the light is fitted in closed form under a
+constant-albedo assumption (--light_ridge L, default 0.001, on its non-constant coefficients; the fitted shading has
+weighted mean 1, so the albedo keeps the picture's exposure) and divided out of the bake (not below --light_floor S,
+default 0.05); padding and fill run on the albedo.  <stem>_texture.png, the one the .mtl names, is then the albedo;
+<stem>_texture_lit.png is the plain bake, padded likewise; <stem>_shading.png is the fitted light on a mid-grey head at the
+fit's resolution; <stem>.npz gains `light` [Cl, 9] and `light_residual`, the weighted rms over the fitted texels of what
+a constant albedo under the fitted light leaves of the bake (with --multiview also `texture_lit` beside `texture`, which is
+the albedo).  --texture_check draws albedo times light, so `rerender_error` keeps its meaning and is comparable with a run
+without --light, and writes the plain bake's error beside it (`rerender_error_lit`).  --turntable turns the normals with
+the mesh while the light stays fixed in the camera's frame, so the shading moves over the face.  --relight FILE (an .npy or
+text file of 9 or 9 C numbers) writes <stem>_relit.png, the fitted pose under that light, and the turntable frames use it.
+--texture_refine runs Adam on the albedo and the light together, the light in a second group with --light_lr (default
+0.005); the .npz holds `light`, the refined one, and `light_fit`, the closed-form one.  With --multiview every view has
+its own light, the views' albedos are what is merged, the merged check shades the merged albedo with each view's light,
+joint refinement keeps one albedo and V lights, the merged turntable uses view 0's light and NAME_identity.npz gains
+`lights` [V, Cl, 9].  The floor, the ridge and the light's learning rate are starting values, not tuned on any picture.
+Without --light nothing changes.
 
 With --multiview V the IMAGE arguments are taken in consecutive groups of V, each group V pictures of one subject (their
 count must be a multiple of V).  It implies --batch V: a group is fitted as one batched LatentInverter with
@@ -432,17 +453,20 @@ def landmark_outputs(inv, index, conf, listed, shape):
     return dict(more, landmarks=fit, landmarks_target=np.asarray(listed, np.float64), lmk_error=np.float64(err))
 
 
-def texture_rerender(tex, weight, views):
+def texture_rerender(tex, weight, views, light=None):
     """With views a list of (uvmap [1, S, S, 2], cover [1, S, S], target [1, C, S, S]), per view (image [1, C, S, S] over
     background -1, error, covered, counted): the texture tex [1, C, T, T] drawn on the view's uv map; error is the mean
     absolute difference to the view's target over the `counted` pixels, those that are covered and where the look-up of
-    the bake's weight [1, 1, T, T] is positive."""
-    from .op import texture
+    the bake's weight [1, 1, T, T] is positive.  light: per view (gamma [1, Cl, 9], normals [1, 3, S, S]); tex is then an
+    albedo and the image is op.light.shade of its look-up."""
+    from .op import light as lighting, texture
 
     out = []
     with torch.no_grad():
-        for uvmap, cover, target in views:
+        for i, (uvmap, cover, target) in enumerate(views):
             img = texture.sample(tex, uvmap, cover, -1.0)
+            if light is not None:
+                img = lighting.shade(img, light[i][1], cover, light[i][0], -1.0, -1.0)
             on = cover & (texture.sample(weight, uvmap, cover, 0.0)[:, 0] > 0)
             n = int(on.sum())
             err = float(((img - target).abs() * on.unsqueeze(1)).sum()) / max(n * int(img.shape[1]), 1)
@@ -450,14 +474,18 @@ def texture_rerender(tex, weight, views):
     return out
 
 
-def texture_refine(tex, views, steps, lr=0.02):
+def texture_refine(tex, views, steps, lr=0.02, light=None, light_lr=0.005):
     """(tex' [1, C, T, T], loss [STEPS]; the loss before every step) with views a list of (uvmap [1, S, S, 2], cover
     [1, S, S], target [1, C, S, S]): Adam (optim.FlatAdam) on the texture alone from tex, on the sum over the views' covered
     pixels of (render - target)^2; one texture for all views (Bt = 1).  The uv maps are fixed, so the tap list is built
     once; a texel no tap reaches has gradient 0 in every step and keeps its value bit for bit.  lr's default is a
-    starting value, not tuned on any trained checkpoint."""
+    starting value, not tuned on any trained checkpoint.
+    light: per view (gamma [1, Cl, 9], normals [1, 3, S, S]); tex is then an albedo, the render is op.light.shade of its
+    look-up, and Adam runs on the albedo and the V lights together, the lights as a second FlatAdam group with light_lr
+    (0.005: a starting value, not tuned) whose gradient the shading node writes into the group's buffer (ggamma_out; on
+    the host it comes through autograd).  Returns (tex', loss, gamma' [V, Cl, 9])."""
     from . import optim
-    from .op import texture
+    from .op import light as lighting, texture
 
     uvmap = torch.cat([u for u, _, _ in views], 0).contiguous()
     cover = torch.cat([c for _, c, _ in views], 0).contiguous()
@@ -470,14 +498,38 @@ def texture_refine(tex, views, steps, lr=0.02):
     texture.tap_plan(uvmap, cover, tuple(p.shape[-2:]), 1)
     on = cover.unsqueeze(1).to(p.dtype)
     losses = []
+    if light is not None:
+        normals = torch.cat([n for _, n in light], 0).contiguous()
+        q = torch.cat([gam for gam, _ in light], 0).detach().clone().contiguous()
+        direct = lighting.native_ok(p, normals, q)                   # the kernels write the light's gradient themselves
+        q.requires_grad_(not direct)
+        light_g = torch.zeros(optim.flat_layout([q])[1], dtype=q.dtype, device=q.device)
+        light_opt = optim.FlatAdam([q], light_g, lr=float(light_lr), step_from=opt)
+        light_slot = optim.flat_views(light_g, [q], [0])[0]
     for _ in range(int(steps)):
-        diff = (texture.sample(p, uvmap, cover, 0.0) - target) * on
-        loss = (diff * diff).sum()
-        (g,) = torch.autograd.grad(loss, p)
+        if light is None:
+            diff = (texture.sample(p, uvmap, cover, 0.0) - target) * on
+            loss = (diff * diff).sum()
+            (g,) = torch.autograd.grad(loss, p)
+        else:
+            flat = texture.sample(p, uvmap, cover, -1.0)
+            render = lighting.shade(flat, normals, cover, q, -1.0, -1.0, ggamma_out=light_g if direct else None)
+            diff = (render - target) * on
+            loss = (diff * diff).sum()
+            if direct:
+                (g,) = torch.autograd.grad(loss, p)
+            else:
+                g, gq = torch.autograd.grad(loss, (p, q))
+                light_slot.copy_(gq)
         slot.copy_(g)
         opt.step()
+        if light is not None:
+            light_opt.step()
         losses.append(loss.detach())
-    return p.detach().clone(), torch.stack(losses).cpu().numpy().astype(np.float64)
+    history = torch.stack(losses).cpu().numpy().astype(np.float64)
+    if light is not None:
+        return p.detach().clone(), history, q.detach().clone()
+    return p.detach().clone(), history
 
 
 class TextureGuide:
@@ -485,11 +537,23 @@ class TextureGuide:
     sample and writes its files."""
 
     def __init__(self, face, size, uv_file=None, source="picture", facing="0.1,0.4", passes=8, fill="mean", check=False,
-                 turntable=0, turntable_yaw=30.0, refine=0, refine_lr=0.02):
+                 turntable=0, turntable_yaw=30.0, refine=0, refine_lr=0.02, light=None):
+        """light: None (the texture is the plain bake) or a dict with any of mono (one white light), floor (unshade's),
+        ridge (the fit's), lr (the light's learning rate under refinement) and relight (a file of 9 or 9 C numbers):
+        every bake is then separated into an albedo and a light (op.light)."""
         from .face_model import load_uv, uv_layout
         from .op import texture
 
         model, tri = face
+        self.light = None
+        if light is not None:
+            self.light = dict(mono=bool(light.get("mono", False)), floor=float(light.get("floor", 0.05)),
+                              ridge=float(light.get("ridge", 1e-3)), lr=float(light.get("lr", 0.005)), relight=None)
+            if not self.light["floor"] > 0 or not self.light["ridge"] >= 0 or not self.light["lr"] > 0:
+                raise SystemExit("reconstruct: --light_floor and --light_lr are positive, --light_ridge is not negative")
+            if light.get("relight"):
+                self.light["relight"] = self.read_light(light["relight"])
+        self.lights = []                                                 # (--multiview: the views' (gamma, normal map))
         self.size = int(size)
         if not 1 <= self.size <= 8192:
             raise SystemExit("reconstruct: --texture T lies in [1, 8192]")
@@ -537,6 +601,44 @@ class TextureGuide:
 
     renders = property(lambda self: self.check or self.refine_steps > 0)
 
+    @staticmethod
+    def read_light(path):
+        """A light from an .npy or a text file of 9 numbers (one white light) or 9 C: float32 [Cl, 9] on the host."""
+        try:
+            values = np.load(path) if path.endswith(".npy") else np.loadtxt(path)
+            values = np.asarray(values, np.float64).reshape(-1)
+        except (OSError, ValueError) as e:
+            raise SystemExit("reconstruct: --relight %s: %s" % (path, e))
+        if values.size == 0 or values.size % 9 or not np.isfinite(values).all():
+            raise SystemExit("reconstruct: --relight takes a file of 9 or 9 C finite numbers, got %d" % values.size)
+        return torch.from_numpy(values.reshape(-1, 9).astype(np.float32))
+
+    def separate(self, tex, weight, n, tri):
+        """(albedo [1, C, T, T], gamma [1, Cl, 9], residual): the bake tex with its weight split into an albedo and the
+        closed-form light of op.light.fit on the texels' normals (the camera-space vertex normals n [1, nv, 3] carried
+        through the texel map); residual is the weighted rms of tex - shade(mean intensity, normals, gamma) over the
+        fitted texels: what a constant albedo under the fitted light leaves unexplained."""
+        from .op import light as lighting
+
+        with torch.no_grad():
+            tn = lighting.texel_attribute(n.to(tex.dtype).contiguous(), tri, self.face, self.coeff)
+            gamma = lighting.fit(tex, tn, weight, mono=self.light["mono"], ridge=self.light["ridge"])
+            on = (weight[:, 0] > 0).contiguous()
+            albedo = lighting.unshade(tex, tn, on, gamma, floor=self.light["floor"])
+            total = weight.sum().clamp_min(1e-12)
+            mean = ((tex * weight).sum((2, 3), keepdim=True) / total).expand_as(tex).contiguous()
+            diff = (tex - lighting.shade(mean, tn, on, gamma, -1.0, -1.0)) * on.unsqueeze(1)
+            residual = float(torch.sqrt((weight * diff * diff).sum() / (total * tex.shape[1])))
+        return albedo, gamma, residual
+
+    def normals_at(self, vd, n, tri, size):
+        """The normal map [1, 3, S, S] the shading reads: the camera-space normals n drawn over the mesh vd as the camera
+        sees it (projected when there is a camera)."""
+        from .op import light as lighting
+
+        with torch.no_grad():
+            return lighting.normal_map(vd.contiguous(), n.to(vd.dtype).contiguous(), tri, size)
+
     def view(self, inv, index):
         """(uvmap [1, S, S, 2], cover [1, S, S], target [1, 3, S, S]) of sample `index`: the uv map of the fitted mesh at the
         fitted pose and camera at the fit's resolution, and the fit's target.  The mesh is fixed from here on, so the tap
@@ -550,18 +652,24 @@ class TextureGuide:
                                           self._layout[2])
         return uvmap, cover, inv.target[k].to(uvmap.dtype).contiguous()
 
-    def checked(self, tex, weight, views, prefix=""):
+    def checked(self, tex, weight, views, prefix="", light=None):
         """(tex as it is written, .npz entries, the re-rendered images): --texture_refine and --texture_check on the padded
-        texture tex over `views`; the entries' names start with `prefix`."""
+        texture tex over `views`; the entries' names start with `prefix`.  light: per view [gamma, normal map] (tex is an
+        albedo); refinement replaces the gammas in place by the refined ones."""
         entries, before = {}, None
         if self.check and self.refine_steps:
-            before = texture_rerender(tex, weight, views)
-        if self.refine_steps:
+            before = texture_rerender(tex, weight, views, light)
+        if self.refine_steps and light is None:
             tex, loss = texture_refine(tex, views, self.refine_steps, self.refine_lr)
             entries[prefix + "texture_refine_loss"] = loss
+        elif self.refine_steps:
+            tex, loss, gammas = texture_refine(tex, views, self.refine_steps, self.refine_lr, light, self.light["lr"])
+            entries[prefix + "texture_refine_loss"] = loss
+            for i, pair in enumerate(light):
+                pair[0] = gammas[i:i + 1].contiguous()
         images = []
         if self.check:
-            after = texture_rerender(tex, weight, views)
+            after = texture_rerender(tex, weight, views, light)
             one = len(views) == 1 and not prefix
             pick = (lambda col: np.float64(col[0])) if one else (lambda col: np.asarray(col, np.float64))
             entries[prefix + "rerender_error"] = pick([r[1] for r in after])
@@ -572,11 +680,12 @@ class TextureGuide:
             images = [r[0] for r in after]
         return tex, entries, images
 
-    def turn(self, tex, v, tri, size, kappa, out_dir, prefix):
+    def turn(self, tex, v, tri, size, kappa, out_dir, prefix, light=None):
         """Writes the --turntable renders <prefix>_turn_KK.png: the mesh v [1, nv, 3] turned about the vertical axis through
         its centroid by yaws spaced evenly in [-DEG, DEG] (one render: 0), projected by the camera kappa [1] when there is
-        one, drawn with tex over background -1."""
-        from .op import camera, texture
+        one, drawn with tex over background -1.  light = (gamma [1, Cl, 9], n [1, nv, 3]): tex is an albedo; the normals
+        turn with the mesh and the light stays fixed in the camera's frame, so the shading moves over the head."""
+        from .op import camera, light as lighting, texture
 
         n = self.turntable
         yaws = np.linspace(-self.turntable_yaw, self.turntable_yaw, n) if n > 1 else np.zeros(1)
@@ -587,8 +696,11 @@ class TextureGuide:
                 turned = torch.matmul(v - centre, utils_3d.euler_mat(angle)) + centre
                 if kappa is not None:
                     turned = camera.project(turned.contiguous(), kappa)
-                img, _ = texture.render(turned.contiguous(), tri, self._layout[0], self.tri_uv, tex, size, -1.0,
-                                        self._layout[2])
+                img, cover = texture.render(turned.contiguous(), tri, self._layout[0], self.tri_uv, tex, size, -1.0,
+                                            self._layout[2])
+                if light is not None:
+                    nmap = self.normals_at(turned, torch.matmul(light[1].to(v.dtype), utils_3d.euler_mat(angle)), tri, size)
+                    img = lighting.shade(img, nmap, cover, light[0], -1.0, -1.0)
                 generate.save_image(img.clamp(-1, 1).cpu(), os.path.join(out_dir, "%s_turn_%02d.png" % (prefix, j)))
 
     @staticmethod
@@ -625,16 +737,53 @@ class TextureGuide:
             cover = float(texture.coverage(self.face, weight)[0])
             out = self.finish(tex, weight)
         more = {}
-        if self.renders:
+        lit = pair = None
+        if self.light is not None:
+            # the bake splits into an albedo and a light; from here on `out` is the albedo and `lit` the plain bake
+            lit, baked = out, tex
+            tex, gamma, residual = self.separate(baked, weight, no, tri)
+            with torch.no_grad():
+                out = self.finish(tex, weight)
+            pair = [gamma, self.normals_at(v, no, tri, self.view_size)]
+            more = dict(light_residual=np.float64(residual))
+        if self.renders or (self.light is not None and self.light["relight"] is not None):
             views = [self.view(inv, index)]
-            out, more, images = self.checked(out, weight, views)
+        if self.renders:
+            out, entries, images = self.checked(out, weight, views, light=None if pair is None else [pair])
+            more.update(entries)
             if images:
                 generate.save_image(images[0].clamp(-1, 1).cpu(), os.path.join(out_dir, stem + "_rerender.png"))
+            if pair is not None and self.check:
+                more["rerender_error_lit"] = np.float64(texture_rerender(lit, weight, views)[0][1])
             if keep is not None:
                 self.views.append(views[0])
+        shown = pair
+        if pair is not None:
+            from .op import light as lighting
+
+            more["light"] = pair[0][0].cpu().numpy()
+            if self.refine_steps:
+                more["light_fit"] = gamma[0].cpu().numpy()
+            if keep is not None:
+                self.lights.append([gamma, pair[1]])                     # (the closed-form light: what the albedo was made with)
+            with torch.no_grad():
+                drawn = (pair[1] != 0).any(1).contiguous()
+                grey = lighting.shade(torch.zeros_like(pair[1]), pair[1], drawn, pair[0], -1.0, -1.0)
+                generate.save_image(grey.clamp(-1, 1).cpu(), os.path.join(out_dir, stem + "_shading.png"))
+                generate.save_image(lit.clamp(-1, 1).cpu(), os.path.join(out_dir, stem + "_texture_lit.png"))
+                if self.light["relight"] is not None:
+                    other = self.light["relight"].to(out.device)
+                    if other.shape[0] not in (1, out.shape[1]):
+                        raise SystemExit("reconstruct: --relight holds %d lights, the texture has %d channels"
+                                         % (other.shape[0], out.shape[1]))
+                    shown = [other[None].contiguous(), pair[1]]
+                    uvmap, seen, _ = views[0]
+                    relit = lighting.shade(texture.sample(out, uvmap, seen, -1.0), pair[1], seen, shown[0], -1.0, -1.0)
+                    generate.save_image(relit.clamp(-1, 1).cpu(), os.path.join(out_dir, stem + "_relit.png"))
         if self.turntable:
             self.turn(out, vo.contiguous(), tri, int(inv.target.shape[-1]),
-                      inv.camera.detach()[k].contiguous() if inv.camera is not None else None, out_dir, stem)
+                      inv.camera.detach()[k].contiguous() if inv.camera is not None else None, out_dir, stem,
+                      None if shown is None else (shown[0], no.contiguous()))
         generate.save_image(out.clamp(-1, 1).cpu(), os.path.join(out_dir, stem + "_texture.png"))
         grey = np.round(weight[0, 0].cpu().numpy().astype(np.float64) * 255.0).astype(np.uint8)
         try:
@@ -647,7 +796,9 @@ class TextureGuide:
         utils_3d.save_textured_obj(os.path.join(out_dir, stem + "_textured.obj"), vo[0].cpu().numpy(), tri.cpu().numpy(),
                                    self.uv.numpy(), self.tri_uv.numpy(), no[0].cpu().numpy(), stem + "_texture.png")
         if keep is not None:
-            keep.append((tex, weight))
+            keep.append((tex, weight))                                   # (with a light: the view's albedo is what is merged)
+            if pair is not None:
+                more["texture_lit"] = baked[0].cpu().numpy()
             return dict(more, texture_coverage=np.float64(cover), texture=tex[0].cpu().numpy(),
                         texture_weight=weight[0, 0].cpu().numpy())
         return dict(more, texture_coverage=np.float64(cover))
@@ -663,12 +814,22 @@ class TextureGuide:
             cover = float(texture.coverage(self.face, weight)[0])
             out = self.finish(tex, weight)
         more = {}
+        lights = None
+        if self.light is not None:
+            # every view keeps its own light; the merged albedo is shaded with each view's (and refined under all of them)
+            lights, self.lights = self.lights[-len(bakes):], []
         if self.renders:
             # the merged texture on every view's own mesh and target: the number the merge is tuned against
             views, self.views = self.views[-len(bakes):], []
-            out, more, _ = self.checked(out, weight, views, "merged_")
+            out, more, _ = self.checked(out, weight, views, "merged_", light=lights)
+        if lights is not None:
+            more["lights"] = torch.cat([pair[0] for pair in lights], 0).cpu().numpy()
         if self.turntable:
-            self.turn(out, v, tri, int(self.view_size), None, out_dir, name + "_merged")
+            shown = None
+            if lights is not None:
+                gamma = lights[0][0] if self.light["relight"] is None else self.light["relight"].to(v.device)[None].contiguous()
+                shown = (gamma, n)
+            self.turn(out, v, tri, int(self.view_size), None, out_dir, name + "_merged", shown)
         generate.save_image(out.clamp(-1, 1).cpu(), os.path.join(out_dir, name + "_merged_texture.png"))
         grey = np.round(weight[0, 0].cpu().numpy().astype(np.float64) * 255.0).astype(np.uint8)
         self.save_grey(grey, os.path.join(out_dir, name + "_merged_texture_weight.png"))
@@ -861,6 +1022,22 @@ def main(argv=None):
                          "(or merge); the refined texture is the one written")
     ap.add_argument("--texture_lr", type=float, default=None, metavar="LR",
                     help="with --texture_refine: Adam's learning rate; a starting value, not tuned [0.02]")
+    ap.add_argument("--light", action="store_true",
+                    help="with --texture: separate every bake into an albedo and a light (second-order spherical "
+                         "harmonics, fitted in closed form); <stem>_texture.png is then the albedo")
+    ap.add_argument("--light_mono", action="store_true",
+                    help="with --light: one white light for all colour channels instead of one per channel")
+    ap.add_argument("--light_floor", type=float, default=None, metavar="S",
+                    help="with --light: the shading is not divided out below S; a starting value, not tuned [0.05]")
+    ap.add_argument("--light_ridge", type=float, default=None, metavar="L",
+                    help="with --light: the ridge on the light's non-constant coefficients, relative to the fitted "
+                         "weight; a starting value, not tuned [0.001]")
+    ap.add_argument("--light_lr", type=float, default=None, metavar="LR",
+                    help="with --light and --texture_refine: Adam's learning rate of the light; a starting value, not "
+                         "tuned [0.005]")
+    ap.add_argument("--relight", default=None, metavar="FILE",
+                    help="with --light: an .npy or text file of 9 or 9 C numbers, another light; <stem>_relit.png is the "
+                         "fitted pose under it and the --turntable frames use it")
     cam = ap.add_mutually_exclusive_group()
     cam.add_argument("--camera_distance", type=float, default=None, metavar="D",
                      help="perspective camera at distance D > 0 from the plane z = 0 of pose space, in half-picture-widths "
@@ -913,6 +1090,14 @@ def main(argv=None):
         ap.error("--uv, --texture_from, --texture_facing, --texture_pad and --texture_fill need --texture")
     if args.texture is None and (args.texture_check or args.turntable is not None or args.texture_refine is not None):
         ap.error("--texture_check, --turntable and --texture_refine need --texture")
+    if args.texture is None and (args.light or args.light_mono or args.light_floor is not None
+                                 or args.light_ridge is not None or args.light_lr is not None or args.relight):
+        ap.error("--light, --light_mono, --light_floor, --light_ridge, --light_lr and --relight need --texture")
+    if not args.light and (args.light_mono or args.light_floor is not None or args.light_ridge is not None
+                           or args.light_lr is not None or args.relight):
+        ap.error("--light_mono, --light_floor, --light_ridge, --light_lr and --relight need --light")
+    if args.light_lr is not None and args.texture_refine is None:
+        ap.error("--light_lr needs --texture_refine")
     if args.turntable_yaw is not None and args.turntable is None:
         ap.error("--turntable_yaw needs --turntable")
     if args.texture_lr is not None and args.texture_refine is None:
@@ -958,7 +1143,11 @@ def main(argv=None):
                             check=args.texture_check, turntable=args.turntable or 0,
                             turntable_yaw=30.0 if args.turntable_yaw is None else args.turntable_yaw,
                             refine=args.texture_refine or 0,
-                            refine_lr=0.02 if args.texture_lr is None else args.texture_lr)
+                            refine_lr=0.02 if args.texture_lr is None else args.texture_lr,
+                            light=({k: v for k, v in (("mono", args.light_mono), ("floor", args.light_floor),
+                                                      ("ridge", args.light_ridge), ("lr", args.light_lr),
+                                                      ("relight", args.relight)) if v is not None}
+                                   if args.light else None))
                if args.texture is not None else None)
     shared = None
     if args.multiview is not None:
