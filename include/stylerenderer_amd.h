@@ -1050,6 +1050,55 @@ int sr_texture_sample_bwd_tex(float* gtex, const float* gout, const float* uv, c
                               const int32_t* entries, int64_t B, int64_t Bt, int64_t C, int64_t H, int64_t W, int64_t Th,
                               int64_t Tw, sr_stream_t stream);
 
+/* The mip-mapped texture look-up (definition: stylerenderer_amd/op/texture.py, mip_build_composite, mip_lod_composite,
+ * mip_sample_composite), csrc/texture_mip.hip.  A (Th, Tw) texture has up to Lmax levels: level 0 is the texture, level
+ * l + 1 has half of each side and exists while both sides of level l are even; 1 <= L <= Lmax of them are used.  The
+ * pyramid pyr [Bt, C, P] holds level l (sides Th >> l, Tw >> l) at offset_l = sum_{j < l} h_j w_j of every plane, P the sum
+ * over all L levels.  Every step is one float32 operation in the stated order, no contraction.
+ * sr_mip_build_fwd: pyr from tex [N, Th, Tw], N = Bt C planes: level 0 a copy,
+ *     p_{l+1}[y, x] = ((p_l[2y, 2x] + p_l[2y, 2x+1]) + (p_l[2y+1, 2x] + p_l[2y+1, 2x+1])) 0.25
+ *   A workgroup reduces a 32 x 32 tile of a source level by up to five levels through LDS; one launch per five levels,
+ *   each reading the last level the one before wrote.  Every element of pyr is written.
+ * sr_mip_build_bwd: gtex [Bt, C, Th, Tw] from gpyr [Bt, C, P], per level-0 texel (y, x):
+ *     t = gpyr_{L-1}[y >> (L-1), x >> (L-1)];  t = gpyr_l[y >> l, x >> l] + 0.25 t for l = L-2 .. 0;  gtex[y, x] = t
+ *   One launch, a lane per texel for all channels: a gather, no scatter.
+ * sr_mip_lod: lod [B, H, W] of uv [B, H, W, 2], cover uint8 [B, H, W].  A pixel is live with cover != 0 and finite (u, v);
+ *   one that is not gets 0.  Along x over the neighbours n = (y, x + 1), (y, x - 1) inside the picture and live:
+ *     du = (u_n - u) Tw;  dv = (v_n - v) Th;  d = du du + dv dv;  qx = min d (0 with no such neighbour);  qy along y
+ *     rho = sqrt(max(qx, qy)), correctly rounded;  l = the largest integer in [0, L-1] with 2^l <= rho
+ *     lambda = rho < 1 ? 0 : l == L-1 ? L-1 : l + (rho 2^-l - 1);  lod = clamp(lambda + bias, 0, L-1)
+ *   One launch, a lane per four consecutive pixels of a row; 16-byte stores when W % 4 == 0 and lod is 16-byte aligned.
+ * sr_mip_sample_fwd: out [B, C, H, W].  Bt == B or 1.  For a live pixel lod is clamped to [0, L-1] (NaN: 0),
+ *     l0 = floor(lod), l1 = min(l0 + 1, L-1), f = lod - l0;  c_l = sr_texture_sample_fwd's blend on level l with
+ *     (Th >> l, Tw >> l);  out = f == 0 ? c_l0 : (1 - f) c_l0 + f c_l1   (f == 0: level l1 is not read)
+ *   Any other pixel gets `background`.  One launch, sr_texture_sample_fwd's staging.
+ * sr_mip_sample_bwd_uv: guv [B, H, W, 2] from gout: guv_l is sr_texture_sample_bwd_uv's formula on level l (its channel
+ *   sums in channel order, its inx / iny gating with the level's sides);  guv = f == 0 ? guv_l0 : (1 - f) guv_l0 + f guv_l1.
+ * sr_mip_sample_bwd_pyr: gpyr [Bt, C, P] from gout and the tap list (off int32 [Bt P + 2], entries int32 [8 B H W]: a CSR
+ *   over the keys bt P + offset_l + ty (Tw >> l) + tx whose entries ((b H + y) W + x) 8 + k ascend within a key; k = 0..3
+ *   are the taps of l0 in sr_texture_sample_bwd_tex's order with the weights (1 - f) w_k, k = 4..7 those of l1 with
+ *   f w_{k-4}; the bucket after the last key holds the entries without a tap; op.texture.mip_tap_plan builds it):
+ *     gpyr[key] = the sum from 0, in list order, of weight g_c[b, y, x]
+ *   One launch, a lane per pyramid element for all channels; every element is written and one without taps gets exactly
+ *   0.  Offsets and entries outside the list or the picture are skipped, never followed.
+ * Th, Tw >= 1 and at most 2^20, Th Tw < 2^31; N, B, H or W of 0 writes nothing (bwd_pyr: zeros) and returns 0; 8 B H W and
+ * Bt P must be below 2^31.  No atomics, no scratch, no memset, no allocation, no host read: all run under graph capture on
+ * `stream`; reruns are bit-identical. */
+int sr_mip_build_fwd(float* pyr, const float* tex, int64_t N, int64_t Th, int64_t Tw, int64_t L, sr_stream_t stream);
+int sr_mip_build_bwd(float* gtex, const float* gpyr, int64_t Bt, int64_t C, int64_t Th, int64_t Tw, int64_t L,
+                     sr_stream_t stream);
+int sr_mip_lod(float* lod, const float* uv, const uint8_t* cover, int64_t B, int64_t H, int64_t W, int64_t Th, int64_t Tw,
+               int64_t L, float bias, sr_stream_t stream);
+int sr_mip_sample_fwd(float* out, const float* pyr, const float* uv, const uint8_t* cover, const float* lod, int64_t B,
+                      int64_t Bt, int64_t C, int64_t H, int64_t W, int64_t Th, int64_t Tw, int64_t L, float background,
+                      sr_stream_t stream);
+int sr_mip_sample_bwd_uv(float* guv, const float* gout, const float* pyr, const float* uv, const uint8_t* cover,
+                         const float* lod, int64_t B, int64_t Bt, int64_t C, int64_t H, int64_t W, int64_t Th, int64_t Tw,
+                         int64_t L, sr_stream_t stream);
+int sr_mip_sample_bwd_pyr(float* gpyr, const float* gout, const float* uv, const uint8_t* cover, const float* lod,
+                          const int32_t* off, const int32_t* entries, int64_t B, int64_t Bt, int64_t C, int64_t H,
+                          int64_t W, int64_t Th, int64_t Tw, int64_t L, sr_stream_t stream);
+
 /* The shared identity of a multi-view fit (definition: stylerenderer_amd/op/share.py), csrc/share.hip.
  * sr_share_rows: g [B, d] in place: s[j] = ((g[0, j] + g[1, j]) + g[2, j]) + ... in row order, then g[b, j] = s[j] for
  *   every b, for the columns j < k (1 <= k <= d); the other columns are not touched.  One launch, one lane per column.  No

@@ -166,6 +166,12 @@ SIGNATURES = {
     "sr_texture_sample_fwd": (_i, [_p] * 4 + [_l] * 7 + [_f, _p]),
     "sr_texture_sample_bwd_uv": (_i, [_p] * 5 + [_l] * 7 + [_p]),
     "sr_texture_sample_bwd_tex": (_i, [_p] * 6 + [_l] * 7 + [_p]),
+    "sr_mip_build_fwd": (_i, [_p] * 2 + [_l] * 4 + [_p]),
+    "sr_mip_build_bwd": (_i, [_p] * 2 + [_l] * 5 + [_p]),
+    "sr_mip_lod": (_i, [_p] * 3 + [_l] * 6 + [_f, _p]),
+    "sr_mip_sample_fwd": (_i, [_p] * 5 + [_l] * 8 + [_f, _p]),
+    "sr_mip_sample_bwd_uv": (_i, [_p] * 6 + [_l] * 8 + [_p]),
+    "sr_mip_sample_bwd_pyr": (_i, [_p] * 7 + [_l] * 8 + [_p]),
     "sr_share_rows": (_i, [_p] + [_l] * 3 + [_p]),
     "sr_camera_fwd": (_i, [_p] * 5 + [_l, _l, _p]),
     "sr_camera_bwd": (_i, [_p] * 6 + [_l, _l, _p]),

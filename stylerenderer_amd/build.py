@@ -42,6 +42,7 @@ SOURCES = [
     ("region.hip", EXACT),
     ("texture.hip", EXACT),
     ("texture_sample.hip", EXACT),
+    ("texture_mip.hip", EXACT),
     ("share.hip", EXACT),
     ("camera.hip", EXACT),
     ("light.hip", EXACT),

@@ -56,7 +56,31 @@ has its centre at u = (tx + 1/2) / Tw, v = 1 - (ty + 1/2) / Th: row 0 is the top
                          (1 - fx) fy, fx fy, one product each.  Two taps of a pixel that clamp onto one texel are added
                          separately; a texel no tap reaches gets exactly 0; with Bt = 1 the sum runs over all B views.
               The texture's gradient is a gather over a tap list (`tap_plan`), not a scatter: no atomics, one order.
-  render      `uv_map` followed by `sample`.
+  render      `uv_map` followed by `sample` (or, with mip = a bias, by `sample_mip`).
+
+  The mip-mapped look-up (csrc/texture_mip.hip), for a texture drawn smaller than it is (DESIGN.md 7k''):
+  mip_layout  ((offset, h, w), ...) of the levels of a (Th, Tw) texture: level 0 is the texture, level l + 1 has half of
+              each side and exists while both sides of level l are even, so every level's texel grid is nested exactly in
+              the one below (no odd-size filter, no uv shift).  The pyramid is packed [Bt, C, P], P = sum h_l w_l.
+  mip_build   pyr from tex: level 0 a copy, p_{l+1}[y, x] = ((p_l[2y, 2x] + p_l[2y, 2x+1]) + (p_l[2y+1, 2x] +
+              p_l[2y+1, 2x+1])) 0.25.  Backward per level-0 texel, a gather: t = g_{L-1}[y >> (L-1), x >> (L-1)], then
+              t = g_l[y >> l, x >> l] + 0.25 t for l = L-2 .. 0, grad_tex[y, x] = t.
+  mip_lod     lod [B, H, W], a constant of the look-up (no gradient).  Along x, over the neighbours n = (y, x + 1) and
+              (y, x - 1) that lie inside the picture and are live:  du = (u_n - u) Tw, dv = (v_n - v) Th,
+              d = du du + dv dv;  qx = the minimum of d (0 with no usable neighbour), qy likewise along y;
+              q = max(qx, qy), rho = sqrt(q) rounded once;  l = the largest integer in [0, L-1] with 2^l <= rho;
+              lambda = 0 for rho < 1, L-1 for l = L-1, else l + (rho 2^-l - 1);  lod = clamp(lambda + bias, 0, L-1).
+              The minimum over the two sides keeps a chart seam, which runs between two pixels, from forcing the
+              coarsest level: one side of a pixel usually lies in its own chart.  No log2: it is not reproducible
+              between host and device; the piecewise-linear fraction stays within 0.09 levels of it.
+  mip_sample  out [B, C, H, W] from pyr, a uv map and a lod.  lod is clamped to [0, L-1] (NaN counts as 0);
+              l0 = floor(lod), l1 = min(l0 + 1, L-1), f = lod - l0;  c_l = `sample`'s definition on level l with
+              (Th_l, Tw_l);  out = c_l0 where f == 0 (level l1 is then neither read nor given a gradient), else
+              (1 - f) c_l0 + f c_l1.  grad_uv = guv_l0 where f == 0, else (1 - f) guv_l0 + f guv_l1, guv_l `sample`'s
+              formula on level l.  grad_pyr is the ordered sum over the 8-tap list of `mip_tap_plan`: k = 0..3 the
+              taps of l0 with the weights (1 - f) w_k, k = 4..7 those of l1 with f w_{k-4}.  lod == 0 everywhere is
+              `sample` bit for bit, forward and both gradients.
+  sample_mip  `mip_build`, `mip_lod` (unless a lod is given) and `mip_sample` in a row.
 
 CPU tensors and float64 take the torch composites `bake_composite`, `pad_host`, `merge_composite` and `sample_composite`,
 which are the definition.  Float32 device tensors take sr_texture_bake / sr_texture_pad / sr_texture_merge through the C ABI: one launch
@@ -714,9 +738,429 @@ def sample(tex, uvmap, cover, background=0.0):
     return _Sample.apply(tex.contiguous(), uvmap.contiguous(), cover, _background(background, tex.dtype), kernels)
 
 
-def render(v, tri, uv, tri_uv, tex, size, background=0.0, keep=None):
+def render(v, tri, uv, tri_uv, tex, size, background=0.0, keep=None, mip=None):
     """(image [B, C, H, W], cover bool [B, H, W]): the posed mesh v [B, nv, 3], tri [nf, 3] with the layout uv, tri_uv
     drawn with the texture tex [B or 1, C, Th, Tw] over `background`: `uv_map` followed by `sample`.  Differentiable in tex
-    and, through the uv map and the rasterizer, in v."""
+    and, through the uv map and the rasterizer, in v.  mip: None, or the lod bias of the mip-mapped look-up
+    (`sample_mip` in `sample`'s place)."""
     uvmap, cover = uv_map(v, tri, uv, tri_uv, size, keep)
+    if mip is not None:
+        return sample_mip(tex, uvmap, cover, bias=float(mip), background=background), cover
     return sample(tex, uvmap, cover, background), cover
+
+
+# ---- the mip-mapped look-up --------------------------------------------------------------------------------------------
+_MIP_PLAN_CACHE = DerivedCache(8)
+MIP_MAX_LEVELS = 21                                                          # (sides up to 2^20, as the kernels take)
+
+
+def mip_layout(size, levels=None):
+    """((offset, h, w), ...) of the pyramid of a (Th, Tw) texture: level 0 is (Th, Tw) at offset 0; level l + 1 has half
+    of each side and exists while both sides of level l are even and, with `levels` given, while l + 1 < levels.  512^2
+    has 10 levels, (12, 20) 3, (33, 65) 1, (128, 64) 7 (the last is 2 x 1).  Level l starts at offset_l of the packed
+    [Bt, C, P] pyramid, P = offset + h w of the last level."""
+    th, tw = _hw(size)
+    if th < 1 or tw < 1:
+        raise ValueError("mip_layout: size must be positive, got (%d, %d)" % (th, tw))
+    if levels is not None and int(levels) < 1:
+        raise ValueError("mip_layout: levels must be at least 1, got %r" % (levels,))
+    out, off, h, w = [], 0, th, tw
+    while True:
+        out.append((off, h, w))
+        off += h * w
+        if h % 2 or w % 2 or len(out) >= MIP_MAX_LEVELS or (levels is not None and len(out) >= int(levels)):
+            break
+        h, w = h // 2, w // 2
+    return tuple(out)
+
+
+def _mip_total(layout):
+    return layout[-1][0] + layout[-1][1] * layout[-1][2]
+
+
+def _layout_of(size, p):
+    """The layout of a packed pyramid of P elements per plane over a (Th, Tw) texture."""
+    full = mip_layout(size)
+    for n in range(1, len(full) + 1):
+        if _mip_total(full[:n]) == int(p):
+            return full[:n]
+    raise ValueError("mip: a pyramid of %d elements per plane is none of a %s texture" % (int(p), tuple(_hw(size))))
+
+
+def _mip_build_forward(tex, layout):
+    bt, c_n = int(tex.shape[0]), int(tex.shape[1])
+    parts, cur = [tex.reshape(bt, c_n, -1)], tex
+    for _ in layout[1:]:
+        cur = ((cur[..., 0::2, 0::2] + cur[..., 0::2, 1::2]) + (cur[..., 1::2, 0::2] + cur[..., 1::2, 1::2])) * 0.25
+        parts.append(cur.reshape(bt, c_n, -1))
+    return torch.cat(parts, 2)
+
+
+def _mip_build_backward(g, layout):
+    """grad_tex [Bt, C, Th, Tw] of the gradient g [Bt, C, P] of the pyramid: the stated chain from the top level down.
+    t_l is held per texel of level l: all level-0 texels under one of them share its value."""
+    bt, c_n = int(g.shape[0]), int(g.shape[1])
+    t = None
+    for off, h, w in reversed(layout):
+        gl = g[..., off:off + h * w].reshape(bt, c_n, h, w)
+        t = gl if t is None else gl + 0.25 * t.repeat_interleave(2, 2).repeat_interleave(2, 3)
+    return t if len(layout) > 1 else t.clone()
+
+
+class _MipBuild(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tex, n_levels, kernels):
+        tc = tex.contiguous()
+        bt, c_n, th, tw = (int(x) for x in tc.shape)
+        ctx.kernels, ctx.size, ctx.n_levels = kernels, (th, tw), n_levels
+        layout = mip_layout((th, tw), n_levels)
+        if not kernels:
+            return _mip_build_forward(tc, layout)
+        pyr = torch.empty((bt, c_n, _mip_total(layout)), dtype=tc.dtype, device=tc.device)
+        native(tc).sr_mip_build_fwd(pyr, tc, bt * c_n, th, tw, len(layout))
+        return pyr
+
+    @staticmethod
+    def backward(ctx, g):
+        layout = mip_layout(ctx.size, ctx.n_levels)
+        if torch.is_grad_enabled() or not ctx.kernels:
+            return _mip_build_backward(g, layout), None, None
+        g = g.contiguous()
+        bt, c_n = int(g.shape[0]), int(g.shape[1])
+        gtex = torch.empty((bt, c_n) + ctx.size, dtype=g.dtype, device=g.device)
+        native(g).sr_mip_build_bwd(gtex, g, bt, c_n, ctx.size[0], ctx.size[1], len(layout))
+        return gtex, None, None
+
+
+def _check_mip_tex(tex, name):
+    if tex.dim() != 4 or not tex.is_floating_point() or min(tex.shape[1:]) < 1:
+        raise ValueError("%s: tex must be a floating-point [Bt, C, Th, Tw], got %s %s" % (name, tex.dtype, tuple(tex.shape)))
+
+
+def mip_build_composite(tex, levels=None):
+    """The defining tensor algebra of `mip_build`, in tex's float type, as an autograd node with the stated backward."""
+    _check_mip_tex(tex, "mip_build")
+    return _MipBuild.apply(tex, None if levels is None else int(levels), False)
+
+
+def mip_build(tex, levels=None):
+    """pyr [Bt, C, P]: the mip pyramid of tex [Bt, C, Th, Tw] in `mip_layout`'s packing: level 0 a copy of tex, every
+    further level the 2 x 2 mean of the one below in the order ((a + b) + (c + d)) 0.25.  Differentiable in tex; the
+    backward is a gather per level-0 texel over its ancestors, one order and no scatter.  Device float32 runs
+    sr_mip_build_fwd (a launch per five levels) and sr_mip_build_bwd (one launch), nothing allocated by a launch and
+    nothing read back; everything else the composite.  The results are the host float32 composite's bit for bit."""
+    _check_mip_tex(tex, "mip_build")
+    kernels = native_ok(tex)
+    if not kernels and is_device_tensor(tex) and strict_native():
+        raise RuntimeError("mip_build: SR_STRICT_NATIVE=1 and the kernels take float32 device tensors only")
+    return _MipBuild.apply(tex, None if levels is None else int(levels), kernels)
+
+
+def _check_mip_map(uvmap, cover, name):
+    if uvmap.dim() != 4 or uvmap.shape[3] != 2 or not uvmap.is_floating_point():
+        raise ValueError("%s: uvmap must be a floating-point [B, H, W, 2], got %s %s" % (name, uvmap.dtype, tuple(uvmap.shape)))
+    if cover.dtype != torch.bool or tuple(cover.shape) != tuple(uvmap.shape[:3]) or cover.device != uvmap.device:
+        raise ValueError("%s: cover must be bool [B, H, W] on uvmap's device, got %s %s"
+                         % (name, cover.dtype, tuple(cover.shape)))
+
+
+def mip_lod_composite(uvmap, cover, size, levels=None, bias=0.0):
+    """The defining tensor algebra of `mip_lod`, in uvmap's float type."""
+    _check_mip_map(uvmap, cover, "mip_lod")
+    th, tw = _hw(size)
+    n_l = len(mip_layout((th, tw), levels))
+    dt = uvmap.dtype
+    bias = _background(bias, dt)
+    with torch.no_grad():
+        u, v = uvmap[..., 0], uvmap[..., 1]
+        live = cover & torch.isfinite(u) & torch.isfinite(v)
+        zero = torch.zeros_like(u)
+        u, v = torch.where(live, u, zero), torch.where(live, v, zero)
+
+        def axis(dim):
+            """The minimum of d over the usable neighbours along `dim` (1: y, 2: x); 0 with none."""
+            n = u.shape[dim]
+            a, b = [slice(None)] * 3, [slice(None)] * 3
+            a[dim], b[dim] = slice(0, n - 1), slice(1, n)
+            a, b = tuple(a), tuple(b)
+            du, dv = (u[b] - u[a]) * float(tw), (v[b] - v[a]) * float(th)     # from a to its neighbour b = a + 1
+            d_next = du * du + dv * dv
+            du, dv = (u[a] - u[b]) * float(tw), (v[a] - v[b]) * float(th)     # from b to its neighbour a = b - 1
+            d_prev = du * du + dv * dv
+            nxt, prv = torch.zeros_like(u), torch.zeros_like(u)
+            has_n, has_p = torch.zeros_like(live), torch.zeros_like(live)
+            nxt[a], has_n[a] = d_next, live[b]
+            prv[b], has_p[b] = d_prev, live[a]
+            both = torch.minimum(nxt, prv)
+            return torch.where(has_n & has_p, both, torch.where(has_n, nxt, torch.where(has_p, prv, zero)))
+
+        # a difference of two finite numbers is finite or an infinity, never NaN; its square is not negative, so the sum
+        # of two squares is no NaN either: an overflow gives d = inf, rho = inf and the top level
+        q = torch.maximum(axis(2), axis(1))
+        rho = _sqrt(q)
+        lvl = torch.zeros(rho.shape, dtype=torch.int64, device=rho.device)
+        for k in range(1, n_l):
+            lvl = lvl + (rho >= float(2 ** k)).long()                        # the exact constants 2^k
+        scale = torch.tensor([2.0 ** -k for k in range(n_l)], dtype=dt, device=rho.device)[lvl]
+        lam = lvl.to(dt) + (rho * scale - 1.0)
+        top = float(n_l - 1)
+        lam = torch.where(lvl == n_l - 1, torch.full_like(lam, top), lam)
+        lam = torch.where(rho < 1, zero, lam)
+        lod = (lam + bias).clamp(0.0, top)
+        return torch.where(live, lod, zero).contiguous()
+
+
+def mip_lod(uvmap, cover, size, levels=None, bias=0.0):
+    """lod [B, H, W] of uvmap's float type: the level of detail at which a (Th, Tw) = size texture with `mip_layout`'s
+    levels is looked up under the uv map [B, H, W, 2] with cover bool [B, H, W]; 0 for a pixel that is not live (cover
+    false or a non-finite coordinate).  rho is the texel distance to the nearer of the two live neighbours along each
+    axis, the larger of the two axes (the module's note has every step and the seam rule); lod is piecewise linear in rho
+    between the powers of two (rho 2^-l - 1 for 2^l <= rho < 2^(l+1)), which stays within 0.09 levels of log2(rho), plus
+    `bias`, clamped to [0, L - 1].  A pixel with no usable neighbour at all gets 0 + bias.  Coordinates so large that a
+    difference overflows give L - 1; no NaN arises from live pixels.  It carries no gradient: the level is a constant of
+    the look-up.  Device float32 runs sr_mip_lod, one launch; everything else `mip_lod_composite`; bit for bit equal."""
+    _check_mip_map(uvmap, cover, "mip_lod")
+    if not (native_ok(uvmap) and is_device_tensor(cover)):
+        if is_device_tensor(uvmap) and strict_native():
+            raise RuntimeError("mip_lod: SR_STRICT_NATIVE=1 and the kernels take float32 device tensors only")
+        return mip_lod_composite(uvmap, cover, size, levels, bias)
+    th, tw = _hw(size)
+    n_l = len(mip_layout((th, tw), levels))
+    uc, cc = uvmap.detach().contiguous(), cover.contiguous()
+    b, h, w = (int(x) for x in uc.shape[:3])
+    lod = torch.empty((b, h, w), dtype=uc.dtype, device=uc.device)
+    native(uc).sr_mip_lod(lod, uc, cc, b, h, w, th, tw, n_l, _background(bias, uc.dtype))
+    return lod
+
+
+def _mip_foot(uvmap, cover, lod, layout):
+    """The per-pixel quantities of the look-up, each [B, H W]: (live, f, (foot0, foot1)) with foot_s = (inx, iny, fx, fy,
+    i00, i01, i10, i11, th_l, tw_l) of level l0 + s, s = 0, 1 (l1 = min(l0 + 1, L - 1)); i.. index one packed plane."""
+    b = uvmap.shape[0]
+    dt, dev = uvmap.dtype, uvmap.device
+    n_l = len(layout)
+    u, v = uvmap[..., 0].reshape(b, -1), uvmap[..., 1].reshape(b, -1)
+    live = cover.reshape(b, -1) & torch.isfinite(u) & torch.isfinite(v)
+    zero = torch.zeros_like(u)
+    u, v = torch.where(live, u, zero), torch.where(live, v, zero)
+    lod = lod.detach().reshape(b, -1).to(dt)
+    lodc = torch.where(lod >= 0, lod.clamp_max(float(n_l - 1)), torch.zeros_like(lod))      # (a NaN compares false)
+    l0f = torch.floor(lodc)
+    f = lodc - l0f
+    l0 = l0f.long()
+    offs = torch.tensor([o for o, _, _ in layout], dtype=torch.int64, device=dev)
+    hs = torch.tensor([h for _, h, _ in layout], dtype=torch.int64, device=dev)
+    ws = torch.tensor([w for _, _, w in layout], dtype=torch.int64, device=dev)
+    feet = []
+    for s in (0, 1):
+        lv = (l0 + s).clamp_max(n_l - 1)
+        off, hi, wi = offs[lv], hs[lv], ws[lv]
+        th, tw = hi.to(dt), wi.to(dt)
+        sx, sy = u * tw - 0.5, (1.0 - v) * th - 0.5
+        inx, iny = (sx >= -1) & (sx <= tw), (sy >= -1) & (sy <= th)
+        sxc = torch.minimum(torch.maximum(sx, torch.full_like(sx, -1.0)), tw)
+        syc = torch.minimum(torch.maximum(sy, torch.full_like(sy, -1.0)), th)
+        x0f, y0f = torch.floor(sxc.detach()), torch.floor(syc.detach())
+        fx, fy = sxc - x0f, syc - y0f
+        x0, y0 = x0f.long(), y0f.long()
+        lo = torch.zeros_like(x0)
+        xa, xb = torch.minimum(torch.maximum(x0, lo), wi - 1), torch.minimum(torch.maximum(x0 + 1, lo), wi - 1)
+        ya, yb = torch.minimum(torch.maximum(y0, lo), hi - 1), torch.minimum(torch.maximum(y0 + 1, lo), hi - 1)
+        feet.append((inx, iny, fx, fy, off + ya * wi + xa, off + ya * wi + xb, off + yb * wi + xa, off + yb * wi + xb,
+                     th, tw))
+    return live, f, feet
+
+
+def _mip_taps(pyr, foot, b):
+    bt, c_n, p = pyr.shape
+    flat = pyr if bt == b else pyr.expand(b, -1, -1)
+    return tuple(torch.gather(flat, 2, i.unsqueeze(1).expand(-1, c_n, -1)) for i in foot[4:8])
+
+
+def _mip_sample_forward(pyr, layout, uvmap, cover, lod, background):
+    b, h, w = (int(x) for x in uvmap.shape[:3])
+    live, f, feet = _mip_foot(uvmap, cover, lod, layout)
+    cols = []
+    for foot in feet:
+        fx, fy = foot[2].unsqueeze(1), foot[3].unsqueeze(1)
+        t00, t01, t10, t11 = _mip_taps(pyr, foot, b)
+        top = (1.0 - fx) * t00 + fx * t01
+        bot = (1.0 - fx) * t10 + fx * t11
+        cols.append(top * (1.0 - fy) + bot * fy)
+    fe = f.unsqueeze(1)
+    colour = torch.where(fe == 0, cols[0], (1.0 - fe) * cols[0] + fe * cols[1])
+    out = torch.where(live.unsqueeze(1), colour, torch.full_like(colour, float(background)))
+    return out.view(b, int(pyr.shape[1]), h, w)
+
+
+def mip_tap_plan(uvmap, cover, lod, size, levels, bt):
+    """(off int32 [Bt P + 2], entries int32 [8 B H W]): the tap list of the mip-mapped look-up, a CSR over the keys
+    bt P + offset_l + ty Tw_l + tx of the packed pyramid (`mip_layout(size, levels)`).  The entries of a key are the taps
+    ((b H + y) W + x) 8 + k that fall on it, ascending; k = 0..3 are the four taps of level l0 in `tap_plan`'s order,
+    k = 4..7 those of l1.  Taps 4..7 of a pixel with f == 0 and all taps of a pixel that is not live lie in the one
+    bucket after the last key.  Built with tensor ops on uvmap's device, nothing read back, the sizes depend on shapes
+    only; cached per uv map, cover and lod (address and version), size, levels and Bt."""
+    th, tw = _hw(size)
+    layout = mip_layout((th, tw), levels)
+    p = _mip_total(layout)
+    b, h, w = (int(x) for x in uvmap.shape[:3])
+    bt = int(bt)
+    if bt not in (1, b):
+        raise ValueError("mip_tap_plan: Bt is B (%d) or 1, got %d" % (b, bt))
+    if 8 * b * h * w >= 2 ** 31 or bt * p >= 2 ** 31 - 1:
+        raise ValueError("mip_tap_plan: 8 B H W and Bt P must be below 2^31")
+    if tuple(lod.shape) != (b, h, w):
+        raise ValueError("mip_tap_plan: lod must be [B, H, W], got %s" % (tuple(lod.shape),))
+    key = (uvmap.data_ptr(), uvmap._version, tuple(uvmap.shape), uvmap.dtype, str(uvmap.device), cover.data_ptr(),
+           cover._version, lod.data_ptr(), lod._version, lod.dtype, th, tw, len(layout), bt)
+    hit = _MIP_PLAN_CACHE.get(key)
+    if hit is not None:
+        return hit[0], hit[1]
+    with torch.no_grad():
+        live, f, feet = _mip_foot(uvmap.detach(), cover, lod, layout)
+        n_keys = bt * p
+        keys = torch.stack(feet[0][4:8] + feet[1][4:8], -1)                  # [B, H W, 8]
+        if bt == b:
+            keys = keys + (torch.arange(b, device=uvmap.device).view(b, 1, 1) * p)
+        used = live.unsqueeze(-1) & torch.stack([torch.ones_like(live)] * 4 + [f != 0] * 4, -1)
+        keys = torch.where(used, keys, torch.full_like(keys, n_keys)).reshape(-1)
+        entries = torch.sort(keys, stable=True)[1].to(torch.int32).contiguous()
+        off = torch.zeros(n_keys + 2, dtype=torch.int32, device=uvmap.device)
+        off[1:] = torch.cumsum(torch.bincount(keys, minlength=n_keys + 1), 0).to(torch.int32)
+    _MIP_PLAN_CACHE.put(key, (off, entries, uvmap, cover, lod))              # (holds all three: the key is their addresses)
+    return off, entries
+
+
+def _mip_sample_backward(pyr, layout, size, uvmap, cover, lod, g, need_uv=True, need_pyr=True):
+    """(grad_uv [B, H, W, 2], grad_pyr [Bt, C, P]) of the gradient g [B, C, H, W] of `mip_sample`'s output: the
+    definition in torch operations, the ordered sum included; a recorded backward differentiates again."""
+    bt, c_n, p = (int(x) for x in pyr.shape)
+    b, h, w = (int(x) for x in uvmap.shape[:3])
+    live, f, feet = _mip_foot(uvmap, cover, lod, layout)
+    gf = g.reshape(b, c_n, h * w)
+    guv = gpyr = None
+    if need_uv:
+        per = []
+        for foot in feet:
+            inx, iny, fx, fy, th, tw = foot[:4] + foot[8:]
+            t00, t01, t10, t11 = _mip_taps(pyr, foot, b)
+            fxe, fye = fx.unsqueeze(1), fy.unsqueeze(1)
+            top = (1.0 - fxe) * t00 + fxe * t01
+            bot = (1.0 - fxe) * t10 + fxe * t11
+            dx = (t01 - t00) * (1.0 - fye) + (t11 - t10) * fye
+            dy = bot - top
+            gx, gy = torch.zeros_like(fx), torch.zeros_like(fy)
+            for c in range(c_n):
+                gx = gx + gf[:, c] * dx[:, c]
+                gy = gy + gf[:, c] * dy[:, c]
+            zero = torch.zeros_like(gx)
+            per.append(torch.stack((torch.where(live & inx, gx * tw, zero), torch.where(live & iny, -(gy * th), zero)), -1))
+        fe = f.unsqueeze(-1)
+        guv = torch.where(fe == 0, per[0], (1.0 - fe) * per[0] + fe * per[1])
+        guv = torch.where(live.unsqueeze(-1), guv, torch.zeros_like(guv)).view(b, h, w, 2)
+    if need_pyr:
+        off, entries = mip_tap_plan(uvmap, cover, lod, size, len(layout), bt)
+        blend = (1.0 - f, f)
+        wgt = []
+        for s, foot in enumerate(feet):
+            fx, fy = foot[2], foot[3]
+            for wk in ((1.0 - fx) * (1.0 - fy), fx * (1.0 - fy), (1.0 - fx) * fy, fx * fy):
+                wgt.append(blend[s] * wk)
+        wgt = torch.stack(wgt, -1)                                             # [B, H W, 8]
+        safe = torch.where(live.unsqueeze(1), gf, torch.zeros_like(gf))        # (what stands under no tap cannot leak)
+        terms = wgt.unsqueeze(1) * safe.unsqueeze(-1)                          # [B, C, H W, 8]
+        terms = terms.permute(1, 0, 2, 3).reshape(c_n, -1)
+        acc = _ordered_sum(terms, off, entries, bt * p)
+        gpyr = acc.view(c_n, bt, p).permute(1, 0, 2).contiguous()
+    return guv, gpyr
+
+
+class _MipSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pyr, uvmap, cover, lod, size, background, kernels):
+        ctx.kernels, ctx.size = kernels, size
+        pc, uc, cc, lc = pyr.contiguous(), uvmap.contiguous(), cover.contiguous(), lod.detach().contiguous()
+        ctx.save_for_backward(pc, uc, cc, lc)
+        layout = _layout_of(size, pc.shape[2])
+        if not kernels:
+            return _mip_sample_forward(pc, layout, uc, cc, lc, background)
+        bt, c_n = int(pc.shape[0]), int(pc.shape[1])
+        b, h, w = (int(x) for x in uc.shape[:3])
+        out = torch.empty((b, c_n, h, w), dtype=pc.dtype, device=pc.device)
+        native(pc).sr_mip_sample_fwd(out, pc, uc, cc, lc, b, bt, c_n, h, w, size[0], size[1], len(layout), background)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        pc, uc, cc, lc = ctx.saved_tensors
+        need_pyr, need_uv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        none = (None,) * 5
+        if not (need_pyr or need_uv):
+            return (None, None) + none
+        size = ctx.size
+        layout = _layout_of(size, pc.shape[2])
+        if torch.is_grad_enabled() or not ctx.kernels:
+            # the definition in torch operations; under create_graph=True it is recorded and differentiates again
+            guv, gpyr = _mip_sample_backward(pc, layout, size, uc, cc, lc, g, need_uv, need_pyr)
+            return (gpyr, guv) + none
+        g = g.contiguous()
+        bt, c_n = int(pc.shape[0]), int(pc.shape[1])
+        b, h, w = (int(x) for x in uc.shape[:3])
+        dims = (b, bt, c_n, h, w, size[0], size[1], len(layout))
+        guv = gpyr = None
+        if need_uv:
+            guv = torch.empty_like(uc)
+            native(pc).sr_mip_sample_bwd_uv(guv, g, pc, uc, cc, lc, *dims)
+        if need_pyr:
+            off, entries = mip_tap_plan(uc, cc, lc, size, len(layout), bt)
+            gpyr = torch.empty_like(pc)
+            native(pc).sr_mip_sample_bwd_pyr(gpyr, g, uc, cc, lc, off, entries, *dims)
+        return (gpyr, guv) + none
+
+
+def _check_mip_sample(pyr, size, uvmap, cover, lod):
+    if pyr.dim() != 3 or not pyr.is_floating_point() or min(pyr.shape[1:]) < 1:
+        raise ValueError("mip_sample: pyr must be a floating-point [Bt, C, P], got %s %s" % (pyr.dtype, tuple(pyr.shape)))
+    _check_mip_map(uvmap, cover, "mip_sample")
+    if uvmap.dtype != pyr.dtype or uvmap.device != pyr.device:
+        raise ValueError("mip_sample: uvmap must be of pyr's float type and device")
+    if tuple(lod.shape) != tuple(uvmap.shape[:3]) or lod.dtype != pyr.dtype or lod.device != pyr.device:
+        raise ValueError("mip_sample: lod must be [B, H, W] of pyr's float type and device, got %s %s"
+                         % (lod.dtype, tuple(lod.shape)))
+    if pyr.shape[0] != uvmap.shape[0] and pyr.shape[0] != 1:
+        raise ValueError("mip_sample: %d views need B pyramids or one, got %d" % (uvmap.shape[0], pyr.shape[0]))
+    th, tw = _hw(size)
+    _layout_of((th, tw), pyr.shape[2])
+    return th, tw
+
+
+def mip_sample_composite(pyr, size, uvmap, cover, lod, background=0.0):
+    """The defining tensor algebra of `mip_sample`, in pyr's float type, as an autograd node with the stated backward."""
+    size = _check_mip_sample(pyr, size, uvmap, cover, lod)
+    return _MipSample.apply(pyr, uvmap, cover, lod, size, _background(background, pyr.dtype), False)
+
+
+def mip_sample(pyr, size, uvmap, cover, lod, background=0.0):
+    """out [B, C, H, W]: the pyramid pyr [Bt, C, P] (`mip_build` of a (Th, Tw) = size texture; Bt = B or 1) looked up at
+    the uv map [B, H, W, 2] at the level of detail lod [B, H, W] (`mip_lod`): bilinear on the two levels around lod,
+    blended by its fraction; a whole lod reads one level.  A pixel that is not live gets `background` and contributes to
+    no gradient.  Differentiable in pyr and uvmap; lod gets none.  The pyramid's gradient walks the 8-tap list of
+    `mip_tap_plan`, cached per (uv map, cover, lod): with all three fixed it is built once and forward and backward can be
+    captured after one call of `mip_tap_plan`.  Device float32 runs sr_mip_sample_fwd / _bwd_uv / _bwd_pyr, one launch
+    each; everything else the composite; bit for bit equal, reruns bit-identical (no atomics)."""
+    size = _check_mip_sample(pyr, size, uvmap, cover, lod)
+    kernels = native_ok(pyr, uvmap, lod) and is_device_tensor(cover)
+    if not kernels and is_device_tensor(pyr) and strict_native():
+        raise RuntimeError("mip_sample: SR_STRICT_NATIVE=1 and the kernels take float32 device tensors only")
+    return _MipSample.apply(pyr, uvmap, cover, lod, size, _background(background, pyr.dtype), kernels)
+
+
+def sample_mip(tex, uvmap, cover, lod=None, bias=0.0, levels=None, background=0.0):
+    """out [B, C, H, W]: tex [Bt, C, Th, Tw] looked up at the uv map through its mip pyramid: `mip_build`, `mip_lod`
+    (with `bias`; skipped when a lod [B, H, W] is given) and `mip_sample`.  Differentiable in tex and uvmap.  levels=1 is
+    `sample`."""
+    _check_sample(tex, uvmap, cover)
+    size = (int(tex.shape[2]), int(tex.shape[3]))
+    if lod is None:
+        lod = mip_lod(uvmap, cover, size, levels, bias)
+    return mip_sample(mip_build(tex, levels), size, uvmap, cover, lod, background)

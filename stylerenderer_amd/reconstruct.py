@@ -9,7 +9,7 @@ for it):
         [--mask_lmk [--mask_tri FILE] [--mask_margin R]] [--mask_dir DIR] [--mask_mesh]
         [--texture [T] [--uv FILE] [--texture_from picture|render] [--texture_facing LO,HI] [--texture_pad N]
          [--texture_fill mean|none] [--texture_check] [--turntable N [--turntable_yaw DEG]]
-         [--texture_refine STEPS [--texture_lr LR]]
+         [--texture_refine STEPS [--texture_lr LR]] [--texture_mip [BIAS]]
          [--light [--light_mono] [--light_floor S] [--light_ridge L] [--light_lr LR] [--relight FILE]]]
         [--camera_distance D | --camera_fov DEG] [--fit_camera] [--camera_lr 0.01] CHECKPOINT IMAGE [IMAGE ...]
 
@@ -93,6 +93,11 @@ under V uv maps) and checked on every view: NAME_identity.npz `merged_texture_re
 (with `merged_rerender_covered`, `merged_rerender_counted` and, after a refinement, `merged_rerender_error_before`): the
 number the merge's sharpness and the facing gate can be tuned against; --turntable also writes NAME_merged_turn_KK.png, the
 identity mesh (pose 0, no camera) with the merged texture.
+--texture_mip [BIAS] (without it nothing changes) sends every one of these draws, the look-up of the bake's weight in
+--texture_check and --relight's picture included, through the texture's mip pyramid (op.texture.sample_mip: a trilinear
+look-up at the level of detail of the uv map's footprint plus BIAS, default 0), so a texture drawn smaller than it is no
+longer aliases.  Refinement keeps level 0 as the parameter and rebuilds the pyramid in every step; the level of detail and
+the tap list are computed once.  <stem>.npz gains `texture_mip`, the bias; the written texture files stay level 0.
 
 With --light (it needs --texture, as its five companions do) every bake is separated into an albedo and a light (op.light:
 Lambertian shading under second-order spherical harmonics, nine coefficients per colour channel, or one white light with
@@ -453,28 +458,34 @@ def landmark_outputs(inv, index, conf, listed, shape):
     return dict(more, landmarks=fit, landmarks_target=np.asarray(listed, np.float64), lmk_error=np.float64(err))
 
 
-def texture_rerender(tex, weight, views, light=None):
+def texture_rerender(tex, weight, views, light=None, mip=None):
     """With views a list of (uvmap [1, S, S, 2], cover [1, S, S], target [1, C, S, S]), per view (image [1, C, S, S] over
     background -1, error, covered, counted): the texture tex [1, C, T, T] drawn on the view's uv map; error is the mean
     absolute difference to the view's target over the `counted` pixels, those that are covered and where the look-up of
     the bake's weight [1, 1, T, T] is positive.  light: per view (gamma [1, Cl, 9], normals [1, 3, S, S]); tex is then an
-    albedo and the image is op.light.shade of its look-up."""
+    albedo and the image is op.light.shade of its look-up.  mip: None, or the lod bias of the mip-mapped look-up
+    (op.texture.sample_mip), which then draws the texture and looks the weight up."""
     from .op import light as lighting, texture
+
+    def look(t, uvmap, cover, background):
+        if mip is None:
+            return texture.sample(t, uvmap, cover, background)
+        return texture.sample_mip(t, uvmap, cover, bias=float(mip), background=background)
 
     out = []
     with torch.no_grad():
         for i, (uvmap, cover, target) in enumerate(views):
-            img = texture.sample(tex, uvmap, cover, -1.0)
+            img = look(tex, uvmap, cover, -1.0)
             if light is not None:
                 img = lighting.shade(img, light[i][1], cover, light[i][0], -1.0, -1.0)
-            on = cover & (texture.sample(weight, uvmap, cover, 0.0)[:, 0] > 0)
+            on = cover & (look(weight, uvmap, cover, 0.0)[:, 0] > 0)
             n = int(on.sum())
             err = float(((img - target).abs() * on.unsqueeze(1)).sum()) / max(n * int(img.shape[1]), 1)
             out.append((img, err, int(cover.sum()), n))
     return out
 
 
-def texture_refine(tex, views, steps, lr=0.02, light=None, light_lr=0.005):
+def texture_refine(tex, views, steps, lr=0.02, light=None, light_lr=0.005, mip=None):
     """(tex' [1, C, T, T], loss [STEPS]; the loss before every step) with views a list of (uvmap [1, S, S, 2], cover
     [1, S, S], target [1, C, S, S]): Adam (optim.FlatAdam) on the texture alone from tex, on the sum over the views' covered
     pixels of (render - target)^2; one texture for all views (Bt = 1).  The uv maps are fixed, so the tap list is built
@@ -483,7 +494,10 @@ def texture_refine(tex, views, steps, lr=0.02, light=None, light_lr=0.005):
     light: per view (gamma [1, Cl, 9], normals [1, 3, S, S]); tex is then an albedo, the render is op.light.shade of its
     look-up, and Adam runs on the albedo and the V lights together, the lights as a second FlatAdam group with light_lr
     (0.005: a starting value, not tuned) whose gradient the shading node writes into the group's buffer (ggamma_out; on
-    the host it comes through autograd).  Returns (tex', loss, gamma' [V, Cl, 9])."""
+    the host it comes through autograd).  Returns (tex', loss, gamma' [V, Cl, 9]).
+    mip: None, or the lod bias of the mip-mapped look-up: level 0 stays the parameter, the pyramid is rebuilt in every
+    step (op.texture.mip_build), the lod and the 8-tap list are computed once, and a step's gradient reaches every texel
+    under a drawn pixel's footprint, not the four the bilinear look-up reads."""
     from . import optim
     from .op import light as lighting, texture
 
@@ -495,7 +509,18 @@ def texture_refine(tex, views, steps, lr=0.02, light=None, light_lr=0.005):
     flat_g = torch.zeros(total, dtype=p.dtype, device=p.device)
     opt = optim.FlatAdam([p], flat_g, lr=float(lr))
     slot = optim.flat_views(flat_g, [p], offs)[0]
-    texture.tap_plan(uvmap, cover, tuple(p.shape[-2:]), 1)
+    tsize = (int(p.shape[-2]), int(p.shape[-1]))
+    if mip is None:
+        texture.tap_plan(uvmap, cover, tsize, 1)
+
+        def look(background):
+            return texture.sample(p, uvmap, cover, background)
+    else:
+        lod = texture.mip_lod(uvmap, cover, tsize, None, float(mip))
+        texture.mip_tap_plan(uvmap, cover, lod, tsize, None, 1)
+
+        def look(background):
+            return texture.mip_sample(texture.mip_build(p), tsize, uvmap, cover, lod, background)
     on = cover.unsqueeze(1).to(p.dtype)
     losses = []
     if light is not None:
@@ -508,11 +533,11 @@ def texture_refine(tex, views, steps, lr=0.02, light=None, light_lr=0.005):
         light_slot = optim.flat_views(light_g, [q], [0])[0]
     for _ in range(int(steps)):
         if light is None:
-            diff = (texture.sample(p, uvmap, cover, 0.0) - target) * on
+            diff = (look(0.0) - target) * on
             loss = (diff * diff).sum()
             (g,) = torch.autograd.grad(loss, p)
         else:
-            flat = texture.sample(p, uvmap, cover, -1.0)
+            flat = look(-1.0)
             render = lighting.shade(flat, normals, cover, q, -1.0, -1.0, ggamma_out=light_g if direct else None)
             diff = (render - target) * on
             loss = (diff * diff).sum()
@@ -537,10 +562,11 @@ class TextureGuide:
     sample and writes its files."""
 
     def __init__(self, face, size, uv_file=None, source="picture", facing="0.1,0.4", passes=8, fill="mean", check=False,
-                 turntable=0, turntable_yaw=30.0, refine=0, refine_lr=0.02, light=None):
+                 turntable=0, turntable_yaw=30.0, refine=0, refine_lr=0.02, light=None, mip=None):
         """light: None (the texture is the plain bake) or a dict with any of mono (one white light), floor (unshade's),
         ridge (the fit's), lr (the light's learning rate under refinement) and relight (a file of 9 or 9 C numbers):
-        every bake is then separated into an albedo and a light (op.light)."""
+        every bake is then separated into an albedo and a light (op.light).  mip: None, or the lod bias with which
+        every draw goes through the mip-mapped look-up (--texture_mip)."""
         from .face_model import load_uv, uv_layout
         from .op import texture
 
@@ -554,6 +580,9 @@ class TextureGuide:
             if light.get("relight"):
                 self.light["relight"] = self.read_light(light["relight"])
         self.lights = []                                                 # (--multiview: the views' (gamma, normal map))
+        self.mip = None if mip is None else float(mip)
+        if self.mip is not None and not np.isfinite(self.mip):
+            raise SystemExit("reconstruct: --texture_mip takes a finite bias")
         self.size = int(size)
         if not 1 <= self.size <= 8192:
             raise SystemExit("reconstruct: --texture T lies in [1, 8192]")
@@ -658,18 +687,19 @@ class TextureGuide:
         albedo); refinement replaces the gammas in place by the refined ones."""
         entries, before = {}, None
         if self.check and self.refine_steps:
-            before = texture_rerender(tex, weight, views, light)
+            before = texture_rerender(tex, weight, views, light, mip=self.mip)
         if self.refine_steps and light is None:
-            tex, loss = texture_refine(tex, views, self.refine_steps, self.refine_lr)
+            tex, loss = texture_refine(tex, views, self.refine_steps, self.refine_lr, mip=self.mip)
             entries[prefix + "texture_refine_loss"] = loss
         elif self.refine_steps:
-            tex, loss, gammas = texture_refine(tex, views, self.refine_steps, self.refine_lr, light, self.light["lr"])
+            tex, loss, gammas = texture_refine(tex, views, self.refine_steps, self.refine_lr, light, self.light["lr"],
+                                               mip=self.mip)
             entries[prefix + "texture_refine_loss"] = loss
             for i, pair in enumerate(light):
                 pair[0] = gammas[i:i + 1].contiguous()
         images = []
         if self.check:
-            after = texture_rerender(tex, weight, views, light)
+            after = texture_rerender(tex, weight, views, light, mip=self.mip)
             one = len(views) == 1 and not prefix
             pick = (lambda col: np.float64(col[0])) if one else (lambda col: np.asarray(col, np.float64))
             entries[prefix + "rerender_error"] = pick([r[1] for r in after])
@@ -697,7 +727,7 @@ class TextureGuide:
                 if kappa is not None:
                     turned = camera.project(turned.contiguous(), kappa)
                 img, cover = texture.render(turned.contiguous(), tri, self._layout[0], self.tri_uv, tex, size, -1.0,
-                                            self._layout[2])
+                                            self._layout[2], mip=self.mip)
                 if light is not None:
                     nmap = self.normals_at(turned, torch.matmul(light[1].to(v.dtype), utils_3d.euler_mat(angle)), tri, size)
                     img = lighting.shade(img, nmap, cover, light[0], -1.0, -1.0)
@@ -736,7 +766,7 @@ class TextureGuide:
                                        facing=self.facing)
             cover = float(texture.coverage(self.face, weight)[0])
             out = self.finish(tex, weight)
-        more = {}
+        more = {} if self.mip is None else {"texture_mip": np.float64(self.mip)}
         lit = pair = None
         if self.light is not None:
             # the bake splits into an albedo and a light; from here on `out` is the albedo and `lit` the plain bake
@@ -745,7 +775,7 @@ class TextureGuide:
             with torch.no_grad():
                 out = self.finish(tex, weight)
             pair = [gamma, self.normals_at(v, no, tri, self.view_size)]
-            more = dict(light_residual=np.float64(residual))
+            more["light_residual"] = np.float64(residual)
         if self.renders or (self.light is not None and self.light["relight"] is not None):
             views = [self.view(inv, index)]
         if self.renders:
@@ -754,7 +784,7 @@ class TextureGuide:
             if images:
                 generate.save_image(images[0].clamp(-1, 1).cpu(), os.path.join(out_dir, stem + "_rerender.png"))
             if pair is not None and self.check:
-                more["rerender_error_lit"] = np.float64(texture_rerender(lit, weight, views)[0][1])
+                more["rerender_error_lit"] = np.float64(texture_rerender(lit, weight, views, mip=self.mip)[0][1])
             if keep is not None:
                 self.views.append(views[0])
         shown = pair
@@ -778,7 +808,9 @@ class TextureGuide:
                                          % (other.shape[0], out.shape[1]))
                     shown = [other[None].contiguous(), pair[1]]
                     uvmap, seen, _ = views[0]
-                    relit = lighting.shade(texture.sample(out, uvmap, seen, -1.0), pair[1], seen, shown[0], -1.0, -1.0)
+                    flat = (texture.sample(out, uvmap, seen, -1.0) if self.mip is None else
+                            texture.sample_mip(out, uvmap, seen, bias=self.mip, background=-1.0))
+                    relit = lighting.shade(flat, pair[1], seen, shown[0], -1.0, -1.0)
                     generate.save_image(relit.clamp(-1, 1).cpu(), os.path.join(out_dir, stem + "_relit.png"))
         if self.turntable:
             self.turn(out, vo.contiguous(), tri, int(inv.target.shape[-1]),
@@ -1022,6 +1054,9 @@ def main(argv=None):
                          "(or merge); the refined texture is the one written")
     ap.add_argument("--texture_lr", type=float, default=None, metavar="LR",
                     help="with --texture_refine: Adam's learning rate; a starting value, not tuned [0.02]")
+    ap.add_argument("--texture_mip", type=float, nargs="?", const=0.0, default=None, metavar="BIAS",
+                    help="with --texture: every draw of --texture_check, --turntable, --relight and --texture_refine looks "
+                         "the texture up through its mip pyramid (trilinear; BIAS is added to the level of detail [0])")
     ap.add_argument("--light", action="store_true",
                     help="with --texture: separate every bake into an albedo and a light (second-order spherical "
                          "harmonics, fitted in closed form); <stem>_texture.png is then the albedo")
@@ -1090,6 +1125,8 @@ def main(argv=None):
         ap.error("--uv, --texture_from, --texture_facing, --texture_pad and --texture_fill need --texture")
     if args.texture is None and (args.texture_check or args.turntable is not None or args.texture_refine is not None):
         ap.error("--texture_check, --turntable and --texture_refine need --texture")
+    if args.texture is None and args.texture_mip is not None:
+        ap.error("--texture_mip needs --texture")
     if args.texture is None and (args.light or args.light_mono or args.light_floor is not None
                                  or args.light_ridge is not None or args.light_lr is not None or args.relight):
         ap.error("--light, --light_mono, --light_floor, --light_ridge, --light_lr and --relight need --texture")
@@ -1147,7 +1184,7 @@ def main(argv=None):
                             light=({k: v for k, v in (("mono", args.light_mono), ("floor", args.light_floor),
                                                       ("ridge", args.light_ridge), ("lr", args.light_lr),
                                                       ("relight", args.relight)) if v is not None}
-                                   if args.light else None))
+                                   if args.light else None), mip=args.texture_mip)
                if args.texture is not None else None)
     shared = None
     if args.multiview is not None:
