@@ -262,6 +262,11 @@ def blur_noise_bias_act(x, kernel, pad, noise, noise_weight, bias, negative_slop
 
     ok = (x.device.type == "cuda" and x.dtype == torch.float32 and x.dim() == 4 and tuple(kernel.shape) == (4, 4)
           and kernel.dtype == torch.float32 and bias is not None and x.numel() > 0)
+    if ok:
+        # the node's backward is the activation backward kernel over the OUTPUT, which reads rows of float4
+        # (csrc/fused_elem.hip vec_ok): an output plane of 7 x 7 passed the forward kernel and raised in backward
+        oh, ow = x.size(2) + pad[0] + pad[1] - 3, x.size(3) + pad[0] + pad[1] - 3
+        ok = (oh * ow) % 4 == 0 and x.size(0) * x.size(1) <= 65535
     if noise is not None:
         noise = noise.contiguous()
         oh, ow = x.size(2) + pad[0] + pad[1] - 3, x.size(3) + pad[0] + pad[1] - 3
