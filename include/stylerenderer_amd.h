@@ -1050,6 +1050,37 @@ int sr_texture_sample_bwd_tex(float* gtex, const float* gout, const float* uv, c
                               const int32_t* entries, int64_t B, int64_t Bt, int64_t C, int64_t H, int64_t W, int64_t Th,
                               int64_t Tw, sr_stream_t stream);
 
+/* The tap list of sr_texture_sample_bwd_tex built on the device (definition: stylerenderer_amd/op/texture.py, tap_plan),
+ * csrc/tap_plan.hip: for a uv map that changes in every step of a captured fit.
+ * sr_tap_plan_build: off int32 [Bt Th Tw + 2] and entries int32 [4 B H W] of uv [B, H, W, 2], cover uint8 [B, H, W], the
+ *   integers of op.texture.tap_plan.  A pixel's four keys come from sr_texture_sample_fwd's arithmetic (one copy of the
+ *   code); a pixel with cover == 0 or a non-finite coordinate files its four taps under the key Bt Th Tw.  A least-
+ *   significant-digit radix sort of (key, entry) pairs with d-bit digits in sr_tap_plan_passes passes: 1 + 3 passes + 1
+ *   launches, the same sequence for the same shapes whatever the data.  Ties keep their input order, so the entries of a
+ *   key ascend; a pair's position is a function of the input alone (no float atomics, no order of retirement), so reruns
+ *   are bit-identical.  No workgroup waits for another; every element of off and entries and every element of scratch
+ *   that is read is written by each build, nothing needs to start at zero.  No allocation, no memset, no host read: it
+ *   runs under graph capture on `stream`.  scratch: sr_tap_plan_scratch_ints int32 elements, 16-byte aligned.  B, H or W
+ *   of 0 writes off = 0 only.  Bt == B or 1; 4 B H W and Bt Th Tw must be below 2^31.
+ * sr_tap_plan_passes: ceil(bits(Bt Th Tw) / d), -1 for sizes out of range.  sr_tap_plan_digit_bits: d.
+ * sr_tap_plan_scratch_ints: a function of the picture's shape alone; -1 for sizes out of range. */
+int sr_tap_plan_digit_bits(void);
+int sr_tap_plan_passes(int64_t Bt, int64_t Th, int64_t Tw);
+int64_t sr_tap_plan_scratch_ints(int64_t B, int64_t H, int64_t W);
+int sr_tap_plan_build(int32_t* off, int32_t* entries, int32_t* scratch, int64_t scratch_ints, const float* uv,
+                      const uint8_t* cover, int64_t B, int64_t Bt, int64_t H, int64_t W, int64_t Th, int64_t Tw,
+                      sr_stream_t stream);
+
+/* The adjoint of the corner explode c[b, 3 f + k] = v[b, tri[f, k]] of op.texture.uv_map (definition:
+ * stylerenderer_amd/op/texture.py, explode), csrc/explode.hip.
+ * sr_explode_bwd: gv [B, nv, 3] from gc [B, 3 nf, 3] and the topology's incidence list (op.rasterize.incidence: adj_off
+ *   int32 [nv + 2], adj int32 [3 nf], the entries k nf + f of a vertex ascending): per coordinate the sum from 0, in list
+ *   order, of gc[b, 3 f + k].  One launch, a lane per vertex of a sample; every element of gv is written, a vertex without
+ *   a corner gets exactly 0.  Offsets and entries outside the list are skipped, never followed.  No atomics, no scratch, no
+ *   allocation, no host read: it runs under graph capture on `stream`; reruns are bit-identical. */
+int sr_explode_bwd(float* gv, const float* gc, const int32_t* adj_off, const int32_t* adj, int64_t B, int64_t nv,
+                   int64_t nf, sr_stream_t stream);
+
 /* The mip-mapped texture look-up (definition: stylerenderer_amd/op/texture.py, mip_build_composite, mip_lod_composite,
  * mip_sample_composite), csrc/texture_mip.hip.  A (Th, Tw) texture has up to Lmax levels: level 0 is the texture, level
  * l + 1 has half of each side and exists while both sides of level l are even; 1 <= L <= Lmax of them are used.  The

@@ -166,7 +166,12 @@ SIGNATURES = {
     "sr_texture_sample_fwd": (_i, [_p] * 4 + [_l] * 7 + [_f, _p]),
     "sr_texture_sample_bwd_uv": (_i, [_p] * 5 + [_l] * 7 + [_p]),
     "sr_texture_sample_bwd_tex": (_i, [_p] * 6 + [_l] * 7 + [_p]),
-    "sr_mip_build_fwd": (_i, [_p] * 2 + [_l] * 4 + [_p]),
+    "sr_tap_plan_digit_bits": (_i, []),
+    "sr_tap_plan_passes": (_i, [_l, _l, _l]),
+    "sr_tap_plan_scratch_ints": (_l, [_l, _l, _l]),
+    "sr_tap_plan_build": (_i, [_p, _p, _p, _l, _p, _p] + [_l] * 6 + [_p]),
+    "sr_explode_bwd": (_i, [_p] * 4 + [_l] * 3 + [_p]),
+    "sr_mip_build_fwd":(_i, [_p] * 2 + [_l] * 4 + [_p]),
     "sr_mip_build_bwd": (_i, [_p] * 2 + [_l] * 5 + [_p]),
     "sr_mip_lod": (_i, [_p] * 3 + [_l] * 6 + [_f, _p]),
     "sr_mip_sample_fwd": (_i, [_p] * 5 + [_l] * 8 + [_f, _p]),

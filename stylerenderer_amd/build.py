@@ -43,6 +43,8 @@ SOURCES = [
     ("texture.hip", EXACT),
     ("texture_sample.hip", EXACT),
     ("texture_mip.hip", EXACT),
+    ("tap_plan.hip", EXACT),
+    ("explode.hip", EXACT),
     ("share.hip", EXACT),
     ("camera.hip", EXACT),
     ("light.hip", EXACT),

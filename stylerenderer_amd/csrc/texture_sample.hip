@@ -22,12 +22,12 @@
 // the definition's, one float32 operation per step in the same order (-ffp-contract=off).  Vector stores and plain C++
 // only: no atomics, no scratch, no memset, no host read, so all three run under graph capture on the caller's stream.
 #include "common.h"
+#include "texture_footprint.h"
 
 namespace {
 
 constexpr int TS_BLOCK = 256;
 constexpr int TS_CH = 4;                                                  // channels a texel's lane carries per walk
-constexpr float TS_FLT_MAX = 3.4028234663852886e38f;
 
 struct SampleArgs {
     const float* tex;        // [Bt, C, Th, Tw]
@@ -36,38 +36,6 @@ struct SampleArgs {
     int64_t tex_bstride;     // C Th Tw, or 0 for a shared texture
     int B, C, H, W, Th, Tw;
 };
-
-// what one pixel needs to blend its C planes
-struct Foot {
-    int o00, o01, o10, o11;      // offsets into one plane of the texture: (ya, xa), (ya, xb), (yb, xa), (yb, xb)
-    float fx, fy;
-    bool live, inx, iny;
-};
-
-__device__ __forceinline__ Foot footprint(float u, float v, bool cover, int Th, int Tw) {
-    Foot f;
-    f.o00 = f.o01 = f.o10 = f.o11 = 0;
-    f.fx = f.fy = 0.f;
-    f.inx = f.iny = false;
-    f.live = cover && fabsf(u) <= TS_FLT_MAX && fabsf(v) <= TS_FLT_MAX;   // (a NaN compares false)
-    if (!f.live) return f;
-    const float tw = (float)Tw, th = (float)Th;
-    const float sx = u * tw - 0.5f, sy = (1.f - v) * th - 0.5f;
-    f.inx = sx >= -1.f && sx <= tw;
-    f.iny = sy >= -1.f && sy <= th;
-    const float sxc = fminf(fmaxf(sx, -1.f), tw), syc = fminf(fmaxf(sy, -1.f), th);
-    const float x0f = floorf(sxc), y0f = floorf(syc);
-    f.fx = sxc - x0f;
-    f.fy = syc - y0f;
-    const int x0 = (int)x0f, y0 = (int)y0f;                               // in [-1, Tw] x [-1, Th]
-    const int xa = min(max(x0, 0), Tw - 1), xb = min(max(x0 + 1, 0), Tw - 1);
-    const int ya = min(max(y0, 0), Th - 1), yb = min(max(y0 + 1, 0), Th - 1);
-    f.o00 = ya * Tw + xa;
-    f.o01 = ya * Tw + xb;
-    f.o10 = yb * Tw + xa;
-    f.o11 = yb * Tw + xb;
-    return f;
-}
 
 template <int V>
 __device__ __forceinline__ void store4(float* p, const float* x, int count) {

@@ -1,5 +1,5 @@
-"""The optional parts of the latent fit (inversion.LatentInverter): the landmark term, the region of the image loss and the
-perspective camera.  Each is a plain object that owns its settings, the buffers the captured iteration reads and the
+"""The optional parts of the latent fit (inversion.LatentInverter): the landmark term, the region of the image loss, the
+perspective camera and the photometric term.  Each is a plain object that owns its settings, the buffers the captured iteration reads and the
 outputs of the last forward; the inverter holds one of each, or None when the part is off, and calls it at one place of
 the iteration.  Nothing here draws random numbers.
 """
@@ -179,6 +179,63 @@ class Region:
         img, m_eff = region_blend(img, target, self.mask, self.normal_map)
         self.mask_fit = m_eff.detach()
         return img
+
+
+class Photometric:
+    """+ weight * sum_{c,y,x} on (render - target)^2 / (C H W) per row: the textured mesh against the picture.  render is
+    op.texture.sample of a texture variable at the uv map of the mesh the consumers see (op.texture.uv_map with its corners
+    through op.texture.explode); on is the uv map's cover, times the region's mask where the inverter has a region.  The
+    normaliser is fixed (like the pixel term's, it is not the covered area), so nothing is read back.  The gradient
+    reaches the texture and, through the uv map and the rasterizer's backward, the mesh: pose, coefficients and camera.
+    It does not reach the latent.  On the device the texture's gradient walks a tap list that a TapPlanner rebuilds in
+    every step (the uv map moves with the pose), in a fixed launch sequence, so the iteration can be captured.
+
+    layout: (uv [nt, 2], tri_uv [nf, 3]) or (uv, tri_uv, keep), row-parallel to the mesh's tri (face_model.uv_layout /
+    load_uv).  texture: the variable [Bt, C, T, T], Bt = 1 (one texture under all rows: the rows are views of one
+    subject) or B; rows [B]: the weighted rows of the last forward; render_fit [B, C, H, W], cover_fit [B, H, W],
+    uvmap_fit [B, H, W, 2]: the textured render of the last forward, its coverage and its uv map."""
+
+    def __init__(self, layout, tri, target, size, weight, shared, device):
+        from .op.landmark import _hw
+
+        if len(layout) not in (2, 3):
+            raise ValueError("LatentInverter: photometric = (uv, tri_uv) or (uv, tri_uv, keep), the texture layout")
+        uv, tri_uv = layout[0], layout[1]
+        keep = layout[2] if len(layout) == 3 else None
+        if tuple(tri_uv.shape) != tuple(tri.shape):
+            raise ValueError("LatentInverter: the layout's tri_uv %s must be row-parallel to the mesh's tri %s"
+                             % (tuple(tri_uv.shape), tuple(tri.shape)))
+        self.batch, self.channels = int(target.shape[0]), int(target.shape[1])
+        self.hw = tuple(int(x) for x in target.shape[-2:])
+        self.size = _hw(size)
+        self.weight = float(weight)
+        self.bt = 1 if shared or self.batch == 1 else self.batch
+        self.tri = tri.detach().to(device).contiguous()
+        self.uv = uv.detach().to(device).contiguous()                   # (uv_map takes it in the mesh's float type)
+        self.tri_uv = tri_uv.detach().to(device).contiguous()
+        self.keep = None if keep is None else keep.detach().to(device).contiguous()
+        self.texture = torch.zeros((self.bt, self.channels) + self.size, device=device, requires_grad=True)
+        self.planner = None
+        if torch.device(device).type == "cuda":
+            from .op.texture import TapPlanner
+
+            self.planner = TapPlanner(self.batch, self.hw[0], self.hw[1], self.size, self.bt, device)
+        self.scale = self.weight / float(self.channels * self.hw[0] * self.hw[1])
+        self.rows = self.render_fit = self.cover_fit = self.uvmap_fit = None
+
+    def __call__(self, v, target, mask=None):
+        """weight * rows [B] of the mesh v [B, nv, 3] the consumers see, kept as `rows`."""
+        from .op.texture import sample, uv_map
+
+        uvmap, cover = uv_map(v, self.tri, self.uv, self.tri_uv, self.hw, self.keep, explode=True)
+        out = sample(self.texture, uvmap, cover, 0.0, planner=self.planner)
+        on = cover.unsqueeze(1).to(out.dtype)
+        if mask is not None:
+            on = on * mask
+        d = out - target
+        self.rows = (on * (d * d)).sum((1, 2, 3)) * self.scale
+        self.render_fit, self.cover_fit, self.uvmap_fit = out.detach(), cover, uvmap.detach()
+        return self.rows
 
 
 class Camera:

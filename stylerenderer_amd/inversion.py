@@ -40,6 +40,10 @@ The optional parts are objects of fit_parts, each None when it is off, and each 
     landmark    fit_parts.LandmarkTerm (landmarks=): the fit's landmarks against the picture's, and the pose's start
     region      fit_parts.Region (mask=, mask_mesh=): the image terms see the target itself outside a region
     cam         fit_parts.Camera (camera=, fit_camera=): the consumers see the mesh through a perspective projection
+    photo       fit_parts.Photometric (photometric=): a texture variable and the textured mesh against the picture.  Unlike
+                the others it has an iteration of its own: `run(steps)` stays the iteration without it, bit for bit, and
+                `run(steps, photometric=True)` runs the iteration with the term (a second captured graph over the same
+                variable buffers).  `set_texture` puts a starting texture (a bake) into the variable
 `_mesh` is the one place that builds the mesh (and applies the camera) for `render`, `posed_mesh` and `fitted_mesh`:
 `fitted_mesh()` returns what the consumers saw, `fitted_mesh(projected=False)` the camera-space mesh; `reset` puts kappa
 back at its start.  With a part off there is no node and no parameter for it: the iteration and its captured graph are
@@ -54,7 +58,7 @@ import torch
 from torch import optim
 
 from . import graphs, utils_3d
-from .fit_parts import Camera, LandmarkTerm, Region
+from .fit_parts import Camera, LandmarkTerm, Photometric, Region
 
 
 class _FlatAdamSet:
@@ -86,7 +90,8 @@ class LatentInverter:
                  n_mean_latent=4096, use_graph=None, optimise_pose=True, *, face=None, fit_shape=False, coeff_lr=0.01,
                  shape_reg=0.0, landmarks=None, landmark_conf=None, landmark_weight=1.0, landmark_beta=1.0,
                  landmark_embedding=None, landmark_lines=None, landmark_axis=None, landmark_vis=None, mask=None,
-                 mask_mesh=False, shared_identity=None, camera=None, fit_camera=False, camera_lr=0.01):
+                 mask_mesh=False, shared_identity=None, camera=None, fit_camera=False, camera_lr=0.01, photometric=None,
+                 photo_size=64, photo_weight=1.0, photo_lr=0.01):
         self.g = generator.eval()
         self.perceptual = perceptual.eval()
         for p in list(self.g.parameters()) + list(self.perceptual.parameters()):
@@ -151,6 +156,8 @@ class LatentInverter:
         # what render leaves for loss: the prior of this forward (None: not added), and the per-sample losses
         self._reg = self._prior_rows = self._rows = None
         on_gpu = self.device.type == "cuda"
+        from .optim import ALIGN, FlatAdam
+
         groups = [{"params": [self.w], "lr": lr}]
         if optimise_pose:
             groups.append({"params": [self.pose], "lr": pose_lr})
@@ -161,8 +168,6 @@ class LatentInverter:
         if on_gpu:
             # one sr_adam_flat launch per variable (optim.FlatAdam, the training loop's optimiser) instead of the ~30
             # multi-tensor passes of torch's capturable foreach Adam: at batch 1 every launch is ~5 us of an 8 ms step
-            from .optim import ALIGN, FlatAdam
-
             self._adams = []
             for g_ in groups:
                 p = g_["params"][0]
@@ -178,6 +183,21 @@ class LatentInverter:
         else:
             self._adams = None
             self.optim = optim.Adam(groups, betas=(0.9, 0.999))
+        # the photometric term (fit_parts.Photometric): a texture variable with its own Adam and step count, stepped by
+        # the iteration with the term only; not part of anything without photometric=
+        self.photo = self._photo_optim = self.graph_photo = None
+        self._photo_on = False
+        if photometric is not None:
+            self.photo = Photometric(photometric, self.tri, self.target, photo_size, photo_weight,
+                                     self.shared_identity is not None, self.device)
+            tex = self.photo.texture
+            if on_gpu:
+                flat_g = torch.zeros((tex.numel() + ALIGN - 1) // ALIGN * ALIGN, device=self.device)
+                self._photo_adam = FlatAdam([tex], flat_g, lr=photo_lr, betas=(0.9, 0.999))
+                self._photo_optim = _FlatAdamSet([(tex, self._photo_adam)])
+            else:
+                self._photo_adam = None
+                self._photo_optim = optim.Adam([{"params": [tex], "lr": photo_lr}], betas=(0.9, 0.999))
         self.use_graph = on_gpu if use_graph is None else bool(use_graph)
         self.graph = None
         self.loss_value = torch.zeros(() if self.batch == 1 else (self.batch,), device=self.device)
@@ -197,6 +217,8 @@ class LatentInverter:
     contour_fit = property(lambda self: None if self.landmark is None else self.landmark.contour_fit)
     landmark_visibility = property(lambda self: None if self.landmark is None else self.landmark.landmark_visibility)
     mask_fit = property(lambda self: None if self.region is None else self.region.mask_fit)
+    with_photometric = property(lambda self: self.photo is not None)
+    texture = property(lambda self: None if self.photo is None else self.photo.texture.detach())   # [Bt, C, T, T]
 
     def _features_of_target(self):
         """The target's LPIPS features: `features`, or with a region the region's choice."""
@@ -241,10 +263,13 @@ class LatentInverter:
     def render(self):
         self._reg = self._prior_rows = None
         lmk = self.landmark
-        if self.with_map or lmk is not None:
+        if self.with_map or lmk is not None or self._photo_on:
             v, n, n_gate, reg, prior_rows = self._mesh(gate=lmk is not None and lmk.vis is not None)
             if lmk is not None:
                 lmk(v, n_gate)
+            if self._photo_on:
+                # the textured mesh against the picture, on the mesh every consumer sees
+                self.photo(v, self.target, None if self.region is None else self.region.mask)
         if not self.with_map:
             # a plain Generator takes no mesh: the model's mesh serves the landmark term only, and the prior is not added
             # (_reg stays None), as it never was on this path
@@ -270,6 +295,8 @@ class LatentInverter:
             value = value + self._reg                    # shape_reg * regulation(coeff), from the node's forward
         if self.landmark is not None:
             value = value + self.landmark.rows.view(())
+        if self._photo_on:
+            value = value + self.photo.rows.view(())
         return value
 
     def _loss_rows(self, img):
@@ -289,7 +316,19 @@ class LatentInverter:
         if self.landmark is not None:
             self._rows = self._rows + self.landmark.rows.detach()
             total = total + self.landmark.rows.sum()
+        if self._photo_on:
+            self._rows = self._rows + self.photo.rows.detach()
+            total = total + self.photo.rows.sum()
         return total
+
+    def _iteration_photo(self):
+        """The iteration with the photometric term: the same steps, the term in the forward, the texture's Adam after
+        the others'."""
+        self._photo_on = True
+        try:
+            self._iteration()
+        finally:
+            self._photo_on = False
 
     def _iteration(self):
         self.w.grad = None
@@ -298,6 +337,8 @@ class LatentInverter:
             self.coeff.grad = None
         if self.camera is not None:
             self.camera.grad = None
+        if self._photo_on:
+            self.photo.texture.grad = None
         img = self.render()
         value = self.loss(img)
         value.backward()
@@ -309,22 +350,30 @@ class LatentInverter:
                 self.coeff.grad = self.coeff.grad.contiguous()
             share_rows_(self.coeff.grad, self.shared_identity)
         self.optim.step()
+        if self._photo_on:
+            self._photo_optim.step()
         self.loss_value.copy_(value.detach() if self.batch == 1 else self._rows)
         self.image = img.detach()
 
     # ---- driver ---------------------------------------------------------------------------------------
-    def _warm_and_capture(self, history, warmup=3):
+    def _warm_and_capture(self, history, warmup=3, photometric=False):
         """`warmup` real iterations on a side stream (lazy initialisation, Adam state), then one capture.
-        Returns the number of optimisation steps already taken (capture itself executes nothing)."""
+        Returns the number of optimisation steps already taken (capture itself executes nothing).  photometric: of the
+        iteration with the term, into a graph of its own."""
+        body = self._iteration_photo if photometric else self._iteration
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for k in range(warmup):
-                self._iteration()
+                body()
                 history[k] = self.loss_value
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        self.graph = graphs.capture(self._iteration)      # memset nodes of torch's reductions repaired: graphs.py
+        graph = graphs.capture(body)                      # memset nodes of torch's reductions repaired: graphs.py
+        if photometric:
+            self.graph_photo = graph
+        else:
+            self.graph = graph
         return warmup
 
     @torch.no_grad()
@@ -363,6 +412,8 @@ class LatentInverter:
             self.coeff.zero_()
         if self.cam is not None:
             self.cam.reset()
+        if self.photo is not None:
+            self._zero_texture()
         if self._adams is not None:
             for _, adam in self._adams:
                 for t in (adam.m, adam.v, adam.step_t, adam.flat_g):
@@ -371,17 +422,53 @@ class LatentInverter:
             self.optim.state.clear()                     # torch's Adam initialises its state at the next step
         self.loss_value.zero_()
 
-    def run(self, steps=400):
+    @torch.no_grad()
+    def _zero_texture(self):
+        """The texture at 0, its Adam's moments and step count at 0."""
+        self.photo.texture.zero_()
+        if self._photo_adam is not None:
+            for t in (self._photo_adam.m, self._photo_adam.v, self._photo_adam.step_t, self._photo_adam.flat_g):
+                t.zero_()
+        else:
+            self._photo_optim.state.clear()
+
+    @torch.no_grad()
+    def set_texture(self, tex):
+        """A starting texture [Bt, C, T, T] (a bake; [C, T, T] at Bt = 1) into the variable, in place (the captured
+        iteration reads that buffer), with the moments and the step count of the texture's Adam back at 0."""
+        if self.photo is None:
+            raise ValueError("LatentInverter.set_texture: this inverter was built without photometric=")
+        var = self.photo.texture
+        t = tex.detach()
+        if t.dim() == 3 and var.shape[0] == 1:
+            t = t.unsqueeze(0)
+        if tuple(t.shape) != tuple(var.shape):
+            raise ValueError("LatentInverter.set_texture: texture %s, the inverter's variable is %s"
+                             % (tuple(t.shape), tuple(var.shape)))
+        self._zero_texture()
+        var.copy_(t)
+
+    def run(self, steps=400, photometric=False):
         """Runs `steps` Adam iterations; returns the loss history [steps] ([steps, B] for B > 1; device tensor: no host
-        read here)."""
+        read here).  photometric=True (an inverter built with photometric=): the iteration with the photometric term,
+        whose texture takes Adam steps too; it is warmed and captured on first use into a graph of its own, and the
+        history then includes the term."""
+        if photometric and self.photo is None:
+            raise ValueError("LatentInverter.run: photometric=True needs an inverter built with photometric=")
         history = torch.zeros((steps,) if self.batch == 1 else (steps, self.batch), device=self.device)
         done = 0
-        if self.use_graph and self.graph is None and steps > 4:
-            done = self._warm_and_capture(history)
+        if photometric:
+            if self.use_graph and self.graph_photo is None and steps > 4:
+                done = self._warm_and_capture(history, photometric=True)
+            graph, body = self.graph_photo, self._iteration_photo
+        else:
+            if self.use_graph and self.graph is None and steps > 4:
+                done = self._warm_and_capture(history)
+            graph, body = self.graph, self._iteration
         for i in range(done, steps):
-            if self.graph is not None:
-                self.graph.replay()
+            if graph is not None:
+                graph.replay()
             else:
-                self._iteration()
+                body()
             history[i] = self.loss_value
         return history

@@ -57,6 +57,10 @@ has its centre at u = (tx + 1/2) / Tw, v = 1 - (ty + 1/2) / Th: row 0 is the top
                          separately; a texel no tap reaches gets exactly 0; with Bt = 1 the sum runs over all B views.
               The texture's gradient is a gather over a tap list (`tap_plan`), not a scatter: no atomics, one order.
   render      `uv_map` followed by `sample` (or, with mip = a bias, by `sample_mip`).
+  TapPlanner  the tap list built by the device in a fixed launch sequence (csrc/tap_plan.hip: a radix sort, the integers
+              of `tap_plan`), for a uv map that moves in every step of a captured fit: `sample(..., planner=p)`.
+  explode     c[b, 3 f + k] = v[b, tri[f, k]], the corners `uv_map` draws, with an adjoint that is an ordered sum over
+              the topology's incidence list (csrc/explode.hip: one launch): `uv_map(..., explode=True)` (DESIGN.md 7k''').
 
   The mip-mapped look-up (csrc/texture_mip.hip), for a texture drawn smaller than it is (DESIGN.md 7k''):
   mip_layout  ((offset, h, w), ...) of the levels of a (Th, Tw) texture: level 0 is the texture, level l + 1 has half of
@@ -487,7 +491,55 @@ def coverage(face, weight):
 
 
 # ---- the uv map of a posed mesh ----------------------------------------------------------------------------------------
-def uv_map(v, tri, uv, tri_uv, size, keep=None):
+_TOPO_CACHE = DerivedCache(8)                                                # the exploded meshes' topologies
+
+
+class _Explode(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, v, tri):
+        ctx.save_for_backward(tri)
+        ctx.nv = int(v.shape[1])
+        return v[:, tri.reshape(-1)].contiguous()
+
+    @staticmethod
+    def backward(ctx, g):
+        from .rasterize import incidence
+
+        tri, = ctx.saved_tensors
+        nv, nf = ctx.nv, int(tri.shape[0])
+        b = int(g.shape[0])
+        off, adj = incidence(tri, nv)[:2]
+        if native_ok(g):
+            gc = g.contiguous()
+            gv = torch.empty((b, nv, 3), dtype=g.dtype, device=g.device)
+            native(gc).sr_explode_bwd(gv, gc, off, adj, b, nv, nf)
+            return gv, None
+        if is_device_tensor(g) and strict_native():
+            raise RuntimeError("explode: SR_STRICT_NATIVE=1 and the kernel takes float32 device tensors only")
+        # the definition: corner k nf + f of the incidence list is row 3 f + k of the exploded mesh
+        terms = g.reshape(b, nf, 3, 3).permute(0, 3, 2, 1).reshape(b * 3, 3 * nf)
+        acc = _ordered_sum(terms, off, adj, nv)                                  # [B 3, nv]
+        return acc.view(b, 3, nv).permute(0, 2, 1).contiguous(), None
+
+
+def explode(v, tri):
+    """c [B, 3 nf, 3] with c[b, 3 f + k] = v[b, tri[f, k]]: the mesh v [B, nv, 3] with the corners of tri int64 [nf, 3]
+    exploded, the same values as v[:, tri.reshape(-1)].  The gradient of a vertex is the sum of its corners' gradients,
+    each coordinate from 0 in the fixed order of op.rasterize.incidence(tri, nv) (built once per topology and cached; its
+    entries k nf + f ascend): on float32 device tensors one launch of sr_explode_bwd, everywhere else the same ordered sum
+    in torch operations, so host and device agree bit for bit and reruns are bit-identical.  A vertex no face uses gets
+    exactly 0.  tri must hold valid vertex numbers and live on v's device."""
+    if v.dim() != 3 or v.shape[2] != 3 or tri.dim() != 2 or tri.shape[1] != 3 or tri.dtype != torch.int64:
+        raise ValueError("explode: v [B, nv, 3] and tri int64 [nf, 3], got %s and %s" % (tuple(v.shape), tuple(tri.shape)))
+    if tri.device != v.device:
+        raise ValueError("explode: tri must be on v's device (the incidence list is cached per topology tensor)")
+    return _Explode.apply(v, tri)
+
+
+_explode_corners = explode                                                   # (uv_map has an argument of that name)
+
+
+def uv_map(v, tri, uv, tri_uv, size, keep=None, explode=False):
     """(uvmap [B, H, W, 2], cover bool [B, H, W]) of the posed mesh v [B, nv, 3], tri [nf, 3] with the layout uv [nt, 2],
     tri_uv [nf, 3] in the pixels `project(., (H, W))` means: the texture coordinates of the surface point under every
     pixel and whether there is one.  A layout has seams, so a vertex has no single uv: the mesh is drawn with its corners
@@ -497,7 +549,9 @@ def uv_map(v, tri, uv, tri_uv, size, keep=None):
     from a third attribute that is 1 on every corner.  With keep (bool [nf], the faces face_model.uv_layout maps) the
     other faces still occlude, but their pixels are not covered (their three attributes are 0).  A non-square size is
     drawn in a square of side max(H, W) and cropped, as `depth_buffer` does.  Host and device results are equal bit for
-    bit (the rasterizer's parity)."""
+    bit (the rasterizer's parity).  explode=True takes the corners through `explode` instead of the indexing: the same
+    values, and a gradient to v that is an ordered sum (one launch on the device) instead of a library's
+    index_put(accumulate=True); tri must then be on v's device."""
     from .rasterize import rasterize
 
     h, w = _hw(size)
@@ -515,13 +569,23 @@ def uv_map(v, tri, uv, tri_uv, size, keep=None):
     if h != w:
         x, y = _square_vertices(v[..., 0], v[..., 1], (h, w))
         v = torch.stack((x, y, v[..., 2]), -1)
-    corners = v[:, tri.to(dev).reshape(-1)].contiguous()                       # [B, 3 nf, 3]
+    if explode:
+        corners = _explode_corners(v, tri)                                     # [B, 3 nf, 3]
+    else:
+        corners = v[:, tri.to(dev).reshape(-1)].contiguous()
     attr = torch.cat((uv.detach().to(device=dev, dtype=dt)[tri_uv.to(dev).reshape(-1)],
                       torch.ones(3 * nf, 1, dtype=dt, device=dev)), 1)
     if keep is not None:
         attr = attr * keep.to(dev).reshape(-1, 1).expand(-1, 3).reshape(-1, 1).to(dt)
     attr = attr.unsqueeze(0).expand(b, -1, -1).contiguous()
-    topo = torch.arange(3 * nf, dtype=torch.int64, device=dev).view(nf, 3)
+    if explode:
+        # one topology tensor per size and device: the rasterizer's backward keys its incidence list by the tensor, and a
+        # captured iteration must find it built
+        topo = _TOPO_CACHE.get((nf, str(dev)))
+        if topo is None:
+            topo = _TOPO_CACHE.put((nf, str(dev)), torch.arange(3 * nf, dtype=torch.int64, device=dev).view(nf, 3))
+    else:
+        topo = torch.arange(3 * nf, dtype=torch.int64, device=dev).view(nf, 3)
     s = max(h, w)
     out = rasterize(corners, attr, topo, s, s, False, 1e-9)[:, :h, :w]
     return out[..., :2].contiguous(), (out[..., 2].detach() != 0).contiguous()
@@ -675,8 +739,8 @@ def _sample_backward(tex, uvmap, cover, g, need_uv=True, need_tex=True):
 
 class _Sample(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, tex, uvmap, cover, background, kernels):
-        ctx.kernels, ctx.background = kernels, background
+    def forward(ctx, tex, uvmap, cover, background, kernels, planner=None):
+        ctx.kernels, ctx.background, ctx.planner = kernels, background, planner
         tc, uc, cc = tex.contiguous(), uvmap.contiguous(), cover.contiguous()
         ctx.save_for_backward(tc, uc, cc)
         if not kernels:
@@ -692,11 +756,11 @@ class _Sample(torch.autograd.Function):
         tc, uc, cc = ctx.saved_tensors
         need_tex, need_uv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (need_tex or need_uv):
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         if torch.is_grad_enabled() or not ctx.kernels:
             # the definition in torch operations; under create_graph=True it is recorded and differentiates again
             guv, gtex = _sample_backward(tc, uc, cc, g, need_uv, need_tex)
-            return gtex, guv, None, None, None
+            return gtex, guv, None, None, None, None
         g = g.contiguous()
         bt, c_n, th, tw = (int(x) for x in tc.shape)
         b, h, w = (int(x) for x in uc.shape[:3])
@@ -705,10 +769,11 @@ class _Sample(torch.autograd.Function):
             guv = torch.empty_like(uc)
             native(tc).sr_texture_sample_bwd_uv(guv, g, tc, uc, cc, b, bt, c_n, h, w, th, tw)
         if need_tex:
-            off, entries = tap_plan(uc, cc, (th, tw), bt)
+            # the tap list: the planner's fixed launch sequence (capturable with a moving uv map), or the cached one
+            off, entries = ctx.planner.build(uc, cc) if ctx.planner is not None else tap_plan(uc, cc, (th, tw), bt)
             gtex = torch.empty_like(tc)
             native(tc).sr_texture_sample_bwd_tex(gtex, g, uc, cc, off, entries, b, bt, c_n, h, w, th, tw)
-        return gtex, guv, None, None, None
+        return gtex, guv, None, None, None, None
 
 
 def _background(background, dtype):
@@ -719,10 +784,73 @@ def sample_composite(tex, uvmap, cover, background=0.0):
     """The defining tensor algebra of `sample`, in tex's float type, as an autograd node whose backward is the stated
     formulas (`_sample_backward`: the ordered sum of the texture's gradient included)."""
     _check_sample(tex, uvmap, cover)
-    return _Sample.apply(tex.contiguous(), uvmap.contiguous(), cover, _background(background, tex.dtype), False)
+    return _Sample.apply(tex.contiguous(), uvmap.contiguous(), cover, _background(background, tex.dtype), False, None)
 
 
-def sample(tex, uvmap, cover, background=0.0):
+TAP_RADIX_BITS = 8                                                           # the digit width d of csrc/tap_plan.hip
+
+
+class TapPlanner:
+    """The tap list of `tap_plan` built by the device in a fixed launch sequence (csrc/tap_plan.hip), for a uv map that
+    changes from call to call: a fit with the pose among its variables rebuilds the list in every step, inside its
+    captured iteration.  A planner is made for one shape: B views of (H, W) pixels on a (Th, Tw) texture, Bt = B or 1.  It
+    owns off int32 [Bt Th Tw + 2], entries int32 [4 B H W] and the scratch, all sized from the shapes alone;
+    `build(uvmap, cover)` writes every element of off and entries (and every element of the scratch it later reads) on the
+    current stream and returns (off, entries), the integers `tap_plan` returns: nothing is allocated, nothing read back,
+    no memset, so the sequence can be captured.  The arrays are the planner's own: the next build overwrites them.
+    `passes` is the number of digit passes, ceil(bits(Bt Th Tw) / TAP_RADIX_BITS); `launches` the kernels of one build.
+    The host definition remains `tap_plan`: a planner takes device tensors only."""
+
+    def __init__(self, b, h, w, size, bt, device):
+        th, tw = _hw(size)
+        b, h, w, bt = int(b), int(h), int(w), int(bt)
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("TapPlanner: a planner builds its list on the device; on the host `tap_plan` is the list")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())       # (tensors name their device with its index)
+        if b < 1 or h < 1 or w < 1 or th < 1 or tw < 1:
+            raise ValueError("TapPlanner: sizes must be positive, got B = %d, (%d, %d), (%d, %d)" % (b, h, w, th, tw))
+        if bt not in (1, b):
+            raise ValueError("TapPlanner: Bt is B (%d) or 1, got %d" % (b, bt))
+        if 4 * b * h * w >= 2 ** 31 or bt * th * tw >= 2 ** 31 - 1:
+            raise ValueError("TapPlanner: 4 B H W and Bt Th Tw must be below 2^31")
+        from .. import _lib
+
+        lib = _lib.lib()
+        if int(lib.sr_tap_plan_digit_bits()) != TAP_RADIX_BITS:
+            raise RuntimeError("TapPlanner: the library sorts %d-bit digits, this module expects %d"
+                               % (int(lib.sr_tap_plan_digit_bits()), TAP_RADIX_BITS))
+        self.shape, self.size, self.bt, self.device = (b, h, w), (th, tw), bt, device
+        self.passes = int(lib.sr_tap_plan_passes(bt, th, tw))
+        self.scratch_ints = int(lib.sr_tap_plan_scratch_ints(b, h, w))
+        if self.passes < 1 or self.scratch_ints < 0:
+            raise ValueError("TapPlanner: sizes out of the kernels' range")
+        self.launches = 2 + 3 * self.passes
+        self.off = torch.empty(bt * th * tw + 2, dtype=torch.int32, device=device)
+        self.entries = torch.empty(4 * b * h * w, dtype=torch.int32, device=device)
+        self.scratch = torch.empty(self.scratch_ints, dtype=torch.int32, device=device)
+
+    def buffers(self):
+        """(off, entries, scratch): everything a build writes."""
+        return self.off, self.entries, self.scratch
+
+    def build(self, uvmap, cover):
+        """(off, entries) of uvmap float32 [B, H, W, 2] and cover bool [B, H, W], contiguous, on the planner's device."""
+        b, h, w = self.shape
+        if tuple(uvmap.shape) != (b, h, w, 2) or uvmap.dtype != torch.float32 or tuple(cover.shape) != (b, h, w) or (
+                cover.dtype != torch.bool):
+            raise ValueError("TapPlanner.build: this planner takes uvmap float32 %s and cover bool %s, got %s %s and %s %s"
+                             % ((b, h, w, 2), (b, h, w), uvmap.dtype, tuple(uvmap.shape), cover.dtype, tuple(cover.shape)))
+        if uvmap.device != self.device or cover.device != self.device:
+            raise ValueError("TapPlanner.build: uvmap and cover must be on the planner's device %s" % self.device)
+        uc, cc = uvmap.detach().contiguous(), cover.contiguous()
+        native(uc).sr_tap_plan_build(self.off, self.entries, self.scratch, self.scratch_ints, uc, cc, b, self.bt, h, w,
+                                     self.size[0], self.size[1])
+        return self.off, self.entries
+
+
+def sample(tex, uvmap, cover, background=0.0, planner=None):
     """out [B, C, H, W]: the texture tex [Bt, C, Th, Tw] (Bt = B, or 1: one texture shared by all views) looked up
     bilinearly at the uv map [B, H, W, 2] of `uv_map`; a pixel with cover false or a non-finite coordinate gets
     `background` and contributes to no gradient.  Differentiable in tex and uvmap (the module's note has both gradients).
@@ -730,12 +858,24 @@ def sample(tex, uvmap, cover, background=0.0):
     nothing read back; everything else `sample_composite`.  The texture's gradient walks the tap list of `tap_plan`, which
     is cached per uv map: with a fixed uv map (refinement, a turntable frame) it is built once and forward and backward can
     be captured after one call of `tap_plan`; a uv map that changes from call to call rebuilds the list in every
-    backward.  The results are the host float32 composite's bit for bit, and reruns are bit-identical (no atomics)."""
+    backward.  With planner = a `TapPlanner` of these shapes the device backward takes its list from `planner.build`
+    instead: the same integers from a fixed launch sequence, so forward and backward can be captured with a uv map that
+    moves between replays (a planner with host tensors is refused).  The results are the host float32 composite's bit
+    for bit, and reruns are bit-identical (no atomics)."""
     _check_sample(tex, uvmap, cover)
     kernels = native_ok(tex, uvmap) and is_device_tensor(cover)
+    if planner is not None:
+        if not kernels:
+            raise ValueError("sample: a planner serves the device kernels (float32 device tensors); the host definition's "
+                             "list is tap_plan")
+        b, h, w = (int(x) for x in uvmap.shape[:3])
+        if planner.shape != (b, h, w) or planner.size != (int(tex.shape[2]), int(tex.shape[3])) or (
+                planner.bt != int(tex.shape[0])) or planner.device != tex.device:
+            raise ValueError("sample: the planner was made for B, H, W = %s, a texture %s and Bt = %d on %s"
+                             % (planner.shape, planner.size, planner.bt, planner.device))
     if not kernels and is_device_tensor(tex) and strict_native():
         raise RuntimeError("sample: SR_STRICT_NATIVE=1 and the kernels take float32 device tensors only")
-    return _Sample.apply(tex.contiguous(), uvmap.contiguous(), cover, _background(background, tex.dtype), kernels)
+    return _Sample.apply(tex.contiguous(), uvmap.contiguous(), cover, _background(background, tex.dtype), kernels, planner)
 
 
 def render(v, tri, uv, tri_uv, tex, size, background=0.0, keep=None, mip=None):

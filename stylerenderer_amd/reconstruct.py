@@ -743,10 +743,28 @@ class TextureGuide:
             with open(os.path.splitext(path)[0] + ".pgm", "wb") as f:
                 f.write(b"P5 %d %d 255\n" % (grey.shape[1], grey.shape[0]) + grey.tobytes())
 
-    def outputs(self, inv, index, out_dir, stem, path, keep=None):
+    def start(self, inv, index, path):
+        """(texture [1, C, T, T], bake, weight) of sample `index` at the inverter's current state: the bake, padded and
+        filled as it would be written: what --photo starts from."""
+        from .op import texture
+
+        k = slice(index, index + 1)
+        v, n, tri = inv.fitted_mesh()
+        v, n = v[k].contiguous(), n[k].contiguous()
+        picture = inv.image[k] if self.source == "render" else load_picture(path).to(v.device)
+        side = min(1024, max(int(inv.target.shape[-1]), self.size))
+        with torch.no_grad():
+            zbuf = texture.depth_buffer(v, tri, side)
+            tex, weight = texture.bake(v, n, tri, self.face, self.coeff, picture.to(v.dtype).contiguous(), zbuf,
+                                       facing=self.facing)
+            return self.finish(tex, weight), tex, weight
+
+    def outputs(self, inv, index, out_dir, stem, path, keep=None, photo=None):
         """Writes the four texture files of sample `index` and returns the .npz entry `texture_coverage`.  keep: a list
         that receives the bake before padding, (tex [1, C, T, T], weight [1, 1, T, T]), and makes the returned entries
-        hold it too (`texture`, `texture_weight`): the views of --multiview, merged afterwards."""
+        hold it too (`texture`, `texture_weight`): the views of --multiview, merged afterwards.  photo: the texture
+        [1, C, T, T] of the photometric phase (--photo); it stands where the padded bake would, and where the bake of the
+        final mesh has weight it is what a light is separated from and what the views hand to the merge."""
         from .op import texture
 
         k = slice(index, index + 1)
@@ -765,7 +783,11 @@ class TextureGuide:
             tex, weight = texture.bake(v, n, tri, self.face, self.coeff, picture.to(v.dtype).contiguous(), zbuf,
                                        facing=self.facing)
             cover = float(texture.coverage(self.face, weight)[0])
-            out = self.finish(tex, weight)
+            if photo is not None:
+                out = photo.to(tex.dtype).contiguous()
+                tex = torch.where(weight > 0, out, torch.zeros_like(out))
+            else:
+                out = self.finish(tex, weight)
         more = {} if self.mip is None else {"texture_mip": np.float64(self.mip)}
         lit = pair = None
         if self.light is not None:
@@ -1057,6 +1079,15 @@ def main(argv=None):
     ap.add_argument("--texture_mip", type=float, nargs="?", const=0.0, default=None, metavar="BIAS",
                     help="with --texture: every draw of --texture_check, --turntable, --relight and --texture_refine looks "
                          "the texture up through its mip pyramid (trilinear; BIAS is added to the level of detail [0])")
+    ap.add_argument("--photo", type=float, nargs="?", const=1.0, default=None, metavar="WEIGHT",
+                    help="with --texture: after the fit and the bake, run --photo_steps iterations of the fit with a "
+                         "photometric term of this weight (the textured mesh against the picture; the texture, the pose, "
+                         "the coefficients and the camera move), starting from the bake, and write every output from the "
+                         "state after them [%(const)g; this and the two below are untuned starting values]")
+    ap.add_argument("--photo_steps", type=int, default=None, metavar="N",
+                    help="iterations of the photometric phase [100; untuned]")
+    ap.add_argument("--photo_lr", type=float, default=None, metavar="LR",
+                    help="learning rate of the texture in the photometric phase [0.01; untuned]")
     ap.add_argument("--light", action="store_true",
                     help="with --texture: separate every bake into an albedo and a light (second-order spherical "
                          "harmonics, fitted in closed form); <stem>_texture.png is then the albedo")
@@ -1127,6 +1158,17 @@ def main(argv=None):
         ap.error("--texture_check, --turntable and --texture_refine need --texture")
     if args.texture is None and args.texture_mip is not None:
         ap.error("--texture_mip needs --texture")
+    if args.photo is None and (args.photo_steps is not None or args.photo_lr is not None):
+        ap.error("--photo_steps and --photo_lr need --photo")
+    if args.photo is not None:
+        if args.texture is None:
+            ap.error("--photo needs --texture")
+        if not (args.photo >= 0 and np.isfinite(args.photo)):
+            ap.error("--photo takes a finite weight that is not negative")
+        args.photo_steps = 100 if args.photo_steps is None else args.photo_steps
+        args.photo_lr = 0.01 if args.photo_lr is None else args.photo_lr
+        if args.photo_steps < 1 or not args.photo_lr >= 0:
+            ap.error("--photo_steps is at least 1 and --photo_lr is not negative")
     if args.texture is None and (args.light or args.light_mono or args.light_floor is not None
                                  or args.light_ridge is not None or args.light_lr is not None or args.relight):
         ap.error("--light, --light_mono, --light_floor, --light_ridge, --light_lr and --relight need --texture")
@@ -1204,11 +1246,52 @@ def main(argv=None):
         look = guide.lookup(path, shape, args.size) + (shape,)
         return x, look, masker.lookup(path, look, args.size) if masker else None
 
-    def more(inv, index, stem, extras, path, keep=None):
-        """The .npz entries with the region's and the texture's (and their files written), when there are any."""
+    photo_args = {}
+    if args.photo is not None:
+        photo_args = dict(photometric=painter._layout, photo_size=args.texture, photo_weight=args.photo,
+                          photo_lr=args.photo_lr)
+
+    def photo_error(tex, view):
+        """The mean absolute difference between the texture drawn on a view and the view's target, over the covered
+        pixels (texture_rerender's error with every texel counted)."""
+        return texture_rerender(tex, torch.ones_like(tex[:, :1]), [view])[0][1]
+
+    def photo_phase(inv, paths):
+        """--photo: the bake of every sample at the fitted state (one merged texture when the rows are views of one
+        subject) into the inverter's texture, then the photometric iterations.  Returns per sample the .npz entries
+        photo_loss, photo_error_before and photo_error_after, and the texture [1, C, T, T] to write."""
+        from .op import texture
+
+        n = len(paths)
+        starts = [painter.start(inv, i, path) for i, path in enumerate(paths)]
+        with torch.no_grad():
+            if inv.photo.bt == 1 and inv.batch > 1:
+                merged, weight, _ = texture.merge(torch.cat([t for _, t, _ in starts], 0),
+                                                  torch.cat([w for _, _, w in starts], 0),
+                                                  2 if args.merge_sharpness is None else args.merge_sharpness)
+                first = painter.finish(merged, weight)
+            else:
+                first = torch.cat([t for t, _, _ in starts] + [starts[-1][0]] * (inv.batch - n), 0)
+        pick = (lambda t, i: t) if inv.photo.bt == 1 else (lambda t, i: t[i:i + 1])
+        before = [photo_error(pick(first, i), painter.view(inv, i)) for i in range(n)]
+        inv.set_texture(first)
+        hist = inv.run(args.photo_steps, photometric=True).cpu().numpy().reshape(args.photo_steps, -1)
+        final = inv.texture.clone()
+        out = []
+        for i in range(n):
+            tex = pick(final, i).contiguous()
+            out.append((dict(photo_loss=np.ascontiguousarray(hist[:, i]), photo_error_before=np.float64(before[i]),
+                             photo_error_after=np.float64(photo_error(tex, painter.view(inv, i)))), tex))
+        return out
+
+    def more(inv, index, stem, extras, path, keep=None, photo=None):
+        """The .npz entries with the region's and the texture's (and their files written), when there are any.  photo:
+        (entries, texture) of the photometric phase."""
         if masker is not None:
             extras = dict(extras or {}, **mask_outputs(inv, index, args.out, stem))
-        if painter is not None:
+        if painter is not None and photo is not None:
+            extras = dict(extras or {}, **photo[0], **painter.outputs(inv, index, args.out, stem, path, keep, photo[1]))
+        elif painter is not None:
             extras = dict(extras or {}, **painter.outputs(inv, index, args.out, stem, path, keep))
         return extras
 
@@ -1231,10 +1314,12 @@ def main(argv=None):
             if masker:
                 lmk_args.update(masker.inverter_args([mask]))
             lmk_args.update(camera_args)
+            lmk_args.update(photo_args)
             inv, hist = reconstruct(g, percept, face, target.to(device), args.steps, args.lr, args.pose_lr, args.coeff_lr,
                                     args.shape_reg, args.n_mean_latent, **lmk_args)
+            photo = photo_phase(inv, [path])[0] if args.photo is not None else None
             extras = landmark_outputs(inv, 0, look[1], look[2], look[3]) if guide else None
-            write_outputs(inv, hist, args.out, stem, extras=more(inv, 0, stem, extras, path))
+            write_outputs(inv, hist, args.out, stem, extras=more(inv, 0, stem, extras, path, photo=photo))
             print("%s: loss %.4f -> %.4f over %d steps, |coeff| %.4f%s" % (
                 path, float(hist[0]), float(hist[-1]), len(hist), float(inv.coeff.detach().norm()), tail(extras)),
                 flush=True)
@@ -1255,6 +1340,8 @@ def main(argv=None):
         if masker:
             lmk_args.update(masker.inverter_args(masks))
         lmk_args.update(camera_args)
+        if inv is None:
+            lmk_args.update(photo_args)
         inv, hist = reconstruct_batch(g, percept, face, torch.cat(targets, 0).to(device), args.steps, args.lr,
                                       args.pose_lr, args.coeff_lr, args.shape_reg, args.n_mean_latent, inv=inv,
                                       shared_identity=shared, **lmk_args)
@@ -1262,11 +1349,12 @@ def main(argv=None):
         name = (args.subject or stems[0]) if shared is not None else None
         bakes = [] if shared is not None and painter is not None else None
         covers = []
+        photos = photo_phase(inv, group) if args.photo is not None else None
         for i, path in enumerate(group):
             stem = stems[i]
             h = np.ascontiguousarray(hist[:, i])
             lmk = landmark_outputs(inv, i, looks[i][1], looks[i][2], looks[i][3]) if guide else None
-            extras = more(inv, i, stem, lmk, path, bakes)
+            extras = more(inv, i, stem, lmk, path, bakes, None if photos is None else photos[i])
             if shared is not None:
                 extras = dict(extras or {}, subject=np.asarray(name), view=np.int64(i))
                 if painter is not None:
