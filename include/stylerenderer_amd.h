@@ -1200,6 +1200,46 @@ int sr_light_moments(double* partial, const float* a, const float* normals, cons
 int sr_light_texel_attr(float* out, const float* attr, const int64_t* tri, const int32_t* face, const float* coeff,
                         int64_t B, int64_t A, int64_t nv, int64_t nf, int64_t Th, int64_t Tw, sr_stream_t stream);
 
+/* Analytic antialiasing at occlusion boundaries (definition: stylerenderer_amd/op/edge.py), csrc/edge.hip.  image, out, g
+ * and gimage are [B, C, H, W], v [B, nv, 3], tri int64 [nf, 3], opp int32 [nf, 3] (op.edge.adjacency: the vertex opposite
+ * edge k in the other face, -1 boundary, -2 never a silhouette), face int32 [B, H, W] (-1 empty) and zbuf [B, H, W] (greater
+ * is nearer).  A pair is a pixel p and its right or lower neighbour q, active iff face[p] != face[q]; the foreground a is q
+ * when face[p] < 0, p when face[q] < 0, else q iff z[q] > z[p]; o is the other pixel, F = face[a].  Per corner of F
+ *     X = (1 + x) (W / 2) - 0.5;  Y = (1 - y) (H / 2) - 0.5
+ * and for the edges k = 0, 1, 2 (corners i = k, j = (k + 1) mod 3), u the coordinate along the pair's axis, s the other one
+ * minus a's, every step one float32 operation in this order:
+ *     crossing iff (s_i < 0) != (s_j < 0);  den = s_i - s_j;  t = s_i / den;  du = u_j - u_i;  c = u_i + du t
+ *     d = c - a_u (a == p) or a_u - c (a == q);  taken iff 0 <= d <= 1
+ *     silhouette iff opp == -1, or opp >= 0 and (P_j - P_i) x (P_own - P_i), (P_j - P_i) x (P_opp - P_i) do not have
+ *     strictly opposite signs
+ * The first k that crosses and is a silhouette is the pair's edge; w = d - 0.5 and o receives when d >= 0.5, else
+ * w = 0.5 - d and a receives: the receiver r gets w (image[other] - image[r]).
+ * sr_edge_aa_fwd: out[p] = image[p] plus what p receives from its pairs, added in the order left, right, upper, lower.  A
+ *   lane per pixel, channels inside; a pixel whose cross shows one face leaves after five loads.
+ * sr_edge_aa_bwd_image: gimage[p] = g[p], then per pair in the same order - w g[p] where p receives, + w g[n] where the
+ *   neighbour n does.
+ * sr_edge_aa_bwd_corner: gc [B, 3 nf, 3], the gradient of the exploded corners (z = 0), all of it written.  Per pair with
+ *   receiver r:  gd = the sum from 0 in channel order of g[r] (image[a] - image[o]);  gsd = gd (a == p) or -gd;
+ *     gu_i = gsd (1 - t);  gu_j = gsd t;  q = (gsd du) / (den den);  gs_i = -(q s_j);  gs_j = q s_i
+ *     gx = gX (W / 2);  gy = gY (-(H / 2))        (X is u in a horizontal pair, s in a vertical one)
+ *   A lane per (sample, face) walks the pixels of the face's bounding box (floor of the least and ceil of the greatest
+ *   corner coordinate, grown by one pixel, clipped) in row-major order, right pair before lower pair, and adds the terms of
+ *   the pairs whose F is its face.  A box of more than sr_edge_big_pixels() pixels is summed by the face's wave: lane l adds
+ *   the pixels l, l + 64, ... in that order, then lane l adds lane l + 32, 16, 8, 4, 2, 1.  A face with a non-finite corner
+ *   gets 0.
+ * Face and vertex numbers outside the mesh switch a pair off and are not followed.  H, W <= 16384.  No atomics, no LDS, no
+ * scratch, no memset, no allocation, no host read: all run under graph capture on `stream`; reruns are bit-identical. */
+int sr_edge_big_pixels(void);
+int sr_edge_aa_fwd(float* out, const float* image, const float* v, const int64_t* tri, const int32_t* opp,
+                   const int32_t* face, const float* zbuf, int64_t B, int64_t C, int64_t H, int64_t W, int64_t nv,
+                   int64_t nf, sr_stream_t stream);
+int sr_edge_aa_bwd_image(float* gimage, const float* g, const float* v, const int64_t* tri, const int32_t* opp,
+                         const int32_t* face, const float* zbuf, int64_t B, int64_t C, int64_t H, int64_t W, int64_t nv,
+                         int64_t nf, sr_stream_t stream);
+int sr_edge_aa_bwd_corner(float* gc, const float* g, const float* image, const float* v, const int64_t* tri,
+                          const int32_t* opp, const int32_t* face, const float* zbuf, int64_t B, int64_t C, int64_t H,
+                          int64_t W, int64_t nv, int64_t nf, sr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,10 @@ SIGNATURES = {
     "sr_light_reduce": (_i, [_p, _p, _l, _l, _l, _i, _p]),
     "sr_light_moments": (_i, [_p] * 4 + [_l] * 4 + [_f, _p]),
     "sr_light_texel_attr": (_i, [_p] * 5 + [_l] * 6 + [_p]),
+    "sr_edge_big_pixels": (_i, []),
+    "sr_edge_aa_fwd": (_i, [_p] * 7 + [_l] * 6 + [_p]),
+    "sr_edge_aa_bwd_image": (_i, [_p] * 7 + [_l] * 6 + [_p]),
+    "sr_edge_aa_bwd_corner": (_i, [_p] * 8 + [_l] * 6 + [_p]),
     "sr_signal_bump": (_i, [_p, _p]),
     "sr_signal_wait": (_i, [_p, ctypes.c_uint32, _p]),
     "sr_signal_set": (_i, [_p, _p, _p]),

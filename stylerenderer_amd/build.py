@@ -74,6 +74,7 @@ SOURCES = [
     ("conv_generic.hip", []),
     ("conv1x1_gemm.hip", []),
     ("inception.hip", []),
+    ("edge.hip", EXACT),
 ]
 
 

@@ -195,7 +195,7 @@ class Photometric:
     subject) or B; rows [B]: the weighted rows of the last forward; render_fit [B, C, H, W], cover_fit [B, H, W],
     uvmap_fit [B, H, W, 2]: the textured render of the last forward, its coverage and its uv map."""
 
-    def __init__(self, layout, tri, target, size, weight, shared, device):
+    def __init__(self, layout, tri, target, size, weight, shared, device, edges=False):
         from .op.landmark import _hw
 
         if len(layout) not in (2, 3):
@@ -222,6 +222,7 @@ class Photometric:
             self.planner = TapPlanner(self.batch, self.hw[0], self.hw[1], self.size, self.bt, device)
         self.scale = self.weight / float(self.channels * self.hw[0] * self.hw[1])
         self.rows = self.render_fit = self.cover_fit = self.uvmap_fit = None
+        self.edges = bool(edges)
 
     def __call__(self, v, target, mask=None):
         """weight * rows [B] of the mesh v [B, nv, 3] the consumers see, kept as `rows`."""
@@ -229,12 +230,78 @@ class Photometric:
 
         uvmap, cover = uv_map(v, self.tri, self.uv, self.tri_uv, self.hw, self.keep, explode=True)
         out = sample(self.texture, uvmap, cover, 0.0, planner=self.planner)
+        if self.edges:
+            return self._with_edges(v, target, mask, out, cover, uvmap)
         on = cover.unsqueeze(1).to(out.dtype)
         if mask is not None:
             on = on * mask
         d = out - target
         self.rows = (on * (d * d)).sum((1, 2, 3)) * self.scale
         self.render_fit, self.cover_fit, self.uvmap_fit = out.detach(), cover, uvmap.detach()
+        return self.rows
+
+    def _with_edges(self, v, target, mask, out, cover, uvmap):
+        """photo_edges: the render composited over the picture (c = render where covered, the picture elsewhere) and
+        antialiased along the mesh's silhouette edges; rows = scale sum m (aa - target)^2, m the region's mask or 1.  At
+        an untouched uncovered pixel the difference is exactly 0; along the outline it depends on where the outline is.
+        The face map is a second rasterizer pass on the same v."""
+        from .op.edge import antialias, face_map
+
+        face, zbuf = face_map(v, self.tri, self.hw)
+        c = torch.where(cover.unsqueeze(1), out, target)
+        aa = antialias(c, v, self.tri, face, zbuf)
+        d = aa - target
+        sq = d * d
+        if mask is not None:
+            sq = mask * sq
+        self.rows = sq.sum((1, 2, 3)) * self.scale
+        self.render_fit, self.cover_fit, self.uvmap_fit = aa.detach(), cover, uvmap.detach()
+        return self.rows
+
+
+class Silhouette:
+    """+ weight * sum_{y,x} (coverage(v) - mask)^2 / (H W) per row: the outline of the mesh the consumers see against the
+    picture's.  coverage is op.edge.coverage, the hard cover antialiased along the mesh's silhouette edges, so the term
+    moves the vertices that form the outline; the face map is one rasterizer pass per step.  The normaliser
+    is fixed, so nothing is read back.  weight = 1.0 is an untuned starting value.
+
+    mask: the buffer [B, H, W] the iteration (and its captured graph) reads; rows [B]: the weighted rows of the last
+    forward; coverage_fit [B, H, W]: the coverage of the last forward."""
+
+    def __init__(self, tri, target, mask, weight, device):
+        self.batch = int(target.shape[0])
+        self.hw = tuple(int(x) for x in target.shape[-2:])
+        self.weight = float(weight)
+        self.tri = tri.detach().to(device).contiguous()
+        self.mask = torch.zeros((self.batch,) + self.hw, device=device)
+        self.scale = self.weight / float(self.hw[0] * self.hw[1])
+        self.rows = self.coverage_fit = None
+        self.set(mask)
+
+    @torch.no_grad()
+    def set(self, mask):
+        """mask [B, H, W] or [B, 1, H, W] ([H, W] at B = 1), finite and in [0, 1], into the buffer."""
+        m = mask.detach() if isinstance(mask, torch.Tensor) else torch.as_tensor(mask)
+        if m.dim() == 4 and m.shape[1] == 1:
+            m = m[:, 0]
+        if self.batch == 1 and tuple(m.shape) == self.hw:
+            m = m.reshape(self.mask.shape)
+        if tuple(m.shape) != tuple(self.mask.shape):
+            raise ValueError("LatentInverter: silhouette %s, the inverter fits %s (a silhouette is [B, H, W] or "
+                             "[B, 1, H, W], or [H, W] for one image)" % (tuple(m.shape), tuple(self.mask.shape)))
+        m = m.to(torch.float32)
+        if not bool(torch.isfinite(m).all()) or float(m.min()) < 0.0 or float(m.max()) > 1.0:
+            raise ValueError("LatentInverter: a silhouette is finite and in [0, 1]")
+        self.mask.copy_(m)
+
+    def __call__(self, v):
+        """weight * rows [B] of the mesh v [B, nv, 3] the consumers see, kept as `rows`."""
+        from .op.edge import coverage
+
+        alpha = coverage(v, self.tri, self.hw)
+        d = alpha - self.mask
+        self.rows = (d * d).sum((1, 2)) * self.scale
+        self.coverage_fit = alpha.detach()
         return self.rows
 
 

@@ -44,6 +44,9 @@ The optional parts are objects of fit_parts, each None when it is off, and each 
                 the others it has an iteration of its own: `run(steps)` stays the iteration without it, bit for bit, and
                 `run(steps, photometric=True)` runs the iteration with the term (a second captured graph over the same
                 variable buffers).  `set_texture` puts a starting texture (a bake) into the variable
+    silhouette  fit_parts.Silhouette (silhouette=): the antialiased coverage of the mesh (op.edge.coverage) against the
+                picture's silhouette, in the one captured step; photo_edges=True takes the same node into the photometric
+                term.  Not part of anything without the arguments
 `_mesh` is the one place that builds the mesh (and applies the camera) for `render`, `posed_mesh` and `fitted_mesh`:
 `fitted_mesh()` returns what the consumers saw, `fitted_mesh(projected=False)` the camera-space mesh; `reset` puts kappa
 back at its start.  With a part off there is no node and no parameter for it: the iteration and its captured graph are
@@ -58,7 +61,7 @@ import torch
 from torch import optim
 
 from . import graphs, utils_3d
-from .fit_parts import Camera, LandmarkTerm, Photometric, Region
+from .fit_parts import Camera, LandmarkTerm, Photometric, Region, Silhouette
 
 
 class _FlatAdamSet:
@@ -91,7 +94,8 @@ class LatentInverter:
                  shape_reg=0.0, landmarks=None, landmark_conf=None, landmark_weight=1.0, landmark_beta=1.0,
                  landmark_embedding=None, landmark_lines=None, landmark_axis=None, landmark_vis=None, mask=None,
                  mask_mesh=False, shared_identity=None, camera=None, fit_camera=False, camera_lr=0.01, photometric=None,
-                 photo_size=64, photo_weight=1.0, photo_lr=0.01):
+                 photo_size=64, photo_weight=1.0, photo_lr=0.01, silhouette=None, silhouette_weight=1.0,
+                 photo_edges=False):
         self.g = generator.eval()
         self.perceptual = perceptual.eval()
         for p in list(self.g.parameters()) + list(self.perceptual.parameters()):
@@ -189,7 +193,7 @@ class LatentInverter:
         self._photo_on = False
         if photometric is not None:
             self.photo = Photometric(photometric, self.tri, self.target, photo_size, photo_weight,
-                                     self.shared_identity is not None, self.device)
+                                     self.shared_identity is not None, self.device, edges=photo_edges)
             tex = self.photo.texture
             if on_gpu:
                 flat_g = torch.zeros((tex.numel() + ALIGN - 1) // ALIGN * ALIGN, device=self.device)
@@ -198,6 +202,12 @@ class LatentInverter:
             else:
                 self._photo_adam = None
                 self._photo_optim = optim.Adam([{"params": [tex], "lr": photo_lr}], betas=(0.9, 0.999))
+        elif photo_edges:
+            raise ValueError("LatentInverter: photo_edges=True needs photometric=")
+        # the silhouette term (fit_parts.Silhouette): not part of the iteration at all without silhouette=
+        self.sil = None
+        if silhouette is not None:
+            self.sil = Silhouette(self.tri, self.target, silhouette, silhouette_weight, self.device)
         self.use_graph = on_gpu if use_graph is None else bool(use_graph)
         self.graph = None
         self.loss_value = torch.zeros(() if self.batch == 1 else (self.batch,), device=self.device)
@@ -218,6 +228,8 @@ class LatentInverter:
     landmark_visibility = property(lambda self: None if self.landmark is None else self.landmark.landmark_visibility)
     mask_fit = property(lambda self: None if self.region is None else self.region.mask_fit)
     with_photometric = property(lambda self: self.photo is not None)
+    with_silhouette = property(lambda self: self.sil is not None)
+    coverage_fit = property(lambda self: None if self.sil is None else self.sil.coverage_fit)    # [B, H, W]
     texture = property(lambda self: None if self.photo is None else self.photo.texture.detach())   # [Bt, C, T, T]
 
     def _features_of_target(self):
@@ -263,10 +275,12 @@ class LatentInverter:
     def render(self):
         self._reg = self._prior_rows = None
         lmk = self.landmark
-        if self.with_map or lmk is not None or self._photo_on:
+        if self.with_map or lmk is not None or self._photo_on or self.sil is not None:
             v, n, n_gate, reg, prior_rows = self._mesh(gate=lmk is not None and lmk.vis is not None)
             if lmk is not None:
                 lmk(v, n_gate)
+            if self.sil is not None:
+                self.sil(v)
             if self._photo_on:
                 # the textured mesh against the picture, on the mesh every consumer sees
                 self.photo(v, self.target, None if self.region is None else self.region.mask)
@@ -295,6 +309,8 @@ class LatentInverter:
             value = value + self._reg                    # shape_reg * regulation(coeff), from the node's forward
         if self.landmark is not None:
             value = value + self.landmark.rows.view(())
+        if self.sil is not None:
+            value = value + self.sil.rows.view(())
         if self._photo_on:
             value = value + self.photo.rows.view(())
         return value
@@ -316,6 +332,9 @@ class LatentInverter:
         if self.landmark is not None:
             self._rows = self._rows + self.landmark.rows.detach()
             total = total + self.landmark.rows.sum()
+        if self.sil is not None:
+            self._rows = self._rows + self.sil.rows.detach()
+            total = total + self.sil.rows.sum()
         if self._photo_on:
             self._rows = self._rows + self.photo.rows.detach()
             total = total + self.photo.rows.sum()
@@ -377,7 +396,7 @@ class LatentInverter:
         return warmup
 
     @torch.no_grad()
-    def reset(self, target, landmarks=None, landmark_conf=None, mask=None):
+    def reset(self, target, landmarks=None, landmark_conf=None, mask=None, silhouette=None):
         """Re-targets the inverter to `target` (the shape of the first): copies it and its LPIPS features into the
         buffers the captured graph reads, puts w back at the mean latent, pose and coeff at zero, and zeroes the Adam
         moments and step counts.  An inverter built with landmarks also takes the new picture's `landmarks` and
@@ -386,8 +405,13 @@ class LatentInverter:
         mean latent, same noise), bit for bit, without a new warm-up or capture.  landmarks_fit, contour_fit and
         landmark_visibility are outputs of the (possibly captured) iteration: they keep the previous picture's values
         until the next step writes them.  An inverter built with a region (mask= or mask_mesh=) takes the new picture's
-        `mask` into its buffer (None: all ones); mask_fit is an output of the iteration like landmarks_fit."""
+        `mask` into its buffer (None: all ones); mask_fit is an output of the iteration like landmarks_fit.  An inverter
+        built with silhouette= takes the new picture's `silhouette` into its buffer in the same way (it has no default:
+        None raises)."""
         target = target.detach()
+        if (self.sil is None) != (silhouette is None):
+            raise ValueError("LatentInverter.reset: silhouette= goes with an inverter built with silhouette=, and such an "
+                             "inverter needs the new picture's; the term is part of the captured iteration or it is not")
         if not self.with_mask and mask is not None:
             raise ValueError("LatentInverter.reset: this inverter was built without a mask; the region blend is part of "
                              "the captured iteration or it is not")
@@ -399,6 +423,8 @@ class LatentInverter:
                              % (tuple(target.shape), tuple(self.target.shape)))
         if self.region is not None:
             self.region.set(mask)
+        if self.sil is not None:
+            self.sil.set(silhouette)
         self.target.copy_(target)
         for buf, f in zip(self.target_feats, self._features_of_target()):
             buf.copy_(f)

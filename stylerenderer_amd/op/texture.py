@@ -878,15 +878,23 @@ def sample(tex, uvmap, cover, background=0.0, planner=None):
     return _Sample.apply(tex.contiguous(), uvmap.contiguous(), cover, _background(background, tex.dtype), kernels, planner)
 
 
-def render(v, tri, uv, tri_uv, tex, size, background=0.0, keep=None, mip=None):
+def render(v, tri, uv, tri_uv, tex, size, background=0.0, keep=None, mip=None, antialias=False):
     """(image [B, C, H, W], cover bool [B, H, W]): the posed mesh v [B, nv, 3], tri [nf, 3] with the layout uv, tri_uv
     drawn with the texture tex [B or 1, C, Th, Tw] over `background`: `uv_map` followed by `sample`.  Differentiable in tex
     and, through the uv map and the rasterizer, in v.  mip: None, or the lod bias of the mip-mapped look-up
-    (`sample_mip` in `sample`'s place)."""
+    (`sample_mip` in `sample`'s place).  antialias=True: the image is blended along the mesh's silhouette edges
+    (op.edge.antialias; one more rasterizer pass for the face map), which also gives v a gradient from the outline; the
+    cover stays the hard one."""
     uvmap, cover = uv_map(v, tri, uv, tri_uv, size, keep)
     if mip is not None:
-        return sample_mip(tex, uvmap, cover, bias=float(mip), background=background), cover
-    return sample(tex, uvmap, cover, background), cover
+        image = sample_mip(tex, uvmap, cover, bias=float(mip), background=background)
+    else:
+        image = sample(tex, uvmap, cover, background)
+    if antialias:
+        from .edge import antialias as edge_antialias
+
+        image = edge_antialias(image, v.contiguous(), tri.to(v.device))
+    return image, cover
 
 
 # ---- the mip-mapped look-up --------------------------------------------------------------------------------------------

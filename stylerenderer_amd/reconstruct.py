@@ -11,6 +11,7 @@ for it):
          [--texture_fill mean|none] [--texture_check] [--turntable N [--turntable_yaw DEG]]
          [--texture_refine STEPS [--texture_lr LR]] [--texture_mip [BIAS]]
          [--light [--light_mono] [--light_floor S] [--light_ridge L] [--light_lr LR] [--relight FILE]]]
+        [--silhouette_dir DIR [--silhouette_weight 1.0]] [--photo_edges] [--render_aa]
         [--camera_distance D | --camera_fov DEG] [--fit_camera] [--camera_lr 0.01] CHECKPOINT IMAGE [IMAGE ...]
 
 For every image: the checkpoint's GeneratorWithMap (`g_ema`) is inverted with inversion.LatentInverter(fit_shape=True)
@@ -152,6 +153,17 @@ depth translation and the scale trade off along a flat direction under a camera 
 compare projections, kappa and angles between fits, not raw t_z or scale.  Not built: a principal-point offset (the crop is
 assumed centred on the optical axis), a closed-form perspective pose start (the orthographic one is the start), lens
 distortion.  Without these options nothing changes.
+
+With --silhouette_dir DIR the fit has a silhouette term (fit_parts.Silhouette): DIR/<stem>.png or .npy (read
+and resized as --mask_dir's files; every picture needs one) against the coverage of the mesh, antialiased along its
+silhouette edges (op.edge.coverage), so the outline pulls on the vertices that form it; per row
+--silhouette_weight * sum (coverage - silhouette)^2 / (H W), in the one captured step (weight 1.0: an untuned starting
+value).  <stem>_coverage.png is the fitted mesh's coverage, <stem>.npz gains `silhouette_loss` (the term at the fitted
+state) and `silhouette_iou` (both thresholded at 0.5).  It works with --batch, --multiview and all three face models.
+--photo_edges (with --photo) lets the outline take part in the photometric term: the render is composited over the picture
+and antialiased along the silhouette before it is compared.  --render_aa antialiases the --turntable renders the same way
+(the relit ones after the shading); --texture_check's re-render is not antialiased (its views carry no mesh).  Without
+these options nothing changes.
 
 Images are PNG / JPG (PIL) or .npy in [-1, 1] (HWC or CHW), resized on the host.  The 3DMM is the Basel Face Model with
 --bfm (face_model.load_bfm), FLAME with --flame (face_model.load_flame, op.skin), the FaceWarehouse bilinear blendshape
@@ -409,6 +421,34 @@ class MaskGuide:
         return "masks: %d of %d images have no file in %s and were fitted without one" % (self.missing, self.seen, self.dir)
 
 
+def load_silhouette(directory, path, size):
+    """[1, size, size] in [0, 1]: the silhouette of the picture `path`, DIR/<stem>.png or .npy, read as a mask is."""
+    stem = os.path.splitext(os.path.basename(path))[0]
+    found = [f for f in (os.path.join(directory, stem + ext) for ext in (".png", ".npy")) if os.path.isfile(f)]
+    if not found:
+        raise SystemExit("reconstruct: --silhouette_dir %s has no %s.png or %s.npy" % (directory, stem, stem))
+    return load_mask(found[0], size)[:, 0]
+
+
+def silhouette_outputs(inv, index, out_dir, stem):
+    """Writes <stem>_coverage.png, the antialiased coverage of the fitted mesh, and returns the .npz entries
+    `silhouette_loss` (the term at the fitted state) and `silhouette_iou` (coverage and silhouette thresholded at 0.5)."""
+    from .op.edge import coverage
+
+    k = slice(index, index + 1)
+    with torch.no_grad():
+        v, _, tri = inv.fitted_mesh()
+        alpha = coverage(v[k].contiguous(), inv.sil.tri, inv.sil.hw)[0]
+        want = inv.sil.mask[index]
+        loss = float(((alpha - want) ** 2).sum()) * inv.sil.scale
+        a, m = alpha > 0.5, want > 0.5
+        union = int((a | m).sum())
+        iou = float((a & m).sum()) / union if union else 1.0
+    pix = np.round(alpha.cpu().numpy().astype(np.float64).clip(0, 1) * 255.0).astype(np.uint8)
+    TextureGuide.save_grey(pix, os.path.join(out_dir, stem + "_coverage.png"))
+    return {"silhouette_loss": np.float64(loss), "silhouette_iou": np.float64(iou)}
+
+
 def mask_outputs(inv, index, out_dir, stem):
     """Writes <stem>_mask.png, the region of the last step's forward (the mask, times the mesh gate), and returns the
     .npz entry `mask_area`, its mean."""
@@ -562,8 +602,9 @@ class TextureGuide:
     sample and writes its files."""
 
     def __init__(self, face, size, uv_file=None, source="picture", facing="0.1,0.4", passes=8, fill="mean", check=False,
-                 turntable=0, turntable_yaw=30.0, refine=0, refine_lr=0.02, light=None, mip=None):
-        """light: None (the texture is the plain bake) or a dict with any of mono (one white light), floor (unshade's),
+                 turntable=0, turntable_yaw=30.0, refine=0, refine_lr=0.02, light=None, mip=None, render_aa=False):
+        """render_aa: the turntable's draws are antialiased along the mesh's silhouette edges (op.edge).
+        light: None (the texture is the plain bake) or a dict with any of mono (one white light), floor (unshade's),
         ridge (the fit's), lr (the light's learning rate under refinement) and relight (a file of 9 or 9 C numbers):
         every bake is then separated into an albedo and a light (op.light).  mip: None, or the lod bias with which
         every draw goes through the mip-mapped look-up (--texture_mip)."""
@@ -581,6 +622,7 @@ class TextureGuide:
                 self.light["relight"] = self.read_light(light["relight"])
         self.lights = []                                                 # (--multiview: the views' (gamma, normal map))
         self.mip = None if mip is None else float(mip)
+        self.render_aa = bool(render_aa)
         if self.mip is not None and not np.isfinite(self.mip):
             raise SystemExit("reconstruct: --texture_mip takes a finite bias")
         self.size = int(size)
@@ -727,10 +769,14 @@ class TextureGuide:
                 if kappa is not None:
                     turned = camera.project(turned.contiguous(), kappa)
                 img, cover = texture.render(turned.contiguous(), tri, self._layout[0], self.tri_uv, tex, size, -1.0,
-                                            self._layout[2], mip=self.mip)
+                                            self._layout[2], mip=self.mip, antialias=self.render_aa and light is None)
                 if light is not None:
                     nmap = self.normals_at(turned, torch.matmul(light[1].to(v.dtype), utils_3d.euler_mat(angle)), tri, size)
                     img = lighting.shade(img, nmap, cover, light[0], -1.0, -1.0)
+                    if self.render_aa:                           # (after the shading: the outline blends lit colours)
+                        from .op.edge import antialias
+
+                        img = antialias(img, turned.contiguous(), tri)
                 generate.save_image(img.clamp(-1, 1).cpu(), os.path.join(out_dir, "%s_turn_%02d.png" % (prefix, j)))
 
     @staticmethod
@@ -918,7 +964,8 @@ def reconstruct_batch(g, percept, face, target, steps, lr=0.05, pose_lr=0.01, co
                                        **inverter_args)
     elif inverter_args:
         inv.reset(target, inverter_args.get("landmarks"), inverter_args.get("landmark_conf"),
-                  **({"mask": inverter_args["mask"]} if inverter_args.get("mask") is not None else {}))
+                  **({"mask": inverter_args["mask"]} if inverter_args.get("mask") is not None else {}),
+                  **({"silhouette": inverter_args["silhouette"]} if inverter_args.get("silhouette") is not None else {}))
     else:
         inv.reset(target)
     hist = inv.run(steps)
@@ -1088,6 +1135,19 @@ def main(argv=None):
                     help="iterations of the photometric phase [100; untuned]")
     ap.add_argument("--photo_lr", type=float, default=None, metavar="LR",
                     help="learning rate of the texture in the photometric phase [0.01; untuned]")
+    ap.add_argument("--photo_edges", action="store_true",
+                    help="with --photo: the term compares the render composited over the picture and antialiased along "
+                         "the mesh's silhouette edges (op.edge), so the outline takes part in it")
+    ap.add_argument("--render_aa", action="store_true",
+                    help="with --turntable: the renders (relit ones included) are antialiased along the mesh's silhouette "
+                         "edges (op.texture.render(antialias=True)); --texture_check's re-render is not (its views "
+                         "carry no mesh)")
+    ap.add_argument("--silhouette_dir", default=None, metavar="DIR",
+                    help="fit the mesh's outline to a silhouette: DIR/<stem>.png or .npy (grey, read and resized as "
+                         "--mask_dir's files) against the antialiased coverage of the mesh (op.edge.coverage); writes "
+                         "<stem>_coverage.png and the .npz entries silhouette_loss and silhouette_iou")
+    ap.add_argument("--silhouette_weight", type=float, default=None, metavar="W",
+                    help="weight of the silhouette term [1.0; an untuned starting value]")
     ap.add_argument("--light", action="store_true",
                     help="with --texture: separate every bake into an albedo and a light (second-order spherical "
                          "harmonics, fitted in closed form); <stem>_texture.png is then the albedo")
@@ -1160,6 +1220,18 @@ def main(argv=None):
         ap.error("--texture_mip needs --texture")
     if args.photo is None and (args.photo_steps is not None or args.photo_lr is not None):
         ap.error("--photo_steps and --photo_lr need --photo")
+    if args.render_aa and not args.turntable:
+        ap.error("--render_aa needs --turntable")
+    if args.photo_edges and args.photo is None:
+        ap.error("--photo_edges needs --photo")
+    if args.silhouette_dir is None and args.silhouette_weight is not None:
+        ap.error("--silhouette_weight needs --silhouette_dir")
+    if args.silhouette_dir is not None:
+        if not os.path.isdir(args.silhouette_dir):
+            ap.error("--silhouette_dir %s is not a directory" % args.silhouette_dir)
+        args.silhouette_weight = 1.0 if args.silhouette_weight is None else args.silhouette_weight
+        if not (args.silhouette_weight >= 0 and np.isfinite(args.silhouette_weight)):
+            ap.error("--silhouette_weight takes a finite weight that is not negative")
     if args.photo is not None:
         if args.texture is None:
             ap.error("--photo needs --texture")
@@ -1226,7 +1298,7 @@ def main(argv=None):
                             light=({k: v for k, v in (("mono", args.light_mono), ("floor", args.light_floor),
                                                       ("ridge", args.light_ridge), ("lr", args.light_lr),
                                                       ("relight", args.relight)) if v is not None}
-                                   if args.light else None), mip=args.texture_mip)
+                                   if args.light else None), mip=args.texture_mip, render_aa=args.render_aa)
                if args.texture is not None else None)
     shared = None
     if args.multiview is not None:
@@ -1250,6 +1322,13 @@ def main(argv=None):
     if args.photo is not None:
         photo_args = dict(photometric=painter._layout, photo_size=args.texture, photo_weight=args.photo,
                           photo_lr=args.photo_lr)
+        if args.photo_edges:
+            photo_args["photo_edges"] = True
+
+    def silhouette_args(paths):
+        """--silhouette_dir: the inverter's silhouette= [B, H, W] of these pictures (and its weight)."""
+        return dict(silhouette=torch.cat([load_silhouette(args.silhouette_dir, path, args.size) for path in paths], 0),
+                    silhouette_weight=args.silhouette_weight)
 
     def photo_error(tex, view):
         """The mean absolute difference between the texture drawn on a view and the view's target, over the covered
@@ -1289,6 +1368,8 @@ def main(argv=None):
         (entries, texture) of the photometric phase."""
         if masker is not None:
             extras = dict(extras or {}, **mask_outputs(inv, index, args.out, stem))
+        if args.silhouette_dir is not None:
+            extras = dict(extras or {}, **silhouette_outputs(inv, index, args.out, stem))
         if painter is not None and photo is not None:
             extras = dict(extras or {}, **photo[0], **painter.outputs(inv, index, args.out, stem, path, keep, photo[1]))
         elif painter is not None:
@@ -1315,6 +1396,8 @@ def main(argv=None):
                 lmk_args.update(masker.inverter_args([mask]))
             lmk_args.update(camera_args)
             lmk_args.update(photo_args)
+            if args.silhouette_dir is not None:
+                lmk_args.update(silhouette_args([path]))
             inv, hist = reconstruct(g, percept, face, target.to(device), args.steps, args.lr, args.pose_lr, args.coeff_lr,
                                     args.shape_reg, args.n_mean_latent, **lmk_args)
             photo = photo_phase(inv, [path])[0] if args.photo is not None else None
@@ -1342,6 +1425,8 @@ def main(argv=None):
         lmk_args.update(camera_args)
         if inv is None:
             lmk_args.update(photo_args)
+        if args.silhouette_dir is not None:
+            lmk_args.update(silhouette_args(group + group[-1:] * (args.batch - len(group))))
         inv, hist = reconstruct_batch(g, percept, face, torch.cat(targets, 0).to(device), args.steps, args.lr,
                                       args.pose_lr, args.coeff_lr, args.shape_reg, args.n_mean_latent, inv=inv,
                                       shared_identity=shared, **lmk_args)
